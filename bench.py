@@ -6,9 +6,15 @@ region-growing labels) over one device-resident synthetic cloud.
 
 N = 1 (default): the configuration north_star quotes its target on -- the
 50 M-point synthetic building cloud at k=16 on ONE GPU (`urban_50m`, SURVEY.md
-8(d) C3; it fits one MI355X).  `secondary` carries BASELINE.json configs[1]
-(1 M facade, k=16) and configs[2] (10 M urban block, k=32), measured live with
-the same protocol, each with its own `roofline` block.
+8(d) C3; it fits one MI355X).
+
+A plain run sets up, warms up, times --steps passes, writes the outputs of the
+last timed pass if --dump-outputs DIR is given, and prints the result line.
+Everything else is measured only with --full: the untimed `audit` pass, the
+`cpu_baseline`, the `secondary` workloads (BASELINE.json configs[1] = 1 M facade,
+k=16, configs[2] = 10 M urban block, k=32, and the uniform control clouds),
+measured live with the same protocol, each with its own `roofline` block, and the
+`concurrent_clouds` figure.
 
 N > 1 (`--gpus N`, one rank per GPU over RCCL): ONE urban_50m cloud is segmented
 by buildingsegment_amd.dist.segment_sharded_dev -- stages 1-2 sharded by Morton
@@ -21,7 +27,13 @@ anything touches the GPU); under torchrun WORLD_SIZE must equal --gpus.
 
 Prints ONE JSON line (rank 0): the driver's contract fields plus `roofline`
 (dominant kernel: algorithmic bytes / HIP-event launch time on the launch stream)
-and `cpu_baseline` (the CPU oracle timed on this box's host cores by rank 0).
+and, with --full, `cpu_baseline` (the CPU oracle timed on the host's cores by rank 0).
+
+--dump-outputs DIR writes what the last timed pass returned to its caller as float64
+DIR/<name>.npy: `neighbours` [m, k], `normals` [m, 3] and `labels` [m] for a fixed,
+seeded sample of m rows (`rows` [m] holds their indices; every row when the cloud is
+small enough), at most DUMP_BYTES in all.  N > 1 writes rank 0's `labels` (identical
+on every rank) the same way.
 """
 from __future__ import annotations
 
@@ -39,6 +51,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes of all sampled rows together
+DUMP_SEED = 0
 WORKLOADS = ["urban_50m", "urban_10m", "facade_1m", "plane_cube_100k", "uniform_1m", "uniform_10m", "urban_2m", "urban_200m"]
 K_DEFAULT = {"facade_1m": 16, "urban_10m": 32, "urban_50m": 16, "urban_2m": 16, "plane_cube_100k": 15,
              "uniform_1m": 16, "uniform_10m": 16, "urban_200m": 16}
@@ -52,17 +66,22 @@ def parse():
     ap.add_argument("--workload", default="urban_50m", choices=WORKLOADS)
     ap.add_argument("--k", type=int, default=0, help="neighbour-list length (0 = workload default)")
     ap.add_argument("--rg-mode", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the audit pass, the CPU baseline, "
+                         "the secondary workloads and the concurrent clouds (each switched off again by its own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of what the last step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-audit", action="store_true",
-                    help="skip the untimed extra pass that replays every plane attempt against the final owners")
+                    help="--full: skip the untimed extra pass that replays every plane attempt against the final owners")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to rehearse the N>1 path "
                          "with several ranks sharing one GPU)")
     ap.add_argument("--secondary", default="facade_1m,urban_10m,uniform_1m,uniform_10m",
-                    help="comma-separated workloads measured live after the headline and reported under "
+                    help="--full: comma-separated workloads measured live after the headline and reported under "
                          "'secondary' ('' = none; ignored for N>1)")
     ap.add_argument("--concurrent", type=int, default=2,
-                    help="N=1 only: also report the aggregate throughput of this many independent copies of the workload "
+                    help="--full, N=1 only: also report the aggregate throughput of this many independent copies of the workload "
                          "segmented at the same time on the one GPU ('concurrent_clouds'; 0/1 = skip)")
     ap.add_argument("--replicas", action="store_true",
                     help="N>1: every rank segments its own copy of the workload (weak scaling of independent "
@@ -149,6 +168,23 @@ def cpu_baseline(name: str, xyz: np.ndarray, k: int):
             "sample": f"{what}: kNN+normals {t1 - t0:.2f}s, region grow {t2 - t1:.2f}s on 1 thread"}
 
 
+def dump_outputs(out_dir: str, n: int, arrays: dict) -> None:
+    """Write a fixed, seeded sample of rows of the device tensors in `arrays` (each with n rows) as float64
+    out_dir/<name>.npy, plus `rows`: the sampled indices.  float64 holds every int32 index and label exactly."""
+    import torch
+    width = 1 + sum(a[0].numel() for a in arrays.values())  # float64 values per row, `rows` included
+    m = min(n, DUMP_BYTES // (8 * width))
+    if m < n:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=m, replace=False))
+    else:
+        rows = np.arange(n)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        d_rows = torch.from_numpy(rows).to(a.device)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a[d_rows].cpu().numpy().astype(np.float64))
+
+
 def roofline_block(n, k, stage, launches_per_step, rg_mode, workload):
     """Dominant kernel by time.  Algorithmic bytes per point:
       kNN+normals: read xyz 12 + write k*4 + write normal 24 (+12: second read of xyz)
@@ -188,7 +224,7 @@ def roofline_block(n, k, stage, launches_per_step, rg_mode, workload):
 
 
 def measure_single(ctx, api, torch, dev, name, k_override, rg_mode, steps, warmup, fence, world=1, all_reduce_max=None,
-                   audit=False):
+                   audit=False, dump_dir=None):
     """Whole path on one GPU per rank (bs_segment_dev), inputs resident in HBM."""
     xyz, k = make_cloud(name)
     if k_override:
@@ -222,6 +258,8 @@ def measure_single(ctx, api, torch, dev, name, k_override, rg_mode, steps, warmu
     tm = ctx.timings()
     for kk in stage:
         stage[kk] /= max(steps, 1)
+    if dump_dir:  # what the last timed pass left in the caller's buffers
+        dump_outputs(dump_dir, n, {"neighbours": d_neigh, "normals": d_normals, "labels": d_plane})
     audit_res = None
     if audit:  # one more, UNTIMED pass with the replay certificate switched on (bs_set_audit)
         ctx.set_audit(True)
@@ -365,11 +403,13 @@ def main():
     common = {"metric": "Mpoints/s segmented (kNN+normal+label)", "unit": "Mpoints/s", "n_gpus": world,
               "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "vs_baseline": None,
               "dtype": "int32 coordinates / f64 normals", "data": "synthetic"}
+    cpu_base = args.full and not args.no_cpu_baseline
+    audit = args.full and not args.no_audit and args.rg_mode in (0, 2)
     out = None
     if world == 1 or args.replicas:
         res, xyz, k = measure_single(ctx, api, torch, dev, args.workload, args.k, args.rg_mode, args.steps, args.warmup,
-                                     fence, world, all_reduce_max if world > 1 else None,
-                                     audit=(world == 1 and not args.no_audit and args.rg_mode in (0, 2)))
+                                     fence, world, all_reduce_max if world > 1 else None, audit=(world == 1 and audit),
+                                     dump_dir=args.dump_outputs if rank == 0 else None)
         if rank == 0:
             out = dict(common)
             out.update({"value": res["value"], "ms_per_step": res["ms_per_step"], "scaling": "weak",
@@ -385,23 +425,22 @@ def main():
                         "roofline": res["roofline"]})
             if "audit" in res:
                 out["audit"] = res["audit"]
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and cpu_base:
                 out["cpu_baseline"] = cpu_baseline(args.workload, xyz, k)
         del xyz
-        if world == 1 and args.secondary:
+        if world == 1 and args.full and args.secondary:
             sec = []
             for name in [s for s in args.secondary.split(",") if s and s != args.workload]:
-                r2, xyz2, k2 = measure_single(ctx, api, torch, dev, name, 0, args.rg_mode, 2, 1, fence,
-                                              audit=(not args.no_audit and args.rg_mode in (0, 2)))
+                r2, xyz2, k2 = measure_single(ctx, api, torch, dev, name, 0, args.rg_mode, 2, 1, fence, audit=audit)
                 for drop in ("radius_mm", "max_nn"):
                     r2.pop(drop)
-                if not args.no_cpu_baseline:  # each secondary beside ITS OWN one-thread CPU oracle run (per-stage split)
+                if cpu_base:  # each secondary beside ITS OWN one-thread CPU oracle run (per-stage split)
                     r2["cpu_baseline"] = cpu_baseline(name, xyz2, k2)
                 del xyz2
                 sec.append(r2)
             if rank == 0 and sec:
                 out["secondary"] = sec
-        if world == 1 and args.concurrent > 1:
+        if world == 1 and args.full and args.concurrent > 1:
             out["concurrent_clouds"] = measure_concurrent(api, torch, dev, args.workload, args.k, args.rg_mode, args.steps,
                                                           args.concurrent)
     else:
@@ -418,7 +457,7 @@ def main():
         # the Morton partition, the halo exchange and every other exchange are inside the timed region
         d_own = torch.from_numpy(xyz[b[rank]:b[rank + 1]]).to(dev)
         d_gidx = torch.arange(b[rank], b[rank + 1], dtype=torch.int32, device=dev)
-        if rank != 0 or args.no_cpu_baseline:
+        if rank != 0 or not cpu_base:
             del xyz
         keys = ["partition_ms", "halo_ms", "knn_normals_ms", "components_ms", "redistribute_ms", "localize_ms", "grow_ms",
                 "labels_ms"]
@@ -426,12 +465,13 @@ def main():
         kst = {"grid_ms": 0.0, "knn_ms": 0.0, "grow_kernel_ms": 0.0, "grow_setup_ms": 0.0}
         launches = 0
         info = {}
+        labels = None
         for _ in range(args.warmup):
             bsd.segment_sharded_dev(ctx, d_own, d_gidx, n, params)
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            _, info = bsd.segment_sharded_dev(ctx, d_own, d_gidx, n, params)
+            labels, info = bsd.segment_sharded_dev(ctx, d_own, d_gidx, n, params)
             for kk in st:
                 st[kk] += info["stage_ms"][kk]
             tm = ctx.timings()  # HIP-event times of this rank's kNN and growth kernels in this step
@@ -443,6 +483,8 @@ def main():
         for kk in st:
             st[kk] = all_reduce_max(st[kk] / max(args.steps, 1))
         n_grow_max = int(all_reduce_max(float(info.get("n_grow", 0))))
+        if rank == 0 and args.dump_outputs and labels is not None:
+            dump_outputs(args.dump_outputs, n, {"labels": labels})
         if rank == 0:
             for kk in kst:
                 kst[kk] /= max(args.steps, 1)
@@ -470,7 +512,7 @@ def main():
                         "stages_ms": st, "rank0_kernel_ms": kst,
                         "stage12_Mpoints_per_s": n / ((st["partition_ms"] + st["halo_ms"] + st["knn_normals_ms"]) * 1e-3) / 1e6,
                         "roofline": roof})
-            if not args.no_cpu_baseline:
+            if cpu_base:
                 out["cpu_baseline"] = cpu_baseline(args.workload, xyz, k)
     if rank == 0:
         print(json.dumps(out), flush=True)

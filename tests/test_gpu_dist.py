@@ -109,7 +109,7 @@ def test_bench_sharded_mode_end_to_end():
     env = dict(os.environ, BS_CLOUD_CACHE="")
     env.pop("BS_CLOUD_CACHE")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload",
-                        "plane_cube_100k", "--steps", "1", "--warmup", "1"], capture_output=True, text=True, timeout=600, env=env)
+                        "plane_cube_100k", "--steps", "1", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
