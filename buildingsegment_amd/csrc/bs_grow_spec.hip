@@ -1305,12 +1305,28 @@ __device__ unsigned long long g_prof2[32];
 
 typedef int v4i __attribute__((ext_vector_type(4)));  // a native 128-bit register tuple (inline-asm operand)
 
-template <int KC>
+#ifdef BS_PROBE
+// why the hot loop was left (every plane of every round; the host prints the counts per round under BS_DEBUG=1):
+// 0 LIFO empty, 1 watchdog, 2 refill, 3 stolen, 4 earlier claim, 5 assumption log, 6 list ring, 7 LIFO window,
+// 8 log ring (third engine); 9 hot-loop steps, 10 complete steps
+__device__ unsigned long long g_exit2[16];
+#define EXIT_COUNT(i) (nexit[i]++)
+#else
+#define EXIT_COUNT(i) \
+  do {                \
+  } while (0)
+#endif
+constexpr int LOGB = 128;  // LDS ring of assumption-log entries (third engine; flushed in bursts of 64)
+
+// V3 = true is the third step engine (BS_GROW_V2=3): the assumption-log entries go through an LDS ring (logbuf), so a
+// step that only has to log stays in the hot loop.  V3 = false compiles to the second engine exactly as before.
+template <int KC, bool V3 = false>
 __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsigned long long* __restrict__ cand, int ncand,
                                                         int4* rec, int32_t* dead, Pool pool,
                                                         PlaneOut* __restrict__ out, int64_t step_cap, int retry_max_list,
                                                         const uint32_t* __restrict__ order)
 {
+  __shared__ int logbuf[V3 ? LOGB : 1];
   __shared__ __attribute__((aligned(16))) int lds_stack[LDS_STACK * KC];
   __shared__ int lbuf[LBUF];
   constexpr int Q = RecLayout<KC>::QUADS;
@@ -1330,6 +1346,7 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
   Slab list = {0, 0}, stack = {0, 0}, log = {0, 0};
   int long_tries = 0;
   int ln = 1, lflushed = 0, sp = 0, lds_lo = 0, logn = 0;
+  int lgflushed = 0;  // (V3) log entries [lgflushed, logn) are in the LDS ring, everything below is in the HBM slab
   uint32_t iters = 0;
   const uint32_t iter_cap = step_cap > 0xFFFFFFF0ll ? 0xFFFFFFF0u : (uint32_t)step_cap;
   int status = ST_DONE;
@@ -1360,6 +1377,19 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
     lflushed = upto;
     return true;
   };
+  auto flush_log = [&](int upto) -> bool {  // (V3) make log entries [lgflushed, upto) durable (upto <= logn)
+    if (upto <= lgflushed)
+      return true;
+    if (!slab_ensure(pool, log, lgflushed, upto, lane))
+      return false;
+    for (int t0 = lgflushed; t0 < upto; t0 += 64) {
+      const int t = t0 + lane;
+      if (t < upto)
+        pool.base[log.off + t] = logbuf[t & (LOGB - 1)];
+    }
+    lgflushed = upto;
+    return true;
+  };
   for (int attempt = 0;; attempt++) {
     status = ST_DONE;
     pendv = false;
@@ -1368,6 +1398,7 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
     sp = 0;
     lds_lo = 0;
     logn = 0;
+    lgflushed = 0;
     cnx = __hiloint2double(s1.y, s1.x);
     cny = __hiloint2double(s1.w, s1.z);
     cnz = __hiloint2double(s2.y, s2.x);
@@ -1395,6 +1426,7 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
       long long pacc[12] = {0};
       long long ncalls = 0, nexp = 0;
       long long tlast = clock64();
+      long long nexit[11] = {0};
 #endif
       // ---- what every step starts with: pop, gather, plane state of the previous expansion, test, settle ----
       // (straight-line code without exits: it is shared by the hot loop and by the complete step)
@@ -1539,6 +1571,7 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
       auto step_complete = [&]() -> int {
         if (__builtin_expect(sp == 0, 0))
           return 2;
+        EXIT_COUNT(10);
         if (__builtin_expect(++iters > iter_cap, 0)) {
           status = ST_WATCHDOG;
           return 2;
@@ -1636,12 +1669,21 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
         const unsigned long long lm = ballot64(assume && g <= last);
         if (lm != 0) {
           const int lcnt = __popcll(lm);
-          if (!slab_ensure(pool, log, logn, logn + lcnt, lane)) {
-            status = ST_NOMEM;
-            return 2;
+          if constexpr (V3) {
+            if (logn + lcnt - lgflushed > LOGB && !flush_log(logn)) {  // the ring is full: a burst to the HBM slab
+              status = ST_NOMEM;
+              return 2;
+            }
+            if (assume && g <= last)
+              logbuf[(logn + __popcll(lm & ((1ull << lane) - 1ull))) & (LOGB - 1)] = cand_id;
+          } else {
+            if (!slab_ensure(pool, log, logn, logn + lcnt, lane)) {
+              status = ST_NOMEM;
+              return 2;
+            }
+            if (assume && g <= last)
+              pool.base[log.off + logn + __popcll(lm & ((1ull << lane) - 1ull))] = cand_id;
           }
-          if (assume && g <= last)
-            pool.base[log.off + logn + __popcll(lm & ((1ull << lane) - 1ull))] = cand_id;
           logn += lcnt;
         }
         const int cnt = __popcll(am);
@@ -1702,6 +1744,7 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
         // ---- the HOT LOOP: the common step only, every exit is a wave-uniform break BEFORE the step has a side effect ----
         for (;;) {
           if (__builtin_expect(sp == 0, 0)) {
+            EXIT_COUNT(0);
             leave = true;
             break;
           }
@@ -1709,10 +1752,14 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
 #ifdef BS_PROBE
           ncalls++;
 #endif
-          if (__builtin_expect(iters >= iter_cap, 0))
+          if (__builtin_expect(iters >= iter_cap, 0)) {
+            EXIT_COUNT(1);
             break;  // (the complete step raises the watchdog)
-          if (__builtin_expect(((sp - NG > 0) ? sp - NG : 0) < lds_lo, 0))
+          }
+          if (__builtin_expect(((sp - NG > 0) ? sp - NG : 0) < lds_lo, 0)) {
+            EXIT_COUNT(2);
             break;  // refill
+          }
           Ev E;
           eval(E);
           // Classification first, ONE rows_wait() for every way on (a wait per exit made the compiler copy the row
@@ -1722,9 +1769,23 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
           const unsigned long long cm = ballot64(contender);
           PROBE(3);
           int gstar = -1, cnt = 0;
-          unsigned long long am = 0;
+          unsigned long long am = 0, lm = 0;
           bool slow = false;
-          if (__builtin_expect(cm != 0, 1)) {
+          if constexpr (V3) {
+            // the assumptions of this step go through the LDS log ring: only a full ring leaves the loop
+            if (__builtin_expect(cm != 0, 1)) {
+              gstar = (__ffsll(cm) - 1) / KC;
+              const unsigned long long gm1 = gmask0 << (gstar * KC);
+              am = cm & gm1;
+              cnt = __popcll(am);
+              lm = ballot64(assume && g <= gstar);
+              slow = (ballot64(contender && E.tg < seed) & gm1) != 0 || ln + cnt - lflushed > LBUF ||
+                     sp - (gstar + 1) + cnt - lds_lo > LDS_STACK;
+            } else {
+              lm = ballot64(assume);  // (only empty calls: every valid one is at or before the last)
+            }
+            slow = slow || logn + __popcll(lm) - lgflushed > LOGB;
+          } else if (__builtin_expect(cm != 0, 1)) {
             gstar = (__ffsll(cm) - 1) / KC;
             const unsigned long long gm1 = gmask0 << (gstar * KC);
             am = cm & gm1;
@@ -1737,16 +1798,40 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
           }
           rows_wait(E);  // (before the claims: a wait behind them would put the atomics' round trip on the chain)
           if (__builtin_expect(E.lost_any, 0)) {
+            EXIT_COUNT(3);
             pendv = false;
             status = ST_STOLEN;
             leave = true;
             break;
           }
-          if (__builtin_expect(slow, 0))
+          if (__builtin_expect(slow, 0)) {
+#ifdef BS_PROBE
+            // the first reason that applies, in the order of the test above
+            const unsigned long long gmp = gstar >= 0 ? gmask0 << (gstar * KC) : 0;
+            if ((ballot64(contender && E.tg < seed) & gmp) != 0)
+              EXIT_COUNT(4);
+            else if (!V3 && ballot64(assume && (gstar < 0 || g <= gstar)) != 0)
+              EXIT_COUNT(5);
+            else if (ln + cnt - lflushed > LBUF)
+              EXIT_COUNT(6);
+            else if (gstar >= 0 && sp - (gstar + 1) + cnt - lds_lo > LDS_STACK)
+              EXIT_COUNT(7);
+            else
+              EXIT_COUNT(8);
+#endif
             break;
+          }
           // ---- committed: from here on the step has side effects ----
+          EXIT_COUNT(9);
           iters++;
           pendv = false;
+          if constexpr (V3) {
+            if (lm != 0) {
+              if (assume && (gstar < 0 || g <= gstar))
+                logbuf[(logn + __popcll(lm & ((1ull << lane) - 1ull))) & (LOGB - 1)] = E.cand_id;
+              logn += __popcll(lm);
+            }
+          }
           const bool ok = contender && g == gstar;
           if (ok) {
             int32_t* tp = rec_tag(rec, Q, E.cand_id);
@@ -1782,6 +1867,10 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
         atomicAdd(&g_prof2[10], (unsigned long long)ncalls);
         atomicAdd(&g_prof2[11], (unsigned long long)nexp);
       }
+      if (lane == 0)
+        for (int i = 0; i < 11; i++)
+          if (nexit[i])
+            atomicAdd(&g_exit2[i], (unsigned long long)nexit[i]);
 #endif
     }
     if (need_state) {  // state of the very last expansion (the plane's reported normal / centre)
@@ -1801,6 +1890,10 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
     }
     if (have_mem && status != ST_NOMEM && !flush_list(ln))  // the whole list is in the HBM slab from here on
       status = ST_NOMEM;
+    if constexpr (V3) {
+      if (have_mem && status != ST_NOMEM && !flush_log(logn))  // and so is the log
+        status = ST_NOMEM;
+    }
     if (status == ST_DONE) {
       const bool lost = pendv && ld_i32(vptr) != seed;
       if (ballot64(lost))
@@ -2665,8 +2758,32 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   // (255 VGPRs, one wave per SIMD) and in rounds with tens of thousands of attempts, where the throughput of the
   // many short attempts counts and the long chains wait for HBM anyway (urban 10 M k=32: 128 vs 112 ms, urban 50 M:
   // 199.5 vs 184.8 ms), the first engine wins.  So: second engine for rounds of few attempts at k <= 16.
-  // BS_GROW_V2=0 / 1 forces one of them (A/B runs, tests).
+  // The third engine (grow_spec2_kernel<KC, true>: the second with the assumption log in an LDS ring) takes every round
+  // at k <= 16, the crowded first one included: there the second engine left its hot loop for 1.5 M assumption logs
+  // of 4.0 M complete steps (profiles/r04_grow_exits_urban_50m.txt); the third one runs round 1 of the 50 M cloud in
+  // 82-86 ms against the first engine's 94-97 ms and the façade's growth launches in 120.6 against 123.1 ms.
+  // BS_GROW_V2=0 / 1 / 3 forces the first / second / third engine (A/B runs, tests).
   const int grow_force = getenv("BS_GROW_V2") ? atoi(getenv("BS_GROW_V2")) : -1;
+  const int grow_eng = grow_force >= 0 ? (grow_force == 0 ? 1 : (grow_force == 3 ? 3 : 2)) : (KC == 16 ? 3 : 1);
+  auto launch_grow = [&](int cnt, size_t lds, const unsigned long long* cd, PlaneOut* o, int rml, const uint32_t* ord) {
+    const int64_t cap = 512 * n + 4096;
+    if (grow_eng == 1) {
+      if (KC == 16)
+        grow_spec_kernel<16><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
+      else
+        grow_spec_kernel<32><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
+    } else if (grow_eng == 2) {
+      if (KC == 16)
+        grow_spec2_kernel<16><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
+      else
+        grow_spec2_kernel<32><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
+    } else {
+      if (KC == 16)
+        grow_spec2_kernel<16, true><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
+      else
+        grow_spec2_kernel<32, true><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
+    }
+  };
   BS_HIP(ctx, hipMemsetAsync(d_misc + 4, 0, 12 * sizeof(int), st));  // [4] refused planes, [5] forged seed + 1, [6] forged one refused, [12..15] refusals by check
   for (;;) {
     rounds++;
@@ -2738,18 +2855,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       // is grown again has the time to finish inside the same launch (urban 10 M: +20 %); in a round of a few
       // chained planes (the facade) the re-growth only repeats work the next round does anyway (-23 %).
       const int rml = (ncand >= retry_big_round && !retry_env) ? 0x7fffffff : retry_max_list;
-      const bool grow_v1 = grow_force >= 0 ? grow_force == 0 : !(KC == 16 && ncand < 65536);
-      if (grow_v1) {
-        if (KC == 16)
-          grow_spec_kernel<16><<<ncand, 64, lds_pad, st>>>(a, d_cand, ncand, rec, dead, pool, d_out, 512 * n + 4096, rml, d_order);
-        else
-          grow_spec_kernel<32><<<ncand, 64, lds_pad, st>>>(a, d_cand, ncand, rec, dead, pool, d_out, 512 * n + 4096, rml, d_order);
-      } else {
-        if (KC == 16)
-          grow_spec2_kernel<16><<<ncand, 64, lds_pad, st>>>(a, d_cand, ncand, rec, dead, pool, d_out, 512 * n + 4096, rml, d_order);
-        else
-          grow_spec2_kernel<32><<<ncand, 64, lds_pad, st>>>(a, d_cand, ncand, rec, dead, pool, d_out, 512 * n + 4096, rml, d_order);
-      }
+      launch_grow(ncand, lds_pad, d_cand, d_out, rml, d_order);
       (void)hipEventRecord(ctx->ev[7], st);
       grow_launches++;
       timed_round = true;
@@ -2861,6 +2967,14 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
                       "flushchk=%.0f list+defer=%.0f push=%.0f top=%.0f (cycles per step, cumulative over rounds)\n",
               hp[10], hp[11], hp[0] / nstep, hp[1] / nstep, hp[2] / nstep, hp[3] / nstep, hp[4] / nstep, hp[5] / nstep, hp[6] / nstep,
               hp[7] / nstep, hp[8] / nstep, hp[9] / nstep);
+      // exits of the hot loop in this round (every plane; the counters are reset after each print)
+      unsigned long long he[16];
+      (void)hipMemcpyFromSymbol(he, HIP_SYMBOL(g_exit2), sizeof(he));
+      fprintf(stderr, "[exits] round %ld attempts %d engine %d | hot steps %llu complete steps %llu | lifo-empty %llu watchdog %llu "
+                      "refill %llu stolen %llu earlier-claim %llu assume-log %llu list-ring %llu lifo-window %llu log-ring %llu\n",
+              (long)rounds, ncand, grow_eng, he[9], he[10], he[0], he[1], he[2], he[3], he[4], he[5], he[6], he[7], he[8]);
+      memset(he, 0, sizeof(he));
+      (void)hipMemcpyToSymbol(HIP_SYMBOL(g_exit2), he, sizeof(he));
     }
 #endif
     if (dbg) {
@@ -3100,20 +3214,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
     if (na > 0)
       BS_HIP(ctx, hipMemcpyAsync(d_cand, hc_sorted.data(), sizeof(unsigned long long) * na, hipMemcpyHostToDevice, st));
     a.F = INF;
-    auto grow_n = [&](int off, int cnt, PlaneOut* o) {
-      const bool grow_v1 = grow_force >= 0 ? grow_force == 0 : !(KC == 16 && cnt < 65536);
-      if (grow_v1) {
-        if (KC == 16)
-          grow_spec_kernel<16><<<cnt, 64, 0, st>>>(a, d_cand + off, cnt, rec, dead, pool, o, 512 * n + 4096, 0, nullptr);
-        else
-          grow_spec_kernel<32><<<cnt, 64, 0, st>>>(a, d_cand + off, cnt, rec, dead, pool, o, 512 * n + 4096, 0, nullptr);
-      } else {
-        if (KC == 16)
-          grow_spec2_kernel<16><<<cnt, 64, 0, st>>>(a, d_cand + off, cnt, rec, dead, pool, o, 512 * n + 4096, 0, nullptr);
-        else
-          grow_spec2_kernel<32><<<cnt, 64, 0, st>>>(a, d_cand + off, cnt, rec, dead, pool, o, 512 * n + 4096, 0, nullptr);
-      }
-    };
+    auto grow_n = [&](int off, int cnt, PlaneOut* o) { launch_grow(cnt, 0, d_cand + off, o, 0, nullptr); };
     auto compare_n = [&](int cnt, int32_t* retry) {
       audit_compare_kernel<<<cnt, VT, 0, st>>>(d_out, cnt, pool.base, prio, d_seeds, ctx->rg_planes.as<PlaneRec>(), np,
                                                ctx->rg_list.as<int32_t>(), a.th_count, d_misc + 8, dead, retry);
