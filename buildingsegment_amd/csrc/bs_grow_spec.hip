@@ -1223,32 +1223,36 @@ __global__ __launch_bounds__(64) void grow_spec_kernel(SpecArgs a, const unsigne
   }
 }
 
-// ---- step engine, second generation (BS_GROW_V2=0 selects the kernel above) -------------------------------------
+// ---- step engine for k <= 16 (BS_GROW_V2=0 selects the kernel above) ---------------------------------------------
 // Same protocol, same arithmetic, same results as grow_spec_kernel -- the step is re-cut around what the stamps of
 // the first engine showed (~3 000 cycles per step of ONE wave; identical at 19.6 k-, 90 k- and 250 k-point planes,
 // i.e. whether the records fit an XCD's L2 or not: the step is bound by the issue of the wave's own instruction
 // stream, not by where the gather is served from).  What changed:
 //  * HOT LOOP + COMPLETE STEP.  The loop that runs per step contains the common step only: pending calls in the LDS
-//    window, the first call with contenders claims without meeting an earlier plane, nothing to log, room in the LDS
-//    rings.  Everything else (refill, slow claim walk, assumption log, ring flushes, the depth-0 rule) is noticed
-//    BEFORE the step has a side effect and handled by ONE run of the complete step outside the loop.  With the rare
-//    paths inlined in the loop body the compiler kept its loop-carried scalars per lane in vector registers under
-//    exec-mask control flow (190-208 VGPRs, 57 spilled SGPRs); uniformity is also said explicitly (readfirstlane)
-//    where the divergence analysis gives up (merged exits behind per-lane branches, per-lane trip counts);
+//    window, the first call with contenders claims without meeting an earlier plane, room in the LDS rings.
+//    Everything else (refill, slow claim walk, ring flushes, the depth-0 rule) is noticed BEFORE the step has a side
+//    effect and handled by ONE run of the complete step outside the loop.  With the rare paths inlined in the loop
+//    body the compiler kept its loop-carried scalars per lane in vector registers under exec-mask control flow
+//    (190-208 VGPRs, 57 spilled SGPRs); uniformity is also said explicitly (readfirstlane) where the divergence
+//    analysis gives up (merged exits behind per-lane branches, per-lane trip counts);
 //  * every vector-memory instruction of the hot loop is inline assembly behind ONE explicit wait: the claim tag rides
 //    in the same 16-byte sc1 load as the normal's third component, and no compiler-placed s_waitcnt vmcnt(0) sits
 //    right behind the previous step's claim atomics (600-900 cycles);
 //  * the LIFO lives in LDS only: its oldest 128 entries are flushed to the HBM slab in one coalesced burst when the
 //    256-entry window is full and come back the same way -- no write-through per push;
-//  * pointIdx entries are collected in an LDS ring and leave in coalesced bursts: no store, no address arithmetic
-//    and no slab-capacity check in the step;
+//  * pointIdx entries and assumption-log entries are collected in LDS rings and leave in coalesced bursts: no store,
+//    no address arithmetic and no slab-capacity check in the step, and a step that only has to log stays in the hot
+//    loop (with the log written straight to the HBM slab by the complete step, 1.5 M of the 4.0 M complete steps of
+//    round 1 at 50 M were there for the log alone: profiles/r04_grow_exits_urban_50m.txt);
 //  * distance and normal test are evaluated side by side (no short circuit);
 //  * the gather is waited for in two parts: the five loads the test needs (flags, position, normal, tag) first, the
 //    candidates' own rows -- issued last, needed by the push only -- after the classification.  Every scattered
 //    64-lane load costs ~70 cycles of the CU's address unit whatever it hits (tools/probe/gather_probe.hip: 369 cycles
 //    for one, 805 for seven), so the four row loads used to hold the test back by ~280 cycles (facade 131 -> 121 ms).
 //    The rows' registers are written by the hardware after the asm statement that names them: there is ONE wait for
-//    them on every path, and tests/test_isa_rows_wait.py checks in the generated ISA that nothing touches them before.
+//    them on every path, and tests/test_isa_gather_v3.py checks in the generated ISA that nothing touches a load's
+//    registers before the wait that covers it.
+// k > 16 stays on the first engine: this one would need 255 VGPRs there (one wave per SIMD) and lost to it.
 // Tried and measured slower (facade 1 M, growth kernels; at the time this engine took 136.6 ms, later 131.2 ms, the
 // first engine 147.5 ms):
 //  * the candidates' neighbour rows fetched cooperatively (four lanes per row, 16 cache lines per instruction
@@ -1307,8 +1311,8 @@ typedef int v4i __attribute__((ext_vector_type(4)));  // a native 128-bit regist
 
 #ifdef BS_PROBE
 // why the hot loop was left (every plane of every round; the host prints the counts per round under BS_DEBUG=1):
-// 0 LIFO empty, 1 watchdog, 2 refill, 3 stolen, 4 earlier claim, 5 assumption log, 6 list ring, 7 LIFO window,
-// 8 log ring (third engine); 9 hot-loop steps, 10 complete steps
+// 0 LIFO empty, 1 watchdog, 2 refill, 3 stolen, 4 earlier claim, 6 list ring, 7 LIFO window, 8 log ring; 9 hot-loop
+// steps, 10 complete steps (5 is unused: the assumption log of the retired second engine)
 __device__ unsigned long long g_exit2[16];
 #define EXIT_COUNT(i) (nexit[i]++)
 #else
@@ -1316,17 +1320,16 @@ __device__ unsigned long long g_exit2[16];
   do {                \
   } while (0)
 #endif
-constexpr int LOGB = 128;  // LDS ring of assumption-log entries (third engine; flushed in bursts of 64)
+constexpr int LOGB = 128;  // LDS ring of assumption-log entries (flushed in bursts of 64)
 
-// V3 = true is the third step engine (BS_GROW_V2=3): the assumption-log entries go through an LDS ring (logbuf), so a
-// step that only has to log stays in the hot loop.  V3 = false compiles to the second engine exactly as before.
-template <int KC, bool V3 = false>
+template <int KC>
 __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsigned long long* __restrict__ cand, int ncand,
                                                         int4* rec, int32_t* dead, Pool pool,
                                                         PlaneOut* __restrict__ out, int64_t step_cap, int retry_max_list,
                                                         const uint32_t* __restrict__ order)
 {
-  __shared__ int logbuf[V3 ? LOGB : 1];
+  static_assert(KC == 16, "k > 16 runs on grow_spec_kernel");
+  __shared__ int logbuf[LOGB];
   __shared__ __attribute__((aligned(16))) int lds_stack[LDS_STACK * KC];
   __shared__ int lbuf[LBUF];
   constexpr int Q = RecLayout<KC>::QUADS;
@@ -1337,7 +1340,7 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
   const int w = order ? (int)(order[blockIdx.x] & (MAX_WAVES - 1)) : (int)blockIdx.x;
   const int lane = threadIdx.x;
   const int g = lane / KC, j = lane % KC;
-  const unsigned long long gmask0 = (KC == 32) ? 0xffffffffull : 0xffffull;
+  const unsigned long long gmask0 = 0xffffull;
   const int K = a.K, nc = K - 1;
   const bool act = j < nc;
   const int64_t t_start = (int64_t)wall_clock64();
@@ -1346,7 +1349,7 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
   Slab list = {0, 0}, stack = {0, 0}, log = {0, 0};
   int long_tries = 0;
   int ln = 1, lflushed = 0, sp = 0, lds_lo = 0, logn = 0;
-  int lgflushed = 0;  // (V3) log entries [lgflushed, logn) are in the LDS ring, everything below is in the HBM slab
+  int lgflushed = 0;  // log entries [lgflushed, logn) are in the LDS ring, everything below is in the HBM slab
   uint32_t iters = 0;
   const uint32_t iter_cap = step_cap > 0xFFFFFFF0ll ? 0xFFFFFFF0u : (uint32_t)step_cap;
   int status = ST_DONE;
@@ -1377,7 +1380,7 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
     lflushed = upto;
     return true;
   };
-  auto flush_log = [&](int upto) -> bool {  // (V3) make log entries [lgflushed, upto) durable (upto <= logn)
+  auto flush_log = [&](int upto) -> bool {  // make log entries [lgflushed, upto) durable (upto <= logn)
     if (upto <= lgflushed)
       return true;
     if (!slab_ensure(pool, log, lgflushed, upto, lane))
@@ -1495,12 +1498,9 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
         }
         PROBE(1);
         // ---- the ONE wait of the gather (the operands tie every later use of the data behind it) ----
-        // (loads return in issue order: with CH + 2 still outstanding the three record loads have landed; the flags and
-        // the candidates' own rows are only needed by the commit and keep streaming in under the test: rows_wait() below)
-        if (CH == 4)
-          asm volatile("s_waitcnt vmcnt(6)" : "+v"(q0), "+v"(q1), "+v"(q2)::"memory");
-        else
-          asm volatile("s_waitcnt vmcnt(10)" : "+v"(q0), "+v"(q1), "+v"(q2)::"memory");
+        // (loads return in issue order: with CH + 2 = 6 still outstanding the three record loads have landed; the flags
+        // and the candidates' own rows are only needed by the commit and keep streaming in under the test: rows_wait() below)
+        asm volatile("s_waitcnt vmcnt(6)" : "+v"(q0), "+v"(q1), "+v"(q2)::"memory");
         PROBE(2);
         E.px = q0.x;
         E.py = q0.y;
@@ -1524,14 +1524,8 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
       // before it reads them, issues another vector-memory instruction, or leaves the step (their destination registers
       // must stay allocated until the loads have landed).
       auto rows_wait = [&](Ev& E) {
-        static_assert(CH == 4 || CH == 8, "row chunks");
-        if constexpr (CH == 4)
-          asm volatile("s_waitcnt vmcnt(0)"
-                       : "+v"(E.rows[0]), "+v"(E.rows[1]), "+v"(E.rows[2]), "+v"(E.rows[3]), "+v"(E.killed_v), "+v"(E.vt)::"memory");
-        else
-          asm volatile("s_waitcnt vmcnt(0)"
-                       : "+v"(E.rows[0]), "+v"(E.rows[1]), "+v"(E.rows[2]), "+v"(E.rows[3]), "+v"(E.rows[4]), "+v"(E.rows[5]),
-                         "+v"(E.rows[6]), "+v"(E.rows[7]), "+v"(E.killed_v), "+v"(E.vt)::"memory");
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(E.rows[0]), "+v"(E.rows[1]), "+v"(E.rows[2]), "+v"(E.rows[3]), "+v"(E.killed_v), "+v"(E.vt)::"memory");
         const bool lost = pendv && E.vt != seed;  // an earlier plane got there first
         E.lost_any = __builtin_amdgcn_readfirstlane(E.killed_v) != 0 || ballot64(lost) != 0;
       };
@@ -1669,21 +1663,12 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
         const unsigned long long lm = ballot64(assume && g <= last);
         if (lm != 0) {
           const int lcnt = __popcll(lm);
-          if constexpr (V3) {
-            if (logn + lcnt - lgflushed > LOGB && !flush_log(logn)) {  // the ring is full: a burst to the HBM slab
-              status = ST_NOMEM;
-              return 2;
-            }
-            if (assume && g <= last)
-              logbuf[(logn + __popcll(lm & ((1ull << lane) - 1ull))) & (LOGB - 1)] = cand_id;
-          } else {
-            if (!slab_ensure(pool, log, logn, logn + lcnt, lane)) {
-              status = ST_NOMEM;
-              return 2;
-            }
-            if (assume && g <= last)
-              pool.base[log.off + logn + __popcll(lm & ((1ull << lane) - 1ull))] = cand_id;
+          if (logn + lcnt - lgflushed > LOGB && !flush_log(logn)) {  // the ring is full: a burst to the HBM slab
+            status = ST_NOMEM;
+            return 2;
           }
+          if (assume && g <= last)
+            logbuf[(logn + __popcll(lm & ((1ull << lane) - 1ull))) & (LOGB - 1)] = cand_id;
           logn += lcnt;
         }
         const int cnt = __popcll(am);
@@ -1771,31 +1756,20 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
           int gstar = -1, cnt = 0;
           unsigned long long am = 0, lm = 0;
           bool slow = false;
-          if constexpr (V3) {
-            // the assumptions of this step go through the LDS log ring: only a full ring leaves the loop
-            if (__builtin_expect(cm != 0, 1)) {
-              gstar = (__ffsll(cm) - 1) / KC;
-              const unsigned long long gm1 = gmask0 << (gstar * KC);
-              am = cm & gm1;
-              cnt = __popcll(am);
-              lm = ballot64(assume && g <= gstar);
-              slow = (ballot64(contender && E.tg < seed) & gm1) != 0 || ln + cnt - lflushed > LBUF ||
-                     sp - (gstar + 1) + cnt - lds_lo > LDS_STACK;
-            } else {
-              lm = ballot64(assume);  // (only empty calls: every valid one is at or before the last)
-            }
-            slow = slow || logn + __popcll(lm) - lgflushed > LOGB;
-          } else if (__builtin_expect(cm != 0, 1)) {
+          // everything this loop cannot do is known here, before the first claim is issued; the assumptions of this
+          // step go through the LDS log ring, only a full ring leaves the loop
+          if (__builtin_expect(cm != 0, 1)) {
             gstar = (__ffsll(cm) - 1) / KC;
             const unsigned long long gm1 = gmask0 << (gstar * KC);
             am = cm & gm1;
             cnt = __popcll(am);
-            // everything this loop cannot do is known here, before the first claim is issued
-            slow = (ballot64(contender && E.tg < seed) & gm1) != 0 || ballot64(assume && g <= gstar) != 0 ||
-                   ln + cnt - lflushed > LBUF || sp - (gstar + 1) + cnt - lds_lo > LDS_STACK;
+            lm = ballot64(assume && g <= gstar);
+            slow = (ballot64(contender && E.tg < seed) & gm1) != 0 || ln + cnt - lflushed > LBUF ||
+                   sp - (gstar + 1) + cnt - lds_lo > LDS_STACK;
           } else {
-            slow = ballot64(assume) != 0;  // only empty calls, but one of them assumed something: the complete step logs it
+            lm = ballot64(assume);  // (only empty calls: every valid one is at or before the last)
           }
+          slow = slow || logn + __popcll(lm) - lgflushed > LOGB;
           rows_wait(E);  // (before the claims: a wait behind them would put the atomics' round trip on the chain)
           if (__builtin_expect(E.lost_any, 0)) {
             EXIT_COUNT(3);
@@ -1810,8 +1784,6 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
             const unsigned long long gmp = gstar >= 0 ? gmask0 << (gstar * KC) : 0;
             if ((ballot64(contender && E.tg < seed) & gmp) != 0)
               EXIT_COUNT(4);
-            else if (!V3 && ballot64(assume && (gstar < 0 || g <= gstar)) != 0)
-              EXIT_COUNT(5);
             else if (ln + cnt - lflushed > LBUF)
               EXIT_COUNT(6);
             else if (gstar >= 0 && sp - (gstar + 1) + cnt - lds_lo > LDS_STACK)
@@ -1825,12 +1797,10 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
           EXIT_COUNT(9);
           iters++;
           pendv = false;
-          if constexpr (V3) {
-            if (lm != 0) {
-              if (assume && (gstar < 0 || g <= gstar))
-                logbuf[(logn + __popcll(lm & ((1ull << lane) - 1ull))) & (LOGB - 1)] = E.cand_id;
-              logn += __popcll(lm);
-            }
+          if (lm != 0) {
+            if (assume && (gstar < 0 || g <= gstar))
+              logbuf[(logn + __popcll(lm & ((1ull << lane) - 1ull))) & (LOGB - 1)] = E.cand_id;
+            logn += __popcll(lm);
           }
           const bool ok = contender && g == gstar;
           if (ok) {
@@ -1890,10 +1860,8 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
     }
     if (have_mem && status != ST_NOMEM && !flush_list(ln))  // the whole list is in the HBM slab from here on
       status = ST_NOMEM;
-    if constexpr (V3) {
-      if (have_mem && status != ST_NOMEM && !flush_log(logn))  // and so is the log
-        status = ST_NOMEM;
-    }
+    if (have_mem && status != ST_NOMEM && !flush_log(logn))  // and so is the log
+      status = ST_NOMEM;
     if (status == ST_DONE) {
       const bool lost = pendv && ld_i32(vptr) != seed;
       if (ballot64(lost))
@@ -2750,39 +2718,22 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   int64_t incons[3] = {0, 0, 0};
   int forge_mode = ctx->forge_mode;
   ctx->forge_mode = 0;
-  const int lds_pad = getenv("BS_GROW_LDS_PAD") ? atoi(getenv("BS_GROW_LDS_PAD")) : 0;  // experiment: unused dynamic LDS lowers the occupancy
   const bool dbg = getenv("BS_DEBUG") != nullptr;  // (not once per attempt: 158 k of them in a first round)
   const bool do_validate3 = getenv("BS_NO_VALIDATE3") == nullptr;  // developer A/B switch
-  // Step engine.  grow_spec2_kernel (hot loop + complete step) is ~8 % faster per step on a chain of steps served
-  // from L2 / Infinity Cache (facade 1 M: 136.7 vs 147.8 ms of growth kernels) but needs more registers: with k > 16
-  // (255 VGPRs, one wave per SIMD) and in rounds with tens of thousands of attempts, where the throughput of the
-  // many short attempts counts and the long chains wait for HBM anyway (urban 10 M k=32: 128 vs 112 ms, urban 50 M:
-  // 199.5 vs 184.8 ms), the first engine wins.  So: second engine for rounds of few attempts at k <= 16.
-  // The third engine (grow_spec2_kernel<KC, true>: the second with the assumption log in an LDS ring) takes every round
-  // at k <= 16, the crowded first one included: there the second engine left its hot loop for 1.5 M assumption logs
-  // of 4.0 M complete steps (profiles/r04_grow_exits_urban_50m.txt); the third one runs round 1 of the 50 M cloud in
-  // 82-86 ms against the first engine's 94-97 ms and the façade's growth launches in 120.6 against 123.1 ms.
-  // BS_GROW_V2=0 / 1 / 3 forces the first / second / third engine (A/B runs, tests).
-  const int grow_force = getenv("BS_GROW_V2") ? atoi(getenv("BS_GROW_V2")) : -1;
-  const int grow_eng = grow_force >= 0 ? (grow_force == 0 ? 1 : (grow_force == 3 ? 3 : 2)) : (KC == 16 ? 3 : 1);
-  auto launch_grow = [&](int cnt, size_t lds, const unsigned long long* cd, PlaneOut* o, int rml, const uint32_t* ord) {
+  // Step engine.  grow_spec2_kernel<16> (hot loop + complete step, assumption log in an LDS ring) takes every round at
+  // k <= 16, the crowded first one included: round 1 of the 50 M cloud in 82-86 ms against the first engine's 94-97 ms,
+  // the facade's growth launches in 120.6 against 123.1 ms.  At k > 16 it would need 255 VGPRs (one wave per SIMD),
+  // and the first engine, grow_spec_kernel, wins there (urban 10 M k=32: 112 against 128 ms).
+  // BS_GROW_V2=0 puts k <= 16 on the first engine as well (the fallback; same results).
+  const bool use_spec2 = KC == 16 && !(getenv("BS_GROW_V2") && atoi(getenv("BS_GROW_V2")) == 0);
+  auto launch_grow = [&](int cnt, const unsigned long long* cd, PlaneOut* o, int rml, const uint32_t* ord) {
     const int64_t cap = 512 * n + 4096;
-    if (grow_eng == 1) {
-      if (KC == 16)
-        grow_spec_kernel<16><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
-      else
-        grow_spec_kernel<32><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
-    } else if (grow_eng == 2) {
-      if (KC == 16)
-        grow_spec2_kernel<16><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
-      else
-        grow_spec2_kernel<32><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
-    } else {
-      if (KC == 16)
-        grow_spec2_kernel<16, true><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
-      else
-        grow_spec2_kernel<32, true><<<cnt, 64, lds, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
-    }
+    if (use_spec2)
+      grow_spec2_kernel<16><<<cnt, 64, 0, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
+    else if (KC == 16)
+      grow_spec_kernel<16><<<cnt, 64, 0, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
+    else
+      grow_spec_kernel<32><<<cnt, 64, 0, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
   };
   BS_HIP(ctx, hipMemsetAsync(d_misc + 4, 0, 12 * sizeof(int), st));  // [4] refused planes, [5] forged seed + 1, [6] forged one refused, [12..15] refusals by check
   for (;;) {
@@ -2855,7 +2806,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       // is grown again has the time to finish inside the same launch (urban 10 M: +20 %); in a round of a few
       // chained planes (the facade) the re-growth only repeats work the next round does anyway (-23 %).
       const int rml = (ncand >= retry_big_round && !retry_env) ? 0x7fffffff : retry_max_list;
-      launch_grow(ncand, lds_pad, d_cand, d_out, rml, d_order);
+      launch_grow(ncand, d_cand, d_out, rml, d_order);
       (void)hipEventRecord(ctx->ev[7], st);
       grow_launches++;
       timed_round = true;
@@ -2967,12 +2918,13 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
                       "flushchk=%.0f list+defer=%.0f push=%.0f top=%.0f (cycles per step, cumulative over rounds)\n",
               hp[10], hp[11], hp[0] / nstep, hp[1] / nstep, hp[2] / nstep, hp[3] / nstep, hp[4] / nstep, hp[5] / nstep, hp[6] / nstep,
               hp[7] / nstep, hp[8] / nstep, hp[9] / nstep);
-      // exits of the hot loop in this round (every plane; the counters are reset after each print)
+      // exits of the hot loop in this round (every plane; the counters are reset after each print; engine 3 is
+      // grow_spec2_kernel, 1 grow_spec_kernel, as in profiles/r04_grow_exits_urban_50m.txt)
       unsigned long long he[16];
       (void)hipMemcpyFromSymbol(he, HIP_SYMBOL(g_exit2), sizeof(he));
       fprintf(stderr, "[exits] round %ld attempts %d engine %d | hot steps %llu complete steps %llu | lifo-empty %llu watchdog %llu "
-                      "refill %llu stolen %llu earlier-claim %llu assume-log %llu list-ring %llu lifo-window %llu log-ring %llu\n",
-              (long)rounds, ncand, grow_eng, he[9], he[10], he[0], he[1], he[2], he[3], he[4], he[5], he[6], he[7], he[8]);
+                      "refill %llu stolen %llu earlier-claim %llu list-ring %llu lifo-window %llu log-ring %llu\n",
+              (long)rounds, ncand, use_spec2 ? 3 : 1, he[9], he[10], he[0], he[1], he[2], he[3], he[4], he[6], he[7], he[8]);
       memset(he, 0, sizeof(he));
       (void)hipMemcpyToSymbol(HIP_SYMBOL(g_exit2), he, sizeof(he));
     }
@@ -3214,7 +3166,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
     if (na > 0)
       BS_HIP(ctx, hipMemcpyAsync(d_cand, hc_sorted.data(), sizeof(unsigned long long) * na, hipMemcpyHostToDevice, st));
     a.F = INF;
-    auto grow_n = [&](int off, int cnt, PlaneOut* o) { launch_grow(cnt, 0, d_cand + off, o, 0, nullptr); };
+    auto grow_n = [&](int off, int cnt, PlaneOut* o) { launch_grow(cnt, d_cand + off, o, 0, nullptr); };
     auto compare_n = [&](int cnt, int32_t* retry) {
       audit_compare_kernel<<<cnt, VT, 0, st>>>(d_out, cnt, pool.base, prio, d_seeds, ctx->rg_planes.as<PlaneRec>(), np,
                                                ctx->rg_list.as<int32_t>(), a.th_count, d_misc + 8, dead, retry);

@@ -87,6 +87,19 @@ GOLD = sorted(p for p in glob.glob(os.path.join(os.path.dirname(__file__), "gold
 @pytest.mark.parametrize("mode", RG_MODES)
 @pytest.mark.parametrize("path", GOLD, ids=[os.path.basename(p)[:-4] for p in GOLD])
 def test_region_grow_matches_reference_golden(gpu_ctx, path, mode):
+    _check_golden(gpu_ctx, path, mode)
+
+
+@pytest.mark.parametrize("path", GOLD, ids=[os.path.basename(p)[:-4] for p in GOLD])
+def test_first_step_engine_fallback_matches_reference_golden(gpu_ctx, path, monkeypatch):
+    """BS_GROW_V2=0 puts the k <= 16 rounds on the first step engine (grow_spec_kernel<16>), the fallback of the
+    default grow_spec2_kernel<16>: the same bits as the reference (the switch is read on every call)."""
+    assert np.load(path)["neigh"].shape[1] <= 16
+    monkeypatch.setenv("BS_GROW_V2", "0")
+    _check_golden(gpu_ctx, path, 2)
+
+
+def _check_golden(gpu_ctx, path, mode):
     g = np.load(path)
     k = g["neigh"].shape[1]
     pi, planes = gpu_ctx.region_grow(g["xyz"], g["normals"], g["neigh"], api.default_params(k=k, rg_mode=mode))

@@ -57,6 +57,17 @@ print("RESULT", h.hexdigest(), len(planes), tm["n_seed_attempts"], tm["audit_att
 """
 
 
+def _order_child(extra):
+    """Runs ORDER_CHILD with `extra` in the environment; returns its digest and stderr (the audit must agree)."""
+    out = subprocess.run([sys.executable, "-c", ORDER_CHILD, ROOT], capture_output=True, text=True,
+                         env=dict(os.environ, **extra), timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    line = [l for l in out.stdout.splitlines() if l.startswith("RESULT")][0].split()
+    digest, n_planes, attempts, audited, mism = line[1], int(line[2]), int(line[3]), int(line[4]), int(line[5])
+    assert mism == 0 and audited == attempts >= n_planes > 0, line
+    return digest, out.stderr
+
+
 def test_big_round_scheduling_switches_do_not_change_the_result():
     """Rounds with >= 4096 attempts use a dispatch order (tile leaders first) and send only the finished attempts
     to the host.  Both are pure scheduling: with the dispatch order switched off (BS_NO_DISPATCH_ORDER) and with
@@ -64,15 +75,17 @@ def test_big_round_scheduling_switches_do_not_change_the_result():
     and the audit replay agrees each time.  4 M-point urban scene (about 10 k attempts in the first round)."""
     results = []
     for extra in ({}, {"BS_NO_DISPATCH_ORDER": "1"}, {"BS_DEBUG": "1"}):
-        env = dict(os.environ, **extra)
-        out = subprocess.run([sys.executable, "-c", ORDER_CHILD, ROOT], capture_output=True, text=True, env=env, timeout=900)
-        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-        line = [l for l in out.stdout.splitlines() if l.startswith("RESULT")][0].split()
-        digest, n_planes, attempts, audited, mism = line[1], int(line[2]), int(line[3]), int(line[4]), int(line[5])
-        assert mism == 0 and audited == attempts >= n_planes > 0, line
+        digest, err = _order_child(extra)
         if extra.get("BS_DEBUG"):
-            assert "ncand_all=" in out.stderr
-            big = [int(l.split("ncand_all=")[1].split()[0]) for l in out.stderr.splitlines() if "ncand_all=" in l]
+            assert "ncand_all=" in err
+            big = [int(l.split("ncand_all=")[1].split()[0]) for l in err.splitlines() if "ncand_all=" in l]
             assert max(big) >= 4096, "the scene is too small to exercise the big-round paths"
         results.append(digest)
     assert results[0] == results[1] == results[2]
+
+
+def test_first_step_engine_fallback_gives_the_same_bits():
+    """BS_GROW_V2=0 puts every k <= 16 round on the first step engine (grow_spec_kernel<16>), the fallback of the
+    default grow_spec2_kernel<16>; the audit replay follows the switch.  On the scene above (a first round of about
+    10 k attempts) the labels, lists, normals and centres are the same bits with either engine."""
+    assert _order_child({})[0] == _order_child({"BS_GROW_V2": "0"})[0]

@@ -1,4 +1,4 @@
-"""The third step engine (grow_spec2_kernel<KC, true>) issues its gather from inline assembly: the loads write their
+"""The hot-loop step engine (grow_spec2_kernel<16>) issues its gather from inline assembly: the loads write their
 destination registers after the asm statement, so until an s_waitcnt covers them no instruction may read or write
 those registers, on any path.  tools/check_gather_wait.py walks the generated gfx950 ISA from the first load of every
 asm block; here on the default flags and on the -DBS_PROBE build (different register allocation).  No GPU needed."""
@@ -24,16 +24,20 @@ def _mod():
 def test_no_instruction_touches_an_asm_load_before_its_wait(flags):
     mod = _mod()
     walked, bad = mod.check(mod.device_asm(list(flags)))
-    assert walked >= 8  # the gather of the hot loop and of the complete step, rows and flags, for k <= 16 and k <= 32
+    assert walked >= 8  # the gather of the hot loop and of the complete step, records and flags, one block per row chunk
     assert not bad, "\n".join(bad)
 
 
-def test_the_check_sees_a_read_of_a_register_in_flight(tmp_path):
+def _check_by_hand(mod, tmp_path, body):
+    p = tmp_path / "k.s"
+    p.write_text("\n".join([mod.KERNELS[0] + "EvNS0_8SpecArgsE:", *body, ".Lfunc_end0:"]))
+    return mod.check(str(p))
+
+
+def test_the_check_sees_a_read_in_flight_on_one_path(tmp_path):
     """A hand-made kernel: the first read of the loaded register comes before the wait (caught), the second after it."""
     mod = _mod()
-    name = mod.KERNELS[0] + "EvNS0_8SpecArgsE"
-    asm = "\n".join([
-        name + ":",
+    walked, bad = _check_by_hand(mod, tmp_path, [
         "\t;;#ASMSTART",
         "\tglobal_load_dwordx4 v[4:7], v[0:1], off",
         "\tglobal_load_dword v8, v[2:3], off sc1",
@@ -46,13 +50,26 @@ def test_the_check_sees_a_read_of_a_register_in_flight(tmp_path):
         "\ts_waitcnt vmcnt(0)",
         "\tv_mov_b32_e32 v11, v8",
         "\ts_endpgm",
-        ".Lfunc_end0:",
-        mod.KERNELS[1] + "EvNS0_8SpecArgsE:",
-        "\ts_endpgm",
-        ".Lfunc_end1:",
     ])
-    p = tmp_path / "k.s"
-    p.write_text(asm)
-    walked, bad = mod.check(str(p))
     assert walked == 1
     assert len(bad) == 1 and "v9, v8, v9" in bad[0], bad
+
+
+def test_the_check_sees_a_row_register_touched_between_the_two_waits(tmp_path):
+    """The two-part wait of the gather, by hand: vmcnt(N > 0) lets the record load land while the row load issued after
+    it is still writing its registers -- a touch of those before the vmcnt(0) is caught, the one after it is not."""
+    mod = _mod()
+    walked, bad = _check_by_hand(mod, tmp_path, [
+        "\t;;#ASMSTART",
+        "\tglobal_load_dwordx4 v[4:7], v[0:1], off",
+        "\tglobal_load_dwordx4 v[12:15], v[2:3], off",
+        "\t;;#ASMEND",
+        "\ts_waitcnt vmcnt(1)",
+        "\tv_mov_b32_e32 v10, v5",
+        "\tv_mov_b32_e32 v11, v13",
+        "\ts_waitcnt vmcnt(0)",
+        "\tv_mov_b32_e32 v16, v14",
+        "\ts_endpgm",
+    ])
+    assert walked == 1
+    assert len(bad) == 1 and "v11, v13" in bad[0], bad
