@@ -25,7 +25,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_cc_hook_dev", "bs_owner_fetch_dev", "bs_labels_from_owner_dev", "bs_remap_rows_dev",
            "bs_plane_seeds_dev", "bs_stream_sync", "bs_comm_rccl", "bs_comm_rccl_unique_id", "bs_comm_rccl_init",
            "bs_comm_rccl_destroy", "bs_comm_local_create", "bs_comm_local_destroy", "bs_segment_sharded",
-           "bs_sharded_planes_fetch"]
+           "bs_sharded_planes_fetch", "bs_footprints_dev", "bs_footprints", "bs_contours_free",
+           "bs_contours_write_obj"]
 
 
 class Params(C.Structure):
@@ -66,6 +67,19 @@ class ShardInfo(C.Structure):
                 ("halo_mm", C.c_double), ("ms_partition", C.c_double), ("ms_halo", C.c_double), ("ms_knn", C.c_double),
                 ("ms_components", C.c_double), ("ms_redistribute", C.c_double), ("ms_grow", C.c_double),
                 ("ms_labels", C.c_double)]
+
+
+class Contours(C.Structure):
+    """bs_contours (include/bs_api.h): CSR point lists of the footprint contours, host memory owned by the library."""
+    _fields_ = [("n_contours", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("offset", C.POINTER(C.c_int64)), ("xy", C.POINTER(C.c_int32)), ("area", C.POINTER(C.c_double)),
+                ("perimeter", C.POINTER(C.c_double))]
+
+
+class FootprintInfo(C.Structure):
+    _fields_ = [("ms_mask", C.c_double), ("ms_close", C.c_double), ("ms_label", C.c_double), ("ms_trace", C.c_double),
+                ("ms_total", C.c_double), ("fg_pixels", C.c_int64), ("border_states", C.c_int64),
+                ("components", C.c_int64), ("jump_rounds", C.c_int64)]
 
 
 class BsError(RuntimeError):
@@ -141,5 +155,13 @@ def load():
     L.bs_segment_sharded.argtypes = [vp, C.POINTER(CommOps), ip, ip, C.c_int64, C.c_int64, pp, C.c_double, ip,
                                      C.POINTER(ShardInfo)]
     L.bs_sharded_planes_fetch.argtypes = [vp, C.POINTER(Planes)]
+    cp = C.POINTER(Contours)
+    L.bs_footprints_dev.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, cp,
+                                    C.POINTER(FootprintInfo)]
+    L.bs_footprints.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, cp,
+                                C.POINTER(FootprintInfo)]
+    L.bs_contours_free.argtypes = [cp]
+    L.bs_contours_free.restype = None
+    L.bs_contours_write_obj.argtypes = [cp, C.c_char_p]
     _LIB = L
     return L

@@ -17,7 +17,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import BsError, Params, Planes, Timings
+from ._lib import BsError, Contours, FootprintInfo, Params, Planes, Timings
 
 
 def default_params(**kw) -> Params:
@@ -207,6 +207,30 @@ class Context:
         self._check(self._L.bs_grid_picture_dev(self._h, d_xyz, n, ext.ctypes.data, bin, bin_height, d_image, C.byref(th)))
         return th.value
 
+    def footprints(self, image, threshold=10, kernel_size=5, iterations=2, return_mask=False):
+        """extracted_contour (my_function.cpp:8-57) on a [height][width][3] f64 raster of grid_picture: quantise
+        channel 1 like save_image, threshold, close with the ellipse, findContours(RETR_EXTERNAL,
+        CHAIN_APPROX_SIMPLE).  Returns a Footprints (contours: list of (n_i, 2) int32 [x, y] arrays, area,
+        perimeter, info) and, with return_mask, the closed [height][width] uint8 mask (0 / 255) as well."""
+        img = np.ascontiguousarray(image, dtype=np.float64)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("footprints: image must be [height][width][3]")
+        h, w, _ = img.shape
+        mask = np.empty((h, w), dtype=np.uint8) if return_mask else None
+        out, inf = Contours(), FootprintInfo()
+        self._check(self._L.bs_footprints(self._h, img.ctypes.data, w, h, threshold, kernel_size, iterations,
+                                          mask.ctypes.data if return_mask else None, C.byref(out), C.byref(inf)))
+        fp = _take_contours(self._L, out, inf)
+        return (fp, mask) if return_mask else fp
+
+    def footprints_dev(self, d_image, width, height, threshold=10, kernel_size=5, iterations=2, d_mask=0):
+        """Device-resident variant: d_image ([height][width][3] f64) and d_mask ([height][width] uint8, optional)
+        are device pointers (ints); the contours come back in host memory."""
+        out, inf = Contours(), FootprintInfo()
+        self._check(self._L.bs_footprints_dev(self._h, d_image or None, width, height, threshold, kernel_size,
+                                              iterations, d_mask or None, C.byref(out), C.byref(inf)))
+        return _take_contours(self._L, out, inf)
+
     def selftest_center_div(self, c, n):
         """Device evaluation of (int32)((uint64)(int64)c / n) through csrc/bs_centerdiv.h."""
         c = np.ascontiguousarray(c, dtype=np.int32)
@@ -279,6 +303,52 @@ class Context:
         planes = _planes_to_list(P)
         self._L.bs_planes_free(C.byref(P))
         return planes
+
+
+@dataclass
+class Footprints:
+    """Contours of bs_footprints in findContours' order, their contourArea / arcLength, and the stage info."""
+    contours: list
+    area: np.ndarray
+    perimeter: np.ndarray
+    width: int
+    height: int
+    info: dict = field(default_factory=dict)
+
+    def kept(self, min_area=500.0, min_perimeter=100.0):
+        """Indices the reference keeps for its drawn overlay (my_function.cpp:40)."""
+        return [i for i in range(len(self.contours)) if self.area[i] > min_area and self.perimeter[i] > min_perimeter]
+
+
+def _take_contours(L, out: Contours, inf: FootprintInfo) -> Footprints:
+    n = out.n_contours
+    try:
+        off = np.ctypeslib.as_array(out.offset, (n + 1,)).copy() if out.offset else np.zeros(1, np.int64)
+        tot = int(off[-1])
+        xy = np.ctypeslib.as_array(out.xy, (2 * tot,)).reshape(tot, 2).copy() if tot else np.zeros((0, 2), np.int32)
+        area = np.ctypeslib.as_array(out.area, (n,)).copy() if n else np.zeros(0)
+        per = np.ctypeslib.as_array(out.perimeter, (n,)).copy() if n else np.zeros(0)
+        w, h = out.width, out.height
+    finally:
+        L.bs_contours_free(C.byref(out))
+    return Footprints([xy[off[i]:off[i + 1]] for i in range(n)], area, per, w, h,
+                      {k: getattr(inf, k) for k, _ in FootprintInfo._fields_})
+
+
+def write_footprints_obj(fp: Footprints, path):
+    """The reference's OBJ (my_function.cpp:64-131) through the library's writer (bs_contours_write_obj), so that
+    Python and host/tmc3 --footprints= write the same bytes."""
+    n = len(fp.contours)
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(c) for c in fp.contours]) if n else []
+    xy = np.ascontiguousarray(np.concatenate(fp.contours) if n else np.zeros((0, 2)), dtype=np.int32)
+    c = Contours()
+    c.n_contours, c.width, c.height = n, fp.width, fp.height
+    c.offset = off.ctypes.data_as(C.POINTER(C.c_int64))
+    c.xy = xy.ctypes.data_as(C.POINTER(C.c_int32))
+    rc = _lib.load().bs_contours_write_obj(C.byref(c), str(path).encode())
+    if rc != 0:
+        raise BsError(rc, f"cannot write {path}")
 
 
 def grid_dims(extent, bin=100):

@@ -190,6 +190,8 @@ void bs_destroy(bs_ctx* c)
     b->release();
   for (auto& b : c->sh)
     b.release();
+  for (auto& b : c->fp)
+    b.release();
   c->rg_hout.release();
   for (auto& e : c->ev)
     if (e)

@@ -1,0 +1,756 @@
+// bs_contour.hip -- building footprints: the reference's extracted_contour (/root/reference/tmc3/my_function.cpp:8-145)
+// on the density raster of bs_grid_picture, without OpenCV and without leaving the device until the point lists are
+// complete.  Stages ("Building footprints"):
+//   1. mask   f64 max of channel 1 (integer atomicMax on the bits of non-negative doubles), then one pass that
+//             quantises like save_image, thresholds, and writes a (W+2) x (H+2) byte mask with a zero frame
+//             (findContours' one-pixel padding)
+//   2. close  `iterations` dilations then as many erosions, one LDS-tiled pass each; the ellipse is a union of
+//             centred horizontal runs, so a pass is an OR / AND over the rows dy of a run of half-width dx(dy)
+//   3. label  union-find over the padded grid (bs_uf.h, parent <= self): foreground 8-connected, background
+//             4-connected; a root is its component's first raster pixel, i.e. findContours' start pixel i0.  A
+//             component is external iff the background pixel above i0 has the frame's root (0).
+//   4. trace  every (pixel, back-direction) state of the border pixels of external components gets its successor
+//             under OpenCV's follower; the state that leads into a start state (i0, s_init) is a list tail, so each
+//             outer border becomes a list, ranked by Wyllie pointer jumping with weights = "emits a point"
+//             (CHAIN_APPROX_SIMPLE: s != b ^ 4).  Hole borders stay cycles and are never read.
+//   5. output contours in descending i0, emitted points scattered by rank, area / perimeter in exact arithmetic.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+#include "bs_common.h"
+#include "bs_uf.h"
+
+namespace bs {
+namespace {
+
+constexpr int32_t END = -1;
+constexpr int TW = 64, TH = 16, RMAX = 7;  // closing tile (outputs) and the largest ellipse radius (15 x 15)
+enum : uint8_t { K_INVALID = 0, K_NORMAL = 1, K_TAIL = 2, K_DEAD = 3, K_EMIT = 4 };
+
+struct Ellipse {
+  int r;
+  int dx[2 * RMAX + 1];  // half-width of the centred run of row dy = i - r
+};
+
+// OpenCV's chain codes in (x, y), y down: 0 E, 1 NE, 2 N, 3 NW, 4 W, 5 SW, 6 S, 7 SE
+__device__ inline int delta(int s, int wp)
+{
+  const int dx = (s == 0 || s == 1 || s == 7) ? 1 : (s >= 3 && s <= 5) ? -1 : 0;
+  const int dy = (s >= 1 && s <= 3) ? -1 : (s >= 5) ? 1 : 0;
+  return dy * wp + dx;
+}
+
+// findContours' first search around an outer start pixel: s = 3, 2, 1, 0, 7, 6, 5 (clockwise from W); -1: none
+__device__ inline int first_search(const uint8_t* m, int p, int wp)
+{
+  for (int s = 3; s != 4; s = (s - 1) & 7)
+    if (m[p + delta(s, wp)])
+      return s;
+  return -1;
+}
+
+__global__ __launch_bounds__(256) void max_kernel(const double* __restrict__ img, int64_t npix,
+                                                  unsigned long long* __restrict__ mx)
+{
+  double m = 0;  // the reference's loop starts at 0; NaN never wins a comparison
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
+    const double v = img[3 * i + 1];
+    if (v > m)
+      m = v;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const double t = __shfl_xor(m, o);
+    if (t > m)
+      m = t;
+  }
+  __shared__ double w[4];
+  if ((threadIdx.x & 63) == 0)
+    w[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < 4; k++)
+      if (w[k] > m)
+        m = w[k];
+    if (m > 0)  // non-negative doubles order like their bit patterns
+      atomicMax(mx, (unsigned long long)__double_as_longlong(m));
+  }
+}
+
+__global__ __launch_bounds__(256) void mask_kernel(const double* __restrict__ img, int w, int h, int thr,
+                                                   const unsigned long long* __restrict__ mx, uint8_t* __restrict__ m)
+{
+  const int64_t wp = w + 2, np = wp * (h + 2);
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= np)
+    return;
+  const int64_t y = i / wp, x = i - y * wp;
+  uint8_t v = 0;
+  if (x >= 1 && x <= w && y >= 1 && y <= h) {
+    const double max1 = __longlong_as_double((long long)*mx);
+    if (max1 != 0) {  // save_image, TMC3.cpp:100-108: (uint8)(255.0 * (1.0 * v / max1))
+      const double t = 255.0 * (1.0 * img[3 * ((y - 1) * w + (x - 1)) + 1] / max1);
+      const int q = t > 0 ? (int)t : 0;
+      v = q > thr;  // threshold(..., 10, 255, THRESH_BINARY), my_function.cpp:20
+    }
+  }
+  m[i] = v;
+}
+
+// one dilation (OR) or erosion (AND) of the interior; outside the image counts as 0 (dilate) / 1 (erode)
+template <bool DILATE>
+__global__ __launch_bounds__(256) void morph_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int w,
+                                                    int h, Ellipse e)
+{
+  __shared__ uint8_t t[(TH + 2 * RMAX) * (TW + 2 * RMAX)];
+  const int r = e.r, lw = TW + 2 * r, lh = TH + 2 * r;
+  const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+  const int64_t wp = w + 2;
+  for (int k = threadIdx.x; k < lw * lh; k += blockDim.x) {
+    const int ly = k / lw, lx = k - ly * lw;
+    const int gx = x0 + lx - r, gy = y0 + ly - r;
+    uint8_t v = DILATE ? 0 : 1;
+    if (gx >= 0 && gx < w && gy >= 0 && gy < h)
+      v = src[(gy + 1) * wp + gx + 1];
+    t[k] = v;
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & 63, ty0 = (threadIdx.x >> 6) * 4;
+  const int gx = x0 + tx;
+  if (gx >= w)
+    return;
+  for (int j = 0; j < 4; j++) {
+    const int ty = ty0 + j, gy = y0 + ty;
+    if (gy >= h)
+      break;
+    uint8_t acc = DILATE ? 0 : 1;
+    for (int dy = -r; dy <= r; dy++) {
+      const int d = e.dx[dy + r];
+      const uint8_t* row = t + (ty + r + dy) * lw + tx + r;
+      for (int dx = -d; dx <= d; dx++) {
+        if (DILATE)
+          acc |= row[dx];
+        else
+          acc &= row[dx];
+      }
+    }
+    dst[(gy + 1) * wp + gx + 1] = acc;
+  }
+}
+
+__global__ __launch_bounds__(256) void cc_init_kernel(int32_t* __restrict__ parent, int64_t np)
+{
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < np)
+    parent[i] = (int32_t)i;
+}
+
+// foreground joins its W, N, NW, NE neighbours (8-connectivity), background its W and N ones (4-connectivity)
+__global__ __launch_bounds__(256) void cc_union_kernel(const uint8_t* __restrict__ m, int wp, int64_t np,
+                                                       int32_t* parent)
+{
+  const int64_t i64 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i64 >= np)
+    return;
+  const int32_t i = (int32_t)i64;
+  const int32_t y = i / wp, x = i - y * wp;
+  const uint8_t v = m[i];
+  const bool w_same = x > 0 && m[i - 1] == v;
+  if (w_same)
+    uf_union(parent, i, i - 1);
+  if (y > 0) {
+    // N is already joined to W through NW when all three share the class
+    if (m[i - wp] == v && !(w_same && m[i - wp - 1] == v))
+      uf_union(parent, i, i - wp);
+    if (v) {
+      if (x > 0 && m[i - wp - 1] && !m[i - wp] && !w_same)
+        uf_union(parent, i, i - wp - 1);
+      if (x < wp - 1 && m[i - wp + 1] && !m[i - wp])
+        uf_union(parent, i, i - wp + 1);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void cc_flatten_kernel(int32_t* parent, int64_t np)
+{
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= np)
+    return;
+  int32_t r = (int32_t)i, p = parent[r];
+  while (p != r) {
+    r = p;
+    p = parent[r];
+  }
+  parent[i] = r;  // (racing writers store the same root; a stale read is still an ancestor)
+}
+
+// bflag: foreground pixel of an external component with a background 8-neighbour (a tracer state owner);
+// rflag: start pixel i0 of an external component
+__global__ __launch_bounds__(256) void flags_kernel(const uint8_t* __restrict__ m, const int32_t* __restrict__ parent,
+                                                    int wp, int64_t np, int32_t* __restrict__ bflag,
+                                                    int32_t* __restrict__ rflag, unsigned long long* __restrict__ n_fg)
+{
+  const int64_t i64 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int32_t i = (int32_t)i64;
+  const bool fg = i64 < np && m[i];
+  int32_t b = 0, r = 0;
+  if (fg) {  // foreground never lies on the frame: all 8 neighbours exist
+    const int32_t root = parent[i];
+    if (parent[root - wp] == 0) {
+      r = root == i;
+      for (int s = 0; s < 8; s++)
+        b |= !m[i + delta(s, wp)];
+    }
+  }
+  const unsigned long long bal = __ballot(fg);
+  if ((threadIdx.x & 63) == 0 && bal)
+    atomicAdd(n_fg, (unsigned long long)__popcll(bal));
+  if (i64 >= np)
+    return;
+  bflag[i] = b;
+  rflag[i] = r;
+}
+
+__global__ __launch_bounds__(256) void lists_kernel(const int32_t* __restrict__ bflag, const int32_t* __restrict__ bscan,
+                                                    const int32_t* __restrict__ rflag, const int32_t* __restrict__ rscan,
+                                                    int64_t np, int32_t* __restrict__ bpix, int32_t* __restrict__ rpix)
+{
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= np)
+    return;
+  if (bflag[i])
+    bpix[bscan[i]] = (int32_t)i;
+  if (rflag[i])
+    rpix[rscan[i]] = (int32_t)i;
+}
+
+// state st = 8 * (border pixel id) + b, b = code pointing back at the previous contour pixel
+__global__ __launch_bounds__(256) void state_kernel(const uint8_t* __restrict__ m, int wp, const int32_t* __restrict__ bpix,
+                                                    const int32_t* __restrict__ bflag, const int32_t* __restrict__ bscan,
+                                                    const int32_t* __restrict__ rflag, int64_t ns,
+                                                    int32_t* __restrict__ succ, uint8_t* __restrict__ kind,
+                                                    int32_t* __restrict__ nxt, uint32_t* __restrict__ val,
+                                                    int32_t* __restrict__ last)
+{
+  const int64_t st64 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (st64 >= ns)
+    return;
+  const int32_t st = (int32_t)st64;
+  const int b = st & 7;
+  const int32_t p = bpix[st >> 3];
+  int32_t sc = END, nx = END;
+  uint32_t w = 0;
+  uint8_t k = K_INVALID;
+  if (m[p + delta(b, wp)]) {
+    int s = b;
+    do {  // the follower: counter-clockwise from b + 1; stops at b at the latest
+      s = (s + 1) & 7;
+    } while (!m[p + delta(s, wp)]);
+    w = s != (b ^ 4);  // CHAIN_APPROX_SIMPLE keeps the pixel iff the direction changes
+    const int32_t q = p + delta(s, wp);
+    const int b2 = (s + 4) & 7;
+    if (!bflag[q]) {
+      k = K_DEAD;
+    } else {
+      sc = bscan[q] * 8 + b2;
+      if (rflag[q] && first_search(m, q, wp) == b2) {
+        k = K_TAIL;  // leads into a start state: cut the cycle here
+      } else {
+        k = K_NORMAL;
+        nx = sc;
+      }
+    }
+  }
+  succ[st] = sc;
+  kind[st] = k | (w ? K_EMIT : 0);
+  nxt[st] = nx;
+  val[st] = w;
+  last[st] = st;
+}
+
+// one Wyllie round: segment [st, nxt) absorbs [nxt, nxt[nxt]); val = emitted states in the segment, last = its last
+__global__ __launch_bounds__(256) void jump_kernel(const int32_t* __restrict__ nxt, const uint32_t* __restrict__ val,
+                                                   const int32_t* __restrict__ last, int64_t ns,
+                                                   int32_t* __restrict__ nxt2, uint32_t* __restrict__ val2,
+                                                   int32_t* __restrict__ last2)
+{
+  const int64_t st = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (st >= ns)
+    return;
+  const int32_t j = nxt[st];
+  if (j == END) {
+    nxt2[st] = END;
+    val2[st] = val[st];
+    last2[st] = last[st];
+  } else {
+    nxt2[st] = nxt[j];
+    val2[st] = val[st] + val[j];  // (cycles wrap; their values are never read)
+    last2[st] = last[j];
+  }
+}
+
+// contour c = C-1-r of the r-th start pixel (ascending raster order): its emitted count and start state
+__global__ __launch_bounds__(256) void contour_count_kernel(const uint8_t* __restrict__ m, int wp,
+                                                            const int32_t* __restrict__ rpix, int32_t nc,
+                                                            const int32_t* __restrict__ bscan,
+                                                            const int32_t* __restrict__ succ,
+                                                            const uint8_t* __restrict__ kind,
+                                                            const int32_t* __restrict__ nxt,
+                                                            const uint32_t* __restrict__ val,
+                                                            const int32_t* __restrict__ last, int64_t* __restrict__ cnt,
+                                                            int32_t* __restrict__ cstart, int* __restrict__ err)
+{
+  const int32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nc)
+    return;
+  const int32_t c = nc - 1 - r, i = rpix[r];
+  const int s0 = first_search(m, i, wp);
+  if (s0 < 0) {  // a single pixel: [i0]
+    cnt[c] = 1;
+    cstart[c] = -1;
+    return;
+  }
+  const int32_t st = bscan[i] * 8 + s0;
+  const int32_t t = last[st];
+  if (nxt[st] != END || (kind[t] & 3) != K_TAIL || succ[t] != st) {
+    atomicOr(err, 1);  // the list did not close within the round bound
+    cnt[c] = 0;
+    cstart[c] = -2;
+    return;
+  }
+  cnt[c] = val[st];
+  cstart[c] = st;
+}
+
+__global__ __launch_bounds__(256) void scatter_kernel(const int32_t* __restrict__ bpix, const int32_t* __restrict__ rscan,
+                                                      const int32_t* __restrict__ succ, const uint8_t* __restrict__ kind,
+                                                      const int32_t* __restrict__ nxt, const uint32_t* __restrict__ val,
+                                                      const int32_t* __restrict__ last, int64_t ns, int wp, int32_t nc,
+                                                      const int64_t* __restrict__ off, int32_t* __restrict__ xy,
+                                                      int32_t* __restrict__ cid, int* __restrict__ err)
+{
+  const int64_t st = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (st >= ns)
+    return;
+  const uint8_t k = kind[st];
+  if (!(k & K_EMIT) || (k & 3) == K_DEAD || nxt[st] != END)
+    return;
+  const int32_t t = last[st];
+  if ((kind[t] & 3) != K_TAIL)
+    return;  // a dead chain
+  const int32_t start = succ[t];
+  const int32_t c = nc - 1 - rscan[bpix[start >> 3]];
+  const int64_t pos = off[c] + (int64_t)(val[start] - val[st]);
+  if (pos < off[c] || pos >= off[c + 1]) {
+    atomicOr(err, 2);
+    return;
+  }
+  const int32_t p = bpix[st >> 3];
+  const int32_t y = p / wp, x = p - y * wp;
+  xy[2 * pos] = x - 1;
+  xy[2 * pos + 1] = y - 1;
+  cid[pos] = c;
+}
+
+__global__ __launch_bounds__(256) void single_kernel(const int32_t* __restrict__ rpix, const int32_t* __restrict__ cstart,
+                                                     int32_t nc, int wp, const int64_t* __restrict__ off,
+                                                     int32_t* __restrict__ xy, int32_t* __restrict__ cid)
+{
+  const int32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc || cstart[c] != -1)
+    return;
+  const int32_t p = rpix[nc - 1 - c];
+  const int32_t y = p / wp, x = p - y * wp;
+  xy[2 * off[c]] = x - 1;
+  xy[2 * off[c] + 1] = y - 1;
+  cid[off[c]] = c;
+}
+
+// per point: the shoelace term (exact in int64) and the float segment length from the previous point as an integer
+// multiple of 2^-23 (every non-zero length is >= 1, hence such a multiple); wave-aggregated atomics per contour
+__global__ __launch_bounds__(256) void measure_kernel(const int32_t* __restrict__ xy, const int32_t* __restrict__ cid,
+                                                      const int64_t* __restrict__ off, int64_t total, int32_t nc,
+                                                      unsigned long long* __restrict__ asum,
+                                                      unsigned long long* __restrict__ psum)
+{
+  const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int32_t c = -1;
+  unsigned long long a = 0, l = 0;
+  if (k < total)
+    c = cid[k];
+  if (c >= nc)
+    c = -1;  // (every position is written exactly once; this only keeps a broken invariant in bounds)
+  if (c >= 0) {
+    const int64_t pk = k == off[c] ? off[c + 1] - 1 : k - 1;
+    const int32_t x = xy[2 * k], y = xy[2 * k + 1], px = xy[2 * pk], py = xy[2 * pk + 1];
+    a = (unsigned long long)((int64_t)px * y - (int64_t)py * x);
+    const float dx = (float)x - (float)px, dy = (float)y - (float)py;
+    const float len = sqrtf(dx * dx + dy * dy);
+    l = (unsigned long long)((double)len * 8388608.0);
+  }
+  const int32_t c0 = __shfl(c, 0);
+  if (__all(c == c0) && c0 >= 0) {
+    for (int o = 32; o > 0; o >>= 1) {
+      a += __shfl_xor(a, o);
+      l += __shfl_xor(l, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      atomicAdd(asum + c0, a);
+      atomicAdd(psum + c0, l);
+    }
+  } else if (c >= 0) {
+    atomicAdd(asum + c, a);
+    atomicAdd(psum + c, l);
+  }
+}
+
+// contourArea = |sum| * 0.5; arcLength: the reference sums float lengths into a double in point order, which is
+// exact (and so equal to the integer sum) while the total stays below 2^30; otherwise sum sequentially here
+__global__ __launch_bounds__(256) void finish_kernel(const int32_t* __restrict__ xy, const int64_t* __restrict__ off,
+                                                     int32_t nc, const unsigned long long* __restrict__ asum,
+                                                     const unsigned long long* __restrict__ psum,
+                                                     double* __restrict__ area, double* __restrict__ perim)
+{
+  const int32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc)
+    return;
+  const int64_t s = (int64_t)asum[c];
+  area[c] = fabs((double)s * 0.5);
+  if (psum[c] < (1ull << 53)) {
+    perim[c] = (double)psum[c] / 8388608.0;
+    return;
+  }
+  const int64_t a = off[c], e = off[c + 1];
+  double per = 0;
+  float px = (float)xy[2 * (e - 1)], py = (float)xy[2 * (e - 1) + 1];
+  for (int64_t k = a; k < e; k++) {
+    const float x = (float)xy[2 * k], y = (float)xy[2 * k + 1];
+    const float dx = x - px, dy = y - py;
+    per += sqrtf(dx * dx + dy * dy);
+    px = x;
+    py = y;
+  }
+  perim[c] = per;
+}
+
+__global__ __launch_bounds__(256) void mask_out_kernel(const uint8_t* __restrict__ m, int w, int h,
+                                                       uint8_t* __restrict__ out)
+{
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= (int64_t)w * h)
+    return;
+  const int64_t y = i / w, x = i - y * w;
+  out[i] = m[(y + 1) * (w + 2) + x + 1] ? 255 : 0;
+}
+
+inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
+
+// getStructuringElement(MORPH_ELLIPSE, Size(s, s)): row i has the run c - dx .. c + dx,
+// dx = cvRound(c * sqrt((r*r - dy*dy) / (r*r))), dy = i - r, r = c = s / 2
+Ellipse make_ellipse(int s)
+{
+  Ellipse e{};
+  e.r = s / 2;
+  const int r = e.r, c = s / 2;
+  const double inv_r2 = r ? 1.0 / ((double)r * r) : 0;
+  for (int i = 0; i < s; i++) {
+    const int dy = i - r;
+    const int dx = (int)std::nearbyint(c * std::sqrt((r * r - dy * dy) * inv_r2));  // round half to even
+    e.dx[i] = std::min(dx, c);
+  }
+  return e;
+}
+
+struct Events {
+  hipEvent_t e[6] = {};
+  ~Events()
+  {
+    for (auto& x : e)
+      if (x)
+        (void)hipEventDestroy(x);
+  }
+  float ms(int i, int j)
+  {
+    float t = 0;
+    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.f;
+  }
+};
+
+}  // namespace
+}  // namespace bs
+
+using namespace bs;
+
+extern "C" void bs_contours_free(bs_contours* c)
+{
+  if (!c)
+    return;
+  free(c->offset);
+  free(c->xy);
+  free(c->area);
+  free(c->perimeter);
+  memset(c, 0, sizeof *c);
+}
+
+extern "C" int bs_footprints_dev(bs_ctx* ctx, const double* d_image, int32_t width, int32_t height, int32_t threshold,
+                                 int32_t kernel_size, int32_t iterations, uint8_t* d_mask, bs_contours* out,
+                                 bs_footprint_info* info)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (!d_image || !out || width < 1 || height < 1 || (int64_t)(width + 2ll) * (height + 2ll) >= (1ll << 31) ||
+      kernel_size < 1 || kernel_size > 2 * RMAX + 1 || kernel_size % 2 == 0 || iterations < 0 || iterations > 16 ||
+      threshold < 0 || threshold > 255)
+    return fail(ctx, BS_ERR_INVALID, "footprints: null pointer or bad raster / threshold / kernel / iterations");
+  memset(out, 0, sizeof *out);
+  BS_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int w = width, h = height, wp = w + 2;
+  const int64_t np = (int64_t)wp * (h + 2), npix = (int64_t)w * h;
+  DevBuf* B = ctx->fp;
+  Events ev;
+  for (auto& e : ev.e)
+    BS_HIP(ctx, hipEventCreate(&e));
+
+  // misc: max bits | error flags | foreground count
+  BS_HIP(ctx, B[0].reserve(np));
+  BS_HIP(ctx, B[1].reserve(np));
+  BS_HIP(ctx, B[2].reserve(4 * np));
+  BS_HIP(ctx, B[3].reserve(4 * np));
+  BS_HIP(ctx, B[4].reserve(4 * np));
+  BS_HIP(ctx, B[5].reserve(4 * np));
+  BS_HIP(ctx, B[6].reserve(4 * np));
+  BS_HIP(ctx, B[7].reserve(64));
+  uint8_t* mA = B[0].as<uint8_t>();
+  uint8_t* mB = B[1].as<uint8_t>();
+  int32_t* parent = B[2].as<int32_t>();
+  int32_t* bflag = B[3].as<int32_t>();
+  int32_t* bscan = B[4].as<int32_t>();
+  int32_t* rflag = B[5].as<int32_t>();
+  int32_t* rscan = B[6].as<int32_t>();
+  unsigned long long* d_max = B[7].as<unsigned long long>();
+  int* d_err = reinterpret_cast<int*>(d_max + 1);
+
+  BS_HIP(ctx, hipEventRecord(ev.e[0], st));
+  BS_HIP(ctx, hipMemsetAsync(B[7].p, 0, 64, st));
+  max_kernel<<<(int)std::min<int64_t>(nblk(npix, 256), 2048), 256, 0, st>>>(d_image, npix, d_max);
+  mask_kernel<<<nblk(np, 256), 256, 0, st>>>(d_image, w, h, threshold, d_max, mA);
+  BS_HIP(ctx, hipEventRecord(ev.e[1], st));
+
+  uint8_t* m = mA;
+  if (iterations > 0) {
+    const Ellipse e = make_ellipse(kernel_size);
+    BS_HIP(ctx, hipMemsetAsync(mB, 0, np, st));  // the frame of the second buffer
+    const dim3 grid(nblk(w, TW), nblk(h, TH));
+    uint8_t* src = mA;
+    uint8_t* dst = mB;
+    for (int it = 0; it < 2 * iterations; it++) {
+      if (it < iterations)
+        morph_kernel<true><<<grid, 256, 0, st>>>(src, dst, w, h, e);
+      else
+        morph_kernel<false><<<grid, 256, 0, st>>>(src, dst, w, h, e);
+      std::swap(src, dst);
+    }
+    m = src;
+  }
+  BS_HIP(ctx, hipEventRecord(ev.e[2], st));
+
+  cc_init_kernel<<<nblk(np, 256), 256, 0, st>>>(parent, np);
+  cc_union_kernel<<<nblk(np, 256), 256, 0, st>>>(m, wp, np, parent);
+  cc_flatten_kernel<<<nblk(np, 256), 256, 0, st>>>(parent, np);
+  flags_kernel<<<nblk(np, 256), 256, 0, st>>>(m, parent, wp, np, bflag, rflag, d_max + 2);
+  size_t tmp = 0;
+  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, bflag, bscan, (int)np, st));
+  BS_HIP(ctx, B[8].reserve(tmp));
+  size_t tb = B[8].cap;
+  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[8].p, tb, bflag, bscan, (int)np, st));
+  tb = B[8].cap;
+  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[8].p, tb, rflag, rscan, (int)np, st));
+  int32_t h_tail[4] = {0, 0, 0, 0};
+  BS_HIP(ctx, hipMemcpyAsync(h_tail + 0, bscan + np - 1, 4, hipMemcpyDeviceToHost, st));
+  BS_HIP(ctx, hipMemcpyAsync(h_tail + 1, bflag + np - 1, 4, hipMemcpyDeviceToHost, st));
+  BS_HIP(ctx, hipMemcpyAsync(h_tail + 2, rscan + np - 1, 4, hipMemcpyDeviceToHost, st));
+  BS_HIP(ctx, hipMemcpyAsync(h_tail + 3, rflag + np - 1, 4, hipMemcpyDeviceToHost, st));
+  BS_HIP(ctx, hipEventRecord(ev.e[3], st));
+  BS_HIP(ctx, hipStreamSynchronize(st));
+  BS_HIP(ctx, hipGetLastError());
+  const int64_t nb = (int64_t)h_tail[0] + h_tail[1];
+  const int32_t nc = h_tail[2] + h_tail[3];
+  const int64_t ns = 8 * nb;
+  if (ns >= (1ll << 31))
+    return fail(ctx, BS_ERR_RANGE, "footprints: more than 2^31 border states");
+
+  BS_HIP(ctx, hipEventRecord(ev.e[4], st));
+  int rounds = 0;
+  int64_t total = 0;
+  std::vector<int64_t> h_off;
+  if (nc > 0) {
+    BS_HIP(ctx, B[9].reserve(4 * nb));
+    BS_HIP(ctx, B[10].reserve(4 * (int64_t)nc));
+    BS_HIP(ctx, B[11].reserve(4 * ns));
+    BS_HIP(ctx, B[12].reserve(ns));
+    for (int k = 13; k < 19; k++)
+      BS_HIP(ctx, B[k].reserve(4 * ns));
+    int32_t* bpix = B[9].as<int32_t>();
+    int32_t* rpix = B[10].as<int32_t>();
+    int32_t* succ = B[11].as<int32_t>();
+    uint8_t* kind = B[12].as<uint8_t>();
+    int32_t* nxt[2] = {B[13].as<int32_t>(), B[14].as<int32_t>()};
+    uint32_t* val[2] = {B[15].as<uint32_t>(), B[16].as<uint32_t>()};
+    int32_t* last[2] = {B[17].as<int32_t>(), B[18].as<int32_t>()};
+    lists_kernel<<<nblk(np, 256), 256, 0, st>>>(bflag, bscan, rflag, rscan, np, bpix, rpix);
+    int cur = 0;
+    if (ns > 0) {
+      state_kernel<<<nblk(ns, 256), 256, 0, st>>>(m, wp, bpix, bflag, bscan, rflag, ns, succ, kind, nxt[0], val[0],
+                                                   last[0]);
+      int lg = 0;
+      while ((1ll << lg) < ns)
+        lg++;
+      rounds = lg + 1;  // a list of length L <= ns closes after ceil(log2 L) rounds
+      for (int it = 0; it < rounds; it++, cur ^= 1)
+        jump_kernel<<<nblk(ns, 256), 256, 0, st>>>(nxt[cur], val[cur], last[cur], ns, nxt[cur ^ 1], val[cur ^ 1],
+                                                    last[cur ^ 1]);
+    }
+    // per-contour: cnt [nc + 1] | off [nc + 1] | cstart [nc] | asum [nc] | psum [nc] | area [nc] | perim [nc]
+    const int64_t n1 = (int64_t)nc + 1;
+    BS_HIP(ctx, B[19].reserve(8 * (2 * n1 + 5 * (int64_t)nc)));
+    int64_t* cnt = B[19].as<int64_t>();
+    int64_t* off = cnt + n1;
+    int32_t* cstart = reinterpret_cast<int32_t*>(off + n1);
+    unsigned long long* asum = reinterpret_cast<unsigned long long*>(off + n1 + nc);
+    unsigned long long* psum = asum + nc;
+    double* d_area = reinterpret_cast<double*>(psum + nc);
+    double* d_perim = d_area + nc;
+    BS_HIP(ctx, hipMemsetAsync(cnt, 0, 8 * (2 * n1 + 5 * (int64_t)nc), st));
+    contour_count_kernel<<<nblk(nc, 256), 256, 0, st>>>(m, wp, rpix, nc, bscan, succ, kind, nxt[cur], val[cur],
+                                                         last[cur], cnt, cstart, d_err);
+    tmp = 0;
+    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, cnt, off, (int)n1, st));
+    BS_HIP(ctx, B[8].reserve(tmp));
+    tb = B[8].cap;
+    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[8].p, tb, cnt, off, (int)n1, st));
+    int h_err = 0;
+    BS_HIP(ctx, hipMemcpyAsync(&total, off + nc, 8, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipStreamSynchronize(st));
+    BS_HIP(ctx, hipGetLastError());
+    if (h_err)
+      return fail(ctx, BS_ERR_INTERNAL, "footprints: a contour list did not close within the jump-round bound");
+    BS_HIP(ctx, B[20].reserve(12 * std::max<int64_t>(total, 1)));
+    int32_t* xy = B[20].as<int32_t>();
+    int32_t* cid = xy + 2 * total;
+    BS_HIP(ctx, hipMemsetAsync(cid, 0xff, 4 * total, st));
+    if (ns > 0)
+      scatter_kernel<<<nblk(ns, 256), 256, 0, st>>>(bpix, rscan, succ, kind, nxt[cur], val[cur], last[cur], ns, wp, nc,
+                                                     off, xy, cid, d_err);
+    single_kernel<<<nblk(nc, 256), 256, 0, st>>>(rpix, cstart, nc, wp, off, xy, cid);
+    measure_kernel<<<nblk(total, 256), 256, 0, st>>>(xy, cid, off, total, nc, asum, psum);
+    finish_kernel<<<nblk(nc, 256), 256, 0, st>>>(xy, off, nc, asum, psum, d_area, d_perim);
+    BS_HIP(ctx, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipStreamSynchronize(st));
+    BS_HIP(ctx, hipGetLastError());
+    if (h_err)
+      return fail(ctx, BS_ERR_INTERNAL, "footprints: an emitted point fell outside its contour's range");
+    out->offset = (int64_t*)malloc(8 * n1);
+    out->xy = (int32_t*)malloc(8 * std::max<int64_t>(total, 1));
+    out->area = (double*)malloc(8 * (size_t)nc);
+    out->perimeter = (double*)malloc(8 * (size_t)nc);
+    if (!out->offset || !out->xy || !out->area || !out->perimeter) {
+      bs_contours_free(out);
+      return fail(ctx, BS_ERR_NOMEM, "footprints: host allocation");
+    }
+    BS_HIP(ctx, hipMemcpyAsync(out->offset, off, 8 * n1, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(out->xy, xy, 8 * total, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(out->area, d_area, 8 * (size_t)nc, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(out->perimeter, d_perim, 8 * (size_t)nc, hipMemcpyDeviceToHost, st));
+  } else {
+    out->offset = (int64_t*)calloc(1, 8);
+    if (!out->offset)
+      return fail(ctx, BS_ERR_NOMEM, "footprints: host allocation");
+  }
+  if (d_mask)
+    mask_out_kernel<<<nblk(npix, 256), 256, 0, st>>>(m, w, h, d_mask);
+  BS_HIP(ctx, hipEventRecord(ev.e[5], st));
+  BS_HIP(ctx, hipStreamSynchronize(st));
+  BS_HIP(ctx, hipGetLastError());
+  out->n_contours = nc;
+  out->width = w;
+  out->height = h;
+  if (info) {
+    info->ms_mask = ev.ms(0, 1);
+    info->ms_close = ev.ms(1, 2);
+    info->ms_label = ev.ms(2, 3);
+    info->ms_trace = ev.ms(4, 5);  // (the host reads the border counts in between)
+    info->ms_total = ev.ms(0, 3) + info->ms_trace;
+    unsigned long long fg = 0;
+    BS_HIP(ctx, hipMemcpy(&fg, d_max + 2, 8, hipMemcpyDeviceToHost));
+    info->fg_pixels = (int64_t)fg;
+    info->border_states = ns;
+    info->components = nc;
+    info->jump_rounds = rounds;
+  }
+  return BS_OK;
+}
+
+extern "C" int bs_footprints(bs_ctx* ctx, const double* image, int32_t width, int32_t height, int32_t threshold,
+                             int32_t kernel_size, int32_t iterations, uint8_t* mask, bs_contours* out,
+                             bs_footprint_info* info)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (!image || !out || width < 1 || height < 1 || (int64_t)(width + 2ll) * (height + 2ll) >= (1ll << 31))
+    return fail(ctx, BS_ERR_INVALID, "footprints: null pointer or bad raster size");
+  BS_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t img_bytes = sizeof(double) * 3 * (size_t)width * height;
+  const size_t mask_bytes = (size_t)width * height;
+  BS_HIP(ctx, ctx->fp[21].reserve(img_bytes));
+  if (mask)
+    BS_HIP(ctx, ctx->fp[22].reserve(mask_bytes));
+  BS_HIP(ctx, hipMemcpyAsync(ctx->fp[21].p, image, img_bytes, hipMemcpyHostToDevice, ctx->stream));
+  const int rc = bs_footprints_dev(ctx, ctx->fp[21].as<double>(), width, height, threshold, kernel_size, iterations,
+                                   mask ? ctx->fp[22].as<uint8_t>() : nullptr, out, info);
+  if (rc != BS_OK)
+    return rc;
+  if (mask) {
+    BS_HIP(ctx, hipMemcpyAsync(mask, ctx->fp[22].p, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return BS_OK;
+}
+
+// my_function.cpp:64-131; the GBK captions of the three header lines and the faces line are written in ASCII.
+// ostream prints a float like printf("%g") of the value widened to double.
+extern "C" int bs_contours_write_obj(const bs_contours* c, const char* path)
+{
+  if (!c || !path || c->n_contours < 0 || (c->n_contours > 0 && (!c->offset || !c->xy)) || c->width < 1 ||
+      c->height < 1)
+    return BS_ERR_INVALID;
+  FILE* f = fopen(path, "w");
+  if (!f)
+    return BS_ERR_INVALID;
+  fprintf(f, "# building footprints extruded to a 3-D model\n# contours: %d\n# x, y normalised to [0,1]\n\n",
+          c->n_contours);
+  for (int32_t i = 0; i < c->n_contours; i++)
+    for (int64_t k = c->offset[i]; k < c->offset[i + 1]; k++) {
+      const float x = static_cast<float>(c->xy[2 * k]) / c->width;
+      const float y = 1.0f - static_cast<float>(c->xy[2 * k + 1]) / c->height;
+      fprintf(f, "v %g %g 0.0\nv %g %g 1\n", (double)x, (double)y, (double)x, (double)y);
+    }
+  fprintf(f, "\n# faces (quads)\n");
+  int64_t base = 1;
+  for (int32_t i = 0; i < c->n_contours; i++) {
+    const int64_t n = c->offset[i + 1] - c->offset[i];
+    for (int64_t k = 0; k < n; k++) {
+      const int64_t nx = (k + 1) % n;
+      fprintf(f, "f %lld %lld %lld %lld\n", (long long)(base + 2 * k), (long long)(base + 2 * nx),
+              (long long)(base + 2 * nx + 1), (long long)(base + 2 * k + 1));
+    }
+    base += 2 * n;
+  }
+  const bool ok = !ferror(f);
+  return (fclose(f) == 0 && ok) ? BS_OK : BS_ERR_INVALID;
+}

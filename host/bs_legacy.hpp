@@ -297,6 +297,22 @@ public:
     }
   }
 
+  // extracted_contour (my_function.cpp:8-145) on the image of compute_gird_picture(), which must have run: the
+  // density PNG the reference reads back holds exactly the bytes bs_footprints quantises, so the image is used
+  // in memory.  Writes the OBJ of every contour to obj_path; returns the contours (caller: bs_contours_free).
+  bs_contours extracted_contour(const std::string& obj_path, int32_t threshold = 10, int32_t kernel_size = 5,
+                                int32_t iterations = 2)
+  {
+    bs_contours c{};
+    legacy_check(bs_footprints(legacy_ctx(), image.data(), width, height, threshold, kernel_size, iterations, nullptr,
+                               &c, nullptr));
+    if (bs_contours_write_obj(&c, obj_path.c_str()) != BS_OK) {
+      bs_contours_free(&c);
+      throw std::runtime_error("extracted_contour: cannot write " + obj_path);
+    }
+    return c;
+  }
+
   int32_t box_min[3], box_max[3];
   int32_t bin = 100, bin_height = 1000;  // TMC3.cpp:179
   int32_t width = 0, height = 0, channels = 3;

@@ -26,7 +26,7 @@ static std::string after_equals(const char* arg)  // Split(path, "=")[1], my_fun
 int main(int argc, char* argv[])
 {
   if (argc < 3) {
-    fprintf(stderr, "usage: %s <x>=<in.ply> <y>=<out.ply> [--raster=<png prefix>]\n", argv[0]);
+    fprintf(stderr, "usage: %s <x>=<in.ply> <y>=<out.ply> [--raster=<png prefix>] [--footprints=<file.obj>]\n", argv[0]);
     return 2;
   }
   const std::string in = after_equals(argv[1]), out = after_equals(argv[2]);
@@ -43,9 +43,13 @@ int main(int argc, char* argv[])
   }
   const size_t n = cloud.getPointCount();
   std::string raster_prefix;  // --raster=<prefix>: the 2-D branch the reference's main keeps commented out (TMC3.cpp:223-225)
-  for (int a = 3; a < argc; a++)
+  std::string obj_path;  // --footprints=<file.obj>: extracted_contour (TMC3.cpp:226) on the raster
+  for (int a = 3; a < argc; a++) {
     if (std::string(argv[a]).rfind("--raster=", 0) == 0)
       raster_prefix = after_equals(argv[a]);
+    if (std::string(argv[a]).rfind("--footprints=", 0) == 0)
+      obj_path = after_equals(argv[a]);
+  }
   try {
     bs::buildingSeg_t<Cloud> seg(cloud);  // bounding box + shift to the origin (TMC3.cpp:209)
     std::vector<VecD> normal;
@@ -59,10 +63,20 @@ int main(int argc, char* argv[])
     srand(1);
     h.set_plane_color(planes);
     fprintf(stderr, "tmc3: %zu points, %zu planes\n", n, planes.size());
-    if (!raster_prefix.empty()) {
+    if (!raster_prefix.empty() || !obj_path.empty()) {
       seg.compute_gird_picture();
-      seg.save_image(raster_prefix);
+      if (!raster_prefix.empty())
+        seg.save_image(raster_prefix);
       fprintf(stderr, "tmc3: raster %d x %d, ground threshold %.0f mm\n", seg.width, seg.height, seg.ground_th);
+    }
+    if (!obj_path.empty()) {
+      bs_contours c = seg.extracted_contour(obj_path);
+      int kept = 0;  // the reference's overlay filter, my_function.cpp:40
+      for (int32_t i = 0; i < c.n_contours; i++)
+        kept += c.area[i] > 500 && c.perimeter[i] > 100;
+      fprintf(stderr, "tmc3: %d footprint contours (%d with area > 500 and perimeter > 100) -> %s\n", c.n_contours,
+              kept, obj_path.c_str());
+      bs_contours_free(&c);
     }
   } catch (const std::exception& e) {
     fprintf(stderr, "tmc3: %s\n", e.what());

@@ -371,6 +371,53 @@ int bs_segment_sharded(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xy
  * committed seeds) and global point indices, ascending id.  Released by bs_planes_free. */
 int bs_sharded_planes_fetch(bs_ctx* ctx, bs_planes* planes);
 
+/* ---- building footprints: the reference's extracted_contour (my_function.cpp:8-145) on the density raster ----
+ *
+ * image is the [height][width][3] f64 raster of bs_grid_picture; channel 1 (density) is read.
+ *   1. quantise as save_image does (TMC3.cpp:100-108): q = (uint8)(255.0 * (1.0 * v / max1)), max1 = max(0, max v),
+ *      q = 0 where max1 == 0 (and where v < 0 or NaN, which the raster never holds)
+ *   2. binarise: foreground iff q > threshold (reference: 10)
+ *   3. close: `iterations` dilations, then as many erosions, with OpenCV's kernel_size x kernel_size ellipse;
+ *      pixels outside the image count as background for dilation and as foreground for erosion
+ *      (reference: 5, 2; iterations = 0 skips the closing)
+ *   4. findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE): the outer border of every 8-connected foreground component
+ *      that is not inside a hole of another one, traced from the component's first pixel in raster order, in
+ *      OpenCV's point order; contours in descending order of that first pixel
+ *   5. contourArea and arcLength(closed) of every contour
+ * d_mask (nullable, device [height][width]) receives the closed mask as 0 / 255.  The result arrays are host
+ * memory owned by the library and released by bs_contours_free (which accepts a zeroed struct).
+ * BS_ERR_INVALID: null pointer, width or height < 1, (width+2)*(height+2) >= 2^31, kernel_size even or outside
+ * 1..15, iterations outside 0..16, threshold outside 0..255.  BS_ERR_RANGE: more border states than the tracer can
+ * index (2^31).  BS_ERR_INTERNAL: a contour's list ranking did not converge within its bound.  Synchronises. */
+typedef struct bs_contours {
+  int32_t n_contours;
+  int32_t width, height; /* raster the contours were taken from (the OBJ normalisation) */
+  int64_t* offset;       /* [n_contours+1] into xy */
+  int32_t* xy;           /* [offset[n_contours]][2]: x = column, y = row */
+  double* area;          /* [n_contours] contourArea */
+  double* perimeter;     /* [n_contours] arcLength(contour, true) */
+} bs_contours;
+
+/* Per-stage device time (HIP events) of the last bs_footprints[_dev] call and the sizes it worked on. */
+typedef struct bs_footprint_info {
+  double ms_mask, ms_close, ms_label, ms_trace, ms_total;
+  int64_t fg_pixels;     /* foreground pixels after the closing */
+  int64_t border_states; /* (pixel, back-direction) states the tracer ranked */
+  int64_t components;    /* external foreground components (= n_contours) */
+  int64_t jump_rounds;   /* pointer-jumping rounds of the list ranking */
+} bs_footprint_info;
+
+int bs_footprints_dev(bs_ctx* ctx, const double* d_image, int32_t width, int32_t height, int32_t threshold,
+                      int32_t kernel_size, int32_t iterations, uint8_t* d_mask, bs_contours* out,
+                      bs_footprint_info* info);
+/* Host-memory variant: image and mask (nullable) are host pointers. */
+int bs_footprints(bs_ctx* ctx, const double* image, int32_t width, int32_t height, int32_t threshold,
+                  int32_t kernel_size, int32_t iterations, uint8_t* mask, bs_contours* out, bs_footprint_info* info);
+void bs_contours_free(bs_contours* c);
+/* The reference's OBJ (my_function.cpp:64-131): every contour extruded into a prism of quads between z = 0 and
+ * z = 1, x = x / width, y = 1 - y / height (float).  Host only; BS_ERR_INVALID if the file cannot be written. */
+int bs_contours_write_obj(const bs_contours* c, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
