@@ -26,7 +26,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_plane_seeds_dev", "bs_stream_sync", "bs_comm_rccl", "bs_comm_rccl_unique_id", "bs_comm_rccl_init",
            "bs_comm_rccl_destroy", "bs_comm_local_create", "bs_comm_local_destroy", "bs_segment_sharded",
            "bs_sharded_planes_fetch", "bs_footprints_dev", "bs_footprints", "bs_contours_free",
-           "bs_contours_write_obj"]
+           "bs_contours_write_obj", "bs_segment_batch", "bs_segment_batch_dev", "bs_batch_planes_fetch",
+           "bs_shift_tiles_to_origin_dev"]
 
 
 class Params(C.Structure):
@@ -163,5 +164,9 @@ def load():
     L.bs_contours_free.argtypes = [cp]
     L.bs_contours_free.restype = None
     L.bs_contours_write_obj.argtypes = [cp, C.c_char_p]
+    L.bs_segment_batch.argtypes = [vp, ip, vp, C.c_int32, pp, ip, dp, ip, C.POINTER(Planes), ip]
+    L.bs_segment_batch_dev.argtypes = [vp, ip, vp, C.c_int32, pp, ip, dp, ip]
+    L.bs_batch_planes_fetch.argtypes = [vp, C.POINTER(Planes), ip]
+    L.bs_shift_tiles_to_origin_dev.argtypes = [vp, ip, vp, C.c_int32, ip]
     _LIB = L
     return L

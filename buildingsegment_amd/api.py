@@ -304,6 +304,58 @@ class Context:
         self._L.bs_planes_free(C.byref(P))
         return planes
 
+    # ---- batches of independent tiles (bs_segment_batch) ----------------------
+    def segment_batch(self, tiles, params: Params | None = None, shift_to_origin: bool = False):
+        """Segment a list of independent int32 [n_t, 3] clouds in one device pass.  Returns one
+        (neigh, normals, plane_idx, planes) per tile, each what segment() returns for that tile alone.
+        shift_to_origin: move every tile to its own bounding-box origin first (TMC3.cpp:55-73 per tile)."""
+        p = params or default_params()
+        xyz, off = pack_tiles(tiles)
+        if shift_to_origin:
+            xyz = shift_tiles_to_origin(xyz, off)
+        n, nt = len(xyz), len(off) - 1
+        neigh = np.empty((n, p.k), dtype=np.int32)
+        normals = np.empty((n, 3), dtype=np.float64)
+        plane_idx = np.empty(n, dtype=np.int32)
+        poff = np.empty(nt + 1, dtype=np.int32)
+        P = Planes()
+        self._batch_tiles = 0
+        self._check(self._L.bs_segment_batch(self._h, xyz.ctypes.data, off.ctypes.data, nt, C.byref(p),
+                                             neigh.ctypes.data, normals.ctypes.data, plane_idx.ctypes.data,
+                                             C.byref(P), poff.ctypes.data))
+        self._batch_tiles = nt
+        planes = _planes_to_list(P)
+        self._L.bs_planes_free(C.byref(P))
+        return [(neigh[off[t]:off[t + 1]], normals[off[t]:off[t + 1]], plane_idx[off[t]:off[t + 1]],
+                 planes[poff[t]:poff[t + 1]]) for t in range(nt)]
+
+    def segment_batch_dev(self, d_xyz, tile_offset, d_plane_idx, params, d_neigh=0, d_normals=0):
+        """Device form: d_xyz holds the concatenated tiles, tile_offset [n_tiles + 1] (host) delimits them; the plane
+        records stay on the device until batch_planes_fetch()."""
+        off = _tile_offsets(tile_offset)
+        self._batch_tiles = 0
+        self._check(self._L.bs_segment_batch_dev(self._h, d_xyz, off.ctypes.data, len(off) - 1, C.byref(params),
+                                                 d_neigh or None, d_normals or None, d_plane_idx))
+        self._batch_tiles = len(off) - 1
+
+    def batch_planes_fetch(self):
+        """The planes of the last batch on this context: one list per tile (ids from 1, tile-local point indices)."""
+        nt = getattr(self, "_batch_tiles", 0)
+        poff = np.zeros(nt + 1, dtype=np.int32)
+        P = Planes()
+        self._check(self._L.bs_batch_planes_fetch(self._h, C.byref(P), poff.ctypes.data if nt else None))
+        planes = _planes_to_list(P)
+        self._L.bs_planes_free(C.byref(P))
+        return [planes[poff[t]:poff[t + 1]] for t in range(nt)]
+
+    def shift_tiles_to_origin_dev(self, d_xyz, tile_offset):
+        """bs_shift_to_origin_dev for every tile of the concatenation separately; returns the minima [n_tiles, 3]."""
+        off = _tile_offsets(tile_offset)
+        mn = np.zeros((len(off) - 1, 3), dtype=np.int32)
+        self._check(self._L.bs_shift_tiles_to_origin_dev(self._h, d_xyz, off.ctypes.data, len(off) - 1,
+                                                         mn.ctypes.data))
+        return mn
+
 
 @dataclass
 class Footprints:
@@ -349,6 +401,49 @@ def write_footprints_obj(fp: Footprints, path):
     rc = _lib.load().bs_contours_write_obj(C.byref(c), str(path).encode())
     if rc != 0:
         raise BsError(rc, f"cannot write {path}")
+
+
+def _tile_offsets(tile_offset) -> np.ndarray:
+    off = np.ascontiguousarray(tile_offset, dtype=np.int64)
+    if off.ndim != 1 or len(off) < 2:
+        raise ValueError("tile_offset must be a 1-D array of n_tiles + 1 >= 2 offsets")
+    return off
+
+
+def pack_tiles(tiles):
+    """Pack a list of integer [n_t, 3] clouds into the batch layout of bs_segment_batch: (xyz int32 [N, 3], the
+    concatenation, and tile_offset int64 [n_tiles + 1], tile t = rows tile_offset[t] .. tile_offset[t + 1] - 1)."""
+    if isinstance(tiles, np.ndarray) or not hasattr(tiles, "__len__") or len(tiles) == 0:
+        raise ValueError("tiles must be a non-empty list of [n, 3] arrays")
+    arrs = []
+    for t, a in enumerate(tiles):
+        a = np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"tile {t}: shape {a.shape}, expected [n, 3]")
+        if a.shape[0] == 0:
+            raise ValueError(f"tile {t} is empty")
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"tile {t}: dtype {a.dtype}, expected integer coordinates (mm)")
+        if a.dtype.itemsize > 4 or a.dtype == np.uint32:
+            if a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max:
+                raise ValueError(f"tile {t}: coordinates do not fit int32")
+        arrs.append(a.astype(np.int32, copy=False))
+    off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(a) for a in arrs])
+    return np.ascontiguousarray(np.concatenate(arrs)), off
+
+
+def shift_tiles_to_origin(xyz, tile_offset) -> np.ndarray:
+    """Host form of bs_shift_tiles_to_origin_dev: every tile of a packed batch minus its own minimum."""
+    off = _tile_offsets(tile_offset)
+    if off[0] != 0 or (np.diff(off) <= 0).any() or off[-1] != len(xyz):
+        raise ValueError("tile_offset must start at 0, rise strictly and end at len(xyz)")
+    xyz = np.asarray(xyz, dtype=np.int64)
+    mn = np.minimum.reduceat(xyz, off[:-1], axis=0)
+    out = xyz - np.repeat(mn, np.diff(off), axis=0)
+    if out.max(initial=0) > np.iinfo(np.int32).max:
+        raise ValueError("a tile's extent does not fit int32")
+    return out.astype(np.int32)
 
 
 def grid_dims(extent, bin=100):

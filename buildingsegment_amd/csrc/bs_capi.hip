@@ -22,7 +22,7 @@ int fail(bs_ctx* ctx, int status, const char* what, hipError_t e)
   return status;
 }
 
-static int check_params(bs_ctx* ctx, const bs_params* p, int64_t n)
+int check_params(bs_ctx* ctx, const bs_params* p, int64_t n)
 {
   if (!p)
     return fail(ctx, BS_ERR_INVALID, "params is NULL");
@@ -68,8 +68,8 @@ __global__ void neigh_range_kernel(const int32_t* __restrict__ neigh, int64_t to
     *bad = 1;
 }
 
-static int region_grow_dev_impl(bs_ctx* ctx, const int32_t* d_xyz, const double* d_normals, const int32_t* d_neigh,
-                                int64_t n, const bs_params* p, int32_t* d_plane_idx, bool trusted_neigh)
+int region_grow_dev_impl(bs_ctx* ctx, const int32_t* d_xyz, const double* d_normals, const int32_t* d_neigh,
+                         int64_t n, const bs_params* p, int32_t* d_plane_idx, bool trusted_neigh)
 {
   if (!ctx)
     return BS_ERR_INVALID;
@@ -102,6 +102,45 @@ static int region_grow_dev_impl(bs_ctx* ctx, const int32_t* d_xyz, const double*
   T.mark(4);
   BS_HIP(ctx, hipEventSynchronize(ctx->ev[4]));
   ctx->tm.grow_ms = T.ms(3, 4);
+  return BS_OK;
+}
+
+// np device plane records + their list pool -> a host bs_planes (what bs_planes_fetch and bs_batch_planes_fetch return)
+int planes_to_host(bs_ctx* ctx, const PlaneRec* d_recs, const int32_t* d_list, int np, int64_t list_used,
+                   bs_planes* out)
+{
+  out->n_planes = np;
+  out->id = (int32_t*)malloc(sizeof(int32_t) * std::max(np, 1));
+  out->normal = (double*)malloc(sizeof(double) * 3 * std::max(np, 1));
+  out->center = (int32_t*)malloc(sizeof(int32_t) * 3 * std::max(np, 1));
+  out->offset = (int64_t*)malloc(sizeof(int64_t) * (np + 1));
+  out->point_idx = (int32_t*)malloc(sizeof(int32_t) * std::max<int64_t>(list_used, 1));
+  PlaneRec* recs = (PlaneRec*)malloc(sizeof(PlaneRec) * std::max(np, 1));
+  if (!out->id || !out->normal || !out->center || !out->offset || !out->point_idx || !recs) {
+    free(recs);
+    bs_planes_free(out);
+    return fail(ctx, BS_ERR_NOMEM, "host allocation failed");
+  }
+  hipError_t he = hipSuccess;
+  if (np > 0)
+    he = hipMemcpy(recs, d_recs, sizeof(PlaneRec) * np, hipMemcpyDeviceToHost);
+  if (he == hipSuccess && list_used > 0)
+    he = hipMemcpy(out->point_idx, d_list, sizeof(int32_t) * list_used, hipMemcpyDeviceToHost);
+  if (he != hipSuccess) {
+    free(recs);
+    bs_planes_free(out);
+    return fail(ctx, BS_ERR_HIP, "bs_planes_fetch: copy of the plane records failed", he);
+  }
+  for (int i = 0; i < np; i++) {
+    out->id[i] = recs[i].id;
+    for (int a = 0; a < 3; a++) {
+      out->normal[3 * i + a] = recs[i].normal[a];
+      out->center[3 * i + a] = recs[i].center[a];
+    }
+    out->offset[i] = recs[i].list_off;
+  }
+  out->offset[np] = list_used;
+  free(recs);
   return BS_OK;
 }
 
@@ -191,6 +230,8 @@ void bs_destroy(bs_ctx* c)
   for (auto& b : c->sh)
     b.release();
   for (auto& b : c->fp)
+    b.release();
+  for (auto& b : c->bt)
     b.release();
   c->rg_hout.release();
   for (auto& e : c->ev)
@@ -348,40 +389,7 @@ int bs_planes_fetch(bs_ctx* ctx, bs_planes* out)
   BS_HIP(ctx, hipSetDevice(ctx->device));
   GrowStats hs;
   BS_HIP(ctx, hipMemcpy(&hs, ctx->rg_stats.p, sizeof hs, hipMemcpyDeviceToHost));
-  const int np = hs.n_planes;
-  out->n_planes = np;
-  out->id = (int32_t*)malloc(sizeof(int32_t) * std::max(np, 1));
-  out->normal = (double*)malloc(sizeof(double) * 3 * std::max(np, 1));
-  out->center = (int32_t*)malloc(sizeof(int32_t) * 3 * std::max(np, 1));
-  out->offset = (int64_t*)malloc(sizeof(int64_t) * (np + 1));
-  out->point_idx = (int32_t*)malloc(sizeof(int32_t) * std::max<int64_t>(hs.list_used, 1));
-  PlaneRec* recs = (PlaneRec*)malloc(sizeof(PlaneRec) * std::max(np, 1));
-  if (!out->id || !out->normal || !out->center || !out->offset || !out->point_idx || !recs) {
-    free(recs);
-    bs_planes_free(out);
-    return fail(ctx, BS_ERR_NOMEM, "host allocation failed");
-  }
-  hipError_t he = hipSuccess;
-  if (np > 0)
-    he = hipMemcpy(recs, ctx->rg_planes.p, sizeof(PlaneRec) * np, hipMemcpyDeviceToHost);
-  if (he == hipSuccess && hs.list_used > 0)
-    he = hipMemcpy(out->point_idx, ctx->rg_list.p, sizeof(int32_t) * hs.list_used, hipMemcpyDeviceToHost);
-  if (he != hipSuccess) {
-    free(recs);
-    bs_planes_free(out);
-    return fail(ctx, BS_ERR_HIP, "bs_planes_fetch: copy of the plane records failed", he);
-  }
-  for (int i = 0; i < np; i++) {
-    out->id[i] = recs[i].id;
-    for (int a = 0; a < 3; a++) {
-      out->normal[3 * i + a] = recs[i].normal[a];
-      out->center[3 * i + a] = recs[i].center[a];
-    }
-    out->offset[i] = recs[i].list_off;
-  }
-  out->offset[np] = hs.list_used;
-  free(recs);
-  return BS_OK;
+  return planes_to_host(ctx, ctx->rg_planes.as<PlaneRec>(), ctx->rg_list.as<int32_t>(), hs.n_planes, hs.list_used, out);
 }
 
 void bs_planes_free(bs_planes* p)

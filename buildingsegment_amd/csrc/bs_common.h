@@ -95,6 +95,56 @@ struct GridDev {
   int64_t n;
 };
 
+// Batched grid (bs_segment_batch): one cell-sorted order over n_tiles concatenated clouds.  Every tile keeps its own
+// bounding box and cell dims at the shared cell edge, and a cell's key is (tile << mbits) | Morton(cell): the sort
+// orders by (tile, Morton cell), so tile t is exactly the sorted positions [tile_off[t], tile_off[t+1]), and the hash
+// table (keyed by that same key) never lets a query of one tile see a cell of another.
+struct TileDesc {
+  int32_t mn[3];   // the tile's bbox min (mm)
+  int32_t dim[3];  // its cells per axis
+};
+
+struct TiledGridDev : GridDev {  // (mn / dim of the base: unused, every query takes its tile's)
+  const TileDesc* tiles;
+  const int32_t* tile_off;  // [n_tiles + 1]: concatenation offsets = sorted-position ranges
+  int32_t n_tiles;
+  int32_t mbits;            // Morton bits of a cell key inside a tile
+};
+
+// scratch of the batch (bs_ctx::bt): offsets as int32, bbox blocks, per-tile bbox, descriptors, plane bases, and the
+// renumbered plane records / lists of bs_batch_planes_fetch
+enum { BT_OFF, BT_BLK, BT_MNMX, BT_DESC, BT_BASE, BT_RECS, BT_LIST, BT_COUNT };
+
+// tile of concatenation index (or sorted position) i: the last t with off[t] <= i (tiles are never empty)
+__host__ __device__ inline int32_t tile_of(const int32_t* off, int32_t n_tiles, int64_t i)
+{
+  int32_t lo = 0, hi = n_tiles - 1;
+  while (lo < hi) {
+    const int32_t mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= i)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  return lo;
+}
+
+__host__ __device__ inline uint64_t spread21(uint64_t v)
+{
+  v &= 0x1FFFFFull;
+  v = (v | (v << 32)) & 0x1F00000000FFFFull;
+  v = (v | (v << 16)) & 0x1F0000FF0000FFull;
+  v = (v | (v << 8)) & 0x100F00F00F00F00Full;
+  v = (v | (v << 4)) & 0x10C30C30C30C30C3ull;
+  v = (v | (v << 2)) & 0x1249249249249249ull;
+  return v;
+}
+
+__host__ __device__ inline uint64_t morton_cell(uint32_t cx, uint32_t cy, uint32_t cz)
+{
+  return spread21(cx) | (spread21(cy) << 1) | (spread21(cz) << 2);
+}
+
 // The fused pipeline's position-ordered scratch (bs_ctx::seg_npos): n * K neighbour positions, then the n normals
 // in POSITION order (the grower builds its records by position and would otherwise gather 24 B per point by
 // original index).
@@ -196,6 +246,10 @@ struct bs_ctx {
   const int32_t* npos_neigh = nullptr;
   const double* npos_normals = nullptr;
   int npos_k = 0;
+  // bs_segment_batch: scratch, and the tiling of the last batch (valid while its region-grow result is)
+  bs::DevBuf bt[bs::BT_COUNT];
+  std::vector<int64_t> bt_off;
+  bool bt_valid = false;
 };
 
 namespace bs {
@@ -214,10 +268,25 @@ int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t
                int k, int cell_hint, GridDev* out);
 int build_spatial_order(bs_ctx* ctx, const int32_t* d_xyz, int64_t n);
 int bbox_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bb[6]);
+// batched grid (bs_batch.hip names the scratch): tile_off_dev = the offsets as int32 on the device
+int tile_bbox_dev(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_off, const std::vector<int64_t>& off,
+                  int32_t* d_mnmx, std::vector<int32_t>& mnmx);
+int build_grid_tiled(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_off, const std::vector<int64_t>& off,
+                     double radius, int k, int cell_hint, TiledGridDev* out);
+void launch_tile_shift(bs_ctx* ctx, int32_t* d_xyz, int64_t n, const int32_t* d_off, int32_t n_tiles,
+                       const int32_t* d_mnmx);
 // knn.hip
 int launch_knn_normals(bs_ctx* ctx, const GridDev& g, int64_t q_begin, int64_t q_end,
                        const bs_params& p, int32_t* d_neigh, double* d_normals, double cert_radius,
                        int64_t* n_uncertified, int32_t* d_npos = nullptr);
+int launch_knn_normals_tiled(bs_ctx* ctx, const TiledGridDev& g, const bs_params& p, int32_t* d_neigh,
+                             double* d_normals, int32_t* d_npos);
+// capi.hip
+int region_grow_dev_impl(bs_ctx* ctx, const int32_t* d_xyz, const double* d_normals, const int32_t* d_neigh,
+                         int64_t n, const bs_params* p, int32_t* d_plane_idx, bool trusted_neigh);
+int check_params(bs_ctx* ctx, const bs_params* p, int64_t n);
+int planes_to_host(bs_ctx* ctx, const PlaneRec* d_recs, const int32_t* d_list, int np, int64_t list_used,
+                   bs_planes* out);
 // grow.hip
 int launch_region_grow_seq(bs_ctx* ctx, const int32_t* d_xyz, const double* d_normals,
                            const int32_t* d_neigh, int64_t n, const bs_params& p,

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 
 #include "bs_common.h"
@@ -67,16 +68,6 @@ __global__ void bbox_kernel(const int32_t* __restrict__ xyz, int64_t n, int32_t*
 // gathers of everything that walks the cell-sorted order (kNN candidates, static masks,
 // reverse lists, owner passes) find their neighbours' lines in the XCD's L2; the raster
 // order (x fastest) separates y/z neighbours by a whole row / layer of the scene.
-__host__ __device__ inline uint64_t spread21(uint64_t v)
-{
-  v &= 0x1FFFFFull;
-  v = (v | (v << 32)) & 0x1F00000000FFFFull;
-  v = (v | (v << 16)) & 0x1F0000FF0000FFull;
-  v = (v | (v << 8)) & 0x100F00F00F00F00Full;
-  v = (v | (v << 4)) & 0x10C30C30C30C30C3ull;
-  v = (v | (v << 2)) & 0x1249249249249249ull;
-  return v;
-}
 __host__ __device__ inline uint32_t compact21(uint64_t v)
 {
   v &= 0x1249249249249249ull;
@@ -97,7 +88,7 @@ __global__ void cellkey_kernel(const int32_t* __restrict__ xyz, int64_t n, int m
   uint32_t cx = (uint32_t)(xyz[3 * i] - mnx) / (uint32_t)cell;
   uint32_t cy = (uint32_t)(xyz[3 * i + 1] - mny) / (uint32_t)cell;
   uint32_t cz = (uint32_t)(xyz[3 * i + 2] - mnz) / (uint32_t)cell;
-  keys[i] = morton ? (spread21(cx) | (spread21(cy) << 1) | (spread21(cz) << 2)) : pack_cell(cx, cy, cz);
+  keys[i] = morton ? morton_cell(cx, cy, cz) : pack_cell(cx, cy, cz);
   if (vals)
     vals[i] = (int32_t)i;
 }
@@ -186,14 +177,12 @@ static int morton_key_bits(int64_t ext, int cell)
   return std::min(63, 3 * bits);
 }
 
-static int count_cells(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, const int mn[3], int cell, int64_t ext,
-                       int64_t* ncell)
+// sort the keys in keys_in over [0, end_bit) and count the distinct ones (synchronises)
+static int sort_count_keys(bs_ctx* ctx, int64_t n, int end_bit, int64_t* ncell)
 {
   hipStream_t st = ctx->stream;
   uint64_t* kin = ctx->keys_in.as<uint64_t>();
   uint64_t* kout = ctx->keys_out.as<uint64_t>();
-  const int end_bit = morton_key_bits(ext, cell);
-  cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, mn[0], mn[1], mn[2], cell, 1, kin, nullptr);
   size_t tb = 0;
   BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, kin, kout, (int)n, 0, end_bit, st));
   BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
@@ -206,6 +195,14 @@ static int count_cells(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, const int m
   BS_HIP(ctx, hipStreamSynchronize(st));
   *ncell = (int64_t)h;
   return BS_OK;
+}
+
+static int count_cells(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, const int mn[3], int cell, int64_t ext,
+                       int64_t* ncell)
+{
+  cellkey_kernel<<<grid_blocks(n, 256), 256, 0, ctx->stream>>>(d_xyz, n, mn[0], mn[1], mn[2], cell, 1,
+                                                               ctx->keys_in.as<uint64_t>(), nullptr);
+  return sort_count_keys(ctx, n, morton_key_bits(ext, cell), ncell);
 }
 
 int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t n, double radius,
@@ -391,6 +388,276 @@ int build_spatial_order(bs_ctx* ctx, const int32_t* d_xyz, int64_t n)
   BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
   BS_HIP(ctx, hipGetLastError());
   ctx->order_n = n;
+  ctx->order_xyz = d_xyz;
+  return BS_OK;
+}
+
+// ---- batched grid (bs_segment_batch) ------------------------------------------------------------------------------
+// n_tiles clouds, concatenated, in ONE cell-sorted order (bs_common.h, TiledGridDev): per-tile boxes from one segmented
+// reduction, keys (tile << mbits) | Morton(cell in the tile's box) at one shared cell edge, the same radix sort and
+// run-length encoding as build_grid, and a hash table keyed by the sort key itself.
+
+namespace {
+
+constexpr int TILE_CHUNK = 4096;  // points per block of the segmented bounding-box reduction
+
+struct TileBlock {
+  int32_t tile, begin, end;
+};
+
+__global__ void tile_bbox_kernel(const int32_t* __restrict__ xyz, const TileBlock* __restrict__ blk,
+                                 int32_t* __restrict__ mnmx)
+{
+  const TileBlock b = blk[blockIdx.x];
+  int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
+  for (int64_t i = b.begin + (int64_t)threadIdx.x; i < b.end; i += blockDim.x) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      const int v = xyz[3 * i + a];
+      mn[a] = min(mn[a], v);
+      mx[a] = max(mx[a], v);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    for (int o = 32; o > 0; o >>= 1) {
+      mn[a] = min(mn[a], __shfl_xor(mn[a], o));
+      mx[a] = max(mx[a], __shfl_xor(mx[a], o));
+    }
+  }
+  __shared__ int smn[3][4], smx[3][4];
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      smn[a][wv] = mn[a];
+      smx[a][wv] = mx[a];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int a = threadIdx.x;
+    int m0 = smn[a][0], m1 = smx[a][0];
+    for (int t = 1; t < (int)(blockDim.x >> 6); t++) {
+      m0 = min(m0, smn[a][t]);
+      m1 = max(m1, smx[a][t]);
+    }
+    atomicMin(&mnmx[6 * b.tile + a], m0);
+    atomicMax(&mnmx[6 * b.tile + 3 + a], m1);
+  }
+}
+
+__global__ void tiled_cellkey_kernel(const int32_t* __restrict__ xyz, int64_t n, const int32_t* __restrict__ off,
+                                     int32_t n_tiles, const TileDesc* __restrict__ tiles, int cell, int mbits,
+                                     uint64_t* __restrict__ keys, int32_t* __restrict__ vals)
+{
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n)
+    return;
+  const int32_t t = tile_of(off, n_tiles, i);
+  const TileDesc d = tiles[t];
+  const uint32_t cx = (uint32_t)(xyz[3 * i] - d.mn[0]) / (uint32_t)cell;
+  const uint32_t cy = (uint32_t)(xyz[3 * i + 1] - d.mn[1]) / (uint32_t)cell;
+  const uint32_t cz = (uint32_t)(xyz[3 * i + 2] - d.mn[2]) / (uint32_t)cell;
+  keys[i] = ((uint64_t)t << mbits) | morton_cell(cx, cy, cz);
+  if (vals)
+    vals[i] = (int32_t)i;
+}
+
+// bs_shift_tiles_to_origin_dev: every point minus its tile's minimum
+__global__ void tile_shift_kernel(int32_t* __restrict__ xyz, int64_t n, const int32_t* __restrict__ off,
+                                  int32_t n_tiles, const int32_t* __restrict__ mnmx)
+{
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n)
+    return;
+  const int32_t t = tile_of(off, n_tiles, i);
+#pragma unroll
+  for (int a = 0; a < 3; a++)
+    xyz[3 * i + a] -= mnmx[6 * t + a];
+}
+
+}  // namespace
+
+// Per-tile {min x,y,z, max x,y,z} into d_mnmx [n_tiles][6] and the host copy mnmx (synchronises).  d_off: the offsets
+// as int32 on the device (unused here, the blocks carry their ranges).
+int tile_bbox_dev(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_off, const std::vector<int64_t>& off,
+                  int32_t* d_mnmx, std::vector<int32_t>& mnmx)
+{
+  (void)d_off;
+  hipStream_t st = ctx->stream;
+  const int32_t nt = (int32_t)off.size() - 1;
+  std::vector<TileBlock> blk;
+  for (int32_t t = 0; t < nt; t++)
+    for (int64_t b = off[t]; b < off[t + 1]; b += TILE_CHUNK)
+      blk.push_back({t, (int32_t)b, (int32_t)std::min<int64_t>(off[t + 1], b + TILE_CHUNK)});
+  mnmx.assign(6 * (size_t)nt, 0);
+  for (int32_t t = 0; t < nt; t++)
+    for (int a = 0; a < 3; a++) {
+      mnmx[6 * t + a] = INT_MAX;
+      mnmx[6 * t + 3 + a] = INT_MIN;
+    }
+  BS_HIP(ctx, ctx->bt[BT_BLK].reserve(sizeof(TileBlock) * std::max<size_t>(blk.size(), 1)));
+  BS_HIP(ctx, hipMemcpyAsync(ctx->bt[BT_BLK].p, blk.data(), sizeof(TileBlock) * blk.size(), hipMemcpyHostToDevice, st));
+  BS_HIP(ctx, hipMemcpyAsync(d_mnmx, mnmx.data(), sizeof(int32_t) * mnmx.size(), hipMemcpyHostToDevice, st));
+  if (!blk.empty())
+    tile_bbox_kernel<<<(int)blk.size(), 256, 0, st>>>(d_xyz, ctx->bt[BT_BLK].as<TileBlock>(), d_mnmx);
+  BS_HIP(ctx, hipMemcpyAsync(mnmx.data(), d_mnmx, sizeof(int32_t) * mnmx.size(), hipMemcpyDeviceToHost, st));
+  BS_HIP(ctx, hipStreamSynchronize(st));
+  BS_HIP(ctx, hipGetLastError());
+  return BS_OK;
+}
+
+void launch_tile_shift(bs_ctx* ctx, int32_t* d_xyz, int64_t n, const int32_t* d_off, int32_t n_tiles,
+                       const int32_t* d_mnmx)
+{
+  tile_shift_kernel<<<grid_blocks(n, 256), 256, 0, ctx->stream>>>(d_xyz, n, d_off, n_tiles, d_mnmx);
+}
+
+// The batch's grid.  The cell edge follows build_grid's rule over the whole batch (the results do not depend on it,
+// only the speed), then doubles until tile bits + Morton bits fit the 63-bit key.  A batch of one tile builds the same
+// sorted order as build_grid on that cloud.
+int build_grid_tiled(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_off, const std::vector<int64_t>& off,
+                     double radius, int k, int cell_hint, TiledGridDev* out)
+{
+  hipStream_t st = ctx->stream;
+  const int32_t nt = (int32_t)off.size() - 1;
+  const int64_t n = off[nt];
+  if (nt < 1 || n <= 0 || n >= (int64_t)INT_MAX - 64)
+    return fail(ctx, BS_ERR_INVALID, "point count out of range");
+  BS_HIP(ctx, ctx->misc.reserve(256));
+  BS_HIP(ctx, ctx->keys_in.reserve(sizeof(uint64_t) * n));
+  BS_HIP(ctx, ctx->keys_out.reserve(sizeof(uint64_t) * n));
+  BS_HIP(ctx, ctx->vals_in.reserve(sizeof(int32_t) * n));
+  BS_HIP(ctx, ctx->vals_out.reserve(sizeof(int32_t) * n));
+  BS_HIP(ctx, ctx->bt[BT_MNMX].reserve(sizeof(int32_t) * 6 * nt));
+  BS_HIP(ctx, ctx->bt[BT_DESC].reserve(sizeof(TileDesc) * nt));
+
+  // 1. per-tile bounding boxes
+  std::vector<int32_t> bb;
+  int rc = tile_bbox_dev(ctx, d_xyz, d_off, off, ctx->bt[BT_MNMX].as<int32_t>(), bb);
+  if (rc != BS_OK)
+    return rc;
+  const int32_t LIM = 1 << 23;
+  int64_t ext = 1;
+  for (int32_t t = 0; t < nt; t++)
+    for (int a = 0; a < 3; a++) {
+      if (bb[6 * t + a] <= -LIM || bb[6 * t + 3 + a] >= LIM) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "tile %d: coordinates must satisfy |c| < 2^23 mm (8.4 km): shift every tile to its "
+                                  "bounding-box origin first (bs_shift_tiles_to_origin_dev)", t);
+        return fail(ctx, BS_ERR_RANGE, msg);
+      }
+      ext = std::max<int64_t>(ext, (int64_t)bb[6 * t + 3 + a] - bb[6 * t + a] + 1);
+    }
+  int tbits = 0;
+  while (((int64_t)1 << tbits) < nt)
+    tbits++;
+  auto fits = [&](int64_t c) { return ext / c + 1 < (1 << 21) && tbits + morton_key_bits(ext, (int)c) <= 63; };
+  std::vector<TileDesc> desc(nt);
+  auto upload_desc = [&](int c) -> hipError_t {
+    for (int32_t t = 0; t < nt; t++)
+      for (int a = 0; a < 3; a++) {
+        desc[t].mn[a] = bb[6 * t + a];
+        desc[t].dim[a] = (int32_t)(((int64_t)bb[6 * t + 3 + a] - bb[6 * t + a]) / c + 1);
+      }
+    return hipMemcpyAsync(ctx->bt[BT_DESC].p, desc.data(), sizeof(TileDesc) * nt, hipMemcpyHostToDevice, st);
+  };
+  BS_HIP(ctx, upload_desc(1));  // (the keys read only the minima)
+  const TileDesc* d_desc = ctx->bt[BT_DESC].as<TileDesc>();
+
+  // 2. cell size (build_grid's rule, counted with the tiled keys)
+  int cell = cell_hint > 0 ? cell_hint : (int)std::max(1.0, std::ceil(radius));
+  if (cell_hint <= 0) {
+    const double target = std::max(4.0, 0.5 * k);
+    const int cmin = cell;
+    for (int it = 0; it < 4 && fits(cell); it++) {
+      const int mb = morton_key_bits(ext, cell);
+      tiled_cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, d_off, nt, d_desc, cell, mb,
+                                                                ctx->keys_in.as<uint64_t>(), nullptr);
+      int64_t nc = 0;
+      rc = sort_count_keys(ctx, n, tbits + mb, &nc);
+      if (rc != BS_OK)
+        return rc;
+      double occ = (double)n / (double)std::max<int64_t>(nc, 1);
+      if (occ >= 0.7 * target && occ <= 1.6 * target)
+        break;
+      double f = std::sqrt(target / occ);
+      f = std::min(4.0, std::max(0.25, f));
+      int ncell = (int)std::floor(cell * f + 0.5);
+      ncell = std::max(ncell, cmin);
+      if (ncell == cell || (int64_t)ncell > ext)
+        break;
+      cell = ncell;
+    }
+  }
+  while (!fits(cell))
+    cell *= 2;
+  const int mbits = morton_key_bits(ext, cell);
+  BS_HIP(ctx, upload_desc(cell));
+
+  // 3. keys + sort: (tile, Morton cell)
+  uint64_t* kin = ctx->keys_in.as<uint64_t>();
+  uint64_t* kout = ctx->keys_out.as<uint64_t>();
+  int32_t* vin = ctx->vals_in.as<int32_t>();
+  int32_t* vout = ctx->vals_out.as<int32_t>();
+  tiled_cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, d_off, nt, d_desc, cell, mbits, kin, vin);
+  size_t tb = 0;
+  const int end_bit = tbits + mbits;
+  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
+  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+
+  // 4. unique cells, starts
+  BS_HIP(ctx, ctx->uniq_keys.reserve(sizeof(uint64_t) * n));
+  BS_HIP(ctx, ctx->uniq_cnt.reserve(sizeof(int32_t) * 2 * n));
+  uint64_t* ukeys = ctx->uniq_keys.as<uint64_t>();
+  int32_t* ucnt = ctx->uniq_cnt.as<int32_t>();
+  int32_t* ustart = ucnt + n;
+  int32_t* d_nruns = ctx->misc.as<int32_t>() + 32;
+  tb = 0;
+  BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(nullptr, tb, kout, ukeys, ucnt, d_nruns, (int)n, st));
+  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
+  BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(ctx->cub_tmp.p, tb, kout, ukeys, ucnt, d_nruns, (int)n, st));
+  int32_t nruns = 0;
+  BS_HIP(ctx, hipMemcpyAsync(&nruns, d_nruns, sizeof nruns, hipMemcpyDeviceToHost, st));
+  BS_HIP(ctx, hipStreamSynchronize(st));
+  if (nruns <= 0)
+    return fail(ctx, BS_ERR_INTERNAL, "grid: no occupied cells");
+  tb = 0;
+  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ucnt, ustart, nruns, st));
+  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
+  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(ctx->cub_tmp.p, tb, ucnt, ustart, nruns, st));
+
+  // 5. hash table keyed by the sort key itself (morton = 0: stored as it is)
+  uint32_t hs = 64;
+  while (hs < (uint32_t)nruns * 2u)
+    hs <<= 1;
+  BS_HIP(ctx, ctx->table.reserve(sizeof(CellEntry) * (size_t)hs));
+  CellEntry* table = ctx->table.as<CellEntry>();
+  table_clear_kernel<<<(hs + 255) / 256, 256, 0, st>>>(table, hs);
+  table_insert_kernel<<<(nruns + 255) / 256, 256, 0, st>>>(ukeys, ucnt, ustart, nruns, 0, table, hs - 1);
+
+  // 6. cell-sorted point copy (w = concatenation index)
+  BS_HIP(ctx, ctx->spts.reserve(sizeof(int4) * n));
+  gather_sorted_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, nullptr, vout, n, ctx->spts.as<int4>());
+  BS_HIP(ctx, hipGetLastError());
+
+  for (int a = 0; a < 3; a++) {
+    out->mn[a] = desc[0].mn[a];
+    out->dim[a] = desc[0].dim[a];
+  }
+  out->cell = cell;
+  out->hmask = hs - 1;
+  out->table = table;
+  out->spts = ctx->spts.as<int4>();
+  out->slocal = vout;
+  out->n = n;
+  out->tiles = d_desc;
+  out->tile_off = d_off;
+  out->n_tiles = nt;
+  out->mbits = mbits;
+  ctx->order_n = n;  // vals_out holds the cell-sorted order of the concatenation
   ctx->order_xyz = d_xyz;
   return BS_OK;
 }

@@ -245,6 +245,7 @@ int launch_region_grow_seq(bs_ctx* ctx, const int32_t* d_xyz, const double* d_no
 {
   hipStream_t st = ctx->stream;
   ctx->rg_valid = false;
+  ctx->bt_valid = false;
   ctx->rg_omega = nullptr;  // (the single-wave grower keeps no owner array: bs_owner_fetch_dev refuses)
   ctx->rg_prio = nullptr;
   ctx->rg_seeds = nullptr;

@@ -2398,6 +2398,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
 {
   hipStream_t st = ctx->stream;
   ctx->rg_valid = false;
+  ctx->bt_valid = false;
   ctx->rg_omega = nullptr;
   ctx->rg_prio = nullptr;
   ctx->rg_seeds = nullptr;

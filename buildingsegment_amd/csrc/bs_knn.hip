@@ -21,6 +21,7 @@
 // selection), are appended to a work list and finished by knn_general_kernel,
 // which keeps explicit sorted lists in scratch and falls back to a full scan.
 #include <cstdlib>
+#include <type_traits>
 
 #include "bs_common.h"
 #include "bs_normal.h"
@@ -32,10 +33,42 @@ namespace {
 constexpr int BS_FAST_RINGS = 2;     // 5x5x5 cells at most in the fast kernel
 constexpr int BS_GENERAL_RINGS = 6;  // then a full scan
 
-__device__ inline bool cell_lookup(const GridDev& g, uint32_t cx, uint32_t cy, uint32_t cz, int& start,
-                                   int& end)
+// Batched grids (TILED, bs_segment_batch): the kernels below take a TiledGridDev, every query first replaces the
+// grid's box by its tile's (tile_enter) and keys its cells by (tile << mbits) | Morton(cell) -- the key the table was
+// built with -- so it never sees a point of another tile.  The single-cloud instances (TILED = false) compile to the
+// code they had before the batch existed.
+template <bool TILED>
+using GridOf = std::conditional_t<TILED, TiledGridDev, GridDev>;
+
+template <bool TILED>
+__device__ inline uint64_t cell_key(uint32_t cx, uint32_t cy, uint32_t cz, uint64_t kbase)
 {
-  const uint64_t k = pack_cell(cx, cy, cz);
+  if constexpr (TILED)
+    return kbase | morton_cell(cx, cy, cz);
+  else
+    return pack_cell(cx, cy, cz);
+}
+
+// the query at sorted position s takes its tile's box; kbase = its key base, [lo, hi) = its sorted positions
+__device__ inline void tile_enter(TiledGridDev& g, int64_t s, uint64_t& kbase, int64_t& lo, int64_t& hi)
+{
+  const int32_t t = tile_of(g.tile_off, g.n_tiles, s);
+  const TileDesc d = g.tiles[t];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    g.mn[a] = d.mn[a];
+    g.dim[a] = d.dim[a];
+  }
+  kbase = (uint64_t)t << g.mbits;
+  lo = g.tile_off[t];
+  hi = g.tile_off[t + 1];
+}
+
+template <bool TILED = false>
+__device__ inline bool cell_lookup(const GridDev& g, uint32_t cx, uint32_t cy, uint32_t cz, int& start,
+                                   int& end, uint64_t kbase = 0)
+{
+  const uint64_t k = cell_key<TILED>(cx, cy, cz, kbase);
   uint32_t h = hash_cell(k) & g.hmask;
   for (;;) {
     const int4 raw = *reinterpret_cast<const int4*>(&g.table[h]);
@@ -88,8 +121,8 @@ __device__ inline void moments_add(Moments& m, int x, int y, int z)
   m.n += 1;
 }
 
-template <int KC>
-__global__ __launch_bounds__(256) void knn_fast_kernel(GridDev g, int64_t q_begin, int64_t q_end, int K,
+template <int KC, bool TILED = false>
+__global__ __launch_bounds__(256) void knn_fast_kernel(GridOf<TILED> g, int64_t q_begin, int64_t q_end, int K,
                                                        int max_nn, double r2, int32_t* __restrict__ neigh,
                                                        double* __restrict__ normals,
                                                        int32_t* __restrict__ fb_list,
@@ -103,6 +136,11 @@ __global__ __launch_bounds__(256) void knn_fast_kernel(GridDev g, int64_t q_begi
   const int32_t loc = g.slocal[s];
   if (loc < q_begin || loc >= q_end)
     return;
+  uint64_t kbase = 0;
+  if constexpr (TILED) {
+    int64_t lo, hi;
+    tile_enter(g, s, kbase, lo, hi);
+  }
   // runner-up: the smallest key that is NOT in the list (only needed when the list fills every slot, K == KC):
   // the (K+1)-th neighbour decides whether the list's boundary is an equal-d^2 tie
   uint64_t runner = ~0ull;
@@ -139,7 +177,7 @@ __global__ __launch_bounds__(256) void knn_fast_kernel(GridDev g, int64_t q_begi
           if (cx < 0 || cx >= g.dim[0])
             continue;
           int cs, ce;
-          if (!cell_lookup(g, (uint32_t)cx, (uint32_t)cy, (uint32_t)cz, cs, ce))
+          if (!cell_lookup<TILED>(g, (uint32_t)cx, (uint32_t)cy, (uint32_t)cz, cs, ce, kbase))
             continue;
           for (int t = cs; t < ce; t++) {
             const int4 c = g.spts[t];
@@ -245,8 +283,8 @@ constexpr int KBUF = 8;  // waiting candidates per thread of knn_fast2_kernel
 // 64-bit sums at the end -- exactly: sum x = n q + sum e, sum x^2 = n q^2 + 2 q sum e + sum e^2, sum xy = n qx qy +
 // qx sum ey + qy sum ex + sum ex ey.  Ten registers instead of nineteen and 24-bit multiplies instead of 64-bit
 // multiply-adds: the kernel drops below 128 registers (4 waves per SIMD instead of 3).
-template <int KC, bool REL32>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 && REL32 && BS_KNN_CAP4 ? 4 : 2))) void knn_fast2_kernel(GridDev g, int64_t q_begin, int64_t q_end, int K,
+template <int KC, bool REL32, bool TILED = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 && REL32 && BS_KNN_CAP4 ? 4 : 2))) void knn_fast2_kernel(GridOf<TILED> g, int64_t q_begin, int64_t q_end, int K,
                                                        int max_nn, double r2, int32_t* __restrict__ neigh,
                                                        double* __restrict__ normals,
                                                        int32_t* __restrict__ fb_list,
@@ -260,6 +298,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 &&
   const int32_t loc = g.slocal[s];
   if (loc < q_begin || loc >= q_end)
     return;
+  uint64_t kbase = 0;
+  if constexpr (TILED) {
+    int64_t lo, hi;
+    tile_enter(g, s, kbase, lo, hi);
+  }
   // runner-up: the smallest key that is NOT in the list (only needed when the list fills every slot, K == KC):
   // the (K+1)-th neighbour decides whether the list's boundary is an equal-d^2 tie
   uint64_t runner = ~0ull;
@@ -356,7 +399,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 &&
             const int dx = dx0 + u * step;
             const int cx = ci[0] + dx;
             want[u] = dx <= rho && cx >= 0 && cx < g.dim[0];
-            ck[u] = pack_cell((uint32_t)(want[u] ? cx : ci[0]), (uint32_t)cy, (uint32_t)cz);
+            ck[u] = cell_key<TILED>((uint32_t)(want[u] ? cx : ci[0]), (uint32_t)cy, (uint32_t)cz, kbase);
             hh[u] = hash_cell(ck[u]) & g.hmask;
             raw[u] = *reinterpret_cast<const int4*>(&g.table[hh[u]]);
           }
@@ -569,7 +612,8 @@ __device__ inline void hybrid_insert(uint64_t* d2s, int32_t* gids, int32_t* poss
   cnt = c + 1;
 }
 
-__global__ __launch_bounds__(64) void knn_general_kernel(GridDev g, int64_t q_begin, int K, int max_nn,
+template <bool TILED = false>
+__global__ __launch_bounds__(64) void knn_general_kernel(GridOf<TILED> g, int64_t q_begin, int K, int max_nn,
                                                          double r2, int32_t* __restrict__ neigh,
                                                          double* __restrict__ normals,
                                                          const int32_t* __restrict__ fb_list,
@@ -582,6 +626,10 @@ __global__ __launch_bounds__(64) void knn_general_kernel(GridDev g, int64_t q_be
   for (int w = blockIdx.x * blockDim.x + threadIdx.x; w < total; w += gridDim.x * blockDim.x) {
     const int32_t s = fb_list[w];
     const int32_t loc = g.slocal[s];
+    uint64_t kbase = 0;
+    int64_t scan_lo = 0, scan_hi = g.n;  // the full scan: the whole cloud, or the query's tile
+    if constexpr (TILED)
+      tile_enter(g, s, kbase, scan_lo, scan_hi);
     const int4 P = g.spts[s];
     const int q[3] = {P.x, P.y, P.z};
     const int ci[3] = {(int)((uint32_t)(P.x - g.mn[0]) / (uint32_t)g.cell),
@@ -608,7 +656,7 @@ __global__ __launch_bounds__(64) void knn_general_kernel(GridDev g, int64_t q_be
             if (cx < 0 || cx >= g.dim[0])
               continue;
             int cs, ce;
-            if (!cell_lookup(g, (uint32_t)cx, (uint32_t)cy, (uint32_t)cz, cs, ce))
+            if (!cell_lookup<TILED>(g, (uint32_t)cx, (uint32_t)cy, (uint32_t)cz, cs, ce, kbase))
               continue;
             for (int t = cs; t < ce; t++) {
               const int4 c = g.spts[t];
@@ -633,7 +681,7 @@ __global__ __launch_bounds__(64) void knn_general_kernel(GridDev g, int64_t q_be
       kc = 0;
       mc = 0;
       runner = ~0ull;
-      for (int64_t t = 0; t < g.n; t++) {
+      for (int64_t t = scan_lo; t < scan_hi; t++) {
         const int4 c = g.spts[t];
         const int64_t ex = (int64_t)c.x - q[0], ey = (int64_t)c.y - q[1], ez = (int64_t)c.z - q[2];
         const uint64_t d2 = (uint64_t)(ex * ex) + (uint64_t)(ey * ey) + (uint64_t)(ez * ez);
@@ -689,7 +737,8 @@ __global__ __launch_bounds__(64) void knn_general_kernel(GridDev g, int64_t q_be
 // 0.4 % of a uniform cloud's queries were 40 % of its stage-2 time.
 constexpr int GCAP = 2048;  // candidates per query in LDS (32 KB)
 
-__global__ __launch_bounds__(64) void knn_general_wave_kernel(GridDev g, int64_t q_begin, int K, int max_nn, double r2,
+template <bool TILED = false>
+__global__ __launch_bounds__(64) void knn_general_wave_kernel(GridOf<TILED> g, int64_t q_begin, int K, int max_nn, double r2,
                                                               int32_t* __restrict__ neigh, double* __restrict__ normals,
                                                               const int32_t* __restrict__ fb_list,
                                                               const int32_t* __restrict__ fb_count, uint64_t cert_r2,
@@ -705,6 +754,11 @@ __global__ __launch_bounds__(64) void knn_general_wave_kernel(GridDev g, int64_t
   for (int w = blockIdx.x; w < total; w += gridDim.x) {
     const int32_t s = fb_list[w];
     const int32_t loc = g.slocal[s];
+    uint64_t kbase = 0;
+    if constexpr (TILED) {
+      int64_t lo, hi;
+      tile_enter(g, s, kbase, lo, hi);
+    }
     const int4 P = g.spts[s];
     const int q[3] = {P.x, P.y, P.z};
     const int ci[3] = {(int)((uint32_t)(P.x - g.mn[0]) / (uint32_t)g.cell),
@@ -721,7 +775,7 @@ __global__ __launch_bounds__(64) void knn_general_wave_kernel(GridDev g, int64_t
         const int cheb = max(max(abs(dx), abs(dy)), abs(dz));
         int cs = 0, ce = 0;
         if (c < ncell && cheb == rho && cx >= 0 && cx < g.dim[0] && cy >= 0 && cy < g.dim[1] && cz >= 0 && cz < g.dim[2]) {
-          if (!cell_lookup(g, (uint32_t)cx, (uint32_t)cy, (uint32_t)cz, cs, ce))
+          if (!cell_lookup<TILED>(g, (uint32_t)cx, (uint32_t)cy, (uint32_t)cz, cs, ce, kbase))
             cs = ce = 0;
         }
         for (int t = cs; __ballot(t < ce) != 0; t++) {
@@ -851,8 +905,9 @@ __global__ void mark_all_kernel(GridDev g, int64_t q_begin, int64_t q_end, int32
 
 }  // namespace
 
-int launch_knn_normals(bs_ctx* ctx, const GridDev& g, int64_t q_begin, int64_t q_end, const bs_params& p,
-                       int32_t* d_neigh, double* d_normals, double cert_radius, int64_t* n_uncertified, int32_t* d_npos)
+template <bool TILED>
+static int launch_knn(bs_ctx* ctx, const GridOf<TILED>& g, int64_t q_begin, int64_t q_end, const bs_params& p,
+                      int32_t* d_neigh, double* d_normals, double cert_radius, int64_t* n_uncertified, int32_t* d_npos)
 {
   hipStream_t st = ctx->stream;
   const int64_t n = g.n;
@@ -889,33 +944,33 @@ int launch_knn_normals(bs_ctx* ctx, const GridDev& g, int64_t q_begin, int64_t q
     const bool buffered = getenv("BS_KNN_BUFFERED") ? atoi(getenv("BS_KNN_BUFFERED")) != 0 : true;
     const bool rel32 = r2 <= 32761.0 && !getenv("BS_KNN_MOMENTS64");  // r <= 181 mm (see REL32)
     if (buffered && p.k <= 16 && rel32)
-      knn_fast2_kernel<16, true><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
+      knn_fast2_kernel<16, true, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
                                                          fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
     else if (buffered && p.k <= 16)
-      knn_fast2_kernel<16, false><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
+      knn_fast2_kernel<16, false, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
                                                           fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
     else if (buffered && rel32)
-      knn_fast2_kernel<32, true><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
+      knn_fast2_kernel<32, true, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
                                                          fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
     else if (buffered)
-      knn_fast2_kernel<32, false><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
+      knn_fast2_kernel<32, false, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
                                                           fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
     else if (p.k <= 16)
-      knn_fast_kernel<16><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
+      knn_fast_kernel<16, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
                                                   fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
     else
-      knn_fast_kernel<32><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
+      knn_fast_kernel<32, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
                                                   fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
   } else {
     mark_all_kernel<<<blocks, 256, 0, st>>>(g, q_begin, q_end, fb_list, fb_count);
   }
   if (getenv("BS_KNN_GENERAL_THREAD")) {  // developer A/B switch: the one-thread kernel for the whole work list
-    knn_general_kernel<<<1024, 64, 0, st>>>(g, q_begin, p.k, p.max_nn, r2, d_neigh, d_normals, fb_list, fb_count, cert_r2,
+    knn_general_kernel<TILED><<<1024, 64, 0, st>>>(g, q_begin, p.k, p.max_nn, r2, d_neigh, d_normals, fb_list, fb_count, cert_r2,
                                             uncert, d_npos, tie_rows);
   } else {
-    knn_general_wave_kernel<<<8192, 64, 0, st>>>(g, q_begin, p.k, p.max_nn, r2, d_neigh, d_normals, fb_list, fb_count, cert_r2,
+    knn_general_wave_kernel<TILED><<<8192, 64, 0, st>>>(g, q_begin, p.k, p.max_nn, r2, d_neigh, d_normals, fb_list, fb_count, cert_r2,
                                                  uncert, d_npos, tie_rows, fb2_list, fb2_count);
-    knn_general_kernel<<<1024, 64, 0, st>>>(g, q_begin, p.k, p.max_nn, r2, d_neigh, d_normals, fb2_list, fb2_count, cert_r2,
+    knn_general_kernel<TILED><<<1024, 64, 0, st>>>(g, q_begin, p.k, p.max_nn, r2, d_neigh, d_normals, fb2_list, fb2_count, cert_r2,
                                             uncert, d_npos, tie_rows);
   }
   BS_HIP(ctx, hipGetLastError());
@@ -931,6 +986,19 @@ int launch_knn_normals(bs_ctx* ctx, const GridDev& g, int64_t q_begin, int64_t q
   if (n_uncertified)
     *n_uncertified = (int64_t)hu;
   return BS_OK;
+}
+
+int launch_knn_normals(bs_ctx* ctx, const GridDev& g, int64_t q_begin, int64_t q_end, const bs_params& p,
+                       int32_t* d_neigh, double* d_normals, double cert_radius, int64_t* n_uncertified, int32_t* d_npos)
+{
+  return launch_knn<false>(ctx, g, q_begin, q_end, p, d_neigh, d_normals, cert_radius, n_uncertified, d_npos);
+}
+
+// every point of the batch is a query; rows and normals by concatenation index, neighbours as concatenation indices
+int launch_knn_normals_tiled(bs_ctx* ctx, const TiledGridDev& g, const bs_params& p, int32_t* d_neigh,
+                             double* d_normals, int32_t* d_npos)
+{
+  return launch_knn<true>(ctx, g, 0, g.n, p, d_neigh, d_normals, 0.0, nullptr, d_npos);
 }
 
 }  // namespace bs

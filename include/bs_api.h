@@ -271,6 +271,31 @@ int bs_set_audit(bs_ctx* ctx, int on);
 /* Copy the plane records of the last region-grow on this context to the host. */
 int bs_planes_fetch(bs_ctx* ctx, bs_planes* planes);
 
+/* ---- batches of independent tiles in one pass ----
+ *
+ * n_tiles independent clouds segmented in one device pass.  xyz is their concatenation; tile t is the points
+ * [tile_offset[t], tile_offset[t+1]) (host array, tile_offset[0] == 0, non-decreasing, every tile >= k points, fewer
+ * than INT32_MAX - 64 points in all).  Every output equals what bs_segment returns for that tile alone, bit for bit:
+ *   neigh rows hold TILE-LOCAL indices; plane_idx numbers planes from 1 in every tile;
+ *   planes is the concatenation of the per-tile plane lists (ids from 1 per tile, point_idx tile-local);
+ *   plane_offset [n_tiles+1] (host out) delimits each tile's planes inside it.
+ * The search grid keys cells by (tile, cell), so tiles that overlap or touch in space never see each other; the
+ * grower runs once over the concatenation (the sequential rule gives each tile its solo result) and
+ * the outputs are renumbered on the device.  BS_ERR_INVALID names the offending tile; BS_ERR_RANGE: a coordinate
+ * outside |c| < 2^23 mm (shift every tile to its own origin first: bs_shift_tiles_to_origin_dev).  neigh, normals,
+ * planes and plane_offset are nullable; the _dev form's d_neigh / d_normals may be NULL (context scratch). */
+int bs_segment_batch(bs_ctx* ctx, const int32_t* xyz, const int64_t* tile_offset, int32_t n_tiles, const bs_params* p,
+                     int32_t* neigh, double* normals, int32_t* plane_idx, bs_planes* planes, int32_t* plane_offset);
+int bs_segment_batch_dev(bs_ctx* ctx, const int32_t* d_xyz, const int64_t* tile_offset, int32_t n_tiles,
+                         const bs_params* p, int32_t* d_neigh, double* d_normals, int32_t* d_plane_idx);
+/* The plane records of the last bs_segment_batch[_dev] on this context, renumbered per tile (see above);
+ * plane_offset [n_tiles+1] (host, nullable). */
+int bs_batch_planes_fetch(bs_ctx* ctx, bs_planes* planes, int32_t* plane_offset);
+/* bs_shift_to_origin_dev applied to every tile separately (TMC3.cpp:55-73 per tile): min_out [n_tiles][3] (host,
+ * nullable) receives each tile's subtracted minimum.  Offsets as above (every tile >= 1 point).  Synchronises. */
+int bs_shift_tiles_to_origin_dev(bs_ctx* ctx, int32_t* d_xyz, const int64_t* tile_offset, int32_t n_tiles,
+                                 int32_t* min_out);
+
 /* ---- building blocks of the multi-GPU path (component-sharded stage 3) ----
  *
  * The reference's seed scan (my_function.cpp:184-217) is global, but information only travels along kNN edges
