@@ -27,7 +27,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_comm_rccl_destroy", "bs_comm_local_create", "bs_comm_local_destroy", "bs_segment_sharded",
            "bs_sharded_planes_fetch", "bs_footprints_dev", "bs_footprints", "bs_contours_free",
            "bs_contours_write_obj", "bs_segment_batch", "bs_segment_batch_dev", "bs_batch_planes_fetch",
-           "bs_shift_tiles_to_origin_dev"]
+           "bs_shift_tiles_to_origin_dev", "bs_tile_boxes_dev", "bs_grid_dims_batch", "bs_grid_picture_batch_dev",
+           "bs_grid_picture_batch", "bs_footprints_batch_dev", "bs_footprints_batch"]
 
 
 class Params(C.Structure):
@@ -168,5 +169,13 @@ def load():
     L.bs_segment_batch_dev.argtypes = [vp, ip, vp, C.c_int32, pp, ip, dp, ip]
     L.bs_batch_planes_fetch.argtypes = [vp, C.POINTER(Planes), ip]
     L.bs_shift_tiles_to_origin_dev.argtypes = [vp, ip, vp, C.c_int32, ip]
+    L.bs_tile_boxes_dev.argtypes = [vp, ip, vp, C.c_int32, ip]
+    L.bs_grid_dims_batch.argtypes = [ip, C.c_int32, C.c_int32, ip, ip, vp]
+    L.bs_grid_picture_batch_dev.argtypes = [vp, ip, vp, C.c_int32, ip, C.c_int32, C.c_int32, dp, dp]
+    L.bs_grid_picture_batch.argtypes = [vp, ip, vp, C.c_int32, ip, C.c_int32, C.c_int32, dp, dp]
+    L.bs_footprints_batch_dev.argtypes = [vp, vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, cp, ip,
+                                          C.POINTER(FootprintInfo)]
+    L.bs_footprints_batch.argtypes = [vp, vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, cp, ip,
+                                      C.POINTER(FootprintInfo)]
     _LIB = L
     return L

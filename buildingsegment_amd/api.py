@@ -356,6 +356,83 @@ class Context:
                                                          mn.ctypes.data))
         return mn
 
+    # ---- batches of rasters and footprints (bs_grid_picture_batch, bs_footprints_batch) ----
+    def tile_boxes_dev(self, d_xyz, tile_offset):
+        """Per-tile {min x, y, z, max x, y, z} of a device-resident concatenation: int32 [n_tiles, 6]."""
+        off = _tile_offsets(tile_offset)
+        box = np.zeros((len(off) - 1, 6), dtype=np.int32)
+        self._check(self._L.bs_tile_boxes_dev(self._h, d_xyz, off.ctypes.data, len(off) - 1, box.ctypes.data))
+        return box
+
+    def grid_picture_batch(self, tiles, extents=None, bin=100, bin_height=1000, shift_to_origin=False):
+        """grid_picture for every tile of a list of int32 [n_t, 3] clouds, in one device pass.  Returns one
+        (image [height][width][3] f64, ground_th) per tile, each what grid_picture returns for that tile alone.
+        extents: [n_tiles, 3] (default: each tile's maximum); shift_to_origin: move every tile to its own
+        bounding-box origin first."""
+        xyz, off = pack_tiles(tiles)
+        if shift_to_origin:
+            xyz = shift_tiles_to_origin(xyz, off)
+        nt = len(off) - 1
+        ext = _tile_extents(np.maximum.reduceat(xyz, off[:-1], axis=0) if extents is None else extents, nt)
+        w, h, po = grid_dims_batch(ext, bin)
+        img = np.empty(3 * int(po[-1]), dtype=np.float64)
+        th = np.empty(nt, dtype=np.float64)
+        self._check(self._L.bs_grid_picture_batch(self._h, xyz.ctypes.data, off.ctypes.data, nt, ext.ctypes.data, bin,
+                                                  bin_height, img.ctypes.data, th.ctypes.data))
+        return [(img[3 * po[t]:3 * po[t + 1]].reshape(h[t], w[t], 3), float(th[t])) for t in range(nt)]
+
+    def grid_picture_batch_dev(self, d_xyz, tile_offset, extents, d_image, bin=100, bin_height=1000):
+        """Device form: d_xyz holds the shifted tiles, d_image receives the images at grid_dims_batch's pixel
+        offsets (device pointers, ints).  Returns the ground thresholds [n_tiles]."""
+        off = _tile_offsets(tile_offset)
+        nt = len(off) - 1
+        ext = _tile_extents(extents, nt)
+        th = np.empty(nt, dtype=np.float64)
+        self._check(self._L.bs_grid_picture_batch_dev(self._h, d_xyz, off.ctypes.data, nt, ext.ctypes.data, bin,
+                                                      bin_height, d_image, th.ctypes.data))
+        return th
+
+    def footprints_batch(self, images, threshold=10, kernel_size=5, iterations=2, return_mask=False):
+        """footprints for every [height][width][3] f64 raster of a list, in one device pass.  Returns one
+        Footprints per tile (with that tile's width and height; info: the whole pass) and, with return_mask, the
+        list of closed masks as well."""
+        if isinstance(images, np.ndarray) or not hasattr(images, "__len__") or len(images) == 0:
+            raise ValueError("images must be a non-empty list of [height][width][3] arrays")
+        imgs = []
+        for t, a in enumerate(images):
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError(f"footprints_batch: tile {t}: image must be [height][width][3], got {a.shape}")
+            imgs.append(a)
+        nt = len(imgs)
+        w = np.array([a.shape[1] for a in imgs], dtype=np.int32)
+        h = np.array([a.shape[0] for a in imgs], dtype=np.int32)
+        po = np.zeros(nt + 1, dtype=np.int64)
+        po[1:] = np.cumsum(w.astype(np.int64) * h)
+        flat = np.ascontiguousarray(np.concatenate([a.reshape(-1) for a in imgs]))
+        mask = np.empty(int(po[-1]), dtype=np.uint8) if return_mask else None
+        out, inf, co = Contours(), FootprintInfo(), np.zeros(nt + 1, dtype=np.int32)
+        self._check(self._L.bs_footprints_batch(self._h, flat.ctypes.data, w.ctypes.data, h.ctypes.data, nt, threshold,
+                                                kernel_size, iterations, mask.ctypes.data if return_mask else None,
+                                                C.byref(out), co.ctypes.data, C.byref(inf)))
+        fps = _take_contours_batch(self._L, out, inf, co, w, h)
+        if return_mask:
+            return fps, [mask[po[t]:po[t + 1]].reshape(h[t], w[t]) for t in range(nt)]
+        return fps
+
+    def footprints_batch_dev(self, d_image, widths, heights, threshold=10, kernel_size=5, iterations=2, d_mask=0):
+        """Device form: d_image holds the tile images at grid_dims_batch's pixel offsets, d_mask (optional) receives
+        the closed masks at the same offsets (device pointers, ints).  Returns one Footprints per tile."""
+        w = np.ascontiguousarray(widths, dtype=np.int32)
+        h = np.ascontiguousarray(heights, dtype=np.int32)
+        if w.ndim != 1 or w.shape != h.shape or len(w) == 0:
+            raise ValueError("widths and heights must be 1-D arrays of the same length >= 1")
+        out, inf, co = Contours(), FootprintInfo(), np.zeros(len(w) + 1, dtype=np.int32)
+        self._check(self._L.bs_footprints_batch_dev(self._h, d_image or None, w.ctypes.data, h.ctypes.data, len(w),
+                                                    threshold, kernel_size, iterations, d_mask or None, C.byref(out),
+                                                    co.ctypes.data, C.byref(inf)))
+        return _take_contours_batch(self._L, out, inf, co, w, h)
+
 
 @dataclass
 class Footprints:
@@ -372,7 +449,8 @@ class Footprints:
         return [i for i in range(len(self.contours)) if self.area[i] > min_area and self.perimeter[i] > min_perimeter]
 
 
-def _take_contours(L, out: Contours, inf: FootprintInfo) -> Footprints:
+def _contour_arrays(L, out: Contours):
+    """(offset, xy, area, perimeter) copied out of a bs_contours, which is released."""
     n = out.n_contours
     try:
         off = np.ctypeslib.as_array(out.offset, (n + 1,)).copy() if out.offset else np.zeros(1, np.int64)
@@ -380,11 +458,25 @@ def _take_contours(L, out: Contours, inf: FootprintInfo) -> Footprints:
         xy = np.ctypeslib.as_array(out.xy, (2 * tot,)).reshape(tot, 2).copy() if tot else np.zeros((0, 2), np.int32)
         area = np.ctypeslib.as_array(out.area, (n,)).copy() if n else np.zeros(0)
         per = np.ctypeslib.as_array(out.perimeter, (n,)).copy() if n else np.zeros(0)
-        w, h = out.width, out.height
     finally:
         L.bs_contours_free(C.byref(out))
+    return off, xy, area, per
+
+
+def _take_contours(L, out: Contours, inf: FootprintInfo) -> Footprints:
+    n, w, h = out.n_contours, out.width, out.height
+    off, xy, area, per = _contour_arrays(L, out)
     return Footprints([xy[off[i]:off[i + 1]] for i in range(n)], area, per, w, h,
                       {k: getattr(inf, k) for k, _ in FootprintInfo._fields_})
+
+
+def _take_contours_batch(L, out: Contours, inf: FootprintInfo, co, widths, heights) -> list:
+    """One Footprints per tile of a bs_footprints_batch result: contours co[t] .. co[t+1] - 1."""
+    off, xy, area, per = _contour_arrays(L, out)
+    info = {k: getattr(inf, k) for k, _ in FootprintInfo._fields_}
+    return [Footprints([xy[off[i]:off[i + 1]] for i in range(co[t], co[t + 1])], area[co[t]:co[t + 1]].copy(),
+                       per[co[t]:co[t + 1]].copy(), int(widths[t]), int(heights[t]), info)
+            for t in range(len(widths))]
 
 
 def write_footprints_obj(fp: Footprints, path):
@@ -444,6 +536,34 @@ def shift_tiles_to_origin(xyz, tile_offset) -> np.ndarray:
     if out.max(initial=0) > np.iinfo(np.int32).max:
         raise ValueError("a tile's extent does not fit int32")
     return out.astype(np.int32)
+
+
+def _tile_extents(extents, n_tiles) -> np.ndarray:
+    ext = np.asarray(extents)
+    if ext.shape != (n_tiles, 3):
+        raise ValueError(f"extents must be [n_tiles, 3] = [{n_tiles}, 3], got {ext.shape}")
+    if not np.issubdtype(ext.dtype, np.integer):
+        raise TypeError(f"extents: dtype {ext.dtype}, expected integers (mm)")
+    if ext.size and (ext.min() < 0 or ext.max() > np.iinfo(np.int32).max):
+        raise ValueError("extents must lie in [0, 2^31)")
+    return np.ascontiguousarray(ext, dtype=np.int32)
+
+
+def grid_dims_batch(extents, bin=100):
+    """grid_dims for every tile: (widths int32 [n_tiles], heights int32 [n_tiles], pixel_offset int64 [n_tiles + 1]);
+    tile t's image is pixels pixel_offset[t] .. pixel_offset[t + 1] - 1 of the batch image (bs_grid_dims_batch)."""
+    ext = np.asarray(extents)
+    if ext.ndim != 2 or len(ext) == 0:
+        raise ValueError("extents must be a non-empty [n_tiles, 3] array")
+    ext = _tile_extents(ext, len(ext))
+    nt = len(ext)
+    w = np.empty(nt, dtype=np.int32)
+    h = np.empty(nt, dtype=np.int32)
+    po = np.empty(nt + 1, dtype=np.int64)
+    rc = _lib.load().bs_grid_dims_batch(ext.ctypes.data, nt, int(bin), w.ctypes.data, h.ctypes.data, po.ctypes.data)
+    if rc != 0:
+        raise ValueError("bs_grid_dims_batch: invalid extent / bin")
+    return w, h, po
 
 
 def grid_dims(extent, bin=100):

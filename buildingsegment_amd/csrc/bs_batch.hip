@@ -1,5 +1,6 @@
 // bs_batch.hip -- n_tiles independent clouds in one device pass (bs_segment_batch[_dev], bs_batch_planes_fetch,
-// bs_shift_tiles_to_origin_dev; declarations: include/bs_api.h, argument: DESIGN.md §4 "Batches of tiles").
+// bs_shift_tiles_to_origin_dev, bs_tile_boxes_dev; declarations: include/bs_api.h, argument: DESIGN.md §4 "Batches of
+// tiles").
 //
 // The grid (bs_grid.hip, build_grid_tiled) and the kNN (bs_knn.hip, TILED instances) never let a query see another
 // tile, so every neighbour row holds indices of its own tile, in the concatenation's numbering.  The growers then run
@@ -86,7 +87,30 @@ __global__ void list_local_kernel(const int32_t* __restrict__ list, const GrowSt
 
 inline int blocks_of(int64_t n, int bs) { return (int)std::max<int64_t>(1, (n + bs - 1) / bs); }
 
-// tile_offset checks shared by every batch entry point; min_pts = k (segmentation) or 1 (shift)
+// the offsets as int32 on the device (BT_OFF)
+int upload_offsets(bs_ctx* ctx, const std::vector<int64_t>& off)
+{
+  std::vector<int32_t> o32(off.begin(), off.end());
+  BS_HIP(ctx, ctx->bt[BT_OFF].reserve(sizeof(int32_t) * o32.size()));
+  BS_HIP(ctx, hipMemcpyAsync(ctx->bt[BT_OFF].p, o32.data(), sizeof(int32_t) * o32.size(), hipMemcpyHostToDevice,
+                             ctx->stream));
+  BS_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (o32 is a host temporary)
+  return BS_OK;
+}
+
+struct Timer {
+  bs_ctx* ctx;
+  void mark(int i) { (void)hipEventRecord(ctx->ev[i], ctx->stream); }
+  double ms(int i, int j)
+  {
+    float t = 0.f;
+    return hipEventElapsedTime(&t, ctx->ev[i], ctx->ev[j]) == hipSuccess ? (double)t : 0.0;
+  }
+};
+
+}  // namespace
+
+// tile_offset checks shared by every batch entry point (bs_common.h); min_pts = k (segmentation) or 1 (shift, rasters)
 int check_tiles(bs_ctx* ctx, const int64_t* off, int32_t n_tiles, int64_t min_pts, int64_t* total)
 {
   char msg[160];
@@ -117,29 +141,6 @@ int check_tiles(bs_ctx* ctx, const int64_t* off, int32_t n_tiles, int64_t min_pt
   *total = off[n_tiles];
   return BS_OK;
 }
-
-// the offsets as int32 on the device (BT_OFF)
-int upload_offsets(bs_ctx* ctx, const std::vector<int64_t>& off)
-{
-  std::vector<int32_t> o32(off.begin(), off.end());
-  BS_HIP(ctx, ctx->bt[BT_OFF].reserve(sizeof(int32_t) * o32.size()));
-  BS_HIP(ctx, hipMemcpyAsync(ctx->bt[BT_OFF].p, o32.data(), sizeof(int32_t) * o32.size(), hipMemcpyHostToDevice,
-                             ctx->stream));
-  BS_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (o32 is a host temporary)
-  return BS_OK;
-}
-
-struct Timer {
-  bs_ctx* ctx;
-  void mark(int i) { (void)hipEventRecord(ctx->ev[i], ctx->stream); }
-  double ms(int i, int j)
-  {
-    float t = 0.f;
-    return hipEventElapsedTime(&t, ctx->ev[i], ctx->ev[j]) == hipSuccess ? (double)t : 0.0;
-  }
-};
-
-}  // namespace
 
 }  // namespace bs
 
@@ -339,6 +340,28 @@ int bs_shift_tiles_to_origin_dev(bs_ctx* ctx, int32_t* d_xyz, const int64_t* til
       for (int a = 0; a < 3; a++)
         min_out[3 * t + a] = bb[6 * t + a];
   ctx->order_n = 0;  // coordinates changed: a cached cell order no longer applies
+  return BS_OK;
+}
+
+int bs_tile_boxes_dev(bs_ctx* ctx, const int32_t* d_xyz, const int64_t* tile_offset, int32_t n_tiles,
+                      int32_t* box_out)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  int64_t n = 0;
+  int rc = check_tiles(ctx, tile_offset, n_tiles, 1, &n);
+  if (rc != BS_OK)
+    return rc;
+  if (!d_xyz || !box_out)
+    return fail(ctx, BS_ERR_INVALID, "null pointer");
+  BS_HIP(ctx, hipSetDevice(ctx->device));
+  std::vector<int64_t> off(tile_offset, tile_offset + n_tiles + 1);
+  BS_HIP(ctx, ctx->bt[BT_MNMX].reserve(sizeof(int32_t) * 6 * n_tiles));
+  std::vector<int32_t> bb;
+  rc = tile_bbox_dev(ctx, d_xyz, nullptr, off, ctx->bt[BT_MNMX].as<int32_t>(), bb);
+  if (rc != BS_OK)
+    return rc;
+  memcpy(box_out, bb.data(), sizeof(int32_t) * bb.size());
   return BS_OK;
 }
 

@@ -233,6 +233,7 @@ void bs_destroy(bs_ctx* c)
     b.release();
   for (auto& b : c->bt)
     b.release();
+  c->tile_desc.release();
   c->rg_hout.release();
   for (auto& e : c->ev)
     if (e)

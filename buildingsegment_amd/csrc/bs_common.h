@@ -250,6 +250,8 @@ struct bs_ctx {
   bs::DevBuf bt[bs::BT_COUNT];
   std::vector<int64_t> bt_off;
   bool bt_valid = false;
+  // per-tile descriptors of bs_grid_picture_batch_dev / bs_footprints_batch_dev (uploaded by each call)
+  bs::DevBuf tile_desc;
 };
 
 namespace bs {
@@ -273,6 +275,8 @@ int tile_bbox_dev(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_off, const
                   int32_t* d_mnmx, std::vector<int32_t>& mnmx);
 int build_grid_tiled(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_off, const std::vector<int64_t>& off,
                      double radius, int k, int cell_hint, TiledGridDev* out);
+// batch.hip: tile_offset checks of every batch entry point (errors name the tile); *total = tile_offset[n_tiles]
+int check_tiles(bs_ctx* ctx, const int64_t* off, int32_t n_tiles, int64_t min_pts, int64_t* total);
 void launch_tile_shift(bs_ctx* ctx, int32_t* d_xyz, int64_t n, const int32_t* d_off, int32_t n_tiles,
                        const int32_t* d_mnmx);
 // knn.hip

@@ -443,6 +443,55 @@ void bs_contours_free(bs_contours* c);
  * z = 1, x = x / width, y = 1 - y / height (float).  Host only; BS_ERR_INVALID if the file cannot be written. */
 int bs_contours_write_obj(const bs_contours* c, const char* path);
 
+/* ---- batches of rasters and footprints: every output the reference's main produces for a block, per tile ----
+ *
+ * Tiles follow the batch conventions above: tile_offset [n_tiles+1] (host, int64) starts at 0 and rises strictly
+ * (every tile >= 1 point).  Every per-tile output equals, bit for bit, what the solo call returns for that tile
+ * alone; error texts name the offending tile.  Limits are the solo ones applied to the batch totals: fewer than
+ * 2^29 points (BS_ERR_RANGE), fewer than 2^31 - 1 pixels (BS_ERR_RANGE), fewer than 2^31 padded pixels
+ * (W+2)(H+2) (BS_ERR_INVALID), fewer than 2^31 border states (BS_ERR_RANGE).  A failed call leaves the context
+ * usable.  A device pipeline runs bs_shift_tiles_to_origin_dev -> bs_tile_boxes_dev (extents = max - min of the
+ * shifted tiles) -> bs_grid_dims_batch -> bs_grid_picture_batch_dev -> bs_footprints_batch_dev. */
+
+/* Per-tile {min x,y,z, max x,y,z} of a device-resident concatenation (host out [n_tiles][6]); synchronises.
+ * A device pipeline gets its raster extents from this without copying the cloud back. */
+int bs_tile_boxes_dev(bs_ctx* ctx, const int32_t* d_xyz, const int64_t* tile_offset, int32_t n_tiles,
+                      int32_t* box_out);
+
+/* Host only, no context: width[t], height[t] as bs_grid_dims for extent[t] ([n_tiles][3]), and
+ * pixel_offset[n_tiles+1] (int64) = exclusive prefix sum of width*height.  Tile t's image is the
+ * [height[t]][width[t]][3] f64 block starting at pixel pixel_offset[t] of the batch image.  BS_ERR_INVALID if
+ * n_tiles < 1, a pointer is NULL or any tile's extent / bin is invalid for bs_grid_dims. */
+int bs_grid_dims_batch(const int32_t* extent, int32_t n_tiles, int32_t bin, int32_t* width, int32_t* height,
+                       int64_t* pixel_offset);
+
+/* bs_grid_picture_dev for every tile (each already shifted to its own origin, e.g. by
+ * bs_shift_tiles_to_origin_dev), in one pass: per-tile ground threshold (ground_th: host [n_tiles], nullable),
+ * images at pixel_offset.  BS_ERR_RANGE names the first tile with a point outside [0, extent[t]].  Synchronises. */
+int bs_grid_picture_batch_dev(bs_ctx* ctx, const int32_t* d_xyz, const int64_t* tile_offset, int32_t n_tiles,
+                              const int32_t* extent, int32_t bin, int32_t bin_height, double* d_image,
+                              double* ground_th);
+/* Host-memory variant: xyz and image are host pointers. */
+int bs_grid_picture_batch(bs_ctx* ctx, const int32_t* xyz, const int64_t* tile_offset, int32_t n_tiles,
+                          const int32_t* extent, int32_t bin, int32_t bin_height, double* image, double* ground_th);
+
+/* bs_footprints_dev for every tile image of the batch layout above (width/height: host [n_tiles]).
+ * out is the concatenation of the per-tile contour lists, tile-major, each tile in its solo order;
+ * contour_offset [n_tiles+1] (host out) delimits them; out->width = out->height = 0.
+ * d_mask (nullable): per-tile closed masks, [height[t]][width[t]] bytes at pixel_offset[t].
+ * info (nullable): stage times of the whole pass and totals over all tiles (jump_rounds: of the one ranking).
+ * Tile t as a bs_contours of its own is the view {n_contours = co[t+1] - co[t], width[t], height[t],
+ * offset = out.offset + co[t], the same xy, area + co[t], perimeter + co[t]}: bs_contours_write_obj reads offset
+ * as absolute positions into xy, so the view writes the same bytes as the solo result.  Release out (not the
+ * views) with bs_contours_free.  Synchronises. */
+int bs_footprints_batch_dev(bs_ctx* ctx, const double* d_image, const int32_t* width, const int32_t* height,
+                            int32_t n_tiles, int32_t threshold, int32_t kernel_size, int32_t iterations,
+                            uint8_t* d_mask, bs_contours* out, int32_t* contour_offset, bs_footprint_info* info);
+/* Host-memory variant: image and mask (nullable) are host pointers. */
+int bs_footprints_batch(bs_ctx* ctx, const double* image, const int32_t* width, const int32_t* height,
+                        int32_t n_tiles, int32_t threshold, int32_t kernel_size, int32_t iterations, uint8_t* mask,
+                        bs_contours* out, int32_t* contour_offset, bs_footprint_info* info);
+
 #ifdef __cplusplus
 }
 #endif
