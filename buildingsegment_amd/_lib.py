@@ -21,7 +21,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_set_stream", "bs_get_timings", "bs_knn_normals", "bs_knn_normals_halo", "bs_region_grow", "bs_segment",
            "bs_planes_free", "bs_plane_colors", "bs_knn_normals_dev", "bs_region_grow_dev",
            "bs_segment_dev", "bs_planes_fetch", "bs_shift_to_origin_dev", "bs_plane_colors_dev",
-           "bs_selftest_center_div", "bs_selftest_forge_next", "bs_set_audit", "bs_ingest_dev", "bs_grid_dims", "bs_grid_picture", "bs_grid_picture_dev",
+           "bs_selftest_center_div", "bs_selftest_forge_next", "bs_set_audit", "bs_selftest_grow_limits",
+           "bs_get_grow_counters", "bs_ingest_dev", "bs_grid_dims", "bs_grid_picture", "bs_grid_picture_dev",
            "bs_cc_hook_dev", "bs_owner_fetch_dev", "bs_labels_from_owner_dev", "bs_remap_rows_dev",
            "bs_plane_seeds_dev", "bs_stream_sync", "bs_comm_rccl", "bs_comm_rccl_unique_id", "bs_comm_rccl_init",
            "bs_comm_rccl_destroy", "bs_comm_local_create", "bs_comm_local_destroy", "bs_segment_sharded",
@@ -53,6 +54,20 @@ class Timings(C.Structure):
                 ("tie_rows", C.c_int64), ("rej_v1_robbed", C.c_int64), ("rej_v1_tag", C.c_int64), ("rej_v1_dup", C.c_int64),
                 ("rej_v3_state", C.c_int64), ("incons_seed", C.c_int64), ("incons_list", C.c_int64),
                 ("incons_log", C.c_int64)]
+
+
+class GrowLimits(C.Structure):
+    """bs_grow_limits (include/bs_api.h): capacities 0 = default, policies < 0 = default."""
+    _fields_ = [("max_waves", C.c_int64), ("pool_cap", C.c_int64), ("max_pending", C.c_int64), ("pstore_cap", C.c_int64),
+                ("retry_max_list", C.c_int32), ("retry_big_round", C.c_int32), ("full_refresh", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class GrowCounters(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in
+                ("rounds", "rounds_capped", "rounds_big", "attempts_nomem", "waves_cut", "max_waves_end", "attempts_stolen",
+                 "dropped_pend_count", "dropped_pend_store", "dropped_other", "full_refreshes", "pool_cap")]
+
 
 API_VERSION = 5  # BS_API_VERSION of include/bs_api.h this loader mirrors
 
@@ -137,6 +152,8 @@ def load():
     L.bs_plane_colors_dev.argtypes = [vp, ip, C.c_int32, C.c_int64, vp]
     L.bs_selftest_forge_next.argtypes = [vp, C.c_int]
     L.bs_set_audit.argtypes = [vp, C.c_int]
+    L.bs_selftest_grow_limits.argtypes = [vp, C.POINTER(GrowLimits)]
+    L.bs_get_grow_counters.argtypes = [vp, C.POINTER(GrowCounters)]
     L.bs_selftest_center_div.argtypes = [vp, ip, vp, ip, C.c_int64]
     L.bs_grid_dims.argtypes = [ip, C.c_int32, ip, ip]
     L.bs_grid_picture.argtypes = [vp, ip, C.c_int64, ip, C.c_int32, C.c_int32, dp, dp]

@@ -249,6 +249,21 @@ class Context:
         timings()['audit_mismatches'] must be 0."""
         self._check(self._L.bs_set_audit(self._h, 1 if on else 0))
 
+    def selftest_grow_limits(self, max_waves=0, pool_cap=0, max_pending=0, pstore_cap=0, retry_max_list=-1,
+                             retry_big_round=-1, full_refresh=False):
+        """Lower the speculative grower's capacities for the following grows on this context (see
+        bs_selftest_grow_limits; capacities 0 = default and only ever lowered, policies -1 = default).
+        Called without arguments it clears every limit.  grow_counters() tells which were reached."""
+        lim = _lib.GrowLimits(int(max_waves), int(pool_cap), int(max_pending), int(pstore_cap), int(retry_max_list),
+                              int(retry_big_round), 1 if full_refresh else 0, 0)
+        self._check(self._L.bs_selftest_grow_limits(self._h, C.byref(lim)))
+
+    def grow_counters(self) -> dict:
+        """bs_grow_counters of the last speculative region grow on this context (also after a failed one)."""
+        g = _lib.GrowCounters()
+        self._check(self._L.bs_get_grow_counters(self._h, C.byref(g)))
+        return {k: getattr(g, k) for k, _ in _lib.GrowCounters._fields_}
+
     # ---- building blocks of the component-sharded stage 3 (device pointers) ----
     def cc_hook_dev(self, d_rows, d_gidx, m, k, d_parent, n_total) -> int:
         """One hooking step of the distributed union-find (bs_cc_hook_dev); returns the unions performed."""

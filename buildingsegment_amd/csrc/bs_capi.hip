@@ -380,6 +380,25 @@ int bs_set_audit(bs_ctx* ctx, int on)
   return BS_OK;
 }
 
+int bs_selftest_grow_limits(bs_ctx* ctx, const bs_grow_limits* lim)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  const bs_grow_limits none = {0, 0, 0, 0, -1, -1, 0, 0};
+  if (lim && (lim->max_waves < 0 || lim->pool_cap < 0 || lim->max_pending < 0 || lim->pstore_cap < 0))
+    return fail(ctx, BS_ERR_INVALID, "bs_selftest_grow_limits: a capacity is negative (0 = default)");
+  ctx->lim = lim ? *lim : none;
+  return BS_OK;
+}
+
+int bs_get_grow_counters(const bs_ctx* ctx, bs_grow_counters* out)
+{
+  if (!ctx || !out)
+    return BS_ERR_INVALID;
+  *out = ctx->gc;
+  return BS_OK;
+}
+
 int bs_planes_fetch(bs_ctx* ctx, bs_planes* out)
 {
   if (!ctx || !out)

@@ -227,6 +227,8 @@ struct bs_ctx {
   int32_t rg_nplanes = 0;
   int forge_mode = 0;  // bs_selftest_forge_next
   int audit = 0;       // bs_set_audit
+  bs_grow_limits lim{0, 0, 0, 0, -1, -1, 0, 0};  // bs_selftest_grow_limits (all defaults)
+  bs_grow_counters gc{};                         // bs_get_grow_counters
   hipStream_t side = nullptr;  // second stream of the grower (validate3 beside the owner passes)
   hipEvent_t sev[2] = {nullptr, nullptr};
   // 2-D raster scratch (bs_raster.hip)

@@ -303,6 +303,7 @@ int launch_region_grow_seq(bs_ctx* ctx, const int32_t* d_xyz, const double* d_no
     ctx->tm.audit_attempts = -1;  // the sequential baseline needs no audit
     ctx->tm.audit_mismatches = 0;
     ctx->tm.audit_ms = 0.0;
+    ctx->gc = bs_grow_counters{};  // no rounds, no pools: nothing to count
   }
   return BS_OK;
 }

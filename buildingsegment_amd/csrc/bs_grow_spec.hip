@@ -2408,15 +2408,25 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   const int64_t planes_cap = n / std::max(1, p.th_point_count) + 64;
   // round pool: lists + stacks + logs of every concurrent attempt
   // concurrent plane attempts per round: more waves let late-index planes start in earlier rounds
+  // (lim: bs_selftest_grow_limits, the in-process form of the BS_* switches below; read once, here and further down)
+  const bs_grow_limits lim = ctx->lim;
+  bs_grow_counters& gc = ctx->gc;
+  gc = bs_grow_counters{};
   int retry_max_list = RETRY_MAX_LIST;
   bool retry_env = false;
   if (const char* e = getenv("BS_RETRY_MAX_LIST")) {
     retry_max_list = atoi(e);
     retry_env = true;
   }
+  if (lim.retry_max_list >= 0) {
+    retry_max_list = lim.retry_max_list;
+    retry_env = true;
+  }
   int retry_big_round = 1024;
   if (const char* e = getenv("BS_RETRY_BIG_ROUND"))
     retry_big_round = atoi(e);
+  if (lim.retry_big_round >= 0)
+    retry_big_round = lim.retry_big_round;
   // Plane attempts per round: ALL candidates.  A round is a barrier bounded by its longest plane, and the big
   // planes of a large scene are independent of each other -- but their seeds are spread over the whole index
   // range: with the lowest 32 768 candidates per round (round 1) the 50 M cloud grew its 136 k-, 131 k- and
@@ -2427,10 +2437,19 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   int max_waves = MAX_WAVES;
   if (const char* e = getenv("BS_MAX_WAVES"))
     max_waves = atoi(e);
+  if (lim.max_waves > 0)
+    max_waves = (int)std::min<int64_t>(lim.max_waves, MAX_WAVES);
   const int wave_cap = (int)std::max<int64_t>(1, std::min<int64_t>(MAX_WAVES, n / 8 + 64));  // sizes the per-attempt arrays
   max_waves = (int)std::max<int64_t>(1, std::min<int64_t>(max_waves, wave_cap));
+  // (sized for wave_cap attempts, not for max_waves: the audit replays wave_cap attempts per batch whatever BS_MAX_WAVES
+  // or bs_selftest_grow_limits say -- on a pool sized for the lowered number its replays ended ST_NOMEM and the audit
+  // failed with "no progress" on a correct result; without a lowered max_waves the two are the same number)
   const unsigned long long pool_cap = (unsigned long long)std::max<int64_t>(
-      std::min<int64_t>(64 * n, (int64_t)3 << 30), 8 * n + (int64_t)(2 * 256 + 32 * 32) * 2 * max_waves);
+      std::min<int64_t>(64 * n, (int64_t)3 << 30), 8 * n + (int64_t)(2 * 256 + 32 * 32) * 2 * wave_cap);
+  // (a lowered pool: the buffer keeps its size, the attempts are told a smaller one)
+  const unsigned long long pool_cap_eff = lim.pool_cap > 0 ? std::min<unsigned long long>(pool_cap, (unsigned long long)lim.pool_cap) : pool_cap;
+  gc.pool_cap = (int64_t)pool_cap_eff;
+  gc.max_waves_end = max_waves;
   BS_HIP(ctx, ctx->rg_list.reserve(sizeof(int32_t) * list_cap));
   BS_HIP(ctx, ctx->rg_planes.reserve(sizeof(PlaneRec) * planes_cap));
   BS_HIP(ctx, ctx->rg_stats.reserve(sizeof(GrowStats)));
@@ -2470,7 +2489,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   CopyDesc* d_copy = (CopyDesc*)(d_pend + MAX_PENDING);
   int32_t* radj = ctx->rg_radj.as<int32_t>();
   unsigned long long* d_pool_top = (unsigned long long*)(d_misc + 16);
-  Pool pool = {ctx->rg_stack.as<int32_t>(), d_pool_top, pool_cap};
+  Pool pool = {ctx->rg_stack.as<int32_t>(), d_pool_top, pool_cap_eff};
 
   SpecArgs a;
   a.xyz = d_xyz;
@@ -2648,6 +2667,8 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   // re-validated instead of being re-grown
   const int64_t pstore_cap = 6 * n + 65536;
   BS_HIP(ctx, ctx->rg_pstore.reserve(sizeof(int32_t) * pstore_cap));
+  const int64_t pstore_lim = lim.pstore_cap > 0 ? std::min<int64_t>(pstore_cap, lim.pstore_cap) : pstore_cap;
+  const int pend_lim = lim.max_pending > 0 ? (int)std::min<int64_t>(MAX_PENDING, lim.max_pending) : MAX_PENDING;
   int32_t* pstore = ctx->rg_pstore.as<int32_t>();
   int64_t pstore_top = 0;
   std::vector<PlaneOut> pending;
@@ -2658,7 +2679,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   int64_t list_used = 0, largest = 0, attempts = 0, rounds = 0, grow_launches = 0;
   double grow_ms = 0.0;
   bool timed_round = false;
-  const bool force_full_refresh = getenv("BS_FULL_REFRESH") != nullptr;  // debugging aid: the pre-incremental behaviour
+  const bool force_full_refresh = lim.full_refresh != 0 || getenv("BS_FULL_REFRESH") != nullptr;  // debugging aid: the pre-incremental behaviour
   bool full_refresh = force_full_refresh;
   int32_t F = 0;
   auto commit_plane = [&](const PlaneOut& o, const int32_t* src_pool) -> int {
@@ -2739,6 +2760,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   BS_HIP(ctx, hipMemsetAsync(d_misc + 4, 0, 12 * sizeof(int), st));  // [4] refused planes, [5] forged seed + 1, [6] forged one refused, [12..15] refusals by check
   for (;;) {
     rounds++;
+    gc.rounds = rounds;
     a.F = F;
     const int npend = (int)pending.size();
     // lowest new plane-attempt candidates under the current owners (pending
@@ -2765,6 +2787,8 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(ctx->cub_tmp.p, tb, cand_raw, d_cand, ncand_all, 0, 64, st));
     }
     const int ncand = std::min<int>(ncand_all, max_waves);
+    gc.rounds_capped += ncand_all > max_waves ? 1 : 0;
+    gc.rounds_big += ncand >= 4096 ? 1 : 0;
     if (npend)
       BS_HIP(ctx, hipMemcpyAsync(d_pend, pending.data(), sizeof(PlaneOut) * npend, hipMemcpyHostToDevice, st));
     if (ncand > 0) {
@@ -2775,6 +2799,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       // of memory between claiming and listing are not recorded anywhere).
       if (full_refresh) {
         refresh_records_kernel<<<nblk(n, 256), 256, 0, st>>>(omega, rec, quads, n);
+        gc.full_refreshes++;
         full_refresh = force_full_refresh;
       } else if (getenv("BS_VERIFY")) {
         BS_HIP(ctx, hipMemsetAsync(d_misc + 3, 0, sizeof(int), st));
@@ -2900,7 +2925,9 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       if (o.status == ST_NOMEM) {
         full_refresh = true;  // its last claims may be neither listed nor reset
         dead_dirty = true;
+        gc.attempts_nomem++;
       }
+      gc.attempts_stolen += o.status == ST_STOLEN ? 1 : 0;  // (a compacted round brings none of these to the host)
     }
     for (int w = 0; w < npend; w++)
       if (!h_pend[w].consistent)
@@ -2909,6 +2936,8 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       if (max_waves == 1)
         return fail(ctx, BS_ERR_NOMEM, "region grow (speculative): round pool exhausted");
       max_waves = std::max(1, max_waves / 8);
+      gc.waves_cut++;
+      gc.max_waves_end = max_waves;
     }
 #ifdef BS_PROBE
     if (dbg) {
@@ -3000,7 +3029,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
     // consistent ones above it stay pending, the rest is dropped from the structure
     std::vector<PlaneOut> next_pending;
     int finals = 0, dropped = 0;
-    int pend_room = MAX_PENDING;  // old pending planes that stay have priority over new ones
+    int pend_room = pend_lim;  // old pending planes that stay have priority over new ones
     for (int w = 0; w < npend; w++)
       pend_room -= (h_pend[w].consistent && h_pend[w].seed >= first_bad) ? 1 : 0;
     {
@@ -3019,6 +3048,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
         if (!o.consistent || !o.v3ok) {
           o.pad = 2;
           dropped++;
+          gc.dropped_other++;
           continue;  // re-enters as a candidate (or orphan maker) next round
         }
         if (o.seed < first_bad) {
@@ -3031,7 +3061,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
             return rc;
         } else if (take_p) {
           next_pending.push_back(o);
-        } else if (pend_room > 0 && pstore_top + o.list_n + o.log_n + 8 <= pstore_cap) {
+        } else if (pend_room > 0 && pstore_top + o.list_n + o.log_n + 8 <= pstore_lim) {
           pend_room--;
           PlaneOut q = o;
           q.list_off = pstore_top;
@@ -3045,6 +3075,10 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
         } else {
           o.pad = 2;  // no room to keep it: drop, it will be grown again
           dropped++;
+          if (pend_room > 0)
+            gc.dropped_pend_store++;
+          else
+            gc.dropped_pend_count++;
         }
       }
     }
@@ -3136,6 +3170,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
     // an owner below the seed is final and taken, everything else is free at the seed's time) and compared
     // with what was committed -- see bs_set_audit in include/bs_api.h.
     const auto t0 = std::chrono::steady_clock::now();
+    pool.cap = pool_cap;  // (the replay is the judge: it never runs on a pool bs_selftest_grow_limits lowered)
     BS_HIP(ctx, hipMemsetAsync(bcand, 1, nb256, st));
     BS_HIP(ctx, hipMemsetAsync(d_misc + 1, 0, sizeof(int32_t), st));
     BS_HIP(ctx, hipMemsetAsync(d_misc + 8, 0, 2 * sizeof(int32_t), st));
@@ -3207,8 +3242,19 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
             if (h_retry[i])
               next.push_back(pend[off + i]);
         }
-        if (next.size() == pend.size())
-          return fail(ctx, BS_ERR_INTERNAL, "audit: a batch of rolled-back attempts made no progress");
+        if (next.size() == pend.size()) {
+          // (what the lowest attempts of the stuck batch ended as: the last sub-batch is still in d_out)
+          const size_t last_off = (pend.size() - 1) / (size_t)wave_cap * (size_t)wave_cap;
+          const int nshow = (int)std::min<size_t>(pend.size() - last_off, 3);
+          std::vector<PlaneOut> ho((size_t)nshow);
+          BS_HIP(ctx, hipMemcpy(ho.data(), d_out, sizeof(PlaneOut) * nshow, hipMemcpyDeviceToHost));
+          std::string msg = "audit: a batch of rolled-back attempts made no progress (" + std::to_string(pend.size()) + " left;";
+          for (const PlaneOut& o : ho)
+            msg += " seed " + std::to_string(o.seed) + " status " + std::to_string(o.status) + " list " + std::to_string(o.list_n) +
+                   " log " + std::to_string(o.log_n) + " thief " + std::to_string(o.thief) + ";";
+          msg += ")";
+          return fail(ctx, BS_ERR_INTERNAL, msg.c_str());
+        }
         pend.swap(next);
         batches++;
       }

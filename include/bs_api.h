@@ -268,6 +268,50 @@ int bs_selftest_forge_next(bs_ctx* ctx, int mode);
  * seed index.  Costs about one extra pass of the longest plane; bs_timings.audit_* report it. */
 int bs_set_audit(bs_ctx* ctx, int on);
 
+/* Self-test of the speculative grower's recovery paths: LOWER the capacities a region grow derives from the
+ * cloud size, so that the code that runs when one of them is exhausted (capped rounds, a round pool that runs
+ * out, finished planes that find no pending room) is reached on clouds of 10^4-10^6 points instead of 10^8.
+ * Sticky: holds for every following grow on the context (bs_region_grow[_dev], bs_segment[_dev],
+ * bs_segment_batch[_dev]) until cleared with lim == NULL; read once per call.  The result of a grow is the same
+ * bits whatever the limits; a round pool too small for the lowest attempt alone ends the call with BS_ERR_NOMEM.
+ *   Capacities (0 = default): only ever lowered -- a value above what the library would choose is clamped to
+ *   it -- and every buffer keeps its normal size, so no setting can cause an access out of bounds.
+ *   Policies (< 0 = default): any non-negative value, with the meaning of the environment switches
+ *   BS_RETRY_MAX_LIST / BS_RETRY_BIG_ROUND (which keep working, as do BS_MAX_WAVES and BS_FULL_REFRESH; a value
+ *   set here wins over the environment).  The audit replay (bs_set_audit) always runs with the full capacities. */
+typedef struct bs_grow_limits {
+  int64_t max_waves;       /* plane attempts grown per round */
+  int64_t pool_cap;        /* round pool (lists + stacks + logs of the round's attempts), int32 entries */
+  int64_t max_pending;     /* finished planes kept while an earlier attempt is open */
+  int64_t pstore_cap;      /* store of their lists and logs, int32 entries */
+  int32_t retry_max_list;  /* a stolen plane is grown again inside the launch while its list is at most this long;
+                              set, it holds in rounds of every size (as BS_RETRY_MAX_LIST does) */
+  int32_t retry_big_round; /* rounds of at least this many attempts re-grow lists of any length (0: every round) */
+  int32_t full_refresh;    /* != 0: rebuild every record's owner fields before every round (BS_FULL_REFRESH) */
+  int32_t reserved;        /* 0 */
+} bs_grow_limits;
+int bs_selftest_grow_limits(bs_ctx* ctx, const bs_grow_limits* lim);
+
+/* What the host loop of the last speculative region grow on this context saw (also filled when that call failed
+ * with BS_ERR_NOMEM): which of the limits above were reached.  All zero after a sequential grow (rg_mode 1). */
+typedef struct bs_grow_counters {
+  int64_t rounds;
+  int64_t rounds_capped;      /* rounds with more candidates than attempts per round: the rest waited */
+  int64_t rounds_big;         /* rounds of >= 4096 attempts (dispatch order, compacted copy-back) */
+  int64_t attempts_nomem;     /* attempts that ended because the round pool was exhausted */
+  int64_t waves_cut;          /* times the LOWEST attempt of a round ran out of pool: attempts per round cut to 1/8 */
+  int64_t max_waves_end;      /* attempts per round when the call ended */
+  int64_t attempts_stolen;    /* attempts that lost a point and were left for the next round.  Counted in rounds
+                                 below 4096 attempts only: a bigger round copies back just the finished and the
+                                 exhausted attempts */
+  int64_t dropped_pend_count; /* finished, consistent planes dropped (and grown again) for lack of a pending slot */
+  int64_t dropped_pend_store; /* ... for lack of room in the pending store */
+  int64_t dropped_other;      /* planes dropped as inconsistent with the settled owners or refused by the validation */
+  int64_t full_refreshes;     /* rounds that began with a full rebuild of the records' owner fields */
+  int64_t pool_cap;           /* the round pool's capacity in force, int32 entries */
+} bs_grow_counters;
+int bs_get_grow_counters(const bs_ctx* ctx, bs_grow_counters* out);
+
 /* Copy the plane records of the last region-grow on this context to the host. */
 int bs_planes_fetch(bs_ctx* ctx, bs_planes* planes);
 

@@ -627,8 +627,11 @@ static int ivec_push(ivec* a, int32_t x)
  * my_function.cpp:199-202), which is how a sharded run turns per-shard results into the global ids. */
 static int region_grow_core(const int32_t* xyz, const double* normals, const int32_t* neigh, int64_t n,
                             int k, int th_thickness, int th_point_count, double cos_th,
-                            int32_t* plane_idx, bso_planes* planes, int64_t* n_seed_attempts, int32_t* owner)
+                            int32_t* plane_idx, bso_planes* planes, int64_t* n_seed_attempts, int32_t* owner,
+                            int64_t** lifo_out)
 {
+  if (lifo_out)
+    *lifo_out = NULL;
   if (!xyz || !normals || !neigh || !plane_idx || n <= 0 || k < 1 || n < k)
     return -1;
   for (int64_t i = 0; i < n; i++)
@@ -643,6 +646,7 @@ static int region_grow_core(const int32_t* xyz, const double* normals, const int
   int64_t* offs = NULL;
   double* pn = NULL;
   int32_t* pc = NULL;
+  int64_t* lifo = NULL; /* [np][4]: see bso_region_grow_lifo */
   int64_t np = 0, pcap = 0, attempts = 0;
   int cur_plane_id = 1; /* my_function.h:119 */
   int rc = 0;
@@ -668,6 +672,8 @@ static int region_grow_core(const int32_t* xyz, const double* normals, const int
     int64_t cur = i;
     int depth0 = 1;
     int failed = 0;
+    /* model of a 256-entry window over the top of the LIFO (bso_region_grow_lifo) */
+    int64_t lo = 0, peak = 0, spills = 0, refills = 0, respills = 0;
     for (;;) {
       /* ---- Broad(cur, depth) :220-258 ---- */
       const int32_t* row = neigh + cur * (int64_t)k;
@@ -721,6 +727,17 @@ static int region_grow_core(const int32_t* xyz, const double* normals, const int
         }
       if (rc || stack.n == 0)
         break;
+      if (stack.n > peak)
+        peak = stack.n;
+      if (stack.n - lo > BSO_LIFO_WINDOW) { /* the pushes of this call no longer fit: the oldest leave */
+        spills++;
+        respills += refills ? 1 : 0;
+        lo = stack.n - BSO_LIFO_WINDOW;
+      }
+      if (stack.n - 1 < lo) { /* the entry to pop left the window earlier: bring a block back */
+        refills++;
+        lo = lo > BSO_LIFO_REFILL ? lo - BSO_LIFO_REFILL : 0;
+      }
       cur = stack.v[--stack.n];
     }
     if (rc)
@@ -733,7 +750,8 @@ static int region_grow_core(const int32_t* xyz, const double* normals, const int
         offs = (int64_t*)realloc(offs, sizeof(int64_t) * (size_t)(pcap + 1));
         pn = (double*)realloc(pn, sizeof(double) * 3 * (size_t)pcap);
         pc = (int32_t*)realloc(pc, sizeof(int32_t) * 3 * (size_t)pcap);
-        if (!offs || !pn || !pc) {
+        lifo = (int64_t*)realloc(lifo, sizeof(int64_t) * 4 * (size_t)pcap);
+        if (!offs || !pn || !pc || !lifo) {
           rc = -3;
           break;
         }
@@ -750,6 +768,10 @@ static int region_grow_core(const int32_t* xyz, const double* normals, const int
         pn[3 * np + a] = cn[a];
         pc[3 * np + a] = cc[a];
       }
+      lifo[4 * np] = peak;
+      lifo[4 * np + 1] = spills;
+      lifo[4 * np + 2] = refills;
+      lifo[4 * np + 3] = respills;
       np++;
       cur_plane_id++;
     } else {
@@ -770,8 +792,13 @@ static int region_grow_core(const int32_t* xyz, const double* normals, const int
     free(offs);
     free(pn);
     free(pc);
+    free(lifo);
     return rc;
   }
+  if (lifo_out)
+    *lifo_out = lifo;
+  else
+    free(lifo);
   if (planes) {
     if (!offs)
       offs = (int64_t*)malloc(sizeof(int64_t));
@@ -797,7 +824,7 @@ int bso_region_grow(const int32_t* xyz, const double* normals, const int32_t* ne
                     int32_t* plane_idx, bso_planes* planes, int64_t* n_seed_attempts)
 {
   return region_grow_core(xyz, normals, neigh, n, k, th_thickness, th_point_count, cos_th, plane_idx, planes,
-                          n_seed_attempts, NULL);
+                          n_seed_attempts, NULL, NULL);
 }
 
 int bso_region_grow_owner(const int32_t* xyz, const double* normals, const int32_t* neigh, int64_t n,
@@ -805,8 +832,18 @@ int bso_region_grow_owner(const int32_t* xyz, const double* normals, const int32
                           int32_t* plane_idx, bso_planes* planes, int64_t* n_seed_attempts, int32_t* owner)
 {
   return region_grow_core(xyz, normals, neigh, n, k, th_thickness, th_point_count, cos_th, plane_idx, planes,
-                          n_seed_attempts, owner);
+                          n_seed_attempts, owner, NULL);
 }
+
+int bso_region_grow_lifo(const int32_t* xyz, const double* normals, const int32_t* neigh, int64_t n,
+                         int k, int th_thickness, int th_point_count, double cos_th,
+                         int32_t* plane_idx, bso_planes* planes, int64_t* n_seed_attempts, int64_t** lifo)
+{
+  return region_grow_core(xyz, normals, neigh, n, k, th_thickness, th_point_count, cos_th, plane_idx, planes,
+                          n_seed_attempts, NULL, lifo);
+}
+
+void bso_free(void* p) { free(p); }
 
 void bso_planes_free(bso_planes* p)
 {

@@ -70,6 +70,24 @@ int bso_region_grow_owner(const int32_t* xyz, const double* normals, const int32
                           int k, int th_thickness, int th_point_count, double cos_th,
                           int32_t* plane_idx, bso_planes* planes, int64_t* n_seed_attempts, int32_t* owner);
 
+/* The same as bso_region_grow, additionally reporting how the LIFO of pending Broad() calls moved while each
+ * COMMITTED plane grew: *lifo (malloc'd, release with bso_free; NULL when no plane) holds four numbers per plane,
+ *   [0] peak of the LIFO's length,
+ *   and the events of a plain model of a window of BSO_LIFO_WINDOW entries over its top (lo = lowest entry
+ *   still inside the window):
+ *   [1] spills    -- after the pushes of a Broad() call the LIFO is more than a window above lo: lo moves up to
+ *                    length - BSO_LIFO_WINDOW,
+ *   [2] refills   -- the entry to pop lies below lo: lo moves down by BSO_LIFO_REFILL,
+ *   [3] re-spills -- spills after the plane's first refill.
+ * The device grower keeps its LIFO top in a window of that size in LDS; a test states with these numbers that its
+ * input drives the stack far above the window and back below it (tests/test_gpu_grow_limits.py). */
+#define BSO_LIFO_WINDOW 256
+#define BSO_LIFO_REFILL 128
+int bso_region_grow_lifo(const int32_t* xyz, const double* normals, const int32_t* neigh, int64_t n,
+                         int k, int th_thickness, int th_point_count, double cos_th,
+                         int32_t* plane_idx, bso_planes* planes, int64_t* n_seed_attempts, int64_t** lifo);
+void bso_free(void* p);
+
 void bso_planes_free(bso_planes* planes);
 
 double bso_det_acos(double x);

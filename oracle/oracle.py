@@ -43,6 +43,10 @@ def lib():
                                       ip, C.POINTER(_Planes), lp]
         L.bso_region_grow_owner.argtypes = [ip, dp, ip, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
                                             ip, C.POINTER(_Planes), lp, ip]
+        L.bso_region_grow_lifo.argtypes = [ip, dp, ip, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_double,
+                                           ip, C.POINTER(_Planes), lp, C.POINTER(lp)]
+        L.bso_free.argtypes = [C.c_void_p]
+        L.bso_free.restype = None
         L.bso_planes_free.argtypes = [C.POINTER(_Planes)]
         L.bso_det_acos.argtypes = [C.c_double]
         L.bso_det_acos.restype = C.c_double
@@ -118,8 +122,13 @@ def _planes_to_py(P):
                           if off[-1] > 0 else np.zeros(0, np.int32))}
 
 
-def region_grow(xyz, normals, neigh, th_thickness=300, th_point_count=400, cos_th=0.88, want_owner=False):
-    """(plane_idx, planes) -- with want_owner also owner [n]: the seed attempt that left each point labelled."""
+def region_grow(xyz, normals, neigh, th_thickness=300, th_point_count=400, cos_th=0.88, want_owner=False,
+                want_lifo=False):
+    """(plane_idx, planes) -- with want_owner also owner [n]: the seed attempt that left each point labelled;
+    with want_lifo (instead) also an int64 [n_planes, 4] array: per committed plane the peak of the LIFO of pending
+    Broad() calls and the spills / refills / re-spills of a 256-entry window over its top (bso_region_grow_lifo)."""
+    if want_owner and want_lifo:
+        raise ValueError("want_owner and want_lifo are separate entry points: ask for one")
     xyz = np.ascontiguousarray(xyz, dtype=np.int32)
     normals = np.ascontiguousarray(normals, dtype=np.float64)
     neigh = np.ascontiguousarray(neigh, dtype=np.int32)
@@ -128,7 +137,11 @@ def region_grow(xyz, normals, neigh, th_thickness=300, th_point_count=400, cos_t
     owner = np.empty(n, dtype=np.int32) if want_owner else None
     P = _Planes()
     att = C.c_int64(0)
-    if want_owner:
+    lifo_p = C.POINTER(C.c_int64)()
+    if want_lifo:
+        rc = lib().bso_region_grow_lifo(_ip(xyz), _dp(normals), _ip(neigh), n, k, th_thickness, th_point_count,
+                                        cos_th, _ip(plane_idx), C.byref(P), C.byref(att), C.byref(lifo_p))
+    elif want_owner:
         rc = lib().bso_region_grow_owner(_ip(xyz), _dp(normals), _ip(neigh), n, k, th_thickness, th_point_count,
                                          cos_th, _ip(plane_idx), C.byref(P), C.byref(att), _ip(owner))
     else:
@@ -138,7 +151,12 @@ def region_grow(xyz, normals, neigh, th_thickness=300, th_point_count=400, cos_t
         raise ValueError(f"bso_region_grow failed: {rc}")
     planes = _planes_to_py(P)
     planes["n_seed_attempts"] = att.value
+    npl = P.n_planes
     lib().bso_planes_free(C.byref(P))
+    if want_lifo:
+        lifo = (np.ctypeslib.as_array(lifo_p, (npl * 4,)).reshape(npl, 4).copy() if npl else np.zeros((0, 4), np.int64))
+        lib().bso_free(lifo_p)
+        return plane_idx, planes, lifo
     if want_owner:
         return plane_idx, planes, owner
     return plane_idx, planes
