@@ -29,7 +29,9 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_sharded_planes_fetch", "bs_footprints_dev", "bs_footprints", "bs_contours_free",
            "bs_contours_write_obj", "bs_segment_batch", "bs_segment_batch_dev", "bs_batch_planes_fetch",
            "bs_shift_tiles_to_origin_dev", "bs_tile_boxes_dev", "bs_grid_dims_batch", "bs_grid_picture_batch_dev",
-           "bs_grid_picture_batch", "bs_footprints_batch_dev", "bs_footprints_batch"]
+           "bs_grid_picture_batch", "bs_footprints_batch_dev", "bs_footprints_batch", "bs_building_map_dev",
+           "bs_building_map", "bs_buildings_free", "bs_assign_buildings_dev", "bs_assign_buildings",
+           "bs_plane_buildings_dev", "bs_plane_buildings", "bs_buildings_write_obj"]
 
 
 class Params(C.Structure):
@@ -97,6 +99,16 @@ class FootprintInfo(C.Structure):
     _fields_ = [("ms_mask", C.c_double), ("ms_close", C.c_double), ("ms_label", C.c_double), ("ms_trace", C.c_double),
                 ("ms_total", C.c_double), ("fg_pixels", C.c_int64), ("border_states", C.c_int64),
                 ("components", C.c_int64), ("jump_rounds", C.c_int64)]
+
+
+class Buildings(C.Structure):
+    """bs_buildings (include/bs_api.h): per-building figures, host memory owned by the library."""
+    _fields_ = [("n_buildings", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("start_xy", C.POINTER(C.c_int32)), ("bbox", C.POINTER(C.c_int32)), ("pixels", C.POINTER(C.c_int64)),
+                ("fg_pixels", C.POINTER(C.c_int64)), ("n_points", C.POINTER(C.c_int64)),
+                ("n_above", C.POINTER(C.c_int64)), ("z_min", C.POINTER(C.c_int32)), ("z_max", C.POINTER(C.c_int32)),
+                ("z_sum", C.POINTER(C.c_int64)), ("ms_label_mask", C.c_double), ("ms_label_fill", C.c_double),
+                ("ms_number", C.c_double), ("ms_map", C.c_double), ("ms_assign", C.c_double)]
 
 
 class BsError(RuntimeError):
@@ -194,5 +206,15 @@ def load():
                                           C.POINTER(FootprintInfo)]
     L.bs_footprints_batch.argtypes = [vp, vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, cp, ip,
                                       C.POINTER(FootprintInfo)]
+    bp = C.POINTER(Buildings)
+    L.bs_building_map_dev.argtypes = [vp, vp, C.c_int32, C.c_int32, ip, bp]
+    L.bs_building_map.argtypes = [vp, vp, C.c_int32, C.c_int32, ip, bp]
+    L.bs_buildings_free.argtypes = [bp]
+    L.bs_buildings_free.restype = None
+    L.bs_assign_buildings_dev.argtypes = [vp, ip, C.c_int64, C.c_int32, C.c_double, ip, C.c_int32, C.c_int32, ip, bp]
+    L.bs_assign_buildings.argtypes = [vp, ip, C.c_int64, C.c_int32, C.c_double, ip, C.c_int32, C.c_int32, ip, bp]
+    L.bs_plane_buildings_dev.argtypes = [vp, ip, ip, C.c_int64, C.c_int32, C.c_int32, ip, vp, vp, vp]
+    L.bs_plane_buildings.argtypes = [vp, ip, ip, C.c_int64, C.c_int32, C.c_int32, ip, vp, vp, vp]
+    L.bs_buildings_write_obj.argtypes = [cp, bp, C.c_int32, ip, C.c_double, C.c_double, C.c_double, C.c_char_p]
     _LIB = L
     return L

@@ -448,6 +448,188 @@ class Context:
                                                     co.ctypes.data, C.byref(inf)))
         return _take_contours_batch(self._L, out, inf, co, w, h)
 
+    # ---- buildings: footprints joined with the points and the planes (bs_building_map, bs_assign_buildings, ...) ----
+    def building_map(self, mask):
+        """Building map of a closed [height][width] mask (non-zero = foreground, e.g. footprints(return_mask=True)):
+        returns (map int32 [height][width]: building of every pixel or -1, Buildings).  Building c is contour c of
+        footprints() on the same mask."""
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if m.ndim != 2:
+            raise ValueError("building_map: mask must be [height][width]")
+        h, w = m.shape
+        bmap = np.empty((h, w), dtype=np.int32)
+        out = _lib.Buildings()
+        self._check(self._L.bs_building_map(self._h, m.ctypes.data, w, h, bmap.ctypes.data, C.byref(out)))
+        return bmap, _take_buildings(self._L, out)
+
+    def building_map_dev(self, d_mask, width, height, d_map):
+        """Device-resident variant: d_mask ([height][width] uint8) and d_map ([height][width] int32, out) are device
+        pointers (ints); the per-building figures come back in host memory."""
+        out = _lib.Buildings()
+        self._check(self._L.bs_building_map_dev(self._h, d_mask or None, width, height, d_map or None, C.byref(out)))
+        return _take_buildings(self._L, out)
+
+    def assign_buildings(self, xyz, bmap, buildings, bin=100, ground_th=0.0):
+        """building_idx int32 [n] of a cloud shifted to its origin: the building of every point's base pixel
+        (x / bin, y / bin) in bmap, -1 outside every building.  Fills the point figures of `buildings` (the object
+        building_map returned for bmap): n_points, n_above, z_min, z_max, z_sum over the points with
+        !(z < ground_th)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError("xyz must be [n, 3]")
+        bmap = np.ascontiguousarray(bmap, dtype=np.int32)
+        h, w = bmap.shape
+        bidx = np.empty(len(xyz), dtype=np.int32)
+        st = _buildings_struct(buildings)
+        self._check(self._L.bs_assign_buildings(self._h, xyz.ctypes.data, len(xyz), bin, float(ground_th),
+                                                bmap.ctypes.data, w, h, bidx.ctypes.data, C.byref(st)))
+        buildings.info["ms_assign"] = st.ms_assign
+        return bidx
+
+    def assign_buildings_dev(self, d_xyz, n, d_map, buildings, d_building_idx, bin=100, ground_th=0.0):
+        """Device-resident variant: d_xyz, d_map ([height][width] of `buildings`) and d_building_idx (int32 [n], out)
+        are device pointers (ints)."""
+        st = _buildings_struct(buildings)
+        self._check(self._L.bs_assign_buildings_dev(self._h, d_xyz or None, n, bin, float(ground_th), d_map or None,
+                                                    buildings.width, buildings.height, d_building_idx or None,
+                                                    C.byref(st)))
+        buildings.info["ms_assign"] = st.ms_assign
+
+    def plane_buildings(self, plane_idx, building_idx, n_planes, n_buildings):
+        """Votes of the planes 1 .. n_planes for the buildings, over the point labels: returns PlaneVotes (arrays
+        [n_planes], entry p - 1 = plane p)."""
+        pi = np.ascontiguousarray(plane_idx, dtype=np.int32)
+        bi = np.ascontiguousarray(building_idx, dtype=np.int32)
+        if pi.shape != bi.shape or pi.ndim != 1:
+            raise ValueError("plane_idx and building_idx must be 1-D arrays of the same length")
+        return self._votes(self._L.bs_plane_buildings, pi.ctypes.data, bi.ctypes.data, len(pi), n_planes, n_buildings)
+
+    def plane_buildings_dev(self, d_plane_idx, d_building_idx, n, n_planes, n_buildings):
+        """Device-resident variant: the two label arrays are device pointers (ints)."""
+        return self._votes(self._L.bs_plane_buildings_dev, d_plane_idx or None, d_building_idx or None, n, n_planes,
+                           n_buildings)
+
+    def _votes(self, fn, p_plane, p_bidx, n, n_planes, n_buildings):
+        m = max(int(n_planes), 0)
+        pb = np.full(m, -1, dtype=np.int32)
+        vin, vtot, vout = (np.zeros(m, dtype=np.int64) for _ in range(3))
+        self._check(fn(self._h, p_plane, p_bidx, n, n_planes, n_buildings, pb.ctypes.data, vin.ctypes.data,
+                       vtot.ctypes.data, vout.ctypes.data))
+        return PlaneVotes(pb, vin, vtot, vout)
+
+    def buildings(self, xyz, plane_idx=None, n_planes=0, bin=100, bin_height=1000, threshold=10, kernel_size=5,
+                  iterations=2):
+        """The whole 2-D branch for a cloud shifted to its origin: raster -> footprints (with the closed mask) ->
+        building map -> point assignment -> plane votes (when plane_idx, the labels of segment(), is given).
+        Returns (Footprints, Buildings); the Buildings carry map, building_idx, ground_th and votes."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        img, th = self.grid_picture(xyz, bin=bin, bin_height=bin_height)
+        fp, mask = self.footprints(img, threshold=threshold, kernel_size=kernel_size, iterations=iterations,
+                                   return_mask=True)
+        bmap, b = self.building_map(mask)
+        b.map, b.ground_th = bmap, th
+        b.building_idx = self.assign_buildings(xyz, bmap, b, bin=bin, ground_th=th)
+        if plane_idx is not None:
+            b.votes = self.plane_buildings(plane_idx, b.building_idx, n_planes, b.n_buildings)
+        return fp, b
+
+
+@dataclass
+class PlaneVotes:
+    """Entry p - 1 is plane p: the building that holds most of its points (-1: none), that building's count, the
+    plane's points, and those outside every building."""
+    plane_building: np.ndarray
+    votes_in: np.ndarray
+    votes_total: np.ndarray
+    votes_outside: np.ndarray
+
+
+@dataclass
+class Buildings:
+    """bs_buildings: building c is contour c of the footprints of the same mask.  The pixel figures come from
+    building_map, the point figures from assign_buildings."""
+    n_buildings: int
+    width: int
+    height: int
+    start_xy: np.ndarray
+    bbox: np.ndarray
+    pixels: np.ndarray
+    fg_pixels: np.ndarray
+    n_points: np.ndarray
+    n_above: np.ndarray
+    z_min: np.ndarray
+    z_max: np.ndarray
+    z_sum: np.ndarray
+    info: dict = field(default_factory=dict)
+    map: np.ndarray | None = field(default=None, repr=False)
+    building_idx: np.ndarray | None = field(default=None, repr=False)
+    ground_th: float = 0.0
+    votes: PlaneVotes | None = None
+
+
+_BUILDING_ARRAYS = (("start_xy", 2, np.int32), ("bbox", 4, np.int32), ("pixels", 1, np.int64), ("fg_pixels", 1, np.int64),
+                    ("n_points", 1, np.int64), ("n_above", 1, np.int64), ("z_min", 1, np.int32), ("z_max", 1, np.int32),
+                    ("z_sum", 1, np.int64))
+
+
+def _take_buildings(L, out) -> Buildings:
+    """Copy a bs_buildings into numpy arrays and release it."""
+    n = out.n_buildings
+    try:
+        arrs = {}
+        for name, cols, dt in _BUILDING_ARRAYS:
+            a = np.ctypeslib.as_array(getattr(out, name), (n * cols,)).copy() if n else np.zeros(0, dt)
+            arrs[name] = a.reshape(n, cols) if cols > 1 else a
+        info = {k: getattr(out, k) for k in ("ms_label_mask", "ms_label_fill", "ms_number", "ms_map", "ms_assign")}
+        return Buildings(n, out.width, out.height, info=info, **arrs)
+    finally:
+        L.bs_buildings_free(C.byref(out))
+
+
+def _buildings_struct(b: Buildings):
+    """A bs_buildings whose arrays are b's own numpy arrays (the library reads and writes them in place)."""
+    st = _lib.Buildings()
+    st.n_buildings, st.width, st.height = b.n_buildings, b.width, b.height
+    keep = []
+    for name, cols, dt in _BUILDING_ARRAYS:
+        a = getattr(b, name)
+        if a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or a.size != b.n_buildings * cols:
+            raise ValueError(f"Buildings.{name} must be a contiguous {np.dtype(dt).name} array of {b.n_buildings * cols}")
+        keep.append(a if a.size else np.zeros(cols, dt))  # (never a null pointer)
+        setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
+    st._keep = keep
+    return st
+
+
+def write_buildings_obj(fp, buildings: Buildings, path, bin=100, origin=None, ground_th=None, min_area=500.0,
+                        min_perimeter=100.0):
+    """LoD1 OBJ in millimetres through the library's writer (bs_buildings_write_obj; the format is written down in
+    include/bs_api.h): the kept footprints extruded from the ground threshold to the mean height of their
+    above-ground points.  origin: the shift that was subtracted from the cloud; ground_th: default buildings.ground_th."""
+    n = len(fp.contours)
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(c) for c in fp.contours]) if n else []
+    xy = np.ascontiguousarray(np.concatenate(fp.contours) if n else np.zeros((0, 2)), dtype=np.int32)
+    area = np.ascontiguousarray(fp.area, dtype=np.float64)
+    per = np.ascontiguousarray(fp.perimeter, dtype=np.float64)
+    if len(area) != n or len(per) != n:
+        raise ValueError("area and perimeter must have one entry per contour")
+    c = Contours()
+    c.n_contours, c.width, c.height = n, fp.width, fp.height
+    c.offset = off.ctypes.data_as(C.POINTER(C.c_int64))
+    c.xy = (xy if xy.size else np.zeros(2, np.int32)).ctypes.data_as(C.POINTER(C.c_int32))
+    c.area = (area if n else np.zeros(1)).ctypes.data_as(C.POINTER(C.c_double))
+    c.perimeter = (per if n else np.zeros(1)).ctypes.data_as(C.POINTER(C.c_double))
+    st = _buildings_struct(buildings)
+    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+    if org is not None and org.shape != (3,):
+        raise ValueError("origin must be [3]")
+    th = buildings.ground_th if ground_th is None else ground_th
+    rc = _lib.load().bs_buildings_write_obj(C.byref(c), C.byref(st), int(bin), org.ctypes.data if org is not None else None,
+                                            float(th), float(min_area), float(min_perimeter), str(path).encode())
+    if rc != 0:
+        raise BsError(rc, f"cannot write {path} (or the contours and the buildings are not of the same mask)")
+
 
 @dataclass
 class Footprints:

@@ -231,6 +231,24 @@ inline bool write_png_rgb8(const std::string& path, int w, int h, const std::vec
   return ok;
 }
 
+// What buildingSeg_t::extracted_buildings returns: the footprints, the per-building figures, every point's building
+// and the planes' votes (include/bs_api.h, "buildings").  The two C structs are released by the destructor.
+struct building_model {
+  bs_contours contours{};
+  bs_buildings buildings{};
+  std::vector<int32_t> building_idx;    // [points]
+  std::vector<int32_t> plane_building;  // [n_planes], entry p - 1 = plane p
+  std::vector<int64_t> votes_in, votes_total, votes_outside;
+  building_model() = default;
+  building_model(const building_model&) = delete;
+  building_model& operator=(const building_model&) = delete;
+  ~building_model()
+  {
+    bs_contours_free(&contours);
+    bs_buildings_free(&buildings);
+  }
+};
+
 // The reference's buildingSeg (TMC3.cpp:50-200) on the C ABI.  As in the
 // reference, the constructor keeps its own copy of the cloud, shifts BOTH the
 // copy and the caller's cloud to the bounding-box origin and sizes the image.
@@ -311,6 +329,39 @@ public:
       throw std::runtime_error("extracted_contour: cannot write " + obj_path);
     }
     return c;
+  }
+
+  // The step after extracted_contour, on the image and ground threshold of compute_gird_picture(): footprints with
+  // their closed mask -> building map -> every point's building and the per-building heights -> the votes of the
+  // planes 1 .. n_planes (plane_idx: the labels of seg_plane, one per point of the cloud).  Writes the LoD1 model in
+  // the cloud's original millimetres (the constructor's shift is the origin) to obj_path and fills `out`.
+  void extracted_buildings(const std::string& obj_path, const int32_t* plane_idx, int32_t n_planes, building_model& out,
+                           int32_t threshold = 10, int32_t kernel_size = 5, int32_t iterations = 2,
+                           double min_area = 500, double min_perimeter = 100)
+  {
+    const int64_t n = (int64_t)pointcloud.getPointCount();
+    std::vector<uint8_t> mask((size_t)width * height);
+    std::vector<int32_t> map((size_t)width * height);
+    bs_contours_free(&out.contours);
+    bs_buildings_free(&out.buildings);
+    legacy_check(bs_footprints(legacy_ctx(), image.data(), width, height, threshold, kernel_size, iterations, mask.data(),
+                               &out.contours, nullptr));
+    legacy_check(bs_building_map(legacy_ctx(), mask.data(), width, height, map.data(), &out.buildings));
+    out.building_idx.assign((size_t)n, -1);
+    legacy_check(bs_assign_buildings(legacy_ctx(), reinterpret_cast<const int32_t*>(&pointcloud[0]), n, bin, ground_th,
+                                     map.data(), width, height, out.building_idx.data(), &out.buildings));
+    const size_t np = (size_t)std::max(n_planes, 0);
+    out.plane_building.assign(np, -1);
+    out.votes_in.assign(np, 0);
+    out.votes_total.assign(np, 0);
+    out.votes_outside.assign(np, 0);
+    if (plane_idx && n_planes > 0)
+      legacy_check(bs_plane_buildings(legacy_ctx(), plane_idx, out.building_idx.data(), n, n_planes,
+                                      out.buildings.n_buildings, out.plane_building.data(), out.votes_in.data(),
+                                      out.votes_total.data(), out.votes_outside.data()));
+    if (bs_buildings_write_obj(&out.contours, &out.buildings, bin, box_min, ground_th, min_area, min_perimeter,
+                               obj_path.c_str()) != BS_OK)
+      throw std::runtime_error("extracted_buildings: cannot write " + obj_path);
   }
 
   int32_t box_min[3], box_max[3];

@@ -26,7 +26,7 @@ static std::string after_equals(const char* arg)  // Split(path, "=")[1], my_fun
 int main(int argc, char* argv[])
 {
   if (argc < 3) {
-    fprintf(stderr, "usage: %s <x>=<in.ply> <y>=<out.ply> [--raster=<png prefix>] [--footprints=<file.obj>]\n", argv[0]);
+    fprintf(stderr, "usage: %s <x>=<in.ply> <y>=<out.ply> [--raster=<png prefix>] [--footprints=<file.obj>] [--buildings=<file.obj>]\n", argv[0]);
     return 2;
   }
   const std::string in = after_equals(argv[1]), out = after_equals(argv[2]);
@@ -44,7 +44,10 @@ int main(int argc, char* argv[])
   const size_t n = cloud.getPointCount();
   std::string raster_prefix;  // --raster=<prefix>: the 2-D branch the reference's main keeps commented out (TMC3.cpp:223-225)
   std::string obj_path;  // --footprints=<file.obj>: extracted_contour (TMC3.cpp:226) on the raster
+  std::string bld_path;  // --buildings=<file.obj>: footprints joined with the points and the planes, LoD1 model in mm
   for (int a = 3; a < argc; a++) {
+    if (std::string(argv[a]).rfind("--buildings=", 0) == 0)
+      bld_path = after_equals(argv[a]);
     if (std::string(argv[a]).rfind("--raster=", 0) == 0)
       raster_prefix = after_equals(argv[a]);
     if (std::string(argv[a]).rfind("--footprints=", 0) == 0)
@@ -63,7 +66,7 @@ int main(int argc, char* argv[])
     srand(1);
     h.set_plane_color(planes);
     fprintf(stderr, "tmc3: %zu points, %zu planes\n", n, planes.size());
-    if (!raster_prefix.empty() || !obj_path.empty()) {
+    if (!raster_prefix.empty() || !obj_path.empty() || !bld_path.empty()) {
       seg.compute_gird_picture();
       if (!raster_prefix.empty())
         seg.save_image(raster_prefix);
@@ -77,6 +80,21 @@ int main(int argc, char* argv[])
       fprintf(stderr, "tmc3: %d footprint contours (%d with area > 500 and perimeter > 100) -> %s\n", c.n_contours,
               kept, obj_path.c_str());
       bs_contours_free(&c);
+    }
+    if (!bld_path.empty()) {
+      bs::building_model m;
+      const int32_t np = (int32_t)planes.size();
+      seg.extracted_buildings(bld_path, reinterpret_cast<const int32_t*>(cloud.planeIdx.data()), np, m);
+      int kept = 0, won = 0;
+      long long inside = 0;
+      for (int32_t i = 0; i < m.contours.n_contours; i++)
+        kept += m.contours.area[i] > 500 && m.contours.perimeter[i] > 100 && m.buildings.n_above[i] > 0;
+      for (int32_t p = 0; p < np; p++)
+        won += m.plane_building[p] >= 0;
+      for (int32_t b : m.building_idx)
+        inside += b >= 0;
+      fprintf(stderr, "tmc3: %d buildings (%d kept), %lld of %zu points inside one, %d planes, %d with a building -> %s\n",
+              m.buildings.n_buildings, kept, inside, n, np, won, bld_path.c_str());
     }
   } catch (const std::exception& e) {
     fprintf(stderr, "tmc3: %s\n", e.what());

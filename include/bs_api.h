@@ -536,6 +536,99 @@ int bs_footprints_batch(bs_ctx* ctx, const double* image, const int32_t* width, 
                         int32_t n_tiles, int32_t threshold, int32_t kernel_size, int32_t iterations, uint8_t* mask,
                         bs_contours* out, int32_t* contour_offset, bs_footprint_info* info);
 
+/* ---- buildings: which points and which planes belong to which footprint ----
+ *
+ * Building map of a closed mask [height][width] (bytes, non-zero = foreground: what bs_footprints[_dev] writes to
+ * its mask), padded with a one-pixel background frame as the tracer pads it:
+ *   outer background = the 4-connected background region that contains the frame;
+ *   filled           = every other pixel (the foreground and whatever a foreground component encloses);
+ *   a building       = an 8-connected component of the filled set; its start pixel is its first pixel in raster
+ *                      order; buildings are numbered from 0 in DESCENDING order of start pixel;
+ *   map[y][x]        = the building of the pixel, -1 for outer background.
+ * Building c is contour c of bs_footprints on the same mask: the same count, start_xy[c] = the contour's first point,
+ * and every point of contour c lies on a pixel of building c.
+ *
+ * Points (cloud shifted to its origin, as for bs_grid_picture): building_idx[i] = map[y_i / bin][x_i / bin], the
+ * base pixel of the point's splat (TMC3.cpp:134-135); a point is above ground iff !(z < ground_th) (TMC3.cpp:139,
+ * ground_th as bs_grid_picture returns it).  With the map of the same cloud's own raster at threshold 10, every
+ * above-ground point has a building >= 0.
+ * Planes: for p = 1 .. n_planes, over the points with plane_idx == p (the labels, not the lists), entry p - 1 of
+ *   votes_total = their number, votes_outside = those with building -1, plane_building = the building >= 0 that
+ *   holds most of them (ties: the lower index; -1 if none holds any), votes_in = that building's count.
+ * Everything is an exact integer and independent of the order of summation. */
+typedef struct bs_buildings {
+  int32_t n_buildings;
+  int32_t width, height; /* raster of the map */
+  /* filled by bs_building_map[_dev] */
+  int32_t* start_xy;  /* [n_buildings][2] first pixel in raster order: x, y */
+  int32_t* bbox;      /* [n_buildings][4] inclusive pixel box: x0, y0, x1, y1 */
+  int64_t* pixels;    /* [n_buildings] filled pixels */
+  int64_t* fg_pixels; /* [n_buildings] ... of which foreground in the mask */
+  /* filled by bs_assign_buildings[_dev] (0 / INT32_MAX / INT32_MIN / 0 before) */
+  int64_t* n_points;  /* [n_buildings] points whose base pixel lies in the building */
+  int64_t* n_above;   /* [n_buildings] ... of which above ground */
+  int32_t* z_min;     /* [n_buildings] over the above-ground points; INT32_MAX if there is none */
+  int32_t* z_max;     /* [n_buildings] INT32_MIN if there is none */
+  int64_t* z_sum;     /* [n_buildings] sum of z over the above-ground points */
+  /* device time (HIP events on the context's stream) of the last calls that filled this struct */
+  double ms_label_mask; /* labelling pass 1: foreground / background of the mask (tile, seam and flatten kernels) */
+  double ms_label_fill; /* labelling pass 2: the filled set */
+  double ms_number;     /* start-pixel flags + scan + read-back of the count */
+  double ms_map;        /* map and pixel figures */
+  double ms_assign;     /* bs_assign_buildings_dev: the assignment kernel */
+} bs_buildings;
+
+/* d_mask [height][width] bytes and d_map [height][width] int32 are device pointers; out's arrays are host memory
+ * owned by the library (bs_buildings_free, which accepts a zeroed struct).  An empty mask gives 0 buildings and a
+ * map of -1.  BS_ERR_INVALID: null pointer, width or height < 1, (width+2)*(height+2) >= 2^31.  Synchronises. */
+int bs_building_map_dev(bs_ctx* ctx, const uint8_t* d_mask, int32_t width, int32_t height, int32_t* d_map,
+                        bs_buildings* out);
+/* Host-memory variant: mask and map are host pointers. */
+int bs_building_map(bs_ctx* ctx, const uint8_t* mask, int32_t width, int32_t height, int32_t* map, bs_buildings* out);
+void bs_buildings_free(bs_buildings* b);
+
+/* d_building_idx [n] int32 (device) receives every point's building; the point figures of inout (the struct the map
+ * call for d_map created: same width and height) are overwritten.  BS_ERR_INVALID: null pointer, n < 1, bin < 1, a
+ * struct of another raster; BS_ERR_RANGE: 2^29 points or more, or a point with a negative x / y or whose pixel lies
+ * outside the image (inout is then left as it was).  Synchronises. */
+int bs_assign_buildings_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, double ground_th,
+                            const int32_t* d_map, int32_t width, int32_t height, int32_t* d_building_idx,
+                            bs_buildings* inout);
+/* Host-memory variant: xyz, map and building_idx are host pointers. */
+int bs_assign_buildings(bs_ctx* ctx, const int32_t* xyz, int64_t n, int32_t bin, double ground_th, const int32_t* map,
+                        int32_t width, int32_t height, int32_t* building_idx, bs_buildings* inout);
+
+/* d_plane_idx / d_building_idx [n] are device pointers, the four result arrays host [n_planes] (entry p - 1 is plane
+ * p; not touched when n_planes == 0).  Labels outside 1 .. n_planes (-1 = unlabelled) are ignored.
+ * BS_ERR_INVALID: null pointer, n < 1, n_planes < 0, n_buildings < 0; BS_ERR_RANGE: 2^29 points or more, or a
+ * building index outside [-1, n_buildings).  Synchronises. */
+int bs_plane_buildings_dev(bs_ctx* ctx, const int32_t* d_plane_idx, const int32_t* d_building_idx, int64_t n,
+                           int32_t n_planes, int32_t n_buildings, int32_t* plane_building, int64_t* votes_in,
+                           int64_t* votes_total, int64_t* votes_outside);
+/* Host-memory variant: plane_idx and building_idx are host pointers. */
+int bs_plane_buildings(bs_ctx* ctx, const int32_t* plane_idx, const int32_t* building_idx, int64_t n, int32_t n_planes,
+                       int32_t n_buildings, int32_t* plane_building, int64_t* votes_in, int64_t* votes_total,
+                       int64_t* votes_outside);
+
+/* LoD1 model in millimetres: every kept footprint extruded from the ground threshold to the mean height of its
+ * above-ground points.  Host only.  c and b describe the same mask (c->n_contours == b->n_buildings).  Contour i is
+ * KEPT iff area[i] > min_area && perimeter[i] > min_perimeter (the reference's filter, my_function.cpp:42, uses 500
+ * and 100) && n_above[i] > 0.  origin [3] is the shift that was subtracted from the cloud (NULL: 0).  The file, every
+ * number a decimal integer, every line ended by '\n':
+ *   "# buildings: <kept> of <n_contours>"
+ *   for every kept contour in order, for every point (x, y) of it in order, two lines
+ *     "v X Y Z0" and "v X Y Z1"   X = x * bin + origin[0], Y = y * bin + origin[1],
+ *                                 Z0 = (int64) ground_th + origin[2]            (truncated towards zero)
+ *                                 Z1 = z_sum[i] / n_above[i] + origin[2]        (quotient truncated towards zero)
+ *   for every kept contour in order, for k = 0 .. n - 1 (n = its points, vertices numbered from 1 in file order,
+ *   base = the contour's first vertex, nx = (k + 1) % n), the reference's side quad (my_function.cpp:109-126)
+ *     "f <base+2k> <base+2nx> <base+2nx+1> <base+2k+1>"
+ *   for every kept contour with n >= 3 in order, the roof over its top vertices
+ *     "f <base+1> <base+3> ... <base+2n-1>"
+ * BS_ERR_INVALID: null pointer, bin < 1, counts that differ, or the file cannot be written. */
+int bs_buildings_write_obj(const bs_contours* c, const bs_buildings* b, int32_t bin, const int32_t* origin,
+                           double ground_th, double min_area, double min_perimeter, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
