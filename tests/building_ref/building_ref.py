@@ -11,6 +11,9 @@ import numpy as np
 I32_MAX, I32_MIN = np.iinfo(np.int32).max, np.iinfo(np.int32).min
 FOUR = np.array([[0, 1, 0], [1, 1, 1], [0, 1, 0]])
 EIGHT = np.ones((3, 3), int)
+# the per-building arrays of building_map and of assign, under the names the device's Buildings gives them
+PIXEL_FIGURES = ("start_xy", "bbox", "pixels", "fg_pixels")
+POINT_FIGURES = ("n_points", "n_above", "z_min", "z_max", "z_sum")
 
 
 def _per_group(keys, n_groups):

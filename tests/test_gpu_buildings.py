@@ -23,8 +23,7 @@ from test_gpu_footprints import SHAPES, SIZES, _spiral  # noqa: E402
 FIXTURES = sorted(glob.glob(os.path.join(HERE, "golden", "raster_*.npz")))
 pytestmark = pytest.mark.gpu
 
-PIXEL_FIGURES = ("start_xy", "bbox", "pixels", "fg_pixels")
-POINT_FIGURES = ("n_points", "n_above", "z_min", "z_max", "z_sum")
+PIXEL_FIGURES, POINT_FIGURES = bref.PIXEL_FIGURES, bref.POINT_FIGURES
 
 
 def _same_map(bmap, b, r):
