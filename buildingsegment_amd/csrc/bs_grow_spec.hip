@@ -325,12 +325,194 @@ __global__ __launch_bounds__(256) void rev_fill_kernel(const uint32_t* __restric
   }
 }
 
+constexpr int OWN_TRIP = 16;  // reverse-list edges (owners of a row) fetched per trip of an owner kernel
+constexpr int WL_CAP = 1024;  // worklist entries a workgroup stages in LDS before it reserves room for them (wl_compact_kernel)
+constexpr int WL_WAVE = 256;  // ... and a single wave where the waves of a workgroup run on their own (wl_add)
+
+// ---- worklists of 256-point groups -----------------------------------------------
+// The groups a pass has to visit are a compact LIST of which every workgroup of the pass takes an equal share,
+// instead of "workgroup b looks at the flags of groups [b sub, (b + 1) sub)": the dirty groups of an inserted or
+// dropped plane are neighbours in Morton order, so under the fixed assignment a few workgroups walked up to `sub`
+// of them one after the other while the rest of the chip had left.  Pass p reads list p & 1, whose length is
+// counter p % 3, appends to the other list under counter (p + 1) % 3 and clears counter (p + 2) % 3 -- the one
+// the pass before it consumed and the pass after it appends to.  Nothing but "a pass reads what earlier launches
+// wrote" orders the workgroups.  Entries are staged in LDS and a workgroup (wl_flush) or a wave (wl_add) reserves
+// room for them with one atomic on the counter per flush: once at the end, and before that whenever WL_CAP entries
+// (a wave: more than WL_WAVE - 64) are staged.  Most waves flush once per pass; in the heaviest passes (124 k groups
+// listed) a wave flushes several times, at most 124 k / 192 = 650 atomics per pass over the whole chip.  A list holds
+// a group at most once (test-and-set on the group's flag where several may name it), so nb256 entries always suffice.
+// (block-uniform call; `staged` = entries in l_buf, the same value in every thread)
+__device__ __forceinline__ void wl_flush(const int* l_buf, int* l_base, int staged, int32_t* list, int* cnt)
+{
+  if (threadIdx.x == 0)
+    *l_base = atomicAdd(cnt, staged);
+  __syncthreads();
+  const int b = *l_base;
+  for (int i = threadIdx.x; i < staged; i += blockDim.x)
+    list[b + i] = l_buf[i];
+  __syncthreads();
+}
+
+// plane_apply_kernel marks the groups it dirties in byte flags, as it always did (a test-and-set per listed point
+// doubled its time); before the first pass of the settle they are moved to the worklist, in ascending order within
+// a workgroup's 1024 flags, so that the first and heaviest pass reads its dirty flags almost sequentially
+__global__ __launch_bounds__(256) void wl_compact_kernel(uint8_t* bdirty, int nb, uint32_t* gflag, int32_t* list, int* cnt)
+{
+  __shared__ int l_buf[WL_CAP];
+  __shared__ int l_base;
+  __shared__ int wsum[4];
+  int staged = 0;
+  for (int j = 0; j < WL_CAP / 256; j++) {
+    const int g = blockIdx.x * WL_CAP + j * 256 + threadIdx.x;
+    bool add = false;
+    if (g < nb && bdirty[g]) {
+      bdirty[g] = 0;
+      add = atomicExch(gflag + g, 1u) == 0u;
+    }
+    // slot = entries of the earlier threads: the list stays sorted
+    const unsigned long long am = ballot64(add);
+    if ((threadIdx.x & 63) == 0)
+      wsum[threadIdx.x >> 6] = __popcll(am);
+    __syncthreads();
+    int before = __popcll(am & ((1ull << (threadIdx.x & 63)) - 1ull)), total = 0;
+    for (int w = 0; w < 4; w++) {
+      before += w < (int)(threadIdx.x >> 6) ? wsum[w] : 0;
+      total += wsum[w];
+    }
+    if (add)
+      l_buf[staged + before] = g;
+    staged += total;
+    __syncthreads();
+  }
+  if (staged)
+    wl_flush(l_buf, &l_base, staged, list, cnt);
+}
+
+// The same for ONE wave, without a barrier: the waves of a workgroup that marks dirty groups each keep WL_WAVE staged
+// entries of their own and go on at their own pace (with the appends of a workgroup behind block barriers the
+// heavy passes after a big round took twice as long as the flag scan they replace: 1.68 against 0.81 ms).
+// wave-uniform calls; `staged` is the same in every lane
+__device__ __forceinline__ void wl_wave_flush(int* wbuf, int& staged, int32_t* list, int* cnt)
+{
+  const int lane = threadIdx.x & 63;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // the lanes' LDS writes before the other lanes' reads
+  __builtin_amdgcn_wave_barrier();
+  int b = 0;
+  if (lane == 0)
+    b = atomicAdd(cnt, staged);
+  b = __shfl(b, 0);
+  for (int i = lane; i < staged; i += 64)
+    list[b + i] = wbuf[i];
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  staged = 0;
+}
+
+// lanes with `want` name group g for the next pass: listed by whoever sets its flag first (callers look at the flag
+// with a plain load before they ask: most groups are named many times per pass)
+__device__ __forceinline__ void wl_add(bool want, int32_t g, uint32_t* gflag, int* wbuf, int& staged, int32_t* list, int* cnt)
+{
+  if (!ballot64(want))
+    return;
+  const bool added = want && atomicExch(gflag + g, 1u) == 0u;
+  const unsigned long long am = ballot64(added);
+  if (am == 0)
+    return;
+  if (added)
+    wbuf[staged + __popcll(am & ((1ull << (threadIdx.x & 63)) - 1ull))] = g;
+  staged += __popcll(am);
+  if (staged > WL_WAVE - 64)
+    wl_wave_flush(wbuf, staged, list, cnt);
+}
+
+struct PullEval {
+  bool flip;    // the point's occurrence bit changed: its row has to hear about it
+  bool walked;  // the reverse list was read
+  uint32_t m0;  // static mask of the point's row
+};
+
+// Re-evaluation of the dirty point c.  Every load that depends on nothing but c is issued in one batch, the reverse
+// list is fetched OWN_TRIP edges per trip -- all edges, then all their occurrence words, then the original indices --
+// so a list of <= 16 edges costs three memory latencies where four edges per trip cost three per trip (mean list: 14).
+// Loads are unconditional with a harmless address where the value is not needed (the point's own entry: one cache line
+// per wave), because a conditional load is a branch and the loads behind it wait for it.
+__device__ __forceinline__ PullEval pull_eval(int64_t c, const uint32_t* __restrict__ hmask, const int32_t* __restrict__ prio,
+                                              const uint8_t* __restrict__ ps, const int32_t* __restrict__ base,
+                                              const int64_t* __restrict__ roff, const int32_t* __restrict__ radj,
+                                              int32_t* __restrict__ omega, uint32_t* occ, int4* rec, int quads,
+                                              const int32_t* __restrict__ minr)
+{
+  int32_t v = base[c];
+  const int32_t mr = minr[c];
+  const int64_t e0 = roff[c], e1 = roff[c + 1];
+  const uint32_t m0 = hmask[c];
+  const uint8_t psc = ps[c];
+  const int32_t pc = prio[c];
+  const uint32_t cbit = 1u << (c & 31);
+  // (bit c is only ever written by the one thread that re-evaluates c in this pass: reading the word early is safe)
+  const uint32_t oword = __hip_atomic_load(occ + (c >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // minr[c] = lowest original index in R(c): a base owner at or below it cannot be undercut by any maker,
+  // occurring or not -- the points of an inserted plane (base = its seed) skip the reverse list altogether
+  const bool walk = v > mr;
+  if (walk) {
+    for (int64_t e = e0; e < e1; e += OWN_TRIP) {
+      int32_t j[OWN_TRIP];
+      uint32_t ow[OWN_TRIP];
+      int32_t pj[OWN_TRIP];
+#pragma unroll
+      for (int i = 0; i < OWN_TRIP; i++)
+        j[i] = radj[e + i < e1 ? e + i : e1 - 1] & POS_MASK;  // (past the end: the last edge again, harmless for a minimum)
+      // occ is a BITMAP (n / 8 bytes: 6 MB at 50 M points, resident in L2 / Infinity Cache), so the ~14
+      // random look-ups per re-evaluated point do not go to HBM
+#pragma unroll
+      for (int i = 0; i < OWN_TRIP; i++)
+        ow[i] = __hip_atomic_load(occ + (j[i] >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+      for (int i = 0; i < OWN_TRIP; i++) {
+        const bool o = ((ow[i] >> (j[i] & 31)) & 1u) != 0;
+        pj[i] = prio[o ? (int64_t)j[i] : c];  // makers are compared by ORIGINAL index; few sources of a list occur
+        pj[i] = o ? pj[i] : INF;
+      }
+#pragma unroll
+      for (int i = 0; i < OWN_TRIP; i++)
+        v = pj[i] < v ? pj[i] : v;
+    }
+  }
+  // (the makers' original indices stored beside the reverse-list entries, instead of prio[j] for the occurring ones:
+  // measured at 50 M -- owner passes 25.9 vs 25.6 ms per pass, rev_fill 8.7 vs 5.7 ms, decide_finish 3.1 vs 2.7 ms:
+  // few sources of a list occur, so the look-up it saves is rare and the extra stream is not)
+  omega[c] = v;
+  reinterpret_cast<int32_t*>(rec + c * quads)[3] = v;  // the growth kernel reads the owner from the record
+  const bool want = m0 != 0 && !(psc & 1) && v >= pc;
+  const bool have = (oword & cbit) != 0;
+  if (want != have) {
+    if (want)
+      __hip_atomic_fetch_or(occ + (c >> 5), cbit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else
+      __hip_atomic_fetch_and(occ + (c >> 5), ~cbit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return {want != have, walk, m0};
+}
+
+// BS_DEBUG statistics of one pass (dbg[0] dirty groups, [1] dirty points, [2] points that walked their list, [3] most
+// groups one workgroup visited: observed under the flag scan, where it depends on where the dirty groups lie;
+// the worklist hands out equal shares, so there it is ceil(groups / workgroups) by construction); wave-uniform call
+__device__ __forceinline__ void pull_stats(int* dbg, bool dirty, bool walked)
+{
+  const int nd = __popcll(ballot64(dirty)), nw = __popcll(ballot64(walked));
+  if ((threadIdx.x & 63) == 0 && nd) {
+    atomicAdd(dbg + 1, nd);
+    atomicAdd(dbg + 2, nw);
+  }
+}
+
+// BS_OWNER_WORKLIST=0: the dirty groups found by their flags, every workgroup looking at its own `sub` groups
 __global__ void pull_pass_kernel(int64_t n, int K, int sub, const uint32_t* __restrict__ hmask,
                                  const int32_t* __restrict__ prio, const uint8_t* __restrict__ ps,
                                  const int32_t* __restrict__ base, const int64_t* __restrict__ roff,
                                  const int32_t* __restrict__ radj, int32_t* __restrict__ omega, uint32_t* occ,
                                  uint8_t* dirty_cur, uint8_t* dirty_next, uint8_t* bdirty_cur, uint8_t* bdirty_next,
-                                 int4* rec, int quads, int* any, const int32_t* __restrict__ minr, const int* prev_any)
+                                 int4* rec, int quads, int* any, const int32_t* __restrict__ minr, const int* prev_any, int* dbg)
 {
   // Only a pass that flipped something leaves dirty points behind: if the previous pass of this group reports none,
   // there is nothing to do -- every workgroup leaves after ONE scalar load (the passes behind the settling one of a
@@ -355,58 +537,26 @@ __global__ void pull_pass_kernel(int64_t n, int K, int sub, const uint32_t* __re
   }
   __syncthreads();
   unsigned long long gm = sub_mask;
+  if (dbg && threadIdx.x == 0 && gm) {
+    atomicAdd(dbg, __popcll(gm));
+    atomicMax(dbg + 3, __popcll(gm));
+  }
   bool flipped = false;
-  while (gm) {
+  while (gm) {  // (block-uniform)
     const int t = __ffsll(gm) - 1;
     gm &= gm - 1;
     const int64_t c = ((g0 + t) << 8) + threadIdx.x;
-    if (c >= n || !dirty_cur[c])
-      continue;
-    dirty_cur[c] = 0;
-    int32_t v = base[c];
-    // minr[c] = lowest original index in R(c): a base owner at or below it cannot be undercut by any maker,
-    // occurring or not -- the points of an inserted plane (base = its seed) skip the reverse list altogether
-    if (v > minr[c]) {
-      const int64_t e1 = roff[c + 1];
-      // four reverse edges at a time, each level of the dependent chain (edge -> occurrence bit -> original
-      // index) issued for all four before the first is waited for: a late pass re-evaluates a few hundred
-      // points and is bound by this chain's latency (~14 edges x 3 loads one after the other: 30 us per pass)
-      for (int64_t e = roff[c]; e < e1; e += 4) {
-        int32_t j[4];
-        uint32_t ow[4];
-        int32_t pj[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-          j[i] = e + i < e1 ? (radj[e + i] & POS_MASK) : -1;
-        // occ is a BITMAP (n / 8 bytes: 6 MB at 50 M points, resident in L2 / Infinity Cache), so the ~14
-        // random look-ups per re-evaluated point do not go to HBM
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-          ow[i] = j[i] >= 0 ? __hip_atomic_load(occ + (j[i] >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-          pj[i] = ((ow[i] >> (j[i] & 31)) & 1u) ? prio[j[i]] : INF;  // makers are compared by ORIGINAL index
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-          v = pj[i] < v ? pj[i] : v;
-      }
+    const bool d = c < n && dirty_cur[c] != 0;
+    PullEval r = {false, false, 0u};
+    if (d) {
+      dirty_cur[c] = 0;
+      r = pull_eval(c, hmask, prio, ps, base, roff, radj, omega, occ, rec, quads, minr);
     }
-    // (the makers' original indices stored beside the reverse-list entries, instead of prio[j] for the occurring ones:
-    // measured at 50 M -- owner passes 25.9 vs 25.6 ms per pass, rev_fill 8.7 vs 5.7 ms, decide_finish 3.1 vs 2.7 ms:
-    // few sources of a list occur, so the look-up it saves is rare and the extra stream is not)
-    omega[c] = v;
-    reinterpret_cast<int32_t*>(rec + c * quads)[3] = v;  // the growth kernel reads the owner from the record
-    const uint32_t m0 = hmask[c];
-    const uint8_t want = (m0 != 0 && !(ps[c] & 1) && v >= prio[c]) ? 1 : 0;
-    const uint32_t cbit = 1u << (c & 31);
-    const uint8_t have = (__hip_atomic_load(occ + (c >> 5), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & cbit) ? 1 : 0;
-    if (want != have) {
-      if (want)
-        __hip_atomic_fetch_or(occ + (c >> 5), cbit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else
-        __hip_atomic_fetch_and(occ + (c >> 5), ~cbit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (dbg)
+      pull_stats(dbg, d, r.walked);
+    if (r.flip) {
       const int32_t* row = reinterpret_cast<const int32_t*>(rec + c * quads + 4);
-      uint32_t m = m0;
+      uint32_t m = r.m0;
       while (m) {
         const int b = __ffs(m) - 1;
         m &= m - 1;
@@ -417,6 +567,98 @@ __global__ void pull_pass_kernel(int64_t n, int K, int sub, const uint32_t* __re
       flipped = true;
     }
   }
+  if (flipped)
+    *any = 1;
+}
+
+// The default: the dirty groups as a worklist (see wl_flush).  A pass whose list is empty leaves after one scalar load.
+// Termination of a settle is the parent's argument unchanged: a point is re-evaluated in the pass AFTER the one that
+// dirtied it, dependencies only run from lower to higher original indices, so the lowest index still changing rises
+// with every pass.
+__global__ __launch_bounds__(256) void pull_list_kernel(int64_t n, int K, const uint32_t* __restrict__ hmask,
+                                                        const int32_t* __restrict__ prio, const uint8_t* __restrict__ ps,
+                                                        const int32_t* __restrict__ base, const int64_t* __restrict__ roff,
+                                                        const int32_t* __restrict__ radj, int32_t* __restrict__ omega,
+                                                        uint32_t* occ, uint8_t* dirty_cur, uint8_t* dirty_next,
+                                                        const int32_t* __restrict__ list_cur, int32_t* list_next,
+                                                        uint32_t* gflag_cur, uint32_t* gflag_next, int* cnt, int s_cur,
+                                                        int s_nxt, int s_clr, int4* rec, int quads, int* any,
+                                                        const int32_t* __restrict__ minr, int* dbg)
+{
+  __shared__ int l_buf[4][WL_WAVE];
+  int* const wbuf = l_buf[threadIdx.x >> 6];
+  const int lane = threadIdx.x & 63;
+  const int ncur = cnt[s_cur];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    cnt[s_clr] = 0;
+    if (dbg && ncur) {
+      dbg[0] = ncur;
+      dbg[3] = (ncur + (int)gridDim.x - 1) / (int)gridDim.x;
+    }
+  }
+  if (ncur == 0)
+    return;
+  int staged = 0;
+  bool flipped = false;
+  // (no barrier in the loop: every wave of the workgroup walks the same entries, 64 points of each group, at its own pace)
+  // an equal share of consecutive entries per workgroup (striding the list instead, workgroup b taking entries b,
+  // b + grid, ..., puts the whole chip on neighbouring groups at any one time when the list is in ascending order:
+  // the first pass of a settle took 1.86 against 1.49 ms)
+  const int per = (ncur + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int i0 = blockIdx.x * per, i1 = min(ncur, i0 + per);
+  if (i0 >= i1)
+    return;
+  int32_t g_next = list_cur[i0];
+  for (int idx = i0; idx < i1; idx++) {
+    const int32_t g = g_next;
+    if (idx + 1 < i1)
+      g_next = list_cur[idx + 1];  // (one latency less per visit: the next entry is on its way during this one)
+    const int64_t c = ((int64_t)g << 8) + threadIdx.x;
+    if (threadIdx.x == 0)
+      gflag_cur[g] = 0;
+    const bool d = c < n && dirty_cur[c] != 0;
+    PullEval r = {false, false, 0u};
+    if (d) {
+      dirty_cur[c] = 0;
+      r = pull_eval(c, hmask, prio, ps, base, roff, radj, omega, occ, rec, quads, minr);
+    }
+    if (dbg)
+      pull_stats(dbg, d, r.walked);
+    if (!ballot64(r.flip))
+      continue;
+    flipped = flipped || r.flip;
+    // The row of a flipped point: every slot's point is dirty, its group is named once per run of equal groups
+    // (neighbouring points mostly name the same one).  OWN_TRIP slots per trip, the group flags of all of them
+    // loaded together: one slot at a time, each waiting for its flag, made the pass after a big round's insertions
+    // -- 2.3 M flips -- 1.49 ms against the flag scan's 0.81.
+    const int32_t* row = reinterpret_cast<const int32_t*>(rec + (d ? c : 0) * quads + 4);
+    for (int b0 = 0; b0 + 1 < K; b0 += OWN_TRIP) {  // (wave-uniform)
+      int32_t gq[OWN_TRIP];
+      uint32_t fl[OWN_TRIP];
+      bool rep[OWN_TRIP];
+#pragma unroll
+      for (int i = 0; i < OWN_TRIP; i++) {
+        const int b = b0 + i;
+        gq[i] = -1;
+        if (r.flip && b + 1 < K && ((r.m0 >> b) & 1u)) {
+          const int32_t q = row[b + 1];
+          dirty_next[q] = 1;
+          gq[i] = q >> 8;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < OWN_TRIP; i++) {
+        const int32_t left = __shfl_up(gq[i], 1);
+        rep[i] = gq[i] >= 0 && (lane == 0 || left != gq[i]) && (i == 0 || gq[i - 1] != gq[i]);
+        fl[i] = __hip_atomic_load(gflag_next + (rep[i] ? gq[i] : g), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+#pragma unroll
+      for (int i = 0; i < OWN_TRIP; i++)
+        wl_add(rep[i] && fl[i] == 0u, gq[i], gflag_next, wbuf, staged, list_next, cnt + s_nxt);
+    }
+  }
+  if (staged)
+    wl_wave_flush(wbuf, staged, list_next, cnt + s_nxt);
   if (flipped)
     *any = 1;
 }
@@ -443,8 +685,13 @@ __global__ void decide_init_kernel(const uint32_t* __restrict__ hmask, int64_t n
 
 __global__ void decide_pass_kernel(int64_t n, int sub, const int32_t* __restrict__ prio,
                                    const int64_t* __restrict__ roff, const int32_t* __restrict__ radj, uint8_t* st,
-                                   uint8_t* bund, int* any)
+                                   uint8_t* bund, int* any, const int* prev_any)
 {
+  // (launched in groups like the owner passes: behind the pass that decided the last point nothing is left to do)
+  if (prev_any && *prev_any == 0)
+    return;
+  // The first passes look at every point and are bound by what they move, not by latency: they stay on four edges
+  // per trip and on the flag scan (as a worklist with 16-edge trips the 13 passes took 5.0-5.1 ms against 4.3).
   __shared__ unsigned long long sub_mask;
   __shared__ int left[64];
   const int64_t nb256 = (n + 255) >> 8;
@@ -604,17 +851,22 @@ __global__ void cand_flag_kernel(const int4* __restrict__ rec, int quads, int K,
       const int32_t oi = omega[i];
       alive = !(oi < F);  // (a pending plane's seed counts as alive: the plane can still be dropped)
       if (pi >= F && oi >= pi && (all_seeds || !(f & 1))) {  // (all_seeds: the audit lists committed seeds too)
-        // all K-1 neighbours free at the seed's time; four owners per trip, loaded unconditionally (a
-        // short-circuit `c && ...` chains up to K-1 dependent loads one after the other)
+        // all K-1 neighbours free at the seed's time; OWN_TRIP owners per trip (all of them at k <= 17), loaded
+        // unconditionally (a short-circuit `c && ...` chains up to K-1 dependent loads one after the other;
+        // a slot past the row reads the last neighbour's owner again)
         c = true;
         const int32_t* row = reinterpret_cast<const int32_t*>(rec + i * quads + 4);
-        for (int u = 1; u < K; u += 4) {
-          int32_t ov[4];
+        for (int u = 1; u < K; u += OWN_TRIP) {
+          int32_t nb[OWN_TRIP];
+          int32_t ov[OWN_TRIP];
 #pragma unroll
-          for (int q = 0; q < 4; q++)
-            ov[q] = u + q < K ? omega[row[u + q]] : INF;
+          for (int q = 0; q < OWN_TRIP; q++)
+            nb[q] = row[u + q < K ? u + q : K - 1];
 #pragma unroll
-          for (int q = 0; q < 4; q++)
+          for (int q = 0; q < OWN_TRIP; q++)
+            ov[q] = omega[nb[q]];
+#pragma unroll
+          for (int q = 0; q < OWN_TRIP; q++)
             c = c && ov[q] >= pi;
         }
       }
@@ -2454,10 +2706,12 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   BS_HIP(ctx, ctx->rg_planes.reserve(sizeof(PlaneRec) * planes_cap));
   BS_HIP(ctx, ctx->rg_stats.reserve(sizeof(GrowStats)));
   // aux layout (int32 units): misc[1024] | hmask | omega | base | dead | prio | rpos(n+64) | vmark | seeds |
-  //                            (u8) flags | ps | occ | dirty0 | dirty1 | PlaneOut[MAX_WAVES + MAX_PENDING] | CopyDesc[]
+  //                            (u8) flags | ps | occ | dirty0 | dirty1 | bdirty0 | bdirty1 | bcand |
+  //                            (i32) worklist0[nb256] | worklist1[nb256] | (u32) gflag0[nb256] | gflag1[nb256] |
+  //                            PlaneOut[MAX_WAVES + MAX_PENDING] | CopyDesc[]
   const size_t n_i32 = (size_t)(7 * n + planes_cap + 1024 + 128);
   const size_t nb256 = (size_t)((n + 255) / 256);
-  const size_t aux_bytes = sizeof(int32_t) * n_i32 + (size_t)5 * n + 3 * nb256 + 8192 +
+  const size_t aux_bytes = sizeof(int32_t) * n_i32 + (size_t)5 * n + 3 * nb256 + 16 * nb256 + 8192 +
                            sizeof(PlaneOut) * ((size_t)wave_cap + MAX_PENDING) +
                            sizeof(CopyDesc) * ((size_t)wave_cap + MAX_PENDING);
   BS_HIP(ctx, ctx->rg_aux.reserve(aux_bytes));
@@ -2484,7 +2738,14 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   uint8_t* bdirty0 = dirty1 + n;  // one flag per 256 points
   uint8_t* bdirty1 = bdirty0 + nb256;
   uint8_t* bcand = bdirty1 + nb256;  // one flag per 256 positions: can the group still hold a plane seed?
-  PlaneOut* d_out = (PlaneOut*)(((uintptr_t)(bcand + nb256) + 255) & ~(uintptr_t)255);
+  // worklists of the owner passes (see wl_flush): two lists of groups and, for the dirty groups, two flag arrays
+  int32_t* wl_list[2];
+  uint32_t* wl_flag[2];
+  wl_list[0] = (int32_t*)(((uintptr_t)(bcand + nb256) + 15) & ~(uintptr_t)15);
+  wl_list[1] = wl_list[0] + nb256;
+  wl_flag[0] = (uint32_t*)(wl_list[1] + nb256);
+  wl_flag[1] = wl_flag[0] + nb256;
+  PlaneOut* d_out = (PlaneOut*)(((uintptr_t)(wl_flag[1] + nb256) + 255) & ~(uintptr_t)255);
   PlaneOut* d_pend = d_out + wave_cap;
   CopyDesc* d_copy = (CopyDesc*)(d_pend + MAX_PENDING);
   int32_t* radj = ctx->rg_radj.as<int32_t>();
@@ -2584,24 +2845,55 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   const int pull_sub = (int)std::max<int64_t>(1, std::min<int64_t>(64, (int64_t)nb256 / 4096));
   // the candidate scan does real work in most groups until the last rounds: fewer groups per workgroup keep it parallel
   const int cand_sub = std::max(1, pull_sub / 8);
+  // Scheduling of the owner passes, read per call.  BS_OWNER_WORKLIST=0: the dirty groups are found
+  // by their flags, `pull_sub` per workgroup (pull_pass_kernel; the re-evaluation of a point is the same code).
+  // BS_OWNER_GRID: fewer workgroups per pass than the default; BS_OWNER_GROUP: fewer passes per host round trip.
+  // Results do not depend on any of them.
+  const bool use_wl = !(getenv("BS_OWNER_WORKLIST") && atoi(getenv("BS_OWNER_WORKLIST")) == 0);
+  // a few thousand workgroups share the list: enough to fill the chip twice over in a heavy pass, and a pass
+  // with a handful of groups costs the launch of the rest (they leave after one scalar load)
+  int own_grid = (int)std::min<size_t>(nb256, 4096);
+  if (const char* e = getenv("BS_OWNER_GRID"))
+    own_grid = std::max(1, std::min(own_grid, atoi(e)));
+  constexpr int PULL_GROUP = 16;
+  int own_group = PULL_GROUP;
+  if (const char* e = getenv("BS_OWNER_GROUP"))
+    own_group = std::max(2, std::min(PULL_GROUP, atoi(e)));
+  int* const wl_cnt = d_misc + 64;  // three list lengths, see wl_flush
+  int64_t wl_pass = 0;              // owner passes launched so far: which list and which counter the next one reads
+  bool wl_marked = false;           // plane_apply_kernel has marked groups since the last settle
+  const bool dbg = getenv("BS_DEBUG") != nullptr;  // (not once per attempt: 158 k of them in a first round)
+  // per-round results read by the host: page-locked (158 k attempts in the first round of the 50 M cloud are
+  // 18 MB each way)
+  BS_HIP(ctx, ctx->rg_hout.reserve(sizeof(PlaneOut) * ((size_t)wave_cap + MAX_PENDING) + 256));
+  PlaneOut* const h_out = ctx->rg_hout.as<PlaneOut>();
+  PlaneOut* const h_pend = h_out + wave_cap;
+  int32_t* const h_flags = reinterpret_cast<int32_t*>(h_pend + MAX_PENDING);  // small scalars copied back per pass / round
+  int32_t* const h_cnt = h_flags + 48;
   {
-    uint8_t* state = dirty1;   // scratch until the dirty flags are cleared below
+    // decided states in groups of own_group passes with one copy-back per group, as propagate() below does it: a pass
+    // behind the deciding one leaves after one scalar load (13 passes and 13 round trips at 50 M before).  Whatever
+    // BS_OWNER_WORKLIST says: the grouping is BS_OWNER_GROUP's.  (`passes`, and with it GrowStats.steps, counts
+    // launches: 16 here at 50 M where it counted 13.)
+    uint8_t* state = dirty1;  // scratch until the dirty flags are cleared below
     uint8_t* bund = bdirty1;
+    int32_t* const d_any = d_misc + 32;  // (d_flip below)
     decide_init_kernel<<<nblk(n, 256), 256, 0, st>>>(hmask, n, state, bund);
     for (int it = 0;; it++) {
-      BS_HIP(ctx, hipMemsetAsync(d_misc, 0, sizeof(int), st));
-      decide_pass_kernel<<<(int)((nb256 + pull_sub - 1) / pull_sub), 256, 0, st>>>(n, pull_sub, prio, roff, radj, state, bund,
-                                                                                  d_misc);
-      int any = 0;
-      BS_HIP(ctx, hipMemcpyAsync(&any, d_misc, sizeof any, hipMemcpyDeviceToHost, st));
+      BS_HIP(ctx, hipMemsetAsync(d_any, 0, sizeof(int32_t) * PULL_GROUP, st));
+      for (int g = 0; g < own_group; g++, passes++)
+        decide_pass_kernel<<<(int)((nb256 + pull_sub - 1) / pull_sub), 256, 0, st>>>(n, pull_sub, prio, roff, radj, state, bund,
+                                                                                    d_any + g, g ? d_any + g - 1 : nullptr);
+      BS_HIP(ctx, hipMemcpyAsync(h_cnt, d_any + own_group - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
       BS_HIP(ctx, hipStreamSynchronize(st));
-      passes++;
-      if (!any)
+      if (h_cnt[0] == 0)
         break;
       if (it > 4 * 1000 * 1000)
         return fail(ctx, BS_ERR_INTERNAL, "orphan fixed point (decided states) did not converge");
     }
     decide_finish_kernel<<<nblk(n, 256), 256, 0, st>>>(n, prio, roff, radj, state, omega, occ, rec, quads, rpos);
+    BS_HIP(ctx, hipMemsetAsync(wl_cnt, 0, 3 * sizeof(int), st));
+    BS_HIP(ctx, hipMemsetAsync(wl_flag[0], 0, sizeof(uint32_t) * 2 * nb256, st));
   }
   BS_HIP(ctx, hipMemsetAsync(dirty0, 0, n, st));
   BS_HIP(ctx, hipMemsetAsync(dirty1, 0, n, st));
@@ -2613,36 +2905,58 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   uint8_t* dnext = dirty1;
   uint8_t* bcur = bdirty0;
   uint8_t* bnext = bdirty1;
-  // per-round results read by the host: page-locked (158 k attempts in the first round of the 50 M cloud are
-  // 18 MB each way)
-  BS_HIP(ctx, ctx->rg_hout.reserve(sizeof(PlaneOut) * ((size_t)wave_cap + MAX_PENDING) + 256));
-  PlaneOut* const h_out = ctx->rg_hout.as<PlaneOut>();
-  PlaneOut* const h_pend = h_out + wave_cap;
-  int32_t* const h_flags = reinterpret_cast<int32_t*>(h_pend + MAX_PENDING);  // small scalars copied back per pass / round
   // The passes are launched in groups of PULL_GROUP with ONE host round trip per group: a pass that finds
   // nothing dirty costs microseconds, a round trip ~50 us, and a plane insertion settles in 8-25 passes.
   // Every pass reports its flips in its own word; the structure is a fixed point when the LAST pass of a
   // group flipped nothing (the passes after the settling one find no dirty point and do nothing).
   // (16 per group: a settling takes 8-26 passes, so ONE round trip usually decides it; the passes launched after
   // the settling one find nothing dirty: 16 x 2-3 us against 45 us per extra round trip with groups of four)
-  constexpr int PULL_GROUP = 16;
+  // (BS_OWNER_GROUP lowers the passes per group.  The worklist of the dirty groups, its counters and wl_pass carry
+  // over from one group to the next and from one settle to the next: the first pass of a group reads what the last
+  // pass of the group before it, or plane_apply_kernel, appended.)
   int32_t* const d_flip = d_misc + 32;
   int32_t* const h_flip = h_flags + 32;
+  int32_t* const d_pstat = d_misc + 128;  // BS_DEBUG: four statistics per pass of a group, see pull_stats
   auto propagate = [&]() -> int {
+    if (use_wl && wl_marked)
+      wl_compact_kernel<<<(int)((nb256 + WL_CAP - 1) / WL_CAP), 256, 0, st>>>(bcur, (int)nb256, wl_flag[wl_pass & 1], wl_list[wl_pass & 1],
+                                                                      wl_cnt + wl_pass % 3);
+    wl_marked = false;
     for (int it = 0; it < 1000000; it++) {
       BS_HIP(ctx, hipMemsetAsync(d_flip, 0, sizeof(int32_t) * PULL_GROUP, st));
-      for (int g = 0; g < PULL_GROUP; g++) {
-        pull_pass_kernel<<<(int)((nb256 + pull_sub - 1) / pull_sub), 256, 0, st>>>(n, K, pull_sub, hmask, prio, ps, base, roff, radj,
-                                                                                  omega, occ, dcur, dnext, bcur, bnext, rec, quads,
-                                                                                  d_flip + g, rpos /* = minr after the setup */,
-                                                                                  g ? d_flip + g - 1 : nullptr);
+      if (dbg)
+        BS_HIP(ctx, hipMemsetAsync(d_pstat, 0, sizeof(int32_t) * 4 * PULL_GROUP, st));
+      for (int g = 0; g < own_group; g++) {
+        if (use_wl) {
+          const int cur = (int)(wl_pass & 1);
+          pull_list_kernel<<<own_grid, 256, 0, st>>>(n, K, hmask, prio, ps, base, roff, radj, omega, occ, dcur, dnext, wl_list[cur],
+                                                    wl_list[cur ^ 1], wl_flag[cur], wl_flag[cur ^ 1], wl_cnt, (int)(wl_pass % 3),
+                                                    (int)((wl_pass + 1) % 3), (int)((wl_pass + 2) % 3), rec, quads, d_flip + g,
+                                                    rpos /* = minr after the setup */, dbg ? d_pstat + 4 * g : nullptr);
+          wl_pass++;
+        } else {
+          pull_pass_kernel<<<(int)((nb256 + pull_sub - 1) / pull_sub), 256, 0, st>>>(n, K, pull_sub, hmask, prio, ps, base, roff, radj,
+                                                                                    omega, occ, dcur, dnext, bcur, bnext, rec, quads,
+                                                                                    d_flip + g, rpos /* = minr after the setup */,
+                                                                                    g ? d_flip + g - 1 : nullptr,
+                                                                                    dbg ? d_pstat + 4 * g : nullptr);
+        }
         passes++;
         std::swap(dcur, dnext);  // dcur now holds the newly dirtied points (the old dcur was cleared by the pass)
         std::swap(bcur, bnext);
       }
       BS_HIP(ctx, hipMemcpyAsync(h_flip, d_flip, sizeof(int32_t) * PULL_GROUP, hipMemcpyDeviceToHost, st));
+      if (dbg) {
+        int32_t hs[4 * PULL_GROUP];
+        BS_HIP(ctx, hipMemcpyAsync(hs, d_pstat, sizeof hs, hipMemcpyDeviceToHost, st));
+        BS_HIP(ctx, hipStreamSynchronize(st));
+        for (int g = 0; g < own_group; g++)
+          if (hs[4 * g])
+            fprintf(stderr, "[bs] owner pass %ld: dirty groups %d, dirty points %d, walked their list %d, most groups in one workgroup %d\n",
+                    (long)(passes - own_group + g), hs[4 * g], hs[4 * g + 1], hs[4 * g + 2], hs[4 * g + 3]);
+      }
       BS_HIP(ctx, hipStreamSynchronize(st));
-      if (!h_flip[PULL_GROUP - 1]) {
+      if (!h_flip[own_group - 1]) {
         if (getenv("BS_VERIFY")) {
           BS_HIP(ctx, hipMemsetAsync(d_misc + 3, 0, sizeof(int), st));
           verify_fixpoint_kernel<<<nblk(n, 256), 256, 0, st>>>(n, hmask, prio, ps, base, roff, radj, omega, occ, d_misc + 3);
@@ -2740,7 +3054,6 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   int64_t incons[3] = {0, 0, 0};
   int forge_mode = ctx->forge_mode;
   ctx->forge_mode = 0;
-  const bool dbg = getenv("BS_DEBUG") != nullptr;  // (not once per attempt: 158 k of them in a first round)
   const bool do_validate3 = getenv("BS_NO_VALIDATE3") == nullptr;  // developer A/B switch
   // Step engine.  grow_spec2_kernel<16> (hot loop + complete step, assumption log in an LDS ring) takes every round at
   // k <= 16, the crowded first one included: round 1 of the 50 M cloud in 82-86 ms against the first engine's 94-97 ms,
@@ -2856,6 +3169,7 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       reset_dead_kernel<<<nblk(ncand, 256), 256, 0, st>>>(d_cand, ncand, dead);
       // insert the finished planes and let the owners settle
       plane_apply_kernel<<<ncand, VT, 0, st>>>(d_out, ncand, pool.base, base, ps, dcur, bcur, omega, occ, rec, quads);
+      wl_marked = true;
       rc = propagate();
       if (rc != BS_OK)
         return rc;
@@ -3089,10 +3403,12 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       if (nh) {
         BS_HIP(ctx, hipMemcpyAsync(d_outh, h_out, sizeof(PlaneOut) * nh, hipMemcpyHostToDevice, st));
         plane_apply_kernel<<<nh, VT, 0, st>>>(d_outh, nh, pool.base, base, ps, dcur, bcur, omega, occ, rec, quads);
+        wl_marked = true;
       }
       if (npend) {
         BS_HIP(ctx, hipMemcpyAsync(d_pend, h_pend, sizeof(PlaneOut) * npend, hipMemcpyHostToDevice, st));
         plane_apply_kernel<<<npend, VT, 0, st>>>(d_pend, npend, pstore, base, ps, dcur, bcur, omega, occ, rec, quads);
+        wl_marked = true;
       }
       rc = propagate();
       if (rc != BS_OK)
