@@ -31,7 +31,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_shift_tiles_to_origin_dev", "bs_tile_boxes_dev", "bs_grid_dims_batch", "bs_grid_picture_batch_dev",
            "bs_grid_picture_batch", "bs_footprints_batch_dev", "bs_footprints_batch", "bs_building_map_dev",
            "bs_building_map", "bs_buildings_free", "bs_assign_buildings_dev", "bs_assign_buildings",
-           "bs_plane_buildings_dev", "bs_plane_buildings", "bs_buildings_write_obj"]
+           "bs_plane_buildings_dev", "bs_plane_buildings", "bs_buildings_write_obj", "bs_roof_homes", "bs_roofs_dev",
+           "bs_roofs", "bs_roofs_free", "bs_roofs_write_obj"]
 
 
 class Params(C.Structure):
@@ -109,6 +110,16 @@ class Buildings(C.Structure):
                 ("n_above", C.POINTER(C.c_int64)), ("z_min", C.POINTER(C.c_int32)), ("z_max", C.POINTER(C.c_int32)),
                 ("z_sum", C.POINTER(C.c_int64)), ("ms_label_mask", C.c_double), ("ms_label_fill", C.c_double),
                 ("ms_number", C.c_double), ("ms_map", C.c_double), ("ms_assign", C.c_double)]
+
+
+class Roofs(C.Structure):
+    """bs_roofs (include/bs_api.h): per-plane roof figures, host memory owned by the library."""
+    _fields_ = [("n_planes", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("fill_rounds", C.c_int32),
+                ("seeded_pixels", C.c_int64), ("filled_pixels", C.c_int64), ("unroofed_pixels", C.c_int64),
+                ("pixels", C.POINTER(C.c_int64)), ("seed_pixels", C.POINTER(C.c_int64)), ("bbox", C.POINTER(C.c_int32)),
+                ("n_support", C.POINTER(C.c_int64)), ("z_min", C.POINTER(C.c_int32)), ("z_max", C.POINTER(C.c_int32)),
+                ("z_sum", C.POINTER(C.c_int64)), ("ms_vote", C.c_double), ("ms_fill", C.c_double),
+                ("ms_figures", C.c_double), ("ms_height", C.c_double)]
 
 
 class BsError(RuntimeError):
@@ -216,5 +227,14 @@ def load():
     L.bs_plane_buildings_dev.argtypes = [vp, ip, ip, C.c_int64, C.c_int32, C.c_int32, ip, vp, vp, vp]
     L.bs_plane_buildings.argtypes = [vp, ip, ip, C.c_int64, C.c_int32, C.c_int32, ip, vp, vp, vp]
     L.bs_buildings_write_obj.argtypes = [cp, bp, C.c_int32, ip, C.c_double, C.c_double, C.c_double, C.c_char_p]
+    rp = C.POINTER(Roofs)
+    L.bs_roof_homes.argtypes = [dp, ip, vp, vp, C.c_int32, C.c_double, ip]
+    roofs_args = [vp, ip, C.c_int64, C.c_int32, C.c_double, ip, C.c_int32, C.c_int32, ip, C.c_int32, ip, dp, ip, C.c_int32,
+                  ip, ip, ip, rp]
+    L.bs_roofs_dev.argtypes = roofs_args
+    L.bs_roofs.argtypes = roofs_args
+    L.bs_roofs_free.argtypes = [rp]
+    L.bs_roofs_free.restype = None
+    L.bs_roofs_write_obj.argtypes = [ip, ip, C.c_int32, C.c_int32, rp, dp, ip, C.c_int32, ip, C.c_char_p]
     _LIB = L
     return L

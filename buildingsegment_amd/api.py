@@ -533,6 +533,61 @@ class Context:
             b.votes = self.plane_buildings(plane_idx, b.building_idx, n_planes, b.n_buildings)
         return fp, b
 
+    # ---- roofs: the plane over every pixel of a building and its height there (bs_roofs, include/bs_api.h) ----------
+    def roofs(self, xyz, bmap, plane_idx, home, normal, center, bin=100, ground_th=0.0, min_votes=1, support=True,
+              height=True):
+        """Roof plane of every building pixel for a cloud shifted to its origin: vote of the counting points per pixel,
+        fill in synchronous rounds, per-plane figures and heights.  bmap is the building map, plane_idx the labels,
+        home / normal / center the per-plane tables (entry p - 1 is plane p; home from roof_homes).  Returns Roofs with
+        roof, support and height [height][width] int32 (support / height None when switched off)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError("xyz must be [n, 3]")
+        bmap = np.ascontiguousarray(bmap, dtype=np.int32)
+        if bmap.ndim != 2:
+            raise ValueError("roofs: bmap must be [height][width]")
+        pi = np.ascontiguousarray(plane_idx, dtype=np.int32)
+        if pi.shape != (len(xyz),):
+            raise ValueError("plane_idx must be [n]")
+        h, w = bmap.shape
+        tabs = _roof_tables(home, normal, center)
+        roof = np.empty((h, w), dtype=np.int32)
+        sup = np.empty((h, w), dtype=np.int32) if support else None
+        hgt = np.empty((h, w), dtype=np.int32) if height else None
+        out = _lib.Roofs()
+        self._check(self._L.bs_roofs(self._h, xyz.ctypes.data, len(xyz), bin, float(ground_th), bmap.ctypes.data, w, h,
+                                     pi.ctypes.data, len(tabs[0]), *[t.ctypes.data for t in tabs], min_votes,
+                                     roof.ctypes.data, sup.ctypes.data if support else None,
+                                     hgt.ctypes.data if height else None, C.byref(out)))
+        return _take_roofs(self._L, out, roof, sup, hgt, tabs, bin)
+
+    def roofs_dev(self, d_xyz, n, d_map, width, height, d_plane_idx, home, normal, center, d_roof, d_support=0,
+                  d_height=0, bin=100, ground_th=0.0, min_votes=1, n_planes=None):
+        """Device-resident variant: d_xyz, d_map, d_plane_idx, d_roof and the optional d_support / d_height are device
+        pointers (ints); the tables stay host arrays.  The Roofs that comes back holds the figures only."""
+        tabs = _roof_tables(home, normal, center)
+        out = _lib.Roofs()
+        self._check(self._L.bs_roofs_dev(self._h, d_xyz or None, n, bin, float(ground_th), d_map or None, width, height,
+                                         d_plane_idx or None, len(tabs[0]) if n_planes is None else n_planes,
+                                         *[t.ctypes.data for t in tabs], min_votes, d_roof or None, d_support or None,
+                                         d_height or None, C.byref(out)))
+        return _take_roofs(self._L, out, None, None, None, tabs, bin)
+
+    def roof_model(self, xyz, plane_idx, planes, bin=100, bin_height=1000, threshold=10, kernel_size=5, iterations=2,
+                   min_normal_z=0.5, min_votes=1):
+        """buildings() -> roof_homes -> roofs for a cloud shifted to its origin, its labels and the planes of segment().
+        Returns (Footprints, Buildings, Roofs); the Roofs carry home, normal, center and bin for write_roofs_obj."""
+        n_planes = len(planes)
+        if [p.id for p in planes] != list(range(1, n_planes + 1)):
+            raise ValueError("roof_model: planes must be the planes 1 .. n of segment(), in order")
+        normal = np.array([p.normal for p in planes], dtype=np.float64).reshape(n_planes, 3)
+        center = np.array([p.center for p in planes], dtype=np.int32).reshape(n_planes, 3)
+        fp, b = self.buildings(xyz, plane_idx, n_planes, bin=bin, bin_height=bin_height, threshold=threshold,
+                               kernel_size=kernel_size, iterations=iterations)
+        home = roof_homes(normal, b.votes.plane_building, b.votes.votes_in, b.votes.votes_total, min_normal_z)
+        r = self.roofs(xyz, b.map, plane_idx, home, normal, center, bin=bin, ground_th=b.ground_th, min_votes=min_votes)
+        return fp, b, r
+
 
 @dataclass
 class PlaneVotes:
@@ -629,6 +684,121 @@ def write_buildings_obj(fp, buildings: Buildings, path, bin=100, origin=None, gr
                                             float(th), float(min_area), float(min_perimeter), str(path).encode())
     if rc != 0:
         raise BsError(rc, f"cannot write {path} (or the contours and the buildings are not of the same mask)")
+
+
+@dataclass
+class Roofs:
+    """bs_roofs: roof / support / height are the [height][width] int32 images (None where they stayed on the device
+    or were not asked for); the per-plane arrays have entry p - 1 for plane p."""
+    n_planes: int
+    width: int
+    image_height: int
+    fill_rounds: int
+    seeded_pixels: int
+    filled_pixels: int
+    unroofed_pixels: int
+    pixels: np.ndarray
+    seed_pixels: np.ndarray
+    bbox: np.ndarray
+    n_support: np.ndarray
+    z_min: np.ndarray
+    z_max: np.ndarray
+    z_sum: np.ndarray
+    info: dict = field(default_factory=dict)
+    roof: np.ndarray | None = field(default=None, repr=False)
+    support: np.ndarray | None = field(default=None, repr=False)
+    height: np.ndarray | None = field(default=None, repr=False)
+    home: np.ndarray | None = field(default=None, repr=False)
+    normal: np.ndarray | None = field(default=None, repr=False)
+    center: np.ndarray | None = field(default=None, repr=False)
+    bin: int = 100
+
+
+_ROOF_ARRAYS = (("pixels", 1, np.int64), ("seed_pixels", 1, np.int64), ("bbox", 4, np.int32), ("n_support", 1, np.int64),
+                ("z_min", 1, np.int32), ("z_max", 1, np.int32), ("z_sum", 1, np.int64))
+
+
+def _roof_tables(home, normal, center):
+    """(home int32 [n], normal f64 [n][3], center int32 [n][3]) as contiguous arrays that are never empty buffers"""
+    home = np.ascontiguousarray(home, dtype=np.int32).reshape(-1)
+    n = len(home)
+    normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
+    center = np.ascontiguousarray(center, dtype=np.int32).reshape(-1, 3)
+    if len(normal) != n or len(center) != n:
+        raise ValueError("home, normal and center must have one entry per plane")
+    return home, normal, center
+
+
+def _take_roofs(L, out, roof, support, height, tabs, bin) -> Roofs:
+    """Copy a bs_roofs into numpy arrays and release it."""
+    n = out.n_planes
+    try:
+        arrs = {}
+        for name, cols, dt in _ROOF_ARRAYS:
+            a = np.ctypeslib.as_array(getattr(out, name), (n * cols,)).copy() if n else np.zeros(0, dt)
+            arrs[name] = a.reshape(n, cols) if cols > 1 else a
+        info = {k: getattr(out, k) for k in ("ms_vote", "ms_fill", "ms_figures", "ms_height")}
+        return Roofs(n, out.width, out.height, out.fill_rounds, out.seeded_pixels, out.filled_pixels,
+                     out.unroofed_pixels, info=info, roof=roof, support=support, height=height, home=tabs[0],
+                     normal=tabs[1], center=tabs[2], bin=bin, **arrs)
+    finally:
+        L.bs_roofs_free(C.byref(out))
+
+
+def roof_homes(normal, plane_building, votes_in, votes_total, min_normal_z=0.5) -> np.ndarray:
+    """home int32 [n_planes] (bs_roof_homes): the building a plane may be a roof in -- its plane_building if the
+    normal's z is at least min_normal_z and the building holds more than half of the plane's points -- or -1."""
+    pb = np.ascontiguousarray(plane_building, dtype=np.int32).reshape(-1)
+    n = len(pb)
+    nrm = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
+    vin = np.ascontiguousarray(votes_in, dtype=np.int64).reshape(-1)
+    vtot = np.ascontiguousarray(votes_total, dtype=np.int64).reshape(-1)
+    if len(nrm) != n or len(vin) != n or len(vtot) != n:
+        raise ValueError("roof_homes: one entry per plane in every array")
+    home = np.full(n, -1, dtype=np.int32)
+    rc = _lib.load().bs_roof_homes(nrm.ctypes.data, pb.ctypes.data, vin.ctypes.data, vtot.ctypes.data, n,
+                                   float(min_normal_z), home.ctypes.data)
+    if rc != 0:
+        raise BsError(rc, "roof_homes")
+    return home
+
+
+def write_roofs_obj(roofs: Roofs, bmap, path, origin=None, roof=None, normal=None, center=None, bin=None):
+    """Roof OBJ in millimetres through the library's writer (bs_roofs_write_obj; the format is written down in
+    include/bs_api.h): one quad per run of pixels with the same building and roof plane, its corners on the plane
+    (clamped to the plane's supporting points).  roof / normal / center / bin default to what `roofs` carries."""
+    roof = roofs.roof if roof is None else roof
+    if roof is None:
+        raise ValueError("write_roofs_obj: the roof image is on the device: pass roof=")
+    roof = np.ascontiguousarray(roof, dtype=np.int32)
+    bmap = np.ascontiguousarray(bmap, dtype=np.int32)
+    if roof.ndim != 2 or bmap.shape != roof.shape:
+        raise ValueError("write_roofs_obj: roof and bmap must be [height][width] of the same size")
+    n = roofs.n_planes
+    nrm = np.ascontiguousarray(roofs.normal if normal is None else normal, dtype=np.float64).reshape(-1, 3)
+    ctr = np.ascontiguousarray(roofs.center if center is None else center, dtype=np.int32).reshape(-1, 3)
+    if len(nrm) != n or len(ctr) != n:
+        raise ValueError("write_roofs_obj: normal and center must have one entry per plane")
+    st = _lib.Roofs()
+    st.n_planes, st.width, st.height = n, roof.shape[1], roof.shape[0]
+    keep = []
+    for name, dt in (("pixels", np.int64), ("z_min", np.int32), ("z_max", np.int32)):
+        a = np.ascontiguousarray(getattr(roofs, name), dtype=dt)
+        if a.shape != (n,):
+            raise ValueError(f"Roofs.{name} must be [{n}]")
+        keep.append(a if n else np.zeros(1, dt))
+        setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
+    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+    if org is not None and org.shape != (3,):
+        raise ValueError("origin must be [3]")
+    h, w = roof.shape
+    rc = _lib.load().bs_roofs_write_obj(roof.ctypes.data, bmap.ctypes.data, w, h, C.byref(st),
+                                        (nrm if n else np.zeros(3)).ctypes.data,
+                                        (ctr if n else np.zeros(3, np.int32)).ctypes.data,
+                                        int(roofs.bin if bin is None else bin),
+                                        org.ctypes.data if org is not None else None, str(path).encode())
+    if rc != 0:
+        raise BsError(rc, f"cannot write {path} (or a roof value above n_planes)")
 
 
 @dataclass

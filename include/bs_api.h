@@ -629,6 +629,100 @@ int bs_plane_buildings(bs_ctx* ctx, const int32_t* plane_idx, const int32_t* bui
 int bs_buildings_write_obj(const bs_contours* c, const bs_buildings* b, int32_t bin, const int32_t* origin,
                            double ground_th, double min_area, double min_perimeter, const char* path);
 
+/* ---- roofs: which plane is the roof over every pixel of a building, and how high it is there ----
+ *
+ * Inputs: the cloud shifted to its origin (n < 2^29), bin and ground_th as for bs_assign_buildings, the building map
+ * map[height][width] as bs_building_map writes it, the labels plane_idx[n] with n_planes, and three host tables per
+ * plane (entry p - 1 is plane p): home int32, normal f64 [3], center int32 [3]; min_votes >= 1.
+ *
+ * 1. Home of a plane (bs_roof_homes).  home[p] = plane_building[p] if normal_z[p] >= min_normal_z (an f64 compare: NaN
+ *    fails) && plane_building[p] >= 0 && 2 * votes_in[p] > votes_total[p]; otherwise -1.  A plane can be a roof only
+ *    in the one building that holds the majority of its points.
+ * 2. Vote.  Point i COUNTS iff !(z < ground_th) && 1 <= plane_idx[i] <= n_planes && home[plane_idx[i]] == map[pixel]
+ *    >= 0, pixel = (x / bin, y / bin), the base pixel of bs_assign_buildings.  Per pixel the winner is the plane with
+ *    the most counting points (ties: the lower id) if it has at least min_votes of them.
+ *      roof[y][x]    = -1 where map is -1; the winner where there is one; 0 otherwise
+ *      support[y][x] = the winner's count, else 0
+ * 3. Fill, in synchronous rounds.  In round r every pixel with roof == 0 after round r - 1 looks at its 4-neighbours
+ *    inside the image that have the same map value and roof > 0 after round r - 1; if there is one, it takes the
+ *    smallest plane id among them.  Rounds run until one changes nothing; fill_rounds = the rounds that changed
+ *    something.  A label moves one pixel per round (an in-place sweep gives another result).  The pixels of a
+ *    building without a seed stay 0.
+ * 4. Figures per plane.  A SUPPORTING point is a counting point whose plane_idx equals the final roof of its pixel.
+ *      pixels (roof == p), seed_pixels (... and support > 0), the inclusive pixel bbox,
+ *      n_support, z_min, z_max, z_sum over the supporting points;
+ *    a plane without any: 0 for the counts, INT32_MAX / INT32_MIN for z_min / z_max and the bbox
+ *    {INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN}.  Totals: seeded_pixels, filled_pixels, unroofed_pixels (roof == 0).
+ * 5. Height H(p, X, Y) at integer millimetres X, Y, in f64 without contraction (n = normal[p], c = center[p]):
+ *      t = nx * ((double)X - cx) + ny * ((double)Y - cy)      two rounded products, one sum
+ *      z = (double)cz - t / nz
+ *      if (!(z >= z_min[p])) z = z_min[p];
+ *      if (z > z_max[p])     z = z_max[p];
+ *      H = (int64) z
+ *    The two comparisons in that order make NaN and +-inf harmless: nz <= 0 is not an error.
+ *      height[y][x] = H(roof, x * bin + bin / 2, y * bin + bin / 2) (integer bin / 2) where roof > 0, INT32_MIN elsewhere.
+ * Everything but the one division is an exact integer and independent of the order of summation. */
+/* (no typedef: the host-memory entry point below has the struct's name, so the type is always `struct bs_roofs`) */
+struct bs_roofs {
+  int32_t n_planes;
+  int32_t width, height;
+  int32_t fill_rounds;     /* rounds of the fill that changed something */
+  int64_t seeded_pixels;   /* pixels the vote gave a roof */
+  int64_t filled_pixels;   /* pixels the fill gave a roof */
+  int64_t unroofed_pixels; /* roof == 0: building pixels no seed reaches */
+  /* per plane, entry p - 1 is plane p; host memory owned by the library */
+  int64_t* pixels;      /* [n_planes] */
+  int64_t* seed_pixels; /* [n_planes] */
+  int32_t* bbox;        /* [n_planes][4] x0, y0, x1, y1 */
+  int64_t* n_support;   /* [n_planes] */
+  int32_t* z_min;       /* [n_planes] */
+  int32_t* z_max;       /* [n_planes] */
+  int64_t* z_sum;       /* [n_planes] */
+  /* device time (HIP events on the context's stream) */
+  double ms_vote;    /* keys, sort, run lengths, per-pixel arg-max, seeds */
+  double ms_fill;    /* all rounds */
+  double ms_figures; /* the point pass and the pixel pass */
+  double ms_height;  /* the height pass (0 without d_height) */
+};
+
+/* Host only, no context.  normal [n_planes][3]; the other inputs and home_out are [n_planes].  BS_ERR_INVALID: a null
+ * pointer with n_planes > 0, or n_planes < 0. */
+int bs_roof_homes(const double* normal, const int32_t* plane_building, const int64_t* votes_in, const int64_t* votes_total,
+                  int32_t n_planes, double min_normal_z, int32_t* home_out);
+
+/* d_xyz, d_map, d_plane_idx, d_roof [height][width] int32, d_support [height][width] int32 (may be NULL) and d_height
+ * [height][width] int32 (may be NULL) are device pointers; home, normal and center are host tables [n_planes] (not read
+ * when n_planes == 0); out's arrays are host memory owned by the library (bs_roofs_free, which accepts a zeroed
+ * struct).  n_planes == 0 is valid: roof is -1 or 0 and no per-plane array is touched.
+ * BS_ERR_INVALID: null pointer, n < 1, bin < 1, width or height < 1 (or width * height >= 2^31), n_planes < 0,
+ * min_votes < 1.  BS_ERR_RANGE: 2^29 points or more, or a point with a negative x / y or whose pixel lies outside the
+ * image; d_roof, d_support and d_height are then left untouched.  A failed call leaves the context usable.
+ * Synchronises. */
+int bs_roofs_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, double ground_th, const int32_t* d_map,
+                 int32_t width, int32_t height, const int32_t* d_plane_idx, int32_t n_planes, const int32_t* home,
+                 const double* normal, const int32_t* center, int32_t min_votes, int32_t* d_roof, int32_t* d_support,
+                 int32_t* d_height, struct bs_roofs* out);
+/* Host-memory variant: xyz, map, plane_idx, roof, support (may be NULL) and height (may be NULL) are host pointers. */
+int bs_roofs(bs_ctx* ctx, const int32_t* xyz, int64_t n, int32_t bin, double ground_th, const int32_t* map,
+             int32_t width, int32_t height, const int32_t* plane_idx, int32_t n_planes, const int32_t* home,
+             const double* normal, const int32_t* center, int32_t min_votes, int32_t* roof, int32_t* support,
+             int32_t* height_out, struct bs_roofs* out);
+void bs_roofs_free(struct bs_roofs* r);
+
+/* Roof surfaces in millimetres, one quad per run of pixels; the walls stay bs_buildings_write_obj's.  Host only: roof
+ * and map are host arrays [height][width], r supplies z_min / z_max of the n_planes planes, normal and center are the
+ * tables of bs_roofs.  origin [3] is the shift that was subtracted from the cloud (NULL: 0).  The file, every number a
+ * decimal integer, every line ended by '\n':
+ *   "# roof runs: <runs> over <planes with pixels > 0> planes"
+ *   for y ascending, for every maximal run [x0, x1] of equal map >= 0 and equal roof >= 1 (x0 ascending), four lines
+ *     "v X+origin[0] Y+origin[1] H(roof, X, Y)+origin[2]"
+ *   for the corners (x0*bin, y*bin), ((x1+1)*bin, y*bin), ((x1+1)*bin, (y+1)*bin), (x0*bin, (y+1)*bin) in that order;
+ *   after all vertices, for run r = 0 ..: "f 4r+1 4r+2 4r+3 4r+4".
+ * BS_ERR_INVALID: null pointer, bin < 1, width or height < 1, a roof value above r->n_planes, or the file cannot be
+ * written. */
+int bs_roofs_write_obj(const int32_t* roof, const int32_t* map, int32_t width, int32_t height, const struct bs_roofs* r,
+                       const double* normal, const int32_t* center, int32_t bin, const int32_t* origin, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
