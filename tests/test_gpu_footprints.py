@@ -143,6 +143,49 @@ def test_urban_rasters(gpu_ctx, n, bin_, tmp_path):
     assert len(fp.contours) >= 1 and fp.info["fg_pixels"] > 1000
 
 
+@pytest.mark.parametrize("column", [False, True], ids=["row", "column"])
+@pytest.mark.parametrize("npix", [1, 4095, 4096, 4097, 8193])
+def test_chunks_of_the_segmented_maximum(gpu_ctx, npix, column):
+    """A block of the maximum takes 4096 pixels.  Under the true maximum (400, in the last pixel) every other pixel
+    quantises to 9, background at threshold 10; a maximum that missed the last block would make them all foreground."""
+    img = np.zeros((npix, 1, 3) if column else (1, npix, 3))
+    img[..., 1] = 15.0
+    img.reshape(-1, 3)[-1, 1] = 400.0
+    fp = _check_image(gpu_ctx, img, iterations=0, threshold=10)
+    last = [0, npix - 1] if column else [npix - 1, 0]
+    assert len(fp.contours) == 1 and fp.contours[0].tolist() == [last]
+
+
+@pytest.mark.parametrize("h", [15, 16, 17])
+@pytest.mark.parametrize("w", [63, 64, 65])
+def test_block_edges_of_the_closing(gpu_ctx, w, h):
+    """A closing block writes 64 x 16 pixels: one block less a row / column, exactly one, and one more."""
+    m = np.random.default_rng(64 * 16).random((h, w)) < 0.5
+    _check_image(gpu_ctx, ref.image_of_mask(m.astype(np.uint8)), iterations=2, kernel_size=5)
+
+
+def test_batch_and_solo_calls_alternate_on_one_context(gpu_ctx):
+    """The solo call is a batch of one in the same scratch: no descriptor or buffer layout of the other tile count
+    may survive into the next call."""
+    rng = np.random.default_rng(65 * 17)
+    tiles = [ref.image_of_mask(m) for m in list(SHAPES.values())[:7]]
+    mid = ref.image_of_mask((rng.random((17, 65)) < 0.5).astype(np.uint8))
+    one = ref.image_of_mask(np.ones((1, 1), np.uint8))
+    want = [ref.footprints(im) for im in tiles]
+
+    def batch():
+        fps, masks = gpu_ctx.footprints_batch(tiles, return_mask=True)
+        for fp, mask, (r, rmask) in zip(fps, masks, want):
+            assert np.array_equal(mask, rmask * 255)
+            _same(fp, r)
+
+    batch()
+    _check_image(gpu_ctx, mid)
+    batch()
+    fp = _check_image(gpu_ctx, one)
+    assert len(fp.contours) == 1 and fp.contours[0].tolist() == [[0, 0]]
+
+
 def _external_components(m):
     """First pixels (x, y), ascending in raster order, of the external 8-connected components, by scipy.ndimage.label."""
     import scipy.ndimage as nd

@@ -187,7 +187,7 @@ def test_errors_name_the_tile_and_leave_the_context_usable(gpu_ctx):
     _check_batch(gpu_ctx, imgs)
 
 
-def test_end_to_end_device_chain(gpu_ctx, tmp_path):
+def test_end_to_end_device_chain(gpu_ctx, oracle, tmp_path):
     torch = pytest.importorskip("torch")
     rng = np.random.default_rng(16)
     raw = [synth.urban(int(rng.integers(50_000, 150_000)), seed=100 + t) + rng.integers(-10 ** 6, 10 ** 6, 3).astype(np.int32)
@@ -213,3 +213,11 @@ def test_end_to_end_device_chain(gpu_ctx, tmp_path):
         api.write_footprints_obj(fps[t], tmp_path / "batch.obj")
         api.write_footprints_obj(solo, tmp_path / "solo.obj")
         assert (tmp_path / "batch.obj").read_bytes() == (tmp_path / "solo.obj").read_bytes()
+    himg = img.cpu().numpy()
+    for t in (0, 5, 10, 15):  # the solo call is a batch of one: these tiles against the CPU references as well
+        sh = synth.shift_to_origin(raw[t])
+        oimg, _ = oracle.grid_picture(sh, extent=sh.max(0))
+        assert np.array_equal(himg[3 * po[t]:3 * po[t + 1]].reshape(h[t], w[t], 3), oimg), f"tile {t}: raster"
+        r, rmask = ref.footprints(oimg)
+        _same(fps[t], r, f"tile {t} against the restatement")
+        assert np.array_equal(hmask[po[t]:po[t + 1]].reshape(h[t], w[t]), rmask * 255)

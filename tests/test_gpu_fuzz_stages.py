@@ -47,12 +47,12 @@ def test_fuzz_stages_batch():
 
 
 def test_two_runs_of_a_case_give_identical_arrays(gpu_ctx, oracle):
-    """the first case of every kind of cloud and image, and the first image larger than one pass of max_kernel"""
+    """the first case of every kind of cloud and image, and the first image of the large size class"""
     seen = set()
     for i in range(F.GPU_TEST_CASES):
         case, p = F.replay_case(F.GPU_TEST_SEED, i)
         key = (case["kind"], case["sub"].split("+")[0])
-        if case["kind"] == "image" and case["ch1"].size > F.MAX_GRID * 256:
+        if case["kind"] == "image" and case["ch1"].size > F.LARGE_IMAGE:
             key = "strides"
         if key in seen:
             continue
@@ -192,7 +192,7 @@ def _unique_max(h, w, at, seed=1, mx=30.0):
 
 @pytest.mark.parametrize("where", ["first", "last"])
 def test_unique_maximum_in_one_far_pixel(gpu_ctx, where):
-    """3001 x 4093 pixels are 23 passes of max_kernel's grid-stride loop; with the maximum missed every q doubles"""
+    """3001 x 4093 pixels are 2999 blocks of max_tiled_kernel; with the maximum missed every q doubles"""
     h, w = 3001, 4093
     img = _unique_max(h, w, 0 if where == "first" else h * w - 1)
     for thr in (64, 127):

@@ -80,3 +80,46 @@ def test_errors(gpu_ctx):
         gpu_ctx.grid_picture(xyz, extent=xyz.max(0) - 1)
     with pytest.raises(ValueError):
         api.grid_dims([10, 10, 10], bin=0)
+
+
+def _uniform(n, zmax=3000, seed=21):
+    """uniform in [0, 3000)^2 x [0, zmax); point 0 at the origin and point 1 at the far corner pin the extent"""
+    rng = np.random.default_rng(seed)
+    xyz = rng.integers(0, 3000, (n, 3)).astype(np.int32)
+    xyz[:, 2] = rng.integers(0, zmax, n)
+    xyz[0] = 0
+    if n > 1:
+        xyz[1] = (2999, 2999, zmax - 1)
+    return xyz
+
+
+@pytest.mark.parametrize("n", [1, 8191, 8192, 8193, 16385])
+def test_histogram_chunks(gpu_ctx, oracle, n):
+    """A histogram block takes 256 x 32 = 8192 points: one point, a chunk less one, exactly one, one more, two and one."""
+    xyz = _uniform(n)
+    img, th = gpu_ctx.grid_picture(xyz, bin_height=100)
+    oimg, oth = oracle.grid_picture(xyz, bin_height=100)
+    assert th == oth and np.array_equal(img, oimg)
+
+
+def test_bins_beyond_the_lds_histogram(gpu_ctx, oracle):
+    """z in [0, 5000] at bin_height 1 are 5001 bins; the block histogram holds 4096, the rest count in memory."""
+    xyz = _uniform(8193, zmax=5001)
+    assert xyz[:, 2].max() == 5000
+    img, th = gpu_ctx.grid_picture(xyz, bin_height=1)
+    oimg, oth = oracle.grid_picture(xyz, bin_height=1)
+    assert th == oth and np.array_equal(img, oimg)
+
+
+def test_out_of_extent_point_fails_the_solo_call_in_its_own_words(gpu_ctx, oracle):
+    xyz = _uniform(8193)
+    ext = xyz.max(0).astype(np.int32)
+    bad = xyz.copy()
+    bad[-1, 0] = ext[0] + 1  # the last point, in the second histogram block
+    with pytest.raises(api.BsError) as ei:
+        gpu_ctx.grid_picture(bad, extent=ext, bin_height=100)
+    assert ei.value.status == -2
+    assert "batch" not in str(ei.value) and "tile" not in str(ei.value)
+    img, th = gpu_ctx.grid_picture(xyz, extent=ext, bin_height=100)  # the context still works
+    oimg, oth = oracle.grid_picture(xyz, extent=ext, bin_height=100)
+    assert th == oth and np.array_equal(img, oimg)

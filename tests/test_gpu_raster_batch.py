@@ -44,7 +44,7 @@ def test_golden_fixtures_as_one_batch(gpu_ctx, oracle):
 
 
 @pytest.mark.parametrize("bin_,bh", [(100, 1000), (37, 250)])
-def test_urban_tiles_equal_solo(gpu_ctx, bin_, bh):
+def test_urban_tiles_equal_solo(gpu_ctx, oracle, bin_, bh):
     rng = np.random.default_rng(bin_)
     tiles = _urban_tiles(6, 60_000, seed=5)
     tiles.append(rng.integers(0, 4000, (30_000, 3)).astype(np.int32))       # uniform block
@@ -55,6 +55,8 @@ def test_urban_tiles_equal_solo(gpu_ctx, bin_, bh):
         simg, sth = gpu_ctx.grid_picture(tiles[t], bin=bin_, bin_height=bh)
         assert th == sth, f"tile {t}"
         assert np.array_equal(img, simg), f"tile {t}: {(img != simg).any(-1).sum()} pixels differ"
+        oimg, oth = oracle.grid_picture(tiles[t], bin=bin_, bin_height=bh)  # the solo call is a batch of one
+        assert th == oth and np.array_equal(img, oimg), f"tile {t} against the oracle"
 
 
 def test_point_order_is_respected_per_tile(gpu_ctx, oracle):
@@ -72,7 +74,7 @@ def test_point_order_is_respected_per_tile(gpu_ctx, oracle):
     assert np.array_equal(res[0][0], res[3][0])
 
 
-def test_shift_to_origin_option(gpu_ctx):
+def test_shift_to_origin_option(gpu_ctx, oracle):
     rng = np.random.default_rng(4)
     raw = [rng.integers(-50_000, 90_000, (20_000, 3)).astype(np.int32) + rng.integers(0, 10 ** 6, 3).astype(np.int32)
            for _ in range(4)]
@@ -80,6 +82,8 @@ def test_shift_to_origin_option(gpu_ctx):
     for t in range(4):
         simg, sth = gpu_ctx.grid_picture(synth.shift_to_origin(raw[t]))
         assert res[t][1] == sth and np.array_equal(res[t][0], simg)
+        oimg, oth = oracle.grid_picture(synth.shift_to_origin(raw[t]))
+        assert res[t][1] == oth and np.array_equal(res[t][0], oimg)
 
 
 def test_device_form_and_tile_boxes(gpu_ctx):
@@ -152,7 +156,7 @@ def test_malformed_offsets_and_parameters(gpu_ctx):
     assert call([0, 3, 6, 10], 3) == 0  # the context still works
 
 
-def test_many_small_tiles(gpu_ctx):
+def test_many_small_tiles(gpu_ctx, oracle):
     rng = np.random.default_rng(8)
     tiles = [rng.integers(0, rng.integers(1, 3000), (int(rng.integers(1, 400)), 3)).astype(np.int32)
              for _ in range(2000)]
@@ -160,3 +164,6 @@ def test_many_small_tiles(gpu_ctx):
     for t in range(0, 2000, 97):
         simg, sth = gpu_ctx.grid_picture(synth.shift_to_origin(tiles[t]))
         assert res[t][1] == sth and np.array_equal(res[t][0], simg), f"tile {t}"
+    for t in range(0, 2000, 50):
+        oimg, oth = oracle.grid_picture(synth.shift_to_origin(tiles[t]))
+        assert res[t][1] == oth and np.array_equal(res[t][0], oimg), f"tile {t} against the oracle"

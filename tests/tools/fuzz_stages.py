@@ -41,7 +41,8 @@ MAX_PIXELS = 1_500_000        # raster of a cloud case
 MAX_IMAGE = (3000, 4100)
 MAX_CLOSE_WORK = 8e8          # pixels * kernel cells * passes of the sequential closing restatement (about 2 s)
 MAX_BINS = 8_000_000
-MAX_GRID = 2048               # bs_contour.hip: blocks of max_kernel; a larger image takes its grid-stride loop
+LARGE_IMAGE = 2048 * 256      # pixels; a size class, not a boundary of any code path: the coverage asks for one image above
+                              # it, so that the per-tile maximum is the atomicMax of well over a hundred blocks
 
 CLOUD_KINDS = ("boxes", "rings", "blob", "column", "pixel", "tower", "clusters", "urban", "sparse", "tiny")
 IMAGE_KINDS = ("smooth", "spikes", "jrows", "unique_max", "equal", "zero")
@@ -384,8 +385,8 @@ def regimes(case, p, O=None):
     if (q == p["threshold"]).any() and (q == p["threshold"] + 1).any():
         out.add("q==thr_and_thr+1")
     out.add(f"padded_width%64=={(img.shape[1] + 2) % 64}")
-    if img.shape[0] * img.shape[1] > MAX_GRID * 256:
-        out.add("max_kernel_strides")
+    if img.shape[0] * img.shape[1] > LARGE_IMAGE:
+        out.add("large_image")
     _, mask = ref.footprints(img, **kw)
     b = bref.building_map(mask)
     nb = b.n_buildings
@@ -413,7 +414,7 @@ def regimes(case, p, O=None):
 
 REGIMES = ("height_bins>4096", "ground_th_bin>=4096", "buildings>256", "buildings==0", "mask!=nonzero",
            "q==thr_and_thr+1", "non_finite_pixel", "courtyard", "vote_tie", "votes_lds", "votes_dense", "votes_sorted",
-           "padded_width%64==0", "padded_width%64==1", "padded_width%64==63", "n<64", "tail_in_a_building", "max_kernel_strides")
+           "padded_width%64==0", "padded_width%64==1", "padded_width%64==63", "n<64", "tail_in_a_building", "large_image")
 # reached at least once: every kind of cloud and image, every point order, every kind of second threshold
 VARIANTS = tuple("kind:" + k for k in CLOUD_KINDS + IMAGE_KINDS) + \
     tuple("order:" + k for k in ("given", "random", "spatial", "pixel")) + \
