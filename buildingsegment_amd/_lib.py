@@ -32,7 +32,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_grid_picture_batch", "bs_footprints_batch_dev", "bs_footprints_batch", "bs_building_map_dev",
            "bs_building_map", "bs_buildings_free", "bs_assign_buildings_dev", "bs_assign_buildings",
            "bs_plane_buildings_dev", "bs_plane_buildings", "bs_buildings_write_obj", "bs_roof_homes", "bs_roofs_dev",
-           "bs_roofs", "bs_roofs_free", "bs_roofs_write_obj"]
+           "bs_roofs", "bs_roofs_free", "bs_roofs_write_obj", "bs_plane_fit_dev", "bs_plane_fit", "bs_plane_fits_free",
+           "bs_plane_fit_apply"]
 
 
 class Params(C.Structure):
@@ -120,6 +121,15 @@ class Roofs(C.Structure):
                 ("n_support", C.POINTER(C.c_int64)), ("z_min", C.POINTER(C.c_int32)), ("z_max", C.POINTER(C.c_int32)),
                 ("z_sum", C.POINTER(C.c_int64)), ("ms_vote", C.c_double), ("ms_fill", C.c_double),
                 ("ms_figures", C.c_double), ("ms_height", C.c_double)]
+
+
+class PlaneFits(C.Structure):
+    """bs_plane_fits (include/bs_api.h): per-plane fit, host memory owned by the library."""
+    _fields_ = [("n_planes", C.c_int32), ("status", C.POINTER(C.c_int32)), ("n_points", C.POINTER(C.c_int64)),
+                ("center", C.POINTER(C.c_int32)), ("normal", C.POINTER(C.c_double)), ("bbox", C.POINTER(C.c_int32)),
+                ("dev_sum", C.POINTER(C.c_int64)), ("moment", C.POINTER(C.c_int64)), ("r_abs_max", C.POINTER(C.c_int32)),
+                ("r_abs_sum", C.POINTER(C.c_int64)), ("r_sq_sum", C.POINTER(C.c_int64)), ("ms_sums", C.c_double),
+                ("ms_moments", C.c_double), ("ms_solve", C.c_double), ("ms_residuals", C.c_double)]
 
 
 class BsError(RuntimeError):
@@ -236,5 +246,11 @@ def load():
     L.bs_roofs_free.argtypes = [rp]
     L.bs_roofs_free.restype = None
     L.bs_roofs_write_obj.argtypes = [ip, ip, C.c_int32, C.c_int32, rp, dp, ip, C.c_int32, ip, C.c_char_p]
+    fitp = C.POINTER(PlaneFits)
+    L.bs_plane_fit_dev.argtypes = [vp, ip, C.c_int64, ip, C.c_int32, ip, fitp]
+    L.bs_plane_fit.argtypes = [vp, ip, C.c_int64, ip, C.c_int32, ip, fitp]
+    L.bs_plane_fits_free.argtypes = [fitp]
+    L.bs_plane_fits_free.restype = None
+    L.bs_plane_fit_apply.argtypes = [fitp, dp, ip]
     _LIB = L
     return L

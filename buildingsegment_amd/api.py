@@ -573,10 +573,36 @@ class Context:
                                          d_height or None, C.byref(out)))
         return _take_roofs(self._L, out, None, None, None, tabs, bin)
 
+    # ---- plane fit: exact centroid, least-squares normal and residuals per plane (bs_plane_fit, include/bs_api.h) ------
+    def plane_fit(self, xyz, plane_idx, n_planes, residuals=False):
+        """Refit the planes 1 .. n_planes from the points that carry their label.  Returns PlaneFits (arrays [n_planes],
+        entry p - 1 = plane p); with residuals=True its `residual` is the [n] int32 truncated distance of every point to
+        its fitted plane (INT32_MIN for the points of no fitted plane)."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError("xyz must be [n, 3]")
+        pi = np.ascontiguousarray(plane_idx, dtype=np.int32)
+        if pi.shape != (len(xyz),):
+            raise ValueError("plane_idx must be [n]")
+        res = np.empty(len(xyz), dtype=np.int32) if residuals else None
+        out = _lib.PlaneFits()
+        self._check(self._L.bs_plane_fit(self._h, xyz.ctypes.data, len(xyz), pi.ctypes.data, n_planes,
+                                         res.ctypes.data if residuals else None, C.byref(out)))
+        return _take_fits(self._L, out, res)
+
+    def plane_fit_dev(self, d_xyz, n, d_plane_idx, n_planes, d_residual=0):
+        """Device-resident variant: d_xyz, d_plane_idx and the optional d_residual [n] int32 are device pointers (ints)."""
+        out = _lib.PlaneFits()
+        self._check(self._L.bs_plane_fit_dev(self._h, d_xyz or None, n, d_plane_idx or None, n_planes, d_residual or None,
+                                             C.byref(out)))
+        return _take_fits(self._L, out, None)
+
     def roof_model(self, xyz, plane_idx, planes, bin=100, bin_height=1000, threshold=10, kernel_size=5, iterations=2,
-                   min_normal_z=0.5, min_votes=1):
+                   min_normal_z=0.5, min_votes=1, refit=False):
         """buildings() -> roof_homes -> roofs for a cloud shifted to its origin, its labels and the planes of segment().
-        Returns (Footprints, Buildings, Roofs); the Roofs carry home, normal, center and bin for write_roofs_obj."""
+        Returns (Footprints, Buildings, Roofs); the Roofs carry home, normal, center and bin for write_roofs_obj.
+        refit=True: plane_fit() after buildings(), and homes and roofs from the refitted normal / center tables (which
+        the Roofs then carry, with the PlaneFits as `fit`)."""
         n_planes = len(planes)
         if [p.id for p in planes] != list(range(1, n_planes + 1)):
             raise ValueError("roof_model: planes must be the planes 1 .. n of segment(), in order")
@@ -584,8 +610,13 @@ class Context:
         center = np.array([p.center for p in planes], dtype=np.int32).reshape(n_planes, 3)
         fp, b = self.buildings(xyz, plane_idx, n_planes, bin=bin, bin_height=bin_height, threshold=threshold,
                                kernel_size=kernel_size, iterations=iterations)
+        fit = None
+        if refit:
+            fit = self.plane_fit(xyz, plane_idx, n_planes)
+            normal, center = plane_fit_apply(fit, normal, center)
         home = roof_homes(normal, b.votes.plane_building, b.votes.votes_in, b.votes.votes_total, min_normal_z)
         r = self.roofs(xyz, b.map, plane_idx, home, normal, center, bin=bin, ground_th=b.ground_th, min_votes=min_votes)
+        r.fit = fit
         return fp, b, r
 
 
@@ -712,6 +743,7 @@ class Roofs:
     normal: np.ndarray | None = field(default=None, repr=False)
     center: np.ndarray | None = field(default=None, repr=False)
     bin: int = 100
+    fit: "PlaneFits | None" = field(default=None, repr=False)  # roof_model(refit=True)
 
 
 _ROOF_ARRAYS = (("pixels", 1, np.int64), ("seed_pixels", 1, np.int64), ("bbox", 4, np.int32), ("n_support", 1, np.int64),
@@ -743,6 +775,68 @@ def _take_roofs(L, out, roof, support, height, tabs, bin) -> Roofs:
                      normal=tabs[1], center=tabs[2], bin=bin, **arrs)
     finally:
         L.bs_roofs_free(C.byref(out))
+
+
+@dataclass
+class PlaneFits:
+    """bs_plane_fits: entry p - 1 is plane p.  status 0 = fitted, 1 = fewer than 3 points, 2 = too large for the exact
+    sums; residual is the per-point image of plane_fit(residuals=True), else None."""
+    n_planes: int
+    status: np.ndarray
+    n_points: np.ndarray
+    center: np.ndarray
+    normal: np.ndarray
+    bbox: np.ndarray
+    dev_sum: np.ndarray
+    moment: np.ndarray
+    r_abs_max: np.ndarray
+    r_abs_sum: np.ndarray
+    r_sq_sum: np.ndarray
+    info: dict = field(default_factory=dict)
+    residual: np.ndarray | None = field(default=None, repr=False)
+
+
+_FIT_ARRAYS = (("status", 1, np.int32), ("n_points", 1, np.int64), ("center", 3, np.int32), ("normal", 3, np.float64),
+               ("bbox", 6, np.int32), ("dev_sum", 3, np.int64), ("moment", 6, np.int64), ("r_abs_max", 1, np.int32),
+               ("r_abs_sum", 1, np.int64), ("r_sq_sum", 1, np.int64))
+
+
+def _take_fits(L, out, residual) -> PlaneFits:
+    """Copy a bs_plane_fits into numpy arrays and release it."""
+    n = out.n_planes
+    try:
+        arrs = {}
+        for name, cols, dt in _FIT_ARRAYS:
+            a = np.ctypeslib.as_array(getattr(out, name), (n * cols,)).copy() if n else np.zeros(0, dt)
+            arrs[name] = a.reshape(n, cols) if cols > 1 else a
+        info = {k: getattr(out, k) for k in ("ms_sums", "ms_moments", "ms_solve", "ms_residuals")}
+        return PlaneFits(n, info=info, residual=residual, **arrs)
+    finally:
+        L.bs_plane_fits_free(C.byref(out))
+
+
+def plane_fit_apply(fits: PlaneFits, normal, center):
+    """New (normal f64 [n_planes][3], center int32 [n_planes][3]) tables (bs_plane_fit_apply): the rows of the fitted
+    planes (status 0) taken from `fits`, the other rows from the tables given (those of segment()'s planes)."""
+    n = fits.n_planes
+    nrm = np.array(normal, dtype=np.float64).reshape(-1, 3)  # (copies)
+    ctr = np.array(center, dtype=np.int32).reshape(-1, 3)
+    if len(nrm) != n or len(ctr) != n:
+        raise ValueError("plane_fit_apply: normal and center must have one row per plane")
+    st = _lib.PlaneFits()
+    st.n_planes = n
+    keep = []
+    for name, cols, dt in (("status", 1, np.int32), ("normal", 3, np.float64), ("center", 3, np.int32)):
+        a = np.ascontiguousarray(getattr(fits, name), dtype=dt)
+        if a.size != n * cols:
+            raise ValueError(f"PlaneFits.{name} must have {n * cols} entries")
+        keep.append(a if n else np.zeros(cols, dt))  # (never a null pointer)
+        setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_double if dt == np.float64 else C.c_int32)))
+    rc = _lib.load().bs_plane_fit_apply(C.byref(st), (nrm if n else np.zeros(3)).ctypes.data,
+                                        (ctr if n else np.zeros(3, np.int32)).ctypes.data)
+    if rc != 0:
+        raise BsError(rc, "plane_fit_apply")
+    return nrm, ctr
 
 
 def roof_homes(normal, plane_building, votes_in, votes_total, min_normal_z=0.5) -> np.ndarray:

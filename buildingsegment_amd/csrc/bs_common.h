@@ -243,6 +243,7 @@ struct bs_ctx {
   bs::DevBuf fp[24];  // scratch of bs_footprints[_dev] (bs_contour.hip)
   bs::DevBuf bd[14];  // scratch of the building map, assignment and votes (bs_building.hip)
   bs::DevBuf rf[16];  // scratch of the roof stage (bs_roof.hip)
+  bs::DevBuf ft[5];   // scratch of the plane fit (bs_fit.hip)
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew

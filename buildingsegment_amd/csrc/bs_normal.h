@@ -195,6 +195,22 @@ struct Moments {
   int32_t n;
 };
 
+// The tail every normal of the library goes through (stage 2 and the plane fit): smallest eigenvector, the
+// zero-norm fallback (0,0,1), orientation to +z.
+BS_HD V3 normal_from_covariance(const Sym3& C)
+{
+  V3 nv = smallest_eigenvector(C);
+  if (bs_det_sqrt(dot_tree(nv, nv)) == 0.0) {
+    nv.x = 0; nv.y = 0; nv.z = 1;
+  }
+  if (nv.x * 0.0 + (nv.y * 0.0 + nv.z * 1.0) < 0.0) {
+    nv.x *= -1.0;
+    nv.y *= -1.0;
+    nv.z *= -1.0;
+  }
+  return nv;
+}
+
 BS_HD V3 normal_from_moments(const Moments& m)
 {
   Sym3 C;
@@ -213,16 +229,7 @@ BS_HD V3 normal_from_moments(const Moments& m)
     C.a02 = c5 - c0 * c2;
     C.a12 = c7 - c1 * c2;
   }
-  V3 nv = smallest_eigenvector(C);
-  if (bs_det_sqrt(dot_tree(nv, nv)) == 0.0) {
-    nv.x = 0; nv.y = 0; nv.z = 1;
-  }
-  if (nv.x * 0.0 + (nv.y * 0.0 + nv.z * 1.0) < 0.0) {
-    nv.x *= -1.0;
-    nv.y *= -1.0;
-    nv.z *= -1.0;
-  }
-  return nv;
+  return normal_from_covariance(C);
 }
 
 }  // namespace bs

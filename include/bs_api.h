@@ -723,6 +723,75 @@ void bs_roofs_free(struct bs_roofs* r);
 int bs_roofs_write_obj(const int32_t* roof, const int32_t* map, int32_t width, int32_t height, const struct bs_roofs* r,
                        const double* normal, const int32_t* center, int32_t bin, const int32_t* origin, const char* path);
 
+/* ---- plane fit: every plane's exact centroid, least-squares normal and residuals from the points that carry its label ----
+ *
+ * bs_segment reproduces the reference's plane record bit for bit, quirks included: its centre is a wrapping 32-bit sum
+ * divided as unsigned (my_function.cpp:241-250) and its normal the mean of the per-point normals.  This stage recomputes
+ * both from the labels, for everything that uses a plane as geometry (bs_roof_homes, bs_roofs, bs_roofs_write_obj).
+ *
+ * Inputs: xyz int32 [n][3] with 1 <= n < 2^29 and every |coordinate| < 2^23 (the domain of stages 1-2), plane_idx int32 [n],
+ * n_planes >= 0.  A point belongs to plane p iff plane_idx == p and 1 <= p <= n_planes (by label, as in
+ * bs_plane_buildings); every other label (-1, 0, n_planes + 1, ...) is ignored.
+ *
+ * Per plane (entry p - 1 is plane p):
+ * 1. Sums.  n_points; S = sum of (x, y, z) in int64; the inclusive box bbox = {x0, y0, z0, x1, y1, z1}.  A plane without
+ *    points gets INT32_MAX / INT32_MIN for the box.
+ * 2. Centroid.  center[a] = S[a] / n_points in int64, C division (truncated towards zero); 0 when n_points == 0.
+ * 3. Verdict.  D = the largest of hi[a] - center[a] and center[a] - lo[a] over the three axes.
+ *      status = 1 if n_points < 3;
+ *      status = 2 if 3 * n_points * D^2 >= 2^63 (evaluated exactly: D^2 >= ceil(2^63 / (3 * n_points)) in 64 bits).  This is
+ *                 the condition under which every integer sum below fits in int64;
+ *      status = 0 otherwise: fitted.
+ * 4. Moments (status 0 only; zero otherwise).  With d_i = p_i - center:
+ *      dev_sum[3] = sum of d                                   (= S - n_points * center, the remainder of the division)
+ *      moment[6]  = sum of (dx*dx, dx*dy, dx*dz, dy*dy, dy*dz, dz*dz), all int64.
+ * 5. Normal (status 0; otherwise (0, 0, 1)).  In f64 without contraction:
+ *      dn = (double)n_points, e[a] = (double)dev_sum[a] / dn, C[ab] = (double)moment[ab] / dn - e[a] * e[b],
+ *    then the smallest eigenvector of C by the solver of stage 2 (csrc/bs_normal.h: Eberly's FastEigen3x3 with
+ *    bs_detmath.h), (0, 0, 1) if its norm is zero, flipped if z < 0: the tail of stage 2's normal, the same code.
+ * 6. Residuals (status 0).  r_i = (int32)(int64)(nx * dx + (ny * dy + nz * dz)) in f64 without contraction, truncated.
+ *    Per plane r_abs_max int32, r_abs_sum int64, r_sq_sum int64 (zero for the other planes).  The optional per-point
+ *    output residual[i] is r_i for a point of a fitted plane and INT32_MIN for every other point.
+ * Everything except the eigen-solve and the one dot product per point is an exact integer and independent of the order
+ * of summation; the solve and the dot product are fixed sequences of IEEE operations, the same on the device and the host. */
+struct bs_plane_fits {
+  int32_t n_planes;
+  /* per plane, entry p - 1 is plane p; host memory owned by the library */
+  int32_t* status;    /* [n_planes] 0 fitted, 1 fewer than 3 points, 2 too large for the exact sums */
+  int64_t* n_points;  /* [n_planes] */
+  int32_t* center;    /* [n_planes][3] */
+  double* normal;     /* [n_planes][3] */
+  int32_t* bbox;      /* [n_planes][6] x0, y0, z0, x1, y1, z1 */
+  int64_t* dev_sum;   /* [n_planes][3] */
+  int64_t* moment;    /* [n_planes][6] xx, xy, xz, yy, yz, zz */
+  int32_t* r_abs_max; /* [n_planes] */
+  int64_t* r_abs_sum; /* [n_planes] */
+  int64_t* r_sq_sum;  /* [n_planes] */
+  /* device time (HIP events on the context's stream) */
+  double ms_sums;      /* pass A over the points (count, S, box) and the per-plane centroid and verdict */
+  double ms_moments;   /* pass B over the points (the six moments) */
+  double ms_solve;     /* the per-plane covariance and eigen-solve */
+  double ms_residuals; /* pass C over the points (residuals and their figures) */
+};
+
+/* d_xyz [n][3], d_plane_idx [n] and d_residual [n] int32 (may be NULL) are device pointers; out's arrays are host memory
+ * owned by the library (bs_plane_fits_free, which accepts a zeroed struct); out is written whole on success (not freed
+ * first).  n_planes == 0 is valid: no per-plane array is touched and every residual is INT32_MIN.
+ * BS_ERR_INVALID: null pointer, n < 1, n_planes < 0.  BS_ERR_RANGE: n >= 2^29, or a coordinate of ANY point outside
+ * |c| < 2^23; out and d_residual are then left untouched and the context stays usable.  Synchronises. */
+int bs_plane_fit_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, const int32_t* d_plane_idx, int32_t n_planes,
+                     int32_t* d_residual, struct bs_plane_fits* out);
+/* Host-memory variant: xyz, plane_idx and residual (may be NULL) are host pointers. */
+int bs_plane_fit(bs_ctx* ctx, const int32_t* xyz, int64_t n, const int32_t* plane_idx, int32_t n_planes, int32_t* residual,
+                 struct bs_plane_fits* out);
+void bs_plane_fits_free(struct bs_plane_fits* f);
+
+/* Host only, no context: the bridge to bs_roof_homes / bs_roofs / bs_roofs_write_obj.  normal f64 [n_planes][3] and center
+ * int32 [n_planes][3] are the tables of bs_segment's planes; row p - 1 of both is overwritten with the fit for every
+ * plane with status 0, the other rows are left alone.  BS_ERR_INVALID: a null pointer (f, or a table / an array of f with
+ * n_planes > 0), or n_planes < 0. */
+int bs_plane_fit_apply(const struct bs_plane_fits* f, double* normal, int32_t* center);
+
 #ifdef __cplusplus
 }
 #endif
