@@ -33,7 +33,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_building_map", "bs_buildings_free", "bs_assign_buildings_dev", "bs_assign_buildings",
            "bs_plane_buildings_dev", "bs_plane_buildings", "bs_buildings_write_obj", "bs_roof_homes", "bs_roofs_dev",
            "bs_roofs", "bs_roofs_free", "bs_roofs_write_obj", "bs_plane_fit_dev", "bs_plane_fit", "bs_plane_fits_free",
-           "bs_plane_fit_apply"]
+           "bs_plane_fit_apply", "bs_solids_count_dev", "bs_solids_emit_dev", "bs_solids", "bs_solids_free",
+           "bs_solids_write_obj"]
 
 
 class Params(C.Structure):
@@ -130,6 +131,22 @@ class PlaneFits(C.Structure):
                 ("dev_sum", C.POINTER(C.c_int64)), ("moment", C.POINTER(C.c_int64)), ("r_abs_max", C.POINTER(C.c_int32)),
                 ("r_abs_sum", C.POINTER(C.c_int64)), ("r_sq_sum", C.POINTER(C.c_int64)), ("ms_sums", C.c_double),
                 ("ms_moments", C.c_double), ("ms_solve", C.c_double), ("ms_residuals", C.c_double)]
+
+
+class Solids(C.Structure):
+    """bs_solids (include/bs_api.h): totals, per-building figures and (host-memory entry point) the mesh, host memory owned
+    by the library."""
+    _fields_ = [("n_buildings", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("bin", C.c_int32),
+                ("base_z", C.c_int32), ("n_pixels", C.c_int64), ("n_vertices", C.c_int64), ("n_faces", C.c_int64),
+                ("n_indices", C.c_int64), ("n_wall_faces", C.c_int64), ("n_crossing_walls", C.c_int64),
+                ("total_volume6", C.c_int64), ("pixels", C.POINTER(C.c_int64)), ("vertices", C.POINTER(C.c_int64)),
+                ("faces", C.POINTER(C.c_int64)), ("wall_faces", C.POINTER(C.c_int64)),
+                ("crossing_walls", C.POINTER(C.c_int64)), ("top_min", C.POINTER(C.c_int32)),
+                ("top_max", C.POINTER(C.c_int32)), ("volume6", C.POINTER(C.c_int64)), ("vertex", C.POINTER(C.c_int32)),
+                ("face_offset", C.POINTER(C.c_int32)), ("face_index", C.POINTER(C.c_int32)),
+                ("face_building", C.POINTER(C.c_int32)), ("face_kind", C.POINTER(C.c_uint8)), ("ms_tops", C.c_double),
+                ("ms_vertices", C.c_double), ("ms_faces", C.c_double), ("ms_figures", C.c_double), ("ms_scans", C.c_double),
+                ("ms_emit_vertices", C.c_double), ("ms_emit_faces", C.c_double)]
 
 
 class BsError(RuntimeError):
@@ -252,5 +269,13 @@ def load():
     L.bs_plane_fits_free.argtypes = [fitp]
     L.bs_plane_fits_free.restype = None
     L.bs_plane_fit_apply.argtypes = [fitp, dp, ip]
+    sp = C.POINTER(Solids)
+    solids_args = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, ip, ip, ip, C.c_int32, C.c_int32, ip, ip, sp]
+    L.bs_solids_count_dev.argtypes = solids_args
+    L.bs_solids.argtypes = solids_args
+    L.bs_solids_emit_dev.argtypes = [vp, ip, ip, ip, ip, vp]
+    L.bs_solids_free.argtypes = [sp]
+    L.bs_solids_free.restype = None
+    L.bs_solids_write_obj.argtypes = [ip, C.c_int64, ip, ip, ip, C.c_int64, C.c_int32, ip, C.c_char_p]
     _LIB = L
     return L

@@ -619,6 +619,55 @@ class Context:
         r.fit = fit
         return fp, b, r
 
+    # ---- solids: a closed oriented mesh per building from the roof image (bs_solids, include/bs_api.h) ---------------
+    def solids(self, bmap, roofs, buildings=None, base_z=None, flat=None, top=True):
+        """Roof, walls and floor of every building as one closed mesh.  bmap is the building map, `roofs` the Roofs of
+        roofs() on it (its roof image, plane tables, z_min / z_max and bin are used).  base_z defaults to
+        (int) buildings.ground_th; flat [n_buildings], the top of the unroofed pixels, to z_sum / n_above truncated
+        (write_buildings_obj's top) and to base_z where n_above == 0.  Returns Solids."""
+        bmap = np.ascontiguousarray(bmap, dtype=np.int32)
+        if roofs.roof is None:
+            raise ValueError("solids: the roof image is on the device: use solids_dev")
+        roof = np.ascontiguousarray(roofs.roof, dtype=np.int32)
+        if bmap.ndim != 2 or roof.shape != bmap.shape:
+            raise ValueError("solids: bmap and roofs.roof must be [height][width] of the same size")
+        base_z, flat = _solid_defaults(buildings, base_z, flat)
+        h, w = bmap.shape
+        tabs = _solid_tables(roofs.normal, roofs.center, roofs.z_min, roofs.z_max)
+        timg = np.empty((h, w, 4), dtype=np.int32) if top else None
+        out = _lib.Solids()
+        self._check(self._L.bs_solids(self._h, bmap.ctypes.data, roof.ctypes.data, w, h, len(flat), len(tabs[0]),
+                                      *[t.ctypes.data for t in tabs], int(roofs.bin), base_z,
+                                      (flat if len(flat) else np.zeros(1, np.int32)).ctypes.data,
+                                      timg.ctypes.data if top else None, C.byref(out)))
+        return _take_solids(self._L, out, timg, True)
+
+    def solids_dev(self, d_map, d_roof, width, height, normal, center, z_min, z_max, bin, base_z, flat, d_top=0):
+        """Device-resident count (bs_solids_count_dev): d_map, d_roof and the optional d_top ([height][width][4] int32)
+        are device pointers (ints), the tables host arrays; len(flat) is n_buildings.  Returns Solids with the figures
+        and the sizes n_vertices / n_faces / n_indices of the buffers solids_emit_dev fills."""
+        tabs = _solid_tables(normal, center, z_min, z_max)
+        flat = np.ascontiguousarray(flat, dtype=np.int32).reshape(-1)
+        out = _lib.Solids()
+        self._check(self._L.bs_solids_count_dev(self._h, d_map or None, d_roof or None, width, height, len(flat),
+                                                len(tabs[0]), *[t.ctypes.data for t in tabs], int(bin), int(base_z),
+                                                (flat if len(flat) else np.zeros(1, np.int32)).ctypes.data,
+                                                d_top or None, C.byref(out)))
+        return _take_solids(self._L, out, None, False)
+
+    def solids_emit_dev(self, d_vertex, d_face_offset, d_face_index, d_face_building, d_face_kind):
+        """The mesh of the last solids_dev on this context into device buffers (ints) of exactly its sizes."""
+        self._check(self._L.bs_solids_emit_dev(self._h, d_vertex or None, d_face_offset or None, d_face_index or None,
+                                               d_face_building or None, d_face_kind or None))
+
+    def solid_model(self, xyz, plane_idx, planes, bin=100, bin_height=1000, threshold=10, kernel_size=5, iterations=2,
+                    min_normal_z=0.5, min_votes=1, refit=False, base_z=None, flat=None):
+        """roof_model() followed by solids(): returns (Footprints, Buildings, Roofs, Solids)."""
+        fp, b, r = self.roof_model(xyz, plane_idx, planes, bin=bin, bin_height=bin_height, threshold=threshold,
+                                   kernel_size=kernel_size, iterations=iterations, min_normal_z=min_normal_z,
+                                   min_votes=min_votes, refit=refit)
+        return fp, b, r, self.solids(b.map, r, b, base_z=base_z, flat=flat)
+
 
 @dataclass
 class PlaneVotes:
@@ -893,6 +942,119 @@ def write_roofs_obj(roofs: Roofs, bmap, path, origin=None, roof=None, normal=Non
                                         org.ctypes.data if org is not None else None, str(path).encode())
     if rc != 0:
         raise BsError(rc, f"cannot write {path} (or a roof value above n_planes)")
+
+
+@dataclass
+class Solids:
+    """bs_solids: the totals, the per-building figures, and the mesh (None after solids_dev: it is written by
+    solids_emit_dev).  vertex is [n_vertices][4] int32 {X, Y, Z, building} in millimetres, face f has the vertices
+    face_index[face_offset[f] : face_offset[f + 1]]; face_kind 0 top, 1 floor, 2 wall.  The volume of building c in
+    mm^3 is volume6[c] * bin^2 / 6."""
+    n_buildings: int
+    width: int
+    image_height: int
+    bin: int
+    base_z: int
+    n_pixels: int
+    n_vertices: int
+    n_faces: int
+    n_indices: int
+    n_wall_faces: int
+    n_crossing_walls: int
+    total_volume6: int
+    pixels: np.ndarray
+    vertices: np.ndarray
+    faces: np.ndarray
+    wall_faces: np.ndarray
+    crossing_walls: np.ndarray
+    top_min: np.ndarray
+    top_max: np.ndarray
+    volume6: np.ndarray
+    info: dict = field(default_factory=dict)
+    top: np.ndarray | None = field(default=None, repr=False)
+    vertex: np.ndarray | None = field(default=None, repr=False)
+    face_offset: np.ndarray | None = field(default=None, repr=False)
+    face_index: np.ndarray | None = field(default=None, repr=False)
+    face_building: np.ndarray | None = field(default=None, repr=False)
+    face_kind: np.ndarray | None = field(default=None, repr=False)
+
+
+_SOLID_ARRAYS = (("pixels", np.int64), ("vertices", np.int64), ("faces", np.int64), ("wall_faces", np.int64),
+                 ("crossing_walls", np.int64), ("top_min", np.int32), ("top_max", np.int32), ("volume6", np.int64))
+_SOLID_TOTALS = ("bin", "base_z", "n_pixels", "n_vertices", "n_faces", "n_indices", "n_wall_faces", "n_crossing_walls",
+                 "total_volume6")
+
+
+def _solid_tables(normal, center, z_min, z_max):
+    """(normal f64 [n][3], center int32 [n][3], z_min, z_max int32 [n]) as contiguous arrays"""
+    z_min = np.ascontiguousarray(z_min, dtype=np.int32).reshape(-1)
+    n = len(z_min)
+    z_max = np.ascontiguousarray(z_max, dtype=np.int32).reshape(-1)
+    normal = np.ascontiguousarray(normal, dtype=np.float64).reshape(-1, 3)
+    center = np.ascontiguousarray(center, dtype=np.int32).reshape(-1, 3)
+    if len(normal) != n or len(center) != n or len(z_max) != n:
+        raise ValueError("normal, center, z_min and z_max must have one entry per plane")
+    return normal, center, z_min, z_max
+
+
+def _solid_defaults(buildings, base_z, flat):
+    """base_z and flat [n_buildings] int32 of Context.solids"""
+    if base_z is None:
+        if buildings is None:
+            raise ValueError("solids: give base_z or the Buildings (for its ground_th)")
+        base_z = int(buildings.ground_th)
+    base_z = int(base_z)
+    if flat is None:
+        if buildings is None:
+            raise ValueError("solids: give flat or the Buildings (for z_sum / n_above)")
+        zs, na = np.asarray(buildings.z_sum, np.int64), np.asarray(buildings.n_above, np.int64)
+        q = np.abs(zs) // np.maximum(na, 1) * np.sign(zs)  # truncated towards zero, as bs_buildings_write_obj divides
+        flat = np.where(na > 0, q, base_z)
+    return base_z, np.ascontiguousarray(flat, dtype=np.int32).reshape(-1)
+
+
+def _take_solids(L, out, top, mesh) -> Solids:
+    """Copy a bs_solids into numpy arrays and release it."""
+    n = out.n_buildings
+    try:
+        arrs = {name: (np.ctypeslib.as_array(getattr(out, name), (n,)).copy() if n else np.zeros(0, dt))
+                for name, dt in _SOLID_ARRAYS}
+        if mesh:
+            nv, nf, ni = out.n_vertices, out.n_faces, out.n_indices
+            arrs["vertex"] = np.ctypeslib.as_array(out.vertex, (nv, 4)).copy() if nv else np.zeros((0, 4), np.int32)
+            arrs["face_offset"] = np.ctypeslib.as_array(out.face_offset, (nf + 1,)).copy()
+            arrs["face_index"] = np.ctypeslib.as_array(out.face_index, (ni,)).copy() if ni else np.zeros(0, np.int32)
+            arrs["face_building"] = np.ctypeslib.as_array(out.face_building, (nf,)).copy() if nf else np.zeros(0, np.int32)
+            arrs["face_kind"] = np.ctypeslib.as_array(out.face_kind, (nf,)).copy() if nf else np.zeros(0, np.uint8)
+        info = {k: getattr(out, k) for k in ("ms_tops", "ms_vertices", "ms_faces", "ms_figures", "ms_scans",
+                                             "ms_emit_vertices", "ms_emit_faces")}
+        return Solids(n, out.width, out.height, *[getattr(out, k) for k in _SOLID_TOTALS], info=info, top=top, **arrs)
+    finally:
+        L.bs_solids_free(C.byref(out))
+
+
+def write_solids_obj(solids, path, origin=None):
+    """The mesh as an OBJ in millimetres through the library's writer (bs_solids_write_obj; the format is written down
+    in include/bs_api.h): all vertices, then per building its faces.  `solids` is a Solids (or anything with vertex,
+    face_offset, face_index, face_building and n_buildings); origin: the shift that was subtracted from the cloud."""
+    if solids.vertex is None:
+        raise ValueError("write_solids_obj: the mesh is on the device")
+    v = np.ascontiguousarray(solids.vertex, dtype=np.int32).reshape(-1, 4)
+    off = np.ascontiguousarray(solids.face_offset, dtype=np.int32).reshape(-1)
+    idx = np.ascontiguousarray(solids.face_index, dtype=np.int32).reshape(-1)
+    fb = np.ascontiguousarray(solids.face_building, dtype=np.int32).reshape(-1)
+    if len(off) != len(fb) + 1 or (len(off) and int(off[-1]) != len(idx)):
+        raise ValueError("write_solids_obj: face_offset must be [n_faces + 1] and end at len(face_index)")
+    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+    if org is not None and org.shape != (3,):
+        raise ValueError("origin must be [3]")
+    pad = np.zeros(4, np.int32)
+    rc = _lib.load().bs_solids_write_obj((v if len(v) else pad).ctypes.data, len(v), off.ctypes.data,
+                                         (idx if len(idx) else pad).ctypes.data, (fb if len(fb) else pad).ctypes.data,
+                                         len(fb), int(solids.n_buildings), org.ctypes.data if org is not None else None,
+                                         str(path).encode())
+    if rc != 0:
+        raise BsError(rc, f"cannot write {path} (or the mesh arrays do not fit each other)")
 
 
 @dataclass

@@ -244,6 +244,12 @@ struct bs_ctx {
   bs::DevBuf bd[14];  // scratch of the building map, assignment and votes (bs_building.hip)
   bs::DevBuf rf[16];  // scratch of the roof stage (bs_roof.hip)
   bs::DevBuf ft[5];   // scratch of the plane fit (bs_fit.hip)
+  // solids (bs_solid.hip): scratch, and what bs_solids_count_dev leaves for bs_solids_emit_dev (tops, clean map, offsets)
+  bs::DevBuf sd[14];
+  bool sd_valid = false;
+  int32_t sd_w = 0, sd_h = 0, sd_bin = 0, sd_base = 0;
+  int64_t sd_nv = 0, sd_nf = 0, sd_ni = 0;
+  double sd_ms_emit[2] = {0, 0};  // vertex pass, face pass of the last emit
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew

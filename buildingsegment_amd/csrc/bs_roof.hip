@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "bs_common.h"
+#include "bs_roofheight.h"
 
 namespace bs {
 namespace {
@@ -423,20 +424,6 @@ __global__ __launch_bounds__(256) void pixfig_kernel(const int32_t* __restrict__
       pixfig_global(f, k, s_pix[k], s_seed[k], s_x0[k], s_y0[k], s_x1[k], s_y1[k]);
   if (threadIdx.x < 3 && s_tot[threadIdx.x])
     atomicAdd(f.totals + threadIdx.x, s_tot[threadIdx.x]);
-}
-
-// H(p, X, Y) of include/bs_api.h; the translation unit is compiled with -ffp-contract=off for the host and the device
-__host__ __device__ inline int64_t roof_height(const double* n, const int32_t* c, int32_t z_min, int32_t z_max, int64_t X,
-                                               int64_t Y)
-{
-  const double a = n[0] * ((double)X - (double)c[0]), b = n[1] * ((double)Y - (double)c[1]);
-  const double t = a + b;
-  double z = (double)c[2] - t / n[2];
-  if (!(z >= (double)z_min))
-    z = (double)z_min;
-  if (z > (double)z_max)
-    z = (double)z_max;
-  return (int64_t)z;
 }
 
 __global__ __launch_bounds__(256) void height_kernel(const int32_t* __restrict__ roof, int w, int h, int bin, int32_t npl,

@@ -792,6 +792,109 @@ void bs_plane_fits_free(struct bs_plane_fits* f);
  * n_planes > 0), or n_planes < 0. */
 int bs_plane_fit_apply(const struct bs_plane_fits* f, double* normal, int32_t* center);
 
+/* ---- solids: a closed, oriented mesh per building (roof, walls, floor) from the roof image ----
+ *
+ * Inputs: map[height][width] (negative: outside, else a building in 0 .. n_buildings - 1) and roof[height][width] of
+ * bs_roofs (<= 0: no roof plane, else 1 .. n_planes), the host tables normal / center / z_min / z_max per plane that
+ * bs_roofs used and returned, bin, base_z, and a host table flat[n_buildings]: the top of a building's unroofed pixels.
+ * Everything is an integer millimetre; the mesh is exact to the pixel.
+ *
+ * 1. Tops.  Pixel (x, y) of building c has four corner heights t[j][i] at the lattice corners (x + i, y + j):
+ *      roof > 0:   max(base_z, H(roof, (x + i) * bin, (y + j) * bin)), H the height function of the roof stage (step 5
+ *                  there: the same f64 sequence and clamps);
+ *      otherwise:  max(base_z, flat[c]).
+ *    top[y][x] = {t00, t10, t01, t11} (tij: i along x), {INT32_MIN x 4} where map < 0.
+ * 2. Vertices.  A lattice corner (X, Y) and a building c with a pixel incident to it carry one vertex for every distinct
+ *    value of {base_z} and the tops of c's incident pixels at that corner: int32 [4] {X * bin, Y * bin, Z, c}, ordered by
+ *    ascending (Y, X, c, Z).  A corner carries at most 8.
+ * 3. Faces.  For every pixel with map >= 0 in row-major order, vertices named (corner, height), counter-clockwise seen
+ *    from above:
+ *      top triangles (00, 10, 11) and (00, 11, 01) at the top heights;
+ *      the floor quad (00, 01, 11, 10) at base_z;
+ *      one wall per directed top edge s -> e, in the order 00->10 (neighbour y - 1), 10->11 (x + 1), 11->01 (y + 1),
+ *      01->00 (x - 1).  a_s, a_e are the pixel's tops at s and e; b_s, b_e the neighbour's tops at the same corners if it
+ *      lies inside the image and belongs to the same building, else both base_z.  The wall exists iff
+ *      (a_s, a_e) != (b_s, b_e); between two pixels of one building only the one with the smaller row-major index emits
+ *      it (on its x + 1 and y + 1 edges).  It is the polygon
+ *        (e, a_e), (s, a_s), the vertices of (s, c) strictly between a_s and b_s walking from a_s, (s, b_s), (e, b_e),
+ *        the vertices of (e, c) strictly between b_e and a_e walking from b_e
+ *      with (s, b_s) left out when b_s == a_s and (e, b_e) when b_e == a_e: 3 to 8 vertices.  A wall with a_s - b_s and
+ *      a_e - b_e of opposite signs is a CROSSING wall: it is emitted as this one polygon (a bow-tie in a vertical plane)
+ *      and counted.
+ *    face_offset int32 [n_faces + 1], face_index int32 [n_indices] (vertex numbers from 0), face_building int32 [n_faces],
+ *    face_kind uint8 [n_faces]: 0 top, 1 floor, 2 wall.
+ * 4. Figures per building: pixels, vertices, faces, wall_faces, crossing_walls, top_min / top_max over its tops
+ *    (INT32_MAX / INT32_MIN without a pixel) and volume6 = the sum over its pixels of 2 t00 + 2 t11 + t10 + t01 - 6 base_z;
+ *    the volume in mm^3 is volume6 * bin^2 / 6 (the fixed diagonal 00-11 makes it exact).  And their totals.
+ * Every directed edge of the mesh occurs exactly as often as its reverse, per building: the mesh is closed and oriented.
+ * It is not always manifold (diagonal contact and alternating heights put four faces on one vertical edge). */
+/* (no typedef: the host-memory entry point below has the struct's name, so the type is always `struct bs_solids`) */
+struct bs_solids {
+  int32_t n_buildings;
+  int32_t width, height;
+  int32_t bin, base_z;
+  int64_t n_pixels, n_vertices, n_faces, n_indices, n_wall_faces, n_crossing_walls, total_volume6; /* totals */
+  /* per building; host memory owned by the library */
+  int64_t* pixels;         /* [n_buildings] */
+  int64_t* vertices;       /* [n_buildings] */
+  int64_t* faces;          /* [n_buildings] */
+  int64_t* wall_faces;     /* [n_buildings] */
+  int64_t* crossing_walls; /* [n_buildings] */
+  int32_t* top_min;        /* [n_buildings] */
+  int32_t* top_max;        /* [n_buildings] */
+  int64_t* volume6;        /* [n_buildings] */
+  /* the mesh, host memory owned by the library: filled by the host-memory entry point only (NULL after the count) */
+  int32_t* vertex;        /* [n_vertices][4] */
+  int32_t* face_offset;   /* [n_faces + 1] */
+  int32_t* face_index;    /* [n_indices] */
+  int32_t* face_building; /* [n_faces] */
+  uint8_t* face_kind;     /* [n_faces] */
+  /* device time (HIP events on the context's stream) */
+  double ms_tops;     /* the corner heights */
+  double ms_vertices; /* vertices per corner */
+  double ms_faces;    /* faces and indices per pixel */
+  double ms_figures;  /* the per-building figures */
+  double ms_scans;    /* the three exclusive sums */
+  double ms_emit_vertices, ms_emit_faces; /* the two passes of the emit (host-memory entry point only) */
+};
+
+/* Tops, counts and figures.  d_map, d_roof and d_top ([height][width][4] int32, may be NULL) are device pointers; the
+ * plane tables (not read when n_planes == 0) and flat (not read when n_buildings == 0) are host arrays.  The offsets
+ * stay in the context for the emit below; out's per-building arrays are host memory owned by the library
+ * (bs_solids_free, which accepts a zeroed struct).
+ * BS_ERR_INVALID: null pointer, width or height < 1 (or (width + 1) * (height + 1) >= 2^31), n_buildings or n_planes < 0,
+ * bin < 1.  BS_ERR_RANGE: a map value >= n_buildings, a roof value > n_planes, roof > 0 where map < 0, or 2^31 or more
+ * vertices or indices; d_top is then left untouched.  A failed call leaves the context usable.  Synchronises. */
+int bs_solids_count_dev(bs_ctx* ctx, const int32_t* d_map, const int32_t* d_roof, int32_t width, int32_t height,
+                        int32_t n_buildings, int32_t n_planes, const double* normal, const int32_t* center,
+                        const int32_t* z_min, const int32_t* z_max, int32_t bin, int32_t base_z, const int32_t* flat,
+                        int32_t* d_top, struct bs_solids* out);
+/* The mesh of the last successful count on this context into device buffers of exactly its sizes: d_vertex
+ * [n_vertices][4], d_face_offset [n_faces + 1], d_face_index [n_indices], d_face_building and d_face_kind [n_faces] (a
+ * pointer to an array of no element may be NULL).  May be called more than once; the map and roof of the count are not
+ * read again.  BS_ERR_INVALID: null pointer, or no successful count (the last one on this context failed, or there was
+ * none).  Synchronises. */
+int bs_solids_emit_dev(bs_ctx* ctx, int32_t* d_vertex, int32_t* d_face_offset, int32_t* d_face_index,
+                       int32_t* d_face_building, uint8_t* d_face_kind);
+/* Host-memory twin: map, roof and top ([height][width][4], may be NULL) are host pointers; both steps, and the mesh
+ * comes back in out's library-owned arrays. */
+int bs_solids(bs_ctx* ctx, const int32_t* map, const int32_t* roof, int32_t width, int32_t height, int32_t n_buildings,
+              int32_t n_planes, const double* normal, const int32_t* center, const int32_t* z_min, const int32_t* z_max,
+              int32_t bin, int32_t base_z, const int32_t* flat, int32_t* top, struct bs_solids* out);
+void bs_solids_free(struct bs_solids* s);
+
+/* The mesh as an OBJ in millimetres.  Host only, no context: the five arrays are host memory.  origin [3] is the shift
+ * that was subtracted from the cloud (NULL: 0).  The file, every number a decimal integer, every line ended by '\n':
+ *   "# solids: <buildings with faces> buildings, <n_vertices> vertices, <n_faces> faces"
+ *   for every vertex in order "v X+origin[0] Y+origin[1] Z+origin[2]"
+ *   for every building c with faces, ascending: "o building_<c>", then its faces in face order (a stable counting sort
+ *   by building), each "f i j k ..." with the vertices numbered from 1.
+ * BS_ERR_INVALID: null pointer, a negative count, face_offset that does not start at 0 or decreases, a vertex number
+ * outside [0, n_vertices), a building outside [0, n_buildings), or the file cannot be written. */
+int bs_solids_write_obj(const int32_t* vertex, int64_t n_vertices, const int32_t* face_offset, const int32_t* face_index,
+                        const int32_t* face_building, int64_t n_faces, int32_t n_buildings, const int32_t* origin,
+                        const char* path);
+
 #ifdef __cplusplus
 }
 #endif
