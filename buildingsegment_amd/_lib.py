@@ -34,7 +34,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_plane_buildings_dev", "bs_plane_buildings", "bs_buildings_write_obj", "bs_roof_homes", "bs_roofs_dev",
            "bs_roofs", "bs_roofs_free", "bs_roofs_write_obj", "bs_plane_fit_dev", "bs_plane_fit", "bs_plane_fits_free",
            "bs_plane_fit_apply", "bs_solids_count_dev", "bs_solids_emit_dev", "bs_solids", "bs_solids_free",
-           "bs_solids_write_obj"]
+           "bs_solids_write_obj", "bs_roof_facets_dev", "bs_roof_facets", "bs_roof_facets_free", "bs_roof_edge_kinds",
+           "bs_roof_edges_write_obj"]
 
 
 class Params(C.Structure):
@@ -147,6 +148,21 @@ class Solids(C.Structure):
                 ("face_building", C.POINTER(C.c_int32)), ("face_kind", C.POINTER(C.c_uint8)), ("ms_tops", C.c_double),
                 ("ms_vertices", C.c_double), ("ms_faces", C.c_double), ("ms_figures", C.c_double), ("ms_scans", C.c_double),
                 ("ms_emit_vertices", C.c_double), ("ms_emit_faces", C.c_double)]
+
+
+class RoofFacets(C.Structure):
+    """bs_roof_facets (include/bs_api.h): totals, per-facet and per-edge figures, host memory owned by the library."""
+    _fields_ = ([("width", C.c_int32), ("height", C.c_int32), ("n_facets", C.c_int64), ("n_edges", C.c_int64),
+                 ("n_pixels", C.c_int64), ("n_border", C.c_int64)] +
+                [("facet_" + k, C.POINTER(t)) for k, t in
+                 (("building", C.c_int32), ("plane", C.c_int32), ("start_xy", C.c_int32), ("pixels", C.c_int64),
+                  ("bbox", C.c_int32), ("inner_edges", C.c_int64), ("outer_edges", C.c_int64), ("top_min", C.c_int32),
+                  ("top_max", C.c_int32), ("top_sum", C.c_int64))] +
+                [("edge_" + k, C.POINTER(t)) for k, t in
+                 (("facet", C.c_int32), ("building", C.c_int32), ("length", C.c_int64), ("n_dir0", C.c_int64),
+                  ("n_step", C.c_int64), ("step_abs_sum", C.c_int64), ("step_abs_max", C.c_int64), ("rise_sum", C.c_int64),
+                  ("bend_sum", C.c_int64), ("z_min", C.c_int32), ("z_max", C.c_int32), ("bbox", C.c_int32))] +
+                [("ms_label", C.c_double), ("ms_number", C.c_double), ("ms_figures", C.c_double), ("ms_edges", C.c_double)])
 
 
 class BsError(RuntimeError):
@@ -277,5 +293,13 @@ def load():
     L.bs_solids_free.argtypes = [sp]
     L.bs_solids_free.restype = None
     L.bs_solids_write_obj.argtypes = [ip, C.c_int64, ip, ip, ip, C.c_int64, C.c_int32, ip, C.c_char_p]
+    fcp = C.POINTER(RoofFacets)
+    facets_args = [vp, ip, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, fcp]
+    L.bs_roof_facets_dev.argtypes = facets_args
+    L.bs_roof_facets.argtypes = facets_args
+    L.bs_roof_facets_free.argtypes = [fcp]
+    L.bs_roof_facets_free.restype = None
+    L.bs_roof_edge_kinds.argtypes = [fcp, C.c_int32, C.c_int32, vp]
+    L.bs_roof_edges_write_obj.argtypes = [ip, ip, ip, C.c_int32, C.c_int32, C.c_int32, fcp, vp, ip, C.c_char_p]
     _LIB = L
     return L

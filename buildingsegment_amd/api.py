@@ -668,6 +668,41 @@ class Context:
                                    min_votes=min_votes, refit=refit)
         return fp, b, r, self.solids(b.map, r, b, base_z=base_z, flat=flat)
 
+    # ---- roof facets and the edges between them (bs_roof_facets, include/bs_api.h) -------------------------------------
+    def roof_facets(self, bmap, roof, top, n_buildings=None, n_planes=None):
+        """The roof facets of every building (4-connected pixels of one building under one plane) and the edges between
+        them.  bmap and roof are [height][width], top [height][width][4] as Solids.top.  n_buildings defaults to
+        bmap.max() + 1, n_planes to max(roof.max(), 0).  Returns RoofFacets."""
+        bmap = np.ascontiguousarray(bmap, dtype=np.int32)
+        roof = np.ascontiguousarray(roof, dtype=np.int32)
+        top = np.ascontiguousarray(top, dtype=np.int32)
+        if bmap.ndim != 2 or bmap.size == 0 or roof.shape != bmap.shape or top.shape != bmap.shape + (4,):
+            raise ValueError("roof_facets: bmap and roof must be [height][width] and top [height][width][4]")
+        h, w = bmap.shape
+        nb = max(int(bmap.max()) + 1, 0) if n_buildings is None else int(n_buildings)
+        npl = max(int(roof.max()), 0) if n_planes is None else int(n_planes)
+        facet = np.empty((h, w), dtype=np.int32)
+        out = _lib.RoofFacets()
+        self._check(self._L.bs_roof_facets(self._h, bmap.ctypes.data, roof.ctypes.data, top.ctypes.data, w, h, nb, npl,
+                                           facet.ctypes.data, C.byref(out)))
+        return _take_roof_facets(self._L, out, facet)
+
+    def roof_facets_dev(self, d_map, d_roof, d_top, width, height, n_buildings, n_planes, d_facet):
+        """Device-resident form (bs_roof_facets_dev): the four images are device pointers (ints), d_facet
+        [height][width] int32 is written.  Returns RoofFacets with facet None."""
+        out = _lib.RoofFacets()
+        self._check(self._L.bs_roof_facets_dev(self._h, d_map or None, d_roof or None, d_top or None, width, height,
+                                               int(n_buildings), int(n_planes), d_facet or None, C.byref(out)))
+        return _take_roof_facets(self._L, out, None)
+
+    def roof_structure(self, bmap, roofs, solids):
+        """roof_facets() from the Roofs of roofs() and the Solids of solids() on the same map."""
+        if solids.top is None:
+            raise ValueError("roof_structure: the Solids carry no top image (solids(top=True))")
+        if roofs.roof is None:
+            raise ValueError("roof_structure: the roof image is on the device: use roof_facets_dev")
+        return self.roof_facets(bmap, roofs.roof, solids.top, n_buildings=solids.n_buildings, n_planes=len(roofs.z_min))
+
 
 @dataclass
 class PlaneVotes:
@@ -1055,6 +1090,123 @@ def write_solids_obj(solids, path, origin=None):
                                          str(path).encode())
     if rc != 0:
         raise BsError(rc, f"cannot write {path} (or the mesh arrays do not fit each other)")
+
+
+@dataclass
+class RoofFacets:
+    """bs_roof_facets: the facet image (None after roof_facets_dev), the totals, the per-facet arrays (facet_*) and the
+    per-edge arrays (edge_*) as include/bs_api.h names them.  Facets are numbered by ascending start pixel, edges by
+    ascending (facet_lo, facet_hi)."""
+    width: int
+    image_height: int
+    n_facets: int
+    n_edges: int
+    n_pixels: int
+    n_border: int
+    facet_building: np.ndarray
+    facet_plane: np.ndarray
+    facet_start_xy: np.ndarray
+    facet_pixels: np.ndarray
+    facet_bbox: np.ndarray
+    facet_inner_edges: np.ndarray
+    facet_outer_edges: np.ndarray
+    facet_top_min: np.ndarray
+    facet_top_max: np.ndarray
+    facet_top_sum: np.ndarray
+    edge_facet: np.ndarray
+    edge_building: np.ndarray
+    edge_length: np.ndarray
+    edge_n_dir0: np.ndarray
+    edge_n_step: np.ndarray
+    edge_step_abs_sum: np.ndarray
+    edge_step_abs_max: np.ndarray
+    edge_rise_sum: np.ndarray
+    edge_bend_sum: np.ndarray
+    edge_z_min: np.ndarray
+    edge_z_max: np.ndarray
+    edge_bbox: np.ndarray
+    info: dict = field(default_factory=dict)
+    facet: np.ndarray | None = field(default=None, repr=False)
+
+
+# (name, dtype, columns) of the per-facet and per-edge arrays of bs_roof_facets
+_FACET_ARRAYS = (("facet_building", np.int32, 1), ("facet_plane", np.int32, 1), ("facet_start_xy", np.int32, 2),
+                 ("facet_pixels", np.int64, 1), ("facet_bbox", np.int32, 4), ("facet_inner_edges", np.int64, 1),
+                 ("facet_outer_edges", np.int64, 1), ("facet_top_min", np.int32, 1), ("facet_top_max", np.int32, 1),
+                 ("facet_top_sum", np.int64, 1))
+_EDGE_ARRAYS = (("edge_facet", np.int32, 2), ("edge_building", np.int32, 1), ("edge_length", np.int64, 1),
+                ("edge_n_dir0", np.int64, 1), ("edge_n_step", np.int64, 1), ("edge_step_abs_sum", np.int64, 1),
+                ("edge_step_abs_max", np.int64, 1), ("edge_rise_sum", np.int64, 1), ("edge_bend_sum", np.int64, 1),
+                ("edge_z_min", np.int32, 1), ("edge_z_max", np.int32, 1), ("edge_bbox", np.int32, 4))
+
+
+def _take_roof_facets(L, out, facet) -> RoofFacets:
+    """Copy a bs_roof_facets into numpy arrays and release it."""
+    try:
+        arrs = {}
+        for group, n in ((_FACET_ARRAYS, out.n_facets), (_EDGE_ARRAYS, out.n_edges)):
+            for name, dt, cols in group:
+                shape = (n, cols) if cols > 1 else (n,)
+                arrs[name] = np.ctypeslib.as_array(getattr(out, name), shape).copy() if n else np.zeros(shape, dt)
+        info = {k: getattr(out, k) for k in ("ms_label", "ms_number", "ms_figures", "ms_edges")}
+        return RoofFacets(out.width, out.height, out.n_facets, out.n_edges, out.n_pixels, out.n_border, info=info,
+                          facet=facet, **arrs)
+    finally:
+        L.bs_roof_facets_free(C.byref(out))
+
+
+def _roof_facets_struct(rf):
+    """a bs_roof_facets over the arrays of a RoofFacets (or anything with its names), and the arrays to keep alive"""
+    st, keep = _lib.RoofFacets(), []
+    st.n_facets, st.n_edges = int(rf.n_facets), int(rf.n_edges)
+    st.n_pixels, st.n_border = int(rf.n_pixels), int(rf.n_border)
+    for group, n in ((_FACET_ARRAYS, st.n_facets), (_EDGE_ARRAYS, st.n_edges)):
+        for name, dt, cols in group:
+            a = np.ascontiguousarray(getattr(rf, name), dtype=dt).reshape(-1)
+            if len(a) != n * cols:
+                raise ValueError(f"RoofFacets.{name} must hold {n * cols} values")
+            keep.append(a if len(a) else np.zeros(1, dt))
+            setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
+    return st, keep
+
+
+def roof_edge_kinds(rf, step_tol=200, bend_tol=0):
+    """The kind of every edge of a RoofFacets (bs_roof_edge_kinds): uint8 [n_edges], 0 flat, 1 ridge, 2 valley, 3 step.
+    step_tol: the mean height difference in millimetres along the border above which it is a step; bend_tol in the units
+    of bend (twice the change of rise per pixel)."""
+    st, keep = _roof_facets_struct(rf)
+    kind = np.zeros(max(st.n_edges, 1), dtype=np.uint8)
+    rc = _lib.load().bs_roof_edge_kinds(C.byref(st), int(step_tol), int(bend_tol), kind.ctypes.data)
+    if rc != 0:
+        raise BsError(rc, "roof_edge_kinds: a negative tolerance")
+    return kind[:st.n_edges]
+
+
+def write_roof_edges_obj(rf, bmap, top, path, bin, kinds=None, origin=None):
+    """The border edges of a RoofFacets as an OBJ of line segments in millimetres through the library's writer
+    (bs_roof_edges_write_obj; the format is written down in include/bs_api.h), one group per edge named by its kind.
+    kinds defaults to roof_edge_kinds(rf); origin: the shift that was subtracted from the cloud."""
+    if rf.facet is None:
+        raise ValueError("write_roof_edges_obj: the facet image is on the device")
+    facet = np.ascontiguousarray(rf.facet, dtype=np.int32)
+    bmap = np.ascontiguousarray(bmap, dtype=np.int32)
+    top = np.ascontiguousarray(top, dtype=np.int32)
+    if facet.ndim != 2 or bmap.shape != facet.shape or top.shape != facet.shape + (4,):
+        raise ValueError("write_roof_edges_obj: facet and bmap must be [height][width] and top [height][width][4]")
+    st, keep = _roof_facets_struct(rf)
+    kinds = roof_edge_kinds(rf) if kinds is None else np.ascontiguousarray(kinds, dtype=np.uint8).reshape(-1)
+    if len(kinds) != st.n_edges:
+        raise ValueError("write_roof_edges_obj: kinds must be [n_edges]")
+    kinds = kinds if len(kinds) else np.zeros(1, np.uint8)
+    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+    if org is not None and org.shape != (3,):
+        raise ValueError("origin must be [3]")
+    h, w = facet.shape
+    rc = _lib.load().bs_roof_edges_write_obj(facet.ctypes.data, bmap.ctypes.data, top.ctypes.data, w, h, int(bin), C.byref(st),
+                                             kinds.ctypes.data, org.ctypes.data if org is not None else None,
+                                             str(path).encode())
+    if rc != 0:
+        raise BsError(rc, f"cannot write {path} (or a facet pair the RoofFacets do not list)")
 
 
 @dataclass

@@ -250,6 +250,7 @@ struct bs_ctx {
   int32_t sd_w = 0, sd_h = 0, sd_bin = 0, sd_base = 0;
   int64_t sd_nv = 0, sd_nf = 0, sd_ni = 0;
   double sd_ms_emit[2] = {0, 0};  // vertex pass, face pass of the last emit
+  bs::DevBuf fc[16];  // scratch of the roof facets and their edges (bs_facet.hip)
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew

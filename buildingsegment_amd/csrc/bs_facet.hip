@@ -1,0 +1,913 @@
+// bs_facet.hip -- the roof facets of every building and the edges between them (DESIGN.md "Roof facets"; the definition
+// is written down in include/bs_api.h under "roof facets").
+//   label    union-find in two levels over the image, 4-connected, for an arbitrary 64-bit class (building << 32 | plane):
+//            one workgroup per TW x TH tile, a row of a tile is one wave.  The start of a lane's run comes from ONE ballot
+//            of "differs from the lane to my left"; only the vertical links go through LDS atomics.  Every pixel gets the
+//            GLOBAL index of its tile-component's first pixel; a seam kernel unites across tile edges with bs_uf.h; one
+//            flatten pass.  parent <= self throughout, so a root is its facet's first raster pixel.  The range checks
+//            ride on the tile kernel: nothing of the caller's is written before they have passed.
+//   number   roots flagged and scanned (hipcub): facet = rank of the root = ascending start pixel; the facet image
+//   figures  one pixel pass: the inner and outer sides of every pixel, its border flags (direction 0 and 1) as one byte,
+//            and the per-facet figures reduced over runs of equal facet inside a wave (a segmented scan over the ballot
+//            of run heads) before ONE set of global atomics per run -- facet ids are unbounded, no LDS table holds them
+//   edges    border flags scanned; one 64-bit key (facet_lo << 32 | facet_hi) and the pixel-edge number 2 * pixel +
+//            direction per border edge; radix sort of the pairs; run heads scanned = the edge of every sorted item; the
+//            figures of a border edge recomputed from top by its number and reduced over runs inside a wave as above
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <climits>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <iterator>
+#include <vector>
+
+#include "bs_common.h"
+#include "bs_uf.h"
+
+namespace bs {
+namespace {
+
+constexpr int TW = 64, TH = 16;  // labelling tile: a row is one wave, 8 KB (classes) + 4 KB (parents) of LDS
+constexpr int GRID_CAP = 4096;   // workgroups of the grid-stride passes
+// scratch of bs_ctx::fc
+enum { FC_PARENT, FC_SCAN, FC_FLAGS, FC_TMP, FC_MISC, FC_FFIG, FC_KEYS, FC_KEYS2, FC_VALS, FC_VALS2, FC_EID, FC_EFIG, FC_IN_MAP,
+       FC_IN_ROOF, FC_IN_TOP, FC_FACET };
+
+inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
+inline int grid_of(int64_t n) { return (int)std::min<int64_t>(nblk(n, 256), GRID_CAP); }
+
+constexpr unsigned long long NONE = ~0ull;  // the class of a pixel outside every building
+
+// class of a pixel: (building << 32) | plane, plane 0 = unroofed
+struct Cls {
+  const int32_t* map;
+  const int32_t* roof;
+  __device__ unsigned long long operator()(int64_t i) const
+  {
+    const int32_t c = map[i];
+    if (c < 0)
+      return NONE;
+    const int32_t r = roof[i];
+    return ((unsigned long long)(uint32_t)c << 32) | (uint32_t)(r > 0 ? r : 0);
+  }
+};
+
+__device__ inline int lds_find(const volatile int* p, int x)
+{
+  int q;
+  while ((q = p[x]) != x)
+    x = q;
+  return x;
+}
+
+// hook the larger root under the smaller one; atomicMin keeps parent <= self under races
+__device__ inline void lds_union(int* p, int a, int b)
+{
+  for (;;) {
+    a = lds_find(p, a);
+    b = lds_find(p, b);
+    if (a == b)
+      return;
+    if (a < b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    const int old = atomicMin(p + a, b);
+    if (old == a)
+      return;
+    a = old;  // a was hooked elsewhere in the meantime: unite that root with b
+  }
+}
+
+// lane of the head of my run: the highest set bit of `heads` at or below my lane (bit 0 is always set)
+__device__ inline int head_lane(unsigned long long heads, int lane) { return 63 - __clzll((long long)(heads & (~0ull >> (63 - lane)))); }
+// last lane of my run: one below the next head above me
+__device__ inline int tail_lane(unsigned long long heads, int lane)
+{
+  const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
+  return above ? __ffsll((long long)above) - 2 : 63;
+}
+
+// ---- label ---------------------------------------------------------------------------------------------------------------
+// One workgroup per tile.  A pixel joins W through its run, and N unless W and NW already carry the link.
+__global__ __launch_bounds__(256) void facet_tile_kernel(Cls cls, int w, int h, int ntx, int32_t nb, int32_t npl,
+                                                         int32_t* __restrict__ parent, int* __restrict__ bad)
+{
+  __shared__ unsigned long long c[TH][TW];
+  __shared__ int p[TH * TW];
+  const int lx = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int by = blockIdx.x / ntx, bx = blockIdx.x - by * ntx;
+  const int x0 = bx * TW, y0 = by * TH, gx = x0 + lx;
+  for (int j = 0; j < TH / 4; j++) {
+    const int ly = wv + 4 * j, gy = y0 + ly;
+    unsigned long long v = NONE;
+    if (gx < w && gy < h) {
+      const int64_t i = (int64_t)gy * w + gx;
+      const int32_t m = cls.map[i], r = cls.roof[i];
+      if (m >= nb || r > npl || (r > 0 && m < 0))
+        atomicOr(bad, 1);
+      v = cls(i);
+    }
+    const unsigned long long left = __shfl_up(v, 1);
+    const unsigned long long heads = __ballot(lx == 0 || v != left);
+    c[ly][lx] = v;
+    p[ly * TW + lx] = ly * TW + (v == NONE ? lx : head_lane(heads, lx));
+  }
+  __syncthreads();
+  for (int j = 0; j < TH / 4; j++) {
+    const int ly = wv + 4 * j;
+    const unsigned long long v = c[ly][lx];
+    if (ly == 0 || v == NONE || c[ly - 1][lx] != v)
+      continue;
+    if (lx > 0 && c[ly][lx - 1] == v && c[ly - 1][lx - 1] == v)
+      continue;
+    lds_union(p, ly * TW + lx, (ly - 1) * TW + lx);
+  }
+  __syncthreads();
+  for (int j = 0; j < TH / 4; j++) {
+    const int ly = wv + 4 * j, gy = y0 + ly;
+    if (gx >= w || gy >= h)
+      continue;
+    int32_t out = -1;
+    if (c[ly][lx] != NONE) {
+      const int r = lds_find(p, ly * TW + lx);
+      out = (y0 + r / TW) * w + x0 + (r & (TW - 1));
+    }
+    parent[(int64_t)gy * w + gx] = out;
+  }
+}
+
+// The links that cross a tile edge.  Threads [0, n_h) walk the rows y = TH * k (k >= 1) and link north, the others the
+// columns x = TW * k (k >= 1) and link west.
+__global__ __launch_bounds__(256) void facet_seam_kernel(Cls cls, int w, int h, int64_t n_h, int64_t total, int32_t* parent)
+{
+  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (t >= total)
+    return;
+  int x, y;
+  int32_t other;
+  if (t < n_h) {
+    const int64_t r = t / w;
+    y = TH * (int)(r + 1);
+    x = (int)(t - r * w);
+    other = (y - 1) * w + x;
+  } else {
+    const int64_t u = t - n_h;
+    const int col = (int)(u / h);
+    y = (int)(u - (int64_t)col * h);
+    x = TW * (col + 1);
+    other = y * w + x - 1;
+  }
+  const int32_t i = y * w + x;
+  const unsigned long long v = cls(i);
+  if (v != NONE && cls(other) == v)
+    uf_union(parent, i, other);
+}
+
+__global__ __launch_bounds__(256) void facet_flatten_kernel(int32_t* parent, int64_t np)
+{
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= np)
+    return;
+  int32_t p = parent[i];
+  if (p < 0)
+    return;
+  int32_t r = (int32_t)i;
+  while (p != r) {
+    r = p;
+    p = parent[r];
+  }
+  parent[i] = r;  // (racing writers store the same root; a stale read is still an ancestor)
+}
+
+// ---- number --------------------------------------------------------------------------------------------------------------
+struct RootFlag {  // start pixel of a facet: a building pixel that is its own root
+  const int32_t* parent;
+  __host__ __device__ int32_t operator()(int32_t i) const { return parent[i] == i; }
+};
+
+__global__ __launch_bounds__(256) void facet_write_kernel(const int32_t* __restrict__ parent, const int32_t* __restrict__ scan,
+                                                          int64_t np, int32_t* __restrict__ facet)
+{
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= np)
+    return;
+  const int32_t r = parent[i];
+  facet[i] = r < 0 ? -1 : scan[r];
+}
+
+// ---- figures -------------------------------------------------------------------------------------------------------------
+struct FacetFig {  // per facet, device
+  unsigned long long* pixels;
+  unsigned long long* inner;
+  unsigned long long* outer;
+  unsigned long long* top_sum;  // (two's complement sums)
+  int32_t* bbox;
+  int32_t* top_min;
+  int32_t* top_max;
+  int32_t* building;
+  int32_t* plane;
+  int32_t* start_xy;
+};
+
+FacetFig facet_fig_at(void* base, size_t n)
+{
+  FacetFig f;
+  f.pixels = (unsigned long long*)base;
+  f.inner = f.pixels + n;
+  f.outer = f.inner + n;
+  f.top_sum = f.outer + n;
+  f.bbox = (int32_t*)(f.top_sum + n);
+  f.top_min = f.bbox + 4 * n;
+  f.top_max = f.top_min + n;
+  f.building = f.top_max + n;
+  f.plane = f.building + n;
+  f.start_xy = f.plane + n;
+  return f;
+}
+constexpr size_t FACET_FIG_BYTES = 4 * 8 + 10 * 4;
+
+__global__ __launch_bounds__(256) void facet_fig_init_kernel(FacetFig f, int64_t nf)
+{
+  const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (k >= nf)
+    return;
+  f.pixels[k] = f.inner[k] = f.outer[k] = f.top_sum[k] = 0;
+  f.bbox[4 * k] = f.bbox[4 * k + 1] = INT32_MAX;
+  f.bbox[4 * k + 2] = f.bbox[4 * k + 3] = INT32_MIN;
+  f.top_min[k] = INT32_MAX;
+  f.top_max[k] = INT32_MIN;
+}
+
+// segmented inclusive scans over the runs of a wave: lane l takes lane l - o while that lane is still in its run
+#define BS_SEG_SCAN(v, op)                           \
+  for (int o = 1; o < 64; o <<= 1) {                 \
+    const auto t_ = __shfl_up(v, o);                 \
+    if (lane - o >= hl)                              \
+      v = op(v, t_);                                 \
+  }
+#define BS_OP_ADD(a, b) ((a) + (b))
+#define BS_OP_MIN(a, b) ((a) < (b) ? (a) : (b))
+#define BS_OP_MAX(a, b) ((a) > (b) ? (a) : (b))
+
+// Sides, border flags and per-facet figures of every pixel.  flags: bit 0 = the edge to (x + 1, y) is a border edge,
+// bit 1 = the edge to (x, y + 1).
+__global__ __launch_bounds__(256) void facet_figures_kernel(const int32_t* __restrict__ map, const int32_t* __restrict__ roof,
+                                                            const int4* __restrict__ top, const int32_t* __restrict__ parent,
+                                                            const int32_t* __restrict__ facet, int w, int h,
+                                                            uint8_t* __restrict__ flags, FacetFig F)
+{
+  const int lane = threadIdx.x & 63;
+  const int64_t npix = (int64_t)w * h, npix64 = (npix + 63) & ~(int64_t)63;  // whole waves stay together
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix64; i += (int64_t)gridDim.x * blockDim.x) {
+    int32_t f = -1, c = -1;
+    int x = 0, y = 0;
+    unsigned sides = 0;  // inner | outer << 16
+    int32_t tmn = INT32_MAX, tmx = INT32_MIN;
+    long long tsum = 0;
+    if (i < npix) {
+      c = map[i];
+      unsigned fl = 0;
+      if (c >= 0) {
+        f = facet[i];
+        y = (int)(i / w);
+        x = (int)(i - (int64_t)y * w);
+        const int4 T = top[i];
+        tmn = min(min(T.x, T.y), min(T.z, T.w));
+        tmx = max(max(T.x, T.y), max(T.z, T.w));
+        tsum = (long long)T.x + T.y + T.z + T.w;
+        // west, north, east, south: outer unless the neighbour is a pixel of the same building
+        const bool sw = x > 0 && map[i - 1] == c, sn = y > 0 && map[i - w] == c;
+        const bool se = x + 1 < w && map[i + 1] == c, ss = y + 1 < h && map[i + w] == c;
+        const bool b_e = se && facet[i + 1] != f, b_s = ss && facet[i + w] != f;
+        const unsigned inner = (unsigned)(sw && facet[i - 1] != f) + (unsigned)(sn && facet[i - w] != f) + b_e + b_s;
+        const unsigned outer = 4u - (unsigned)sw - (unsigned)sn - (unsigned)se - (unsigned)ss;
+        sides = inner | (outer << 16);
+        fl = (unsigned)b_e | ((unsigned)b_s << 1);
+        if (parent[i] == (int32_t)i) {  // the start pixel names the facet
+          const int32_t r = roof[i];
+          F.building[f] = c;
+          F.plane[f] = r > 0 ? r : 0;
+          F.start_xy[2 * f] = x;
+          F.start_xy[2 * f + 1] = y;
+        }
+      }
+      flags[i] = (uint8_t)fl;
+    }
+    const int32_t prev = __shfl_up(f, 1);
+    const unsigned long long heads = __ballot(lane == 0 || prev != f);
+    const int hl = head_lane(heads, lane), tl = tail_lane(heads, lane);
+    int xmn = x, xmx = x, ymn = y;
+    BS_SEG_SCAN(sides, BS_OP_ADD)
+    BS_SEG_SCAN(tsum, BS_OP_ADD)
+    BS_SEG_SCAN(tmn, BS_OP_MIN)
+    BS_SEG_SCAN(tmx, BS_OP_MAX)
+    BS_SEG_SCAN(xmn, BS_OP_MIN)
+    BS_SEG_SCAN(xmx, BS_OP_MAX)
+    BS_SEG_SCAN(ymn, BS_OP_MIN)
+    if (lane == tl && f >= 0) {  // (y ascends along a run: this lane holds its largest)
+      atomicAdd(F.pixels + f, (unsigned long long)(tl - hl + 1));
+      if (sides & 0xFFFFu)
+        atomicAdd(F.inner + f, (unsigned long long)(sides & 0xFFFFu));
+      if (sides >> 16)
+        atomicAdd(F.outer + f, (unsigned long long)(sides >> 16));
+      atomicAdd(F.top_sum + f, (unsigned long long)tsum);
+      atomicMin(F.top_min + f, tmn);
+      atomicMax(F.top_max + f, tmx);
+      atomicMin(F.bbox + 4 * (int64_t)f, xmn);
+      atomicMin(F.bbox + 4 * (int64_t)f + 1, ymn);
+      atomicMax(F.bbox + 4 * (int64_t)f + 2, xmx);
+      atomicMax(F.bbox + 4 * (int64_t)f + 3, y);
+    }
+  }
+}
+
+// ---- edges ---------------------------------------------------------------------------------------------------------------
+struct FlagCount {
+  __host__ __device__ int32_t operator()(uint8_t v) const { return (v & 1) + (v >> 1); }
+};
+using FlagIt = hipcub::TransformInputIterator<int32_t, FlagCount, const uint8_t*>;
+
+__global__ __launch_bounds__(256) void edge_emit_kernel(const uint8_t* __restrict__ flags, const int32_t* __restrict__ eoff,
+                                                        const int32_t* __restrict__ facet, int w, int64_t npix,
+                                                        unsigned long long* __restrict__ keys, int32_t* __restrict__ vals)
+{
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
+    const unsigned fl = flags[i];
+    if (!fl)
+      continue;
+    const unsigned fa = (unsigned)facet[i];
+    int32_t at = eoff[i];
+    if (fl & 1u) {
+      const unsigned fb = (unsigned)facet[i + 1];
+      keys[at] = ((unsigned long long)min(fa, fb) << 32) | max(fa, fb);
+      vals[at] = (int32_t)(2 * i);
+      at++;
+    }
+    if (fl & 2u) {
+      const unsigned fb = (unsigned)facet[i + w];
+      keys[at] = ((unsigned long long)min(fa, fb) << 32) | max(fa, fb);
+      vals[at] = (int32_t)(2 * i + 1);
+    }
+  }
+}
+
+struct HeadFlag {  // first sorted item of an edge
+  const unsigned long long* keys;
+  __host__ __device__ int32_t operator()(int32_t j) const { return j == 0 || keys[j] != keys[j - 1]; }
+};
+
+struct EdgeFig {  // per edge, device
+  unsigned long long* length;
+  unsigned long long* n_dir0;
+  unsigned long long* n_step;
+  unsigned long long* step_abs_sum;
+  unsigned long long* step_abs_max;
+  unsigned long long* rise_sum;  // (two's complement sums)
+  unsigned long long* bend_sum;
+  int32_t* facet;
+  int32_t* building;
+  int32_t* z_min;
+  int32_t* z_max;
+  int32_t* bbox;
+};
+
+EdgeFig edge_fig_at(void* base, size_t n)
+{
+  EdgeFig f;
+  f.length = (unsigned long long*)base;
+  f.n_dir0 = f.length + n;
+  f.n_step = f.n_dir0 + n;
+  f.step_abs_sum = f.n_step + n;
+  f.step_abs_max = f.step_abs_sum + n;
+  f.rise_sum = f.step_abs_max + n;
+  f.bend_sum = f.rise_sum + n;
+  f.facet = (int32_t*)(f.bend_sum + n);
+  f.building = f.facet + 2 * n;
+  f.z_min = f.building + n;
+  f.z_max = f.z_min + n;
+  f.bbox = f.z_max + n;
+  return f;
+}
+constexpr size_t EDGE_FIG_BYTES = 7 * 8 + 9 * 4;
+
+__global__ __launch_bounds__(256) void edge_fig_init_kernel(EdgeFig f, int64_t ne)
+{
+  const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (k >= ne)
+    return;
+  f.length[k] = f.n_dir0[k] = f.n_step[k] = f.step_abs_sum[k] = f.step_abs_max[k] = f.rise_sum[k] = f.bend_sum[k] = 0;
+  f.z_min[k] = INT32_MAX;
+  f.z_max[k] = INT32_MIN;
+  f.bbox[4 * k] = f.bbox[4 * k + 1] = INT32_MAX;
+  f.bbox[4 * k + 2] = f.bbox[4 * k + 3] = INT32_MIN;
+}
+
+// One lane per sorted border edge: its figures from top by the pixel-edge number, reduced over the runs of equal edge
+// inside the wave, one set of atomics per run.  eid is the INCLUSIVE sum of the run heads: edge = eid - 1.
+__global__ __launch_bounds__(256) void edge_reduce_kernel(const unsigned long long* __restrict__ keys,
+                                                          const int32_t* __restrict__ vals, const int32_t* __restrict__ eid,
+                                                          int64_t nbord, const int32_t* __restrict__ map,
+                                                          const int4* __restrict__ top, const int32_t* __restrict__ facet,
+                                                          int w, EdgeFig E)
+{
+  const int lane = threadIdx.x & 63;
+  const int64_t n64 = (nbord + 63) & ~(int64_t)63;  // whole waves stay together
+  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n64; j += (int64_t)gridDim.x * blockDim.x) {
+    int32_t e = -1;
+    bool dir0 = false, step = false;
+    long long asum = 0, amax = 0, rise = 0, bend = 0;
+    int32_t zmn = INT32_MAX, zmx = INT32_MIN;
+    int X0 = INT32_MAX, Y0 = INT32_MAX, X1 = INT32_MIN, Y1 = INT32_MIN;
+    if (j < nbord) {
+      e = eid[j] - 1;
+      const int32_t v = vals[j];
+      const int64_t a = v >> 1;
+      const int d = v & 1;
+      const int64_t b = a + (d ? w : 1);
+      const int y = (int)(a / w), x = (int)(a - (int64_t)y * w);
+      const int4 A = top[a], B = top[b];
+      // the tops at the shared corners s and e, and the rise of each pixel across the edge
+      const long long a_s = d ? A.z : A.y, a_e = A.w, b_s = B.x, b_e = d ? B.y : B.z;
+      const long long sa = d ? ((long long)A.z + A.w) - ((long long)A.x + A.y) : ((long long)A.y + A.w) - ((long long)A.x + A.z);
+      const long long sb = d ? ((long long)B.z + B.w) - ((long long)B.x + B.y) : ((long long)B.y + B.w) - ((long long)B.x + B.z);
+      const long long ds = a_s - b_s, de = a_e - b_e;
+      dir0 = d == 0;
+      step = ds != 0 || de != 0;
+      const long long as_abs = ds < 0 ? -ds : ds, ae_abs = de < 0 ? -de : de;
+      asum = as_abs + ae_abs;
+      amax = as_abs > ae_abs ? as_abs : ae_abs;
+      rise = facet[a] > facet[b] ? ds + de : -(ds + de);
+      bend = sa - sb;
+      zmn = (int32_t)min(min(a_s, a_e), min(b_s, b_e));
+      zmx = (int32_t)max(max(a_s, a_e), max(b_s, b_e));
+      X0 = d ? x : x + 1;
+      Y0 = d ? y + 1 : y;
+      X1 = x + 1;
+      Y1 = y + 1;
+      const int32_t before = j == 0 ? 0 : eid[j - 1];
+      if (before != e + 1) {  // the first item of the edge names it
+        const unsigned long long k = keys[j];
+        E.facet[2 * (int64_t)e] = (int32_t)(k >> 32);
+        E.facet[2 * (int64_t)e + 1] = (int32_t)(k & 0xFFFFFFFFull);
+        E.building[e] = map[a];
+      }
+    }
+    const int32_t prev = __shfl_up(e, 1);
+    const unsigned long long heads = __ballot(lane == 0 || prev != e);
+    const unsigned long long m_dir0 = __ballot(dir0), m_step = __ballot(step);
+    const int hl = head_lane(heads, lane), tl = tail_lane(heads, lane);
+    BS_SEG_SCAN(asum, BS_OP_ADD)
+    BS_SEG_SCAN(amax, BS_OP_MAX)
+    BS_SEG_SCAN(rise, BS_OP_ADD)
+    BS_SEG_SCAN(bend, BS_OP_ADD)
+    BS_SEG_SCAN(zmn, BS_OP_MIN)
+    BS_SEG_SCAN(zmx, BS_OP_MAX)
+    BS_SEG_SCAN(X0, BS_OP_MIN)
+    BS_SEG_SCAN(Y0, BS_OP_MIN)
+    BS_SEG_SCAN(X1, BS_OP_MAX)
+    BS_SEG_SCAN(Y1, BS_OP_MAX)
+    if (lane == tl && e >= 0) {
+      const int len = tl - hl + 1;
+      const unsigned long long run = (len == 64 ? ~0ull : ((1ull << len) - 1)) << hl;
+      const unsigned nd0 = (unsigned)__popcll(m_dir0 & run), nst = (unsigned)__popcll(m_step & run);
+      atomicAdd(E.length + e, (unsigned long long)len);
+      if (nd0)
+        atomicAdd(E.n_dir0 + e, (unsigned long long)nd0);
+      if (nst) {
+        atomicAdd(E.n_step + e, (unsigned long long)nst);
+        atomicAdd(E.step_abs_sum + e, (unsigned long long)asum);
+        atomicMax(E.step_abs_max + e, (unsigned long long)amax);
+        atomicAdd(E.rise_sum + e, (unsigned long long)rise);
+      }
+      atomicAdd(E.bend_sum + e, (unsigned long long)bend);
+      atomicMin(E.z_min + e, zmn);
+      atomicMax(E.z_max + e, zmx);
+      atomicMin(E.bbox + 4 * (int64_t)e, X0);
+      atomicMin(E.bbox + 4 * (int64_t)e + 1, Y0);
+      atomicMax(E.bbox + 4 * (int64_t)e + 2, X1);
+      atomicMax(E.bbox + 4 * (int64_t)e + 3, Y1);
+    }
+  }
+}
+
+struct Events {
+  hipEvent_t e[11] = {};
+  ~Events()
+  {
+    for (auto& x : e)
+      if (x)
+        (void)hipEventDestroy(x);
+  }
+  double ms(int i, int j)
+  {
+    float t = 0;
+    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.0;
+  }
+};
+
+template <class T>
+bool alloc(T** p, size_t n)
+{
+  *p = (T*)calloc(std::max<size_t>(n, 1), sizeof(T));
+  return *p != nullptr;
+}
+
+// (every array is allocated even after a failure: bs_roof_facets_free takes them all)
+bool alloc_facets(struct bs_roof_facets* s, size_t nf)
+{
+  const bool ok[] = {alloc(&s->facet_building, nf),    alloc(&s->facet_plane, nf),       alloc(&s->facet_start_xy, 2 * nf),
+                     alloc(&s->facet_pixels, nf),      alloc(&s->facet_bbox, 4 * nf),    alloc(&s->facet_inner_edges, nf),
+                     alloc(&s->facet_outer_edges, nf), alloc(&s->facet_top_min, nf),     alloc(&s->facet_top_max, nf),
+                     alloc(&s->facet_top_sum, nf)};
+  return std::all_of(std::begin(ok), std::end(ok), [](bool b) { return b; });
+}
+
+bool alloc_edges(struct bs_roof_facets* s, size_t ne)
+{
+  const bool ok[] = {alloc(&s->edge_facet, 2 * ne),     alloc(&s->edge_building, ne),     alloc(&s->edge_length, ne),
+                     alloc(&s->edge_n_dir0, ne),        alloc(&s->edge_n_step, ne),       alloc(&s->edge_step_abs_sum, ne),
+                     alloc(&s->edge_step_abs_max, ne),  alloc(&s->edge_rise_sum, ne),     alloc(&s->edge_bend_sum, ne),
+                     alloc(&s->edge_z_min, ne),         alloc(&s->edge_z_max, ne),        alloc(&s->edge_bbox, 4 * ne)};
+  return std::all_of(std::begin(ok), std::end(ok), [](bool b) { return b; });
+}
+
+struct Guard {  // frees a half-built result unless it is handed over
+  struct bs_roof_facets* s;
+  bool keep = false;
+  ~Guard()
+  {
+    if (!keep)
+      bs_roof_facets_free(s);
+  }
+};
+
+// (a pixel edge is numbered 2 * pixel + direction in 32 bits)
+bool bad_image(int32_t w, int32_t h) { return w < 1 || h < 1 || (int64_t)w * h >= (1ll << 30); }
+
+const char* const FACETS_INVALID = "roof facets: null pointer, width or height < 1, width * height >= 2^30, n_buildings or "
+                                   "n_planes < 0, or d_top not 16-byte aligned";
+
+int bits_of(int64_t n)  // bits that hold 0 .. n - 1 (at least 1)
+{
+  int b = 1;
+  while (b < 32 && (1ll << b) < n)
+    b++;
+  return b;
+}
+
+}  // namespace
+}  // namespace bs
+
+using namespace bs;
+
+extern "C" void bs_roof_facets_free(struct bs_roof_facets* s)
+{
+  if (!s)
+    return;
+  free(s->facet_building);
+  free(s->facet_plane);
+  free(s->facet_start_xy);
+  free(s->facet_pixels);
+  free(s->facet_bbox);
+  free(s->facet_inner_edges);
+  free(s->facet_outer_edges);
+  free(s->facet_top_min);
+  free(s->facet_top_max);
+  free(s->facet_top_sum);
+  free(s->edge_facet);
+  free(s->edge_building);
+  free(s->edge_length);
+  free(s->edge_n_dir0);
+  free(s->edge_n_step);
+  free(s->edge_step_abs_sum);
+  free(s->edge_step_abs_max);
+  free(s->edge_rise_sum);
+  free(s->edge_bend_sum);
+  free(s->edge_z_min);
+  free(s->edge_z_max);
+  free(s->edge_bbox);
+  memset(s, 0, sizeof *s);
+}
+
+extern "C" int bs_roof_facets_dev(bs_ctx* ctx, const int32_t* d_map, const int32_t* d_roof, const int32_t* d_top,
+                                  int32_t width, int32_t height, int32_t n_buildings, int32_t n_planes, int32_t* d_facet,
+                                  struct bs_roof_facets* out)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (!d_map || !d_roof || !d_top || !d_facet || !out || bad_image(width, height) || n_buildings < 0 || n_planes < 0 ||
+      (reinterpret_cast<uintptr_t>(d_top) & 15u))  // (the four tops of a pixel are one 16-byte load)
+    return fail(ctx, BS_ERR_INVALID, FACETS_INVALID);
+  BS_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int w = width, h = height;
+  const int64_t npix = (int64_t)w * h;
+  const int ntx = nblk(w, TW), nty = nblk(h, TH);
+  DevBuf* B = ctx->fc;
+  const int4* top = reinterpret_cast<const int4*>(d_top);
+  const Cls cls{d_map, d_roof};
+  Events ev;
+  for (auto& e : ev.e)
+    BS_HIP(ctx, hipEventCreate(&e));
+
+  hipcub::CountingInputIterator<int32_t> idx(0);
+  size_t t1 = 0, t2 = 0;
+  BS_HIP(ctx, B[FC_PARENT].reserve(4 * (size_t)npix));
+  BS_HIP(ctx, B[FC_SCAN].reserve(4 * (size_t)npix));
+  BS_HIP(ctx, B[FC_FLAGS].reserve((size_t)npix));
+  BS_HIP(ctx, B[FC_MISC].reserve(256));
+  int32_t* parent = B[FC_PARENT].as<int32_t>();
+  int32_t* scan = B[FC_SCAN].as<int32_t>();  // ranks of the roots, then the offsets of the border edges
+  uint8_t* flags = B[FC_FLAGS].as<uint8_t>();
+  int* d_bad = B[FC_MISC].as<int>();
+  hipcub::TransformInputIterator<int32_t, RootFlag, hipcub::CountingInputIterator<int32_t>> roots(idx, RootFlag{parent});
+  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t1, roots, scan, (int)npix, st));
+  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, FlagIt(flags, FlagCount()), scan, (int)npix, st));
+  BS_HIP(ctx, B[FC_TMP].reserve(std::max<size_t>(std::max(t1, t2), 256)));
+
+  // ---- label (into the context: nothing of the caller's is written before the checks have passed) ----
+  BS_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, st));
+  BS_HIP(ctx, hipEventRecord(ev.e[0], st));
+  facet_tile_kernel<<<ntx * nty, 256, 0, st>>>(cls, w, h, ntx, n_buildings, n_planes, parent, d_bad);
+  {
+    const int64_t n_h = (int64_t)(nty - 1) * w, total = n_h + (int64_t)(ntx - 1) * h;
+    if (total > 0)
+      facet_seam_kernel<<<nblk(total, 256), 256, 0, st>>>(cls, w, h, n_h, total, parent);
+  }
+  facet_flatten_kernel<<<nblk(npix, 256), 256, 0, st>>>(parent, npix);
+  BS_HIP(ctx, hipEventRecord(ev.e[1], st));
+  // ---- number ----
+  size_t tb = B[FC_TMP].cap;
+  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[FC_TMP].p, tb, roots, scan, (int)npix, st));
+  BS_HIP(ctx, hipEventRecord(ev.e[2], st));
+  int h_bad = 0;
+  int32_t last_rank = 0, last_parent = -1;
+  BS_HIP(ctx, hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st));
+  BS_HIP(ctx, hipMemcpyAsync(&last_rank, scan + npix - 1, 4, hipMemcpyDeviceToHost, st));
+  BS_HIP(ctx, hipMemcpyAsync(&last_parent, parent + npix - 1, 4, hipMemcpyDeviceToHost, st));
+  BS_HIP(ctx, hipStreamSynchronize(st));
+  BS_HIP(ctx, hipGetLastError());
+  if (h_bad)
+    return fail(ctx, BS_ERR_RANGE,
+                "roof facets: a map value >= n_buildings, a roof value > n_planes, or a roof > 0 outside every building");
+  const int64_t nf = (int64_t)last_rank + (last_parent == (int32_t)(npix - 1));
+
+  struct bs_roof_facets res;
+  memset(&res, 0, sizeof res);
+  Guard guard{&res};
+  if (!alloc_facets(&res, (size_t)nf))
+    return fail(ctx, BS_ERR_NOMEM, "roof facets: host allocation");
+  BS_HIP(ctx, B[FC_FFIG].reserve(FACET_FIG_BYTES * (size_t)std::max<int64_t>(nf, 1)));
+  const FacetFig F = facet_fig_at(B[FC_FFIG].p, (size_t)std::max<int64_t>(nf, 1));
+  BS_HIP(ctx, hipEventRecord(ev.e[3], st));
+  if (nf > 0)
+    facet_fig_init_kernel<<<nblk(nf, 256), 256, 0, st>>>(F, nf);
+  facet_write_kernel<<<nblk(npix, 256), 256, 0, st>>>(parent, scan, npix, d_facet);
+  BS_HIP(ctx, hipEventRecord(ev.e[4], st));
+  // ---- figures ----
+  facet_figures_kernel<<<grid_of(npix), 256, 0, st>>>(d_map, d_roof, top, parent, d_facet, w, h, flags, F);
+  BS_HIP(ctx, hipEventRecord(ev.e[5], st));
+  // ---- edges: at most 2 * width * height < 2^31 border edges (the check on the image), so every sum below fits 32 bits ----
+  tb = B[FC_TMP].cap;
+  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[FC_TMP].p, tb, FlagIt(flags, FlagCount()), scan, (int)npix, st));
+  BS_HIP(ctx, hipEventRecord(ev.e[6], st));
+  int32_t last_off = 0;
+  uint8_t last_flag = 0;
+  BS_HIP(ctx, hipMemcpyAsync(&last_off, scan + npix - 1, 4, hipMemcpyDeviceToHost, st));
+  BS_HIP(ctx, hipMemcpyAsync(&last_flag, flags + npix - 1, 1, hipMemcpyDeviceToHost, st));
+  if (nf > 0) {
+    const size_t n = (size_t)nf;
+    BS_HIP(ctx, hipMemcpyAsync(res.facet_pixels, F.pixels, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.facet_inner_edges, F.inner, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.facet_outer_edges, F.outer, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.facet_top_sum, F.top_sum, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.facet_bbox, F.bbox, 16 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.facet_top_min, F.top_min, 4 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.facet_top_max, F.top_max, 4 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.facet_building, F.building, 4 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.facet_plane, F.plane, 4 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.facet_start_xy, F.start_xy, 8 * n, hipMemcpyDeviceToHost, st));
+  }
+  BS_HIP(ctx, hipStreamSynchronize(st));
+  BS_HIP(ctx, hipGetLastError());
+  const int64_t nbord = (int64_t)last_off + (last_flag & 1) + (last_flag >> 1);
+  int64_t ne = 0;
+  double ms_sort = 0, ms_reduce = 0;
+  if (nbord > 0) {
+    const int nbi = (int)nbord;
+    const int end_bit = 32 + bits_of(nf);
+    BS_HIP(ctx, B[FC_KEYS].reserve(8 * (size_t)nbord));
+    BS_HIP(ctx, B[FC_KEYS2].reserve(8 * (size_t)nbord));
+    BS_HIP(ctx, B[FC_VALS].reserve(4 * (size_t)nbord));
+    BS_HIP(ctx, B[FC_VALS2].reserve(4 * (size_t)nbord));
+    BS_HIP(ctx, B[FC_EID].reserve(4 * (size_t)nbord));
+    unsigned long long* keys = B[FC_KEYS].as<unsigned long long>();
+    unsigned long long* sorted = B[FC_KEYS2].as<unsigned long long>();
+    int32_t* vals = B[FC_VALS].as<int32_t>();
+    int32_t* svals = B[FC_VALS2].as<int32_t>();
+    int32_t* eid = B[FC_EID].as<int32_t>();
+    hipcub::TransformInputIterator<int32_t, HeadFlag, hipcub::CountingInputIterator<int32_t>> heads(idx, HeadFlag{sorted});
+    size_t t3 = 0, t4 = 0;
+    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t3, keys, sorted, vals, svals, nbi, 0, end_bit, st));
+    BS_HIP(ctx, hipcub::DeviceScan::InclusiveSum(nullptr, t4, heads, eid, nbi, st));
+    BS_HIP(ctx, B[FC_TMP].reserve(std::max(t3, t4)));
+    BS_HIP(ctx, hipEventRecord(ev.e[7], st));
+    edge_emit_kernel<<<grid_of(npix), 256, 0, st>>>(flags, scan, d_facet, w, npix, keys, vals);
+    tb = B[FC_TMP].cap;
+    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(B[FC_TMP].p, tb, keys, sorted, vals, svals, nbi, 0, end_bit, st));
+    tb = B[FC_TMP].cap;
+    BS_HIP(ctx, hipcub::DeviceScan::InclusiveSum(B[FC_TMP].p, tb, heads, eid, nbi, st));
+    BS_HIP(ctx, hipEventRecord(ev.e[8], st));
+    int32_t h_ne = 0;
+    BS_HIP(ctx, hipMemcpyAsync(&h_ne, eid + nbord - 1, 4, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipStreamSynchronize(st));
+    BS_HIP(ctx, hipGetLastError());
+    ne = h_ne;
+    if (!alloc_edges(&res, (size_t)ne))
+      return fail(ctx, BS_ERR_NOMEM, "roof facets: host allocation");
+    BS_HIP(ctx, B[FC_EFIG].reserve(EDGE_FIG_BYTES * (size_t)ne));
+    const EdgeFig E = edge_fig_at(B[FC_EFIG].p, (size_t)ne);
+    BS_HIP(ctx, hipEventRecord(ev.e[9], st));
+    edge_fig_init_kernel<<<nblk(ne, 256), 256, 0, st>>>(E, ne);
+    edge_reduce_kernel<<<grid_of(nbord), 256, 0, st>>>(sorted, svals, eid, nbord, d_map, top, d_facet, w, E);
+    BS_HIP(ctx, hipEventRecord(ev.e[10], st));
+    const size_t n = (size_t)ne;
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_length, E.length, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_n_dir0, E.n_dir0, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_n_step, E.n_step, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_step_abs_sum, E.step_abs_sum, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_step_abs_max, E.step_abs_max, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_rise_sum, E.rise_sum, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_bend_sum, E.bend_sum, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_facet, E.facet, 8 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_building, E.building, 4 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_z_min, E.z_min, 4 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_z_max, E.z_max, 4 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(res.edge_bbox, E.bbox, 16 * n, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipStreamSynchronize(st));
+    BS_HIP(ctx, hipGetLastError());
+    ms_sort = ev.ms(7, 8);
+    ms_reduce = ev.ms(9, 10);
+  } else if (!alloc_edges(&res, 0)) {
+    return fail(ctx, BS_ERR_NOMEM, "roof facets: host allocation");
+  }
+  int64_t npx = 0;
+  for (int64_t k = 0; k < nf; k++)
+    npx += res.facet_pixels[k];
+  res.width = w;
+  res.height = h;
+  res.n_facets = nf;
+  res.n_edges = ne;
+  res.n_pixels = npx;
+  res.n_border = nbord;
+  res.ms_label = ev.ms(0, 1);
+  res.ms_number = ev.ms(1, 2) + ev.ms(3, 4);
+  res.ms_figures = ev.ms(4, 5);
+  res.ms_edges = ev.ms(5, 6) + ms_sort + ms_reduce;
+  *out = res;
+  guard.keep = true;
+  return BS_OK;
+}
+
+extern "C" int bs_roof_facets(bs_ctx* ctx, const int32_t* map, const int32_t* roof, const int32_t* top, int32_t width,
+                              int32_t height, int32_t n_buildings, int32_t n_planes, int32_t* facet,
+                              struct bs_roof_facets* out)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (!map || !roof || !top || !facet || !out || bad_image(width, height) || n_buildings < 0 || n_planes < 0)
+    return fail(ctx, BS_ERR_INVALID, FACETS_INVALID);
+  BS_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t npix = (size_t)width * height;
+  DevBuf* B = ctx->fc;
+  BS_HIP(ctx, B[FC_IN_MAP].reserve(4 * npix));
+  BS_HIP(ctx, B[FC_IN_ROOF].reserve(4 * npix));
+  BS_HIP(ctx, B[FC_IN_TOP].reserve(16 * npix));
+  BS_HIP(ctx, B[FC_FACET].reserve(4 * npix));
+  BS_HIP(ctx, hipMemcpyAsync(B[FC_IN_MAP].p, map, 4 * npix, hipMemcpyHostToDevice, st));
+  BS_HIP(ctx, hipMemcpyAsync(B[FC_IN_ROOF].p, roof, 4 * npix, hipMemcpyHostToDevice, st));
+  BS_HIP(ctx, hipMemcpyAsync(B[FC_IN_TOP].p, top, 16 * npix, hipMemcpyHostToDevice, st));
+  const int rc = bs_roof_facets_dev(ctx, B[FC_IN_MAP].as<int32_t>(), B[FC_IN_ROOF].as<int32_t>(), B[FC_IN_TOP].as<int32_t>(),
+                                    width, height, n_buildings, n_planes, B[FC_FACET].as<int32_t>(), out);
+  if (rc != BS_OK)
+    return rc;
+  hipError_t e = hipMemcpyAsync(facet, B[FC_FACET].p, 4 * npix, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess)
+    e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    bs_roof_facets_free(out);
+    return fail(ctx, BS_ERR_HIP, "roof facets: copy to the host", e);
+  }
+  return BS_OK;
+}
+
+// The rules are written down in include/bs_api.h.
+extern "C" int bs_roof_edge_kinds(const struct bs_roof_facets* f, int32_t step_tol, int32_t bend_tol, uint8_t* kind_out)
+{
+  if (!f || !kind_out || step_tol < 0 || bend_tol < 0 || f->n_edges < 0)
+    return BS_ERR_INVALID;
+  if (f->n_edges > 0 && (!f->edge_length || !f->edge_step_abs_sum || !f->edge_bend_sum))
+    return BS_ERR_INVALID;
+  for (int64_t e = 0; e < f->n_edges; e++) {
+    const int64_t len = f->edge_length[e];
+    uint8_t k = 0;
+    if (f->edge_step_abs_sum[e] > 2 * (int64_t)step_tol * len)
+      k = 3;
+    else if (f->edge_bend_sum[e] > (int64_t)bend_tol * len)
+      k = 1;
+    else if (f->edge_bend_sum[e] < -(int64_t)bend_tol * len)
+      k = 2;
+    kind_out[e] = k;
+  }
+  return BS_OK;
+}
+
+// The format is written down in include/bs_api.h.
+extern "C" int bs_roof_edges_write_obj(const int32_t* facet, const int32_t* map, const int32_t* top, int32_t width,
+                                       int32_t height, int32_t bin, const struct bs_roof_facets* f, const uint8_t* kind,
+                                       const int32_t* origin, const char* path)
+{
+  if (!facet || !map || !top || !f || !kind || !path || bin < 1 || bad_image(width, height) || f->n_edges < 0 ||
+      (f->n_edges > 0 && !f->edge_facet))
+    return BS_ERR_INVALID;
+  const int w = width, h = height;
+  const int64_t ne = f->n_edges;
+  for (int64_t e = 0; e < ne; e++)
+    if (kind[e] > 3)
+      return BS_ERR_INVALID;
+  // the edge of a facet pair: binary search in the ascending (lo, hi) list
+  auto edge_of = [&](int32_t fa, int32_t fb) -> int64_t {
+    const int32_t lo = std::min(fa, fb), hi = std::max(fa, fb);
+    int64_t a = 0, b = ne;
+    while (a < b) {
+      const int64_t m = (a + b) / 2;
+      const int32_t mlo = f->edge_facet[2 * m], mhi = f->edge_facet[2 * m + 1];
+      if (mlo < lo || (mlo == lo && mhi < hi))
+        a = m + 1;
+      else
+        b = m;
+    }
+    return (a < ne && f->edge_facet[2 * a] == lo && f->edge_facet[2 * a + 1] == hi) ? a : -1;
+  };
+  // the border edges in ascending (y, x, direction), then a stable counting sort by edge
+  std::vector<int32_t> seg, seg_edge;
+  std::vector<int64_t> first((size_t)ne + 1, 0);
+  for (int64_t i = 0; i < (int64_t)w * h; i++) {
+    const int32_t c = map[i];
+    if (c < 0)
+      continue;
+    const int x = (int)(i % w), y = (int)(i / w);
+    for (int d = 0; d < 2; d++) {
+      if (d == 0 ? x + 1 >= w : y + 1 >= h)
+        continue;
+      const int64_t q = i + (d ? w : 1);
+      if (map[q] != c || facet[q] == facet[i])
+        continue;
+      const int64_t e = edge_of(facet[i], facet[q]);
+      if (e < 0)
+        return BS_ERR_INVALID;
+      seg.push_back((int32_t)(2 * i + d));
+      seg_edge.push_back((int32_t)e);
+      first[(size_t)e + 1]++;
+    }
+  }
+  for (int64_t e = 0; e < ne; e++)
+    first[(size_t)e + 1] += first[(size_t)e];
+  std::vector<int32_t> order(seg.size());
+  {
+    std::vector<int64_t> at(first.begin(), first.end() - 1);
+    for (size_t k = 0; k < seg.size(); k++)
+      order[(size_t)at[seg_edge[k]]++] = seg[k];
+  }
+  FILE* fo = fopen(path, "w");
+  if (!fo)
+    return BS_ERR_INVALID;
+  static const char* const NAMES[4] = {"flat", "ridge", "valley", "step"};
+  const int64_t o[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
+  fprintf(fo, "# roof edges: %lld edges, %lld segments\n", (long long)ne, (long long)seg.size());
+  long long nv = 0;
+  for (int64_t e = 0; e < ne; e++) {
+    fprintf(fo, "g edge_%lld_%s\n", (long long)e, NAMES[kind[e]]);
+    for (int64_t k = first[(size_t)e]; k < first[(size_t)e + 1]; k++) {
+      const int32_t v = order[(size_t)k];
+      const int64_t a = v >> 1, b = a + ((v & 1) ? w : 1);
+      const int d = v & 1, x = (int)(a % w), y = (int)(a / w);
+      const int32_t* A = top + 4 * a;
+      const int32_t* Bt = top + 4 * b;
+      const int64_t zs = std::max(d ? A[2] : A[1], Bt[0]), ze = std::max(A[3], d ? Bt[1] : Bt[2]);
+      const int64_t xs = d ? x : x + 1, ys = d ? y + 1 : y;
+      fprintf(fo, "v %lld %lld %lld\n", (long long)(xs * bin + o[0]), (long long)(ys * bin + o[1]), (long long)(zs + o[2]));
+      fprintf(fo, "v %lld %lld %lld\n", (long long)((int64_t)(x + 1) * bin + o[0]), (long long)((int64_t)(y + 1) * bin + o[1]),
+              (long long)(ze + o[2]));
+      fprintf(fo, "l %lld %lld\n", nv + 1, nv + 2);
+      nv += 2;
+    }
+  }
+  const bool ok = !ferror(fo);
+  return (fclose(fo) == 0 && ok) ? BS_OK : BS_ERR_INVALID;
+}

@@ -895,6 +895,113 @@ int bs_solids_write_obj(const int32_t* vertex, int64_t n_vertices, const int32_t
                         const int32_t* face_building, int64_t n_faces, int32_t n_buildings, const int32_t* origin,
                         const char* path);
 
+/* ---- roof facets: the roof faces of every building and the edges between them (the roof topology graph) ----
+ *
+ * Inputs: map[height][width] (negative: outside, else a building in 0 .. n_buildings - 1), roof[height][width] of bs_roofs
+ * (<= 0: no roof plane, else 1 .. n_planes) and top[height][width][4] = {t00, t10, t01, t11} as bs_solids_count_dev writes
+ * it (tij at lattice corner (x + i, y + j)); top is read only where map >= 0.  The plane of a building pixel is
+ * P = roof > 0 ? roof : 0; plane 0 is "unroofed".
+ *
+ * 1. Facets.  A facet is a 4-connected component of building pixels with equal (map, P).  Its start pixel is its first
+ *    pixel in raster order.  Facets are numbered from 0 in ASCENDING order of start pixel (the buildings of
+ *    bs_building_map are numbered in DESCENDING order of theirs: the contour order).  facet[y][x] is the facet of the
+ *    pixel, -1 where map < 0.  Two pixels of equal (map, P) that touch only diagonally are different facets; adjacent
+ *    pixels of different buildings are never joined, even under the same plane.
+ * 2. Pixel edges.  For pixel A = (x, y) with map >= 0 look at B = (x + 1, y) (direction 0) and B = (x, y + 1)
+ *    (direction 1).  The edge is a BORDER edge iff B is inside the image, map[B] == map[A] and facet[B] != facet[A]; it is
+ *    numbered 2 * (y * width + x) + direction.  Any of the four sides of a pixel whose other side is outside the image,
+ *    has map < 0 or belongs to another building is an OUTER edge of the pixel's facet.
+ * 3. Heights of a border edge, all in int64.  The shared corners are s and e:
+ *      direction 0: s = (x + 1, y), e = (x + 1, y + 1); a_s = A.t10, a_e = A.t11, b_s = B.t00, b_e = B.t01;
+ *                   s_A = (A.t10 + A.t11) - (A.t00 + A.t01), s_B the same expression on B;
+ *      direction 1: s = (x, y + 1), e = (x + 1, y + 1); a_s = A.t01, a_e = A.t11, b_s = B.t00, b_e = B.t10;
+ *                   s_A = (A.t01 + A.t11) - (A.t00 + A.t10), s_B the same expression on B.
+ *    bend = s_A - s_B: positive where the surface falls away across the edge (convex: a ridge), negative in a valley; it
+ *    does not depend on which facet has the lower id.
+ * 4. Edges.  An edge is an unordered pair of facets with at least one border edge between them; edges are listed in
+ *    ascending (facet_lo, facet_hi).  Per edge: facet[2] = {lo, hi}, building, length (its border edges), n_dir0 (those of
+ *    direction 0), n_step (those with (a_s, a_e) != (b_s, b_e): exactly the pixel edges where the solids put an inner
+ *    wall), step_abs_sum = sum of |a_s - b_s| + |a_e - b_e|, step_abs_max = the largest single |a - b|, rise_sum = sum of
+ *    (h_s - l_s) + (h_e - l_e) with h the side of facet_hi and l the side of facet_lo (signed), bend_sum = sum of bend,
+ *    z_min / z_max over all a_s, a_e, b_s, b_e, and bbox[4] = {X0, Y0, X1, Y1}: the inclusive box of the lattice corners s
+ *    and e of its border edges, in lattice units.
+ * 5. Per facet: building, plane, start_xy[2], pixels, bbox[4] (inclusive pixel box {x0, y0, x1, y1}), inner_edges (border
+ *    edges it takes part in), outer_edges, top_min / top_max over the four tops of its pixels, top_sum (all four tops of
+ *    every pixel).
+ * 6. Totals: n_facets, n_edges, n_pixels, n_border (= the sum of length).
+ * Everything is an exact integer and independent of the order of summation. */
+/* (no typedef: the host-memory entry point below has the struct's name, so the type is always `struct bs_roof_facets`) */
+struct bs_roof_facets {
+  int32_t width, height;
+  int64_t n_facets, n_edges, n_pixels, n_border; /* totals */
+  /* per facet; host memory owned by the library */
+  int32_t* facet_building;    /* [n_facets] */
+  int32_t* facet_plane;       /* [n_facets] */
+  int32_t* facet_start_xy;    /* [n_facets][2] */
+  int64_t* facet_pixels;      /* [n_facets] */
+  int32_t* facet_bbox;        /* [n_facets][4] */
+  int64_t* facet_inner_edges; /* [n_facets] */
+  int64_t* facet_outer_edges; /* [n_facets] */
+  int32_t* facet_top_min;     /* [n_facets] */
+  int32_t* facet_top_max;     /* [n_facets] */
+  int64_t* facet_top_sum;     /* [n_facets] */
+  /* per edge; host memory owned by the library */
+  int32_t* edge_facet;        /* [n_edges][2] */
+  int32_t* edge_building;     /* [n_edges] */
+  int64_t* edge_length;       /* [n_edges] */
+  int64_t* edge_n_dir0;       /* [n_edges] */
+  int64_t* edge_n_step;       /* [n_edges] */
+  int64_t* edge_step_abs_sum; /* [n_edges] */
+  int64_t* edge_step_abs_max; /* [n_edges] */
+  int64_t* edge_rise_sum;     /* [n_edges] */
+  int64_t* edge_bend_sum;     /* [n_edges] */
+  int32_t* edge_z_min;        /* [n_edges] */
+  int32_t* edge_z_max;        /* [n_edges] */
+  int32_t* edge_bbox;         /* [n_edges][4] */
+  /* device time (HIP events on the context's stream) */
+  double ms_label;   /* tiles, seams, flatten */
+  double ms_number;  /* roots scanned, the facet image */
+  double ms_figures; /* the per-facet figures and the border flags */
+  double ms_edges;   /* keys, sort, run heads, the per-edge figures */
+};
+
+/* d_map, d_roof, d_top ([height][width][4] int32) and d_facet ([height][width] int32, written) are device pointers; out's
+ * arrays are host memory owned by the library (bs_roof_facets_free, which accepts a zeroed struct).  An image without a
+ * building pixel is valid: 0 facets, 0 edges, facet -1 everywhere.
+ * BS_ERR_INVALID: null pointer, width or height < 1, width * height >= 2^30 (the number of a pixel edge fits 31 bits),
+ * n_buildings or n_planes < 0, or d_top not 16-byte aligned (every device allocation is).  BS_ERR_RANGE: a map value >= n_buildings, a roof value > n_planes, or roof > 0 where
+ * map < 0 (the checks of bs_solids_count_dev).  On any error d_facet and out are left untouched, and the context stays
+ * usable.  Synchronises. */
+int bs_roof_facets_dev(bs_ctx* ctx, const int32_t* d_map, const int32_t* d_roof, const int32_t* d_top, int32_t width,
+                       int32_t height, int32_t n_buildings, int32_t n_planes, int32_t* d_facet, struct bs_roof_facets* out);
+/* Host-memory twin: map, roof, top and facet are host pointers. */
+int bs_roof_facets(bs_ctx* ctx, const int32_t* map, const int32_t* roof, const int32_t* top, int32_t width, int32_t height,
+                   int32_t n_buildings, int32_t n_planes, int32_t* facet, struct bs_roof_facets* out);
+void bs_roof_facets_free(struct bs_roof_facets* f);
+
+/* The kind of every edge into kind_out [n_edges].  Host only, no context.  In int64:
+ *   3 STEP    if step_abs_sum > 2 * step_tol * length,
+ *   1 RIDGE   else if bend_sum > bend_tol * length,
+ *   2 VALLEY  else if bend_sum < -bend_tol * length,
+ *   0 FLAT    otherwise.
+ * step_tol is the mean height difference in millimetres along the border; bend_tol is in the units of bend: twice the
+ * change of rise per pixel.  BS_ERR_INVALID: null pointer or a negative tolerance. */
+int bs_roof_edge_kinds(const struct bs_roof_facets* f, int32_t step_tol, int32_t bend_tol, uint8_t* kind_out);
+
+/* The border edges as an OBJ of line segments in millimetres.  Host only, no context: facet, map and top are host
+ * images, kind [n_edges] the kinds above, origin [3] the shift that was subtracted from the cloud (NULL: 0).  The border
+ * edges are found from facet and map and grouped by edge with a stable counting sort.  The file, every number a decimal
+ * integer, every line ended by '\n':
+ *   "# roof edges: <n_edges> edges, <n_border> segments"
+ *   for every edge e ascending: "g edge_<e>_<flat|ridge|valley|step>", then for each of its border edges in ascending
+ *   (y, x, direction) of pixel A three lines: "v X*bin+origin[0] Y*bin+origin[1] Z+origin[2]" for corner s and for corner
+ *   e, with Z = max(a, b) at that corner, and "l i j" with the vertices numbered from 1 in file order.
+ * BS_ERR_INVALID: null pointer (origin apart), bin < 1, width or height < 1, a kind above 3, a facet pair the struct
+ * does not list, or the file cannot be written. */
+int bs_roof_edges_write_obj(const int32_t* facet, const int32_t* map, const int32_t* top, int32_t width, int32_t height,
+                            int32_t bin, const struct bs_roof_facets* f, const uint8_t* kind, const int32_t* origin,
+                            const char* path);
+
 #ifdef __cplusplus
 }
 #endif
