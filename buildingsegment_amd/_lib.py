@@ -35,7 +35,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_roofs", "bs_roofs_free", "bs_roofs_write_obj", "bs_plane_fit_dev", "bs_plane_fit", "bs_plane_fits_free",
            "bs_plane_fit_apply", "bs_solids_count_dev", "bs_solids_emit_dev", "bs_solids", "bs_solids_free",
            "bs_solids_write_obj", "bs_roof_facets_dev", "bs_roof_facets", "bs_roof_facets_free", "bs_roof_edge_kinds",
-           "bs_roof_edges_write_obj"]
+           "bs_roof_edges_write_obj", "bs_facet_outlines_count_dev", "bs_facet_outlines_emit_dev", "bs_facet_outlines",
+           "bs_outlines_free", "bs_outlines_write_obj"]
 
 
 class Params(C.Structure):
@@ -163,6 +164,19 @@ class RoofFacets(C.Structure):
                   ("n_step", C.c_int64), ("step_abs_sum", C.c_int64), ("step_abs_max", C.c_int64), ("rise_sum", C.c_int64),
                   ("bend_sum", C.c_int64), ("z_min", C.c_int32), ("z_max", C.c_int32), ("bbox", C.c_int32))] +
                 [("ms_label", C.c_double), ("ms_number", C.c_double), ("ms_figures", C.c_double), ("ms_edges", C.c_double)])
+
+
+class Outlines(C.Structure):
+    """bs_outlines (include/bs_api.h): totals, per-ring and per-label arrays and (host-memory entry point) the vertices,
+    host memory owned by the library."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_labels", C.c_int32), ("has_z", C.c_int32),
+                ("n_half", C.c_int64), ("n_rings", C.c_int64), ("n_vertices", C.c_int64),
+                ("ring_label", C.POINTER(C.c_int32)), ("ring_start", C.POINTER(C.c_int32)),
+                ("ring_length", C.POINTER(C.c_int64)), ("ring_vertices", C.POINTER(C.c_int64)),
+                ("ring_area2", C.POINTER(C.c_int64)), ("ring_bbox", C.POINTER(C.c_int32)),
+                ("ring_offset", C.POINTER(C.c_int64)), ("label_ring_offset", C.POINTER(C.c_int64)),
+                ("xy", C.POINTER(C.c_int32)), ("z", C.POINTER(C.c_int32)), ("ms_halfedges", C.c_double),
+                ("ms_leaders", C.c_double), ("ms_rank", C.c_double), ("ms_rings", C.c_double), ("ms_emit", C.c_double)]
 
 
 class BsError(RuntimeError):
@@ -301,5 +315,12 @@ def load():
     L.bs_roof_facets_free.restype = None
     L.bs_roof_edge_kinds.argtypes = [fcp, C.c_int32, C.c_int32, vp]
     L.bs_roof_edges_write_obj.argtypes = [ip, ip, ip, C.c_int32, C.c_int32, C.c_int32, fcp, vp, ip, C.c_char_p]
+    olp = C.POINTER(Outlines)
+    L.bs_facet_outlines_count_dev.argtypes = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, olp]
+    L.bs_facet_outlines.argtypes = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, olp]
+    L.bs_facet_outlines_emit_dev.argtypes = [vp, ip, ip]
+    L.bs_outlines_free.argtypes = [olp]
+    L.bs_outlines_free.restype = None
+    L.bs_outlines_write_obj.argtypes = [olp, C.c_int32, ip, C.c_char_p]
     _LIB = L
     return L

@@ -703,6 +703,46 @@ class Context:
             raise ValueError("roof_structure: the roof image is on the device: use roof_facets_dev")
         return self.roof_facets(bmap, roofs.roof, solids.top, n_buildings=solids.n_buildings, n_planes=len(roofs.z_min))
 
+    # ---- facet outlines: polygon rings with holes per label (bs_facet_outlines, include/bs_api.h) ------------------------
+    def facet_outlines(self, label, top=None, n_labels=None):
+        """Every label of a label image ([height][width], negative = outside) as polygon rings with holes; with top
+        ([height][width][4] as Solids.top) every vertex carries a Z.  n_labels defaults to label.max() + 1.  Returns
+        Outlines."""
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        if label.ndim != 2 or label.size == 0:
+            raise ValueError("facet_outlines: label must be [height][width]")
+        if top is not None:
+            top = np.ascontiguousarray(top, dtype=np.int32)
+            if top.shape != label.shape + (4,):
+                raise ValueError("facet_outlines: top must be [height][width][4]")
+        h, w = label.shape
+        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        out = _lib.Outlines()
+        self._check(self._L.bs_facet_outlines(self._h, label.ctypes.data, None if top is None else top.ctypes.data, w, h, nl,
+                                              C.byref(out)))
+        return _take_outlines(self._L, out, True)
+
+    def facet_outlines_dev(self, d_label, d_top, width, height, n_labels):
+        """Device-resident count (bs_facet_outlines_count_dev): d_label and d_top (0: no Z) are device pointers (ints).
+        Returns Outlines with xy and z None and the size n_vertices of the buffers facet_outlines_emit_dev fills."""
+        out = _lib.Outlines()
+        self._check(self._L.bs_facet_outlines_count_dev(self._h, d_label or None, d_top or None, width, height,
+                                                        int(n_labels), C.byref(out)))
+        return _take_outlines(self._L, out, False)
+
+    def facet_outlines_emit_dev(self, d_xy, d_z=0):
+        """The vertices of the last facet_outlines_dev on this context into device buffers (ints) of exactly its sizes:
+        d_xy [n_vertices][2], d_z [n_vertices] (0 iff the count had no top)."""
+        self._check(self._L.bs_facet_outlines_emit_dev(self._h, d_xy or None, d_z or None))
+
+    def roof_outlines(self, roof_facets, solids):
+        """facet_outlines() of the facet image of roof_facets() / roof_structure() with the tops of solids()."""
+        if roof_facets.facet is None:
+            raise ValueError("roof_outlines: the facet image is on the device: use facet_outlines_dev")
+        if solids.top is None:
+            raise ValueError("roof_outlines: the Solids carry no top image (solids(top=True))")
+        return self.facet_outlines(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets)
+
 
 @dataclass
 class PlaneVotes:
@@ -1207,6 +1247,98 @@ def write_roof_edges_obj(rf, bmap, top, path, bin, kinds=None, origin=None):
                                              str(path).encode())
     if rc != 0:
         raise BsError(rc, f"cannot write {path} (or a facet pair the RoofFacets do not list)")
+
+
+@dataclass
+class Outlines:
+    """bs_outlines: the totals, the per-ring arrays (ring_*), label_ring_offset and the vertices xy / z (None after
+    facet_outlines_dev; z None without top) as include/bs_api.h names them.  Rings are listed by ascending (label, start);
+    ring r has the vertices ring_offset[r] .. ring_offset[r + 1]."""
+    width: int
+    image_height: int
+    n_labels: int
+    n_half: int
+    n_rings: int
+    n_vertices: int
+    ring_label: np.ndarray
+    ring_start: np.ndarray
+    ring_length: np.ndarray
+    ring_vertices: np.ndarray
+    ring_area2: np.ndarray
+    ring_bbox: np.ndarray
+    ring_offset: np.ndarray
+    label_ring_offset: np.ndarray
+    has_z: bool = False
+    info: dict = field(default_factory=dict)
+    xy: np.ndarray | None = field(default=None, repr=False)
+    z: np.ndarray | None = field(default=None, repr=False)
+
+
+# (name, dtype, columns) of the per-ring arrays of bs_outlines
+_RING_ARRAYS = (("ring_label", np.int32, 1), ("ring_start", np.int32, 1), ("ring_length", np.int64, 1),
+                ("ring_vertices", np.int64, 1), ("ring_area2", np.int64, 1), ("ring_bbox", np.int32, 4))
+
+
+def _take_outlines(L, out, vertices) -> Outlines:
+    """Copy a bs_outlines into numpy arrays and release it."""
+    try:
+        nr, nv = out.n_rings, out.n_vertices
+        arrs = {}
+        for name, dt, cols in _RING_ARRAYS:
+            shape = (nr, cols) if cols > 1 else (nr,)
+            arrs[name] = np.ctypeslib.as_array(getattr(out, name), shape).copy() if nr else np.zeros(shape, dt)
+        arrs["ring_offset"] = np.ctypeslib.as_array(out.ring_offset, (nr + 1,)).copy()
+        arrs["label_ring_offset"] = np.ctypeslib.as_array(out.label_ring_offset, (out.n_labels + 1,)).copy()
+        xy = z = None
+        if vertices:
+            xy = np.ctypeslib.as_array(out.xy, (nv, 2)).copy() if nv else np.zeros((0, 2), np.int32)
+            if out.has_z:
+                z = np.ctypeslib.as_array(out.z, (nv,)).copy() if nv else np.zeros(0, np.int32)
+        info = {k: getattr(out, k) for k in ("ms_halfedges", "ms_leaders", "ms_rank", "ms_rings", "ms_emit")}
+        return Outlines(out.width, out.height, out.n_labels, out.n_half, nr, nv, has_z=bool(out.has_z), info=info, xy=xy, z=z,
+                        **arrs)
+    finally:
+        L.bs_outlines_free(C.byref(out))
+
+
+def _outlines_struct(o):
+    """a bs_outlines over the arrays of an Outlines (or anything with its names), and the arrays to keep alive"""
+    st, keep = _lib.Outlines(), []
+    st.n_labels, st.n_rings, st.n_vertices = int(o.n_labels), int(o.n_rings), int(o.n_vertices)
+    st.n_half = int(o.n_half)
+
+    def put(name, dt, n):
+        a = np.ascontiguousarray(getattr(o, name), dtype=dt).reshape(-1)
+        if len(a) != n:
+            raise ValueError(f"Outlines.{name} must hold {n} values")
+        keep.append(a if len(a) else np.zeros(1, dt))
+        setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
+
+    for name, dt, cols in _RING_ARRAYS:
+        put(name, dt, st.n_rings * cols)
+    put("ring_offset", np.int64, st.n_rings + 1)
+    put("label_ring_offset", np.int64, st.n_labels + 1)
+    put("xy", np.int32, 2 * st.n_vertices)
+    if o.z is not None:
+        put("z", np.int32, st.n_vertices)
+        st.has_z = 1
+    return st, keep
+
+
+def write_outlines_obj(outlines, path, bin, origin=None):
+    """The rings of an Outlines as an OBJ of closed polylines in millimetres through the library's writer
+    (bs_outlines_write_obj; the format is written down in include/bs_api.h), one group per ring.  origin: the shift that
+    was subtracted from the cloud."""
+    if outlines.xy is None:
+        raise ValueError("write_outlines_obj: the vertices are on the device")
+    st, keep = _outlines_struct(outlines)
+    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+    if org is not None and org.shape != (3,):
+        raise ValueError("origin must be [3]")
+    rc = _lib.load().bs_outlines_write_obj(C.byref(st), int(bin), org.ctypes.data if org is not None else None,
+                                           str(path).encode())
+    if rc != 0:
+        raise BsError(rc, f"cannot write {path} (or the ring arrays do not fit each other)")
 
 
 @dataclass

@@ -241,6 +241,8 @@ void bs_destroy(bs_ctx* c)
     b.release();
   for (auto& b : c->fc)
     b.release();
+  for (auto& b : c->ol)
+    b.release();
   for (auto& b : c->bt)
     b.release();
   c->tile_desc.release();

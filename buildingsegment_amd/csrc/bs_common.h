@@ -251,6 +251,13 @@ struct bs_ctx {
   int64_t sd_nv = 0, sd_nf = 0, sd_ni = 0;
   double sd_ms_emit[2] = {0, 0};  // vertex pass, face pass of the last emit
   bs::DevBuf fc[16];  // scratch of the roof facets and their edges (bs_facet.hip)
+  // facet outlines (bs_outline.hip): scratch, and what bs_facet_outlines_count_dev leaves for bs_facet_outlines_emit_dev
+  // (per half-edge: its number, its place in the vertex arrays or -1, its Z)
+  bs::DevBuf ol[27];
+  bool ol_valid = false, ol_has_z = false;
+  int32_t ol_w = 0;
+  int64_t ol_nhalf = 0, ol_nv = 0;
+  double ol_ms_emit = 0;  // the last emit
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew

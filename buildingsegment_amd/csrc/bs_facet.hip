@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "bs_common.h"
+#include "bs_segscan.h"
 #include "bs_uf.h"
 
 namespace bs {
@@ -80,15 +81,6 @@ __device__ inline void lds_union(int* p, int a, int b)
       return;
     a = old;  // a was hooked elsewhere in the meantime: unite that root with b
   }
-}
-
-// lane of the head of my run: the highest set bit of `heads` at or below my lane (bit 0 is always set)
-__device__ inline int head_lane(unsigned long long heads, int lane) { return 63 - __clzll((long long)(heads & (~0ull >> (63 - lane)))); }
-// last lane of my run: one below the next head above me
-__device__ inline int tail_lane(unsigned long long heads, int lane)
-{
-  const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
-  return above ? __ffsll((long long)above) - 2 : 63;
 }
 
 // ---- label ---------------------------------------------------------------------------------------------------------------
@@ -241,17 +233,6 @@ __global__ __launch_bounds__(256) void facet_fig_init_kernel(FacetFig f, int64_t
   f.top_min[k] = INT32_MAX;
   f.top_max[k] = INT32_MIN;
 }
-
-// segmented inclusive scans over the runs of a wave: lane l takes lane l - o while that lane is still in its run
-#define BS_SEG_SCAN(v, op)                           \
-  for (int o = 1; o < 64; o <<= 1) {                 \
-    const auto t_ = __shfl_up(v, o);                 \
-    if (lane - o >= hl)                              \
-      v = op(v, t_);                                 \
-  }
-#define BS_OP_ADD(a, b) ((a) + (b))
-#define BS_OP_MIN(a, b) ((a) < (b) ? (a) : (b))
-#define BS_OP_MAX(a, b) ((a) > (b) ? (a) : (b))
 
 // Sides, border flags and per-facet figures of every pixel.  flags: bit 0 = the edge to (x + 1, y) is a border edge,
 // bit 1 = the edge to (x, y + 1).

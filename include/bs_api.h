@@ -1002,6 +1002,105 @@ int bs_roof_edges_write_obj(const int32_t* facet, const int32_t* map, const int3
                             int32_t bin, const struct bs_roof_facets* f, const uint8_t* kind, const int32_t* origin,
                             const char* path);
 
+/* ---- facet outlines: every label of a label image as polygon rings with holes ----
+ *
+ * Input: label[height][width] of int32, negative = outside, else 0 .. n_labels - 1; in the pipeline the facet image of
+ * bs_roof_facets.  The definition holds for any label image; the identities marked (*) need every label to be one
+ * 4-connected component, which the facet image guarantees.  Optionally top[height][width][4] = {t00, t10, t01, t11} as
+ * bs_solids_count_dev writes it.
+ *
+ * Corners and directions.  Lattice corners are (X, Y) with 0 <= X <= width, 0 <= Y <= height.  delta[0] = (0, -1),
+ * delta[1] = (1, 0), delta[2] = (0, 1), delta[3] = (-1, 0).  in(r, p): r is inside the image and label[r] == label[p].
+ *
+ * Half-edges.  Pixel p = (x, y) with label >= 0 has four sides, walked counter-clockwise seen from above (the order of the
+ * solids' walls): side 0 (x, y) -> (x + 1, y), side 1 (x + 1, y) -> (x + 1, y + 1), side 2 (x + 1, y + 1) -> (x, y + 1),
+ * side 3 (x, y + 1) -> (x, y).  Side k is a half-edge iff !in(p + delta[k], p); its number is h = 4 * (y * width + x) + k.
+ * A half-edge has a pixel of its label on its left and none on its right.
+ *
+ * Successor.  For half-edge (p, k) let p' = p + delta[(k + 1) % 4] and q = p' + delta[k].
+ *   If !in(p', p):      succ = (p, (k + 1) % 4)   (a left turn, it stays on the pixel);
+ *   else if !in(q, p):  succ = (p', k)            (straight on);
+ *   else                succ = (q, (k + 3) % 4)   (a right turn).
+ * The first rule wins where two pixels of one label touch only diagonally, so a ring never crosses itself; it may visit
+ * such a corner twice.  succ is a bijection on the half-edges, and its cycles are the rings.
+ *
+ * Vertices.  A half-edge g is a vertex iff its predecessor has another side number; locally, with a = p + delta[(k + 3) % 4]
+ * and b = a + delta[k]: iff !in(a, p) || in(b, p).  The vertex is g's start corner.  With top its Z is the top of g's own
+ * pixel at that corner (all pixels of one facet agree on it); without top there is no Z.
+ *
+ * Rings.  The start of a ring is its lowest half-edge number h0 (not always a vertex: the ring of a hole two pixels wide
+ * starts in the middle of a straight run).  The vertex list of a ring holds its vertex half-edges in walk order from h0,
+ * beginning with the first vertex at or after h0.  Rings are listed by ascending (label, h0).  Per ring: ring_label,
+ * ring_start (h0), ring_length (its half-edges), ring_vertices, ring_area2 = the sum of Xs * Ye - Xe * Ys over its
+ * half-edges s -> e in int64 (twice the signed area: positive for an outer ring, negative for a hole), ring_bbox[4] =
+ * {X0, Y0, X1, Y1}, the inclusive box of its lattice corners, and ring_offset[n_rings + 1] into the vertex arrays.  Per
+ * label: label_ring_offset[n_labels + 1]; the rings of a label are contiguous.  Totals: n_half, n_rings, n_vertices.
+ * Vertex arrays: xy int32 [n_vertices][2] in lattice units, z int32 [n_vertices] only with top.
+ * Everything is an exact integer and independent of the order of summation.
+ *
+ * Identities.  The sum of ring_length is n_half.  The sum of ring_area2 over a label is twice its pixels.  Every ring has
+ * an even number of vertices, at least 4.  (*) The first ring of a label is its only ring with positive area.  (*) The
+ * ring_start of that ring is 4 * (the label's first pixel in raster order).  (*) With the facet image, the sum of
+ * ring_length over facet f is facet_inner_edges[f] + facet_outer_edges[f] of bs_roof_facets. */
+struct bs_outlines {
+  int32_t width, height;
+  int32_t n_labels;
+  int32_t has_z; /* the count had a top image */
+  int64_t n_half, n_rings, n_vertices; /* totals */
+  /* per ring; host memory owned by the library */
+  int32_t* ring_label;    /* [n_rings] */
+  int32_t* ring_start;    /* [n_rings] */
+  int64_t* ring_length;   /* [n_rings] */
+  int64_t* ring_vertices; /* [n_rings] */
+  int64_t* ring_area2;    /* [n_rings] */
+  int32_t* ring_bbox;     /* [n_rings][4] */
+  int64_t* ring_offset;   /* [n_rings + 1] */
+  /* per label */
+  int64_t* label_ring_offset; /* [n_labels + 1] */
+  /* the vertices, host memory owned by the library: filled by the host-memory entry point only (NULL after the count) */
+  int32_t* xy; /* [n_vertices][2] */
+  int32_t* z;  /* [n_vertices], NULL without top */
+  /* device time (HIP events on the context's stream) */
+  double ms_halfedges; /* side flags, their exclusive sum, numbers, successors, vertex flags */
+  double ms_leaders;   /* the doubling rounds */
+  double ms_rank;      /* the cut and the Wyllie rounds */
+  double ms_rings;     /* slots, figures, sort, offsets, the place of every vertex */
+  double ms_emit;      /* the emit (host-memory entry point only) */
+};
+
+/* Rings, figures and sizes.  d_label and d_top ([height][width][4] int32, may be NULL: no Z) are device pointers.  The
+ * half-edges and the place of every vertex stay in the context for the emit below; out's arrays are host memory owned by
+ * the library (bs_outlines_free, which accepts a zeroed struct).  An image without a labelled pixel is valid: 0 rings,
+ * every offset 0.
+ * BS_ERR_INVALID: null pointer, width or height < 1, width * height >= 2^29 (a half-edge number fits 31 bits; refused from
+ * the arguments, before anything is read), n_labels < 0, or d_top not 16-byte aligned.  BS_ERR_RANGE: a label >= n_labels.
+ * On any error out is left untouched, and the context stays usable.  Synchronises (three times: n_half, n_rings,
+ * n_vertices; once without a labelled pixel). */
+int bs_facet_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t width, int32_t height,
+                                int32_t n_labels, struct bs_outlines* out);
+/* The vertices of the last successful count on this context into device buffers of exactly its sizes: d_xy
+ * [n_vertices][2], d_z [n_vertices] (NULL iff the count had no top; with no vertex both may be NULL).  May be called more
+ * than once; the images of the count are not read again.  BS_ERR_INVALID: no successful count (the last one on this
+ * context failed, or there was none), d_xy NULL, or d_z given or missing against the count.  Synchronises. */
+int bs_facet_outlines_emit_dev(bs_ctx* ctx, int32_t* d_xy, int32_t* d_z);
+/* Host-memory twin: label and top (may be NULL) are host pointers; both steps, and the vertices come back in out's
+ * library-owned xy and z. */
+int bs_facet_outlines(bs_ctx* ctx, const int32_t* label, const int32_t* top, int32_t width, int32_t height,
+                      int32_t n_labels, struct bs_outlines* out);
+void bs_outlines_free(struct bs_outlines* o);
+
+/* The rings as an OBJ of closed polylines in millimetres.  Host only, no context: o with its xy (and z, or NULL) as the
+ * host-memory entry point fills them; origin [3] is the shift that was subtracted from the cloud (NULL: 0).  The file,
+ * every number a decimal integer, every line ended by '\n':
+ *   "# facet outlines: <n_labels> labels, <n_rings> rings, <n_vertices> vertices"
+ *   for every ring r in order: "g label_<l>_ring_<i>_<outer|hole>" with l its label, i = r - label_ring_offset[l] its
+ *   number within the label, outer iff ring_area2 > 0; then its vertices "v X*bin+origin[0] Y*bin+origin[1] Z+origin[2]"
+ *   (Z = 0 without z); then one closed polyline "l i1 ... in i1", the vertices numbered from 1 in file order.
+ * BS_ERR_INVALID: null pointer (origin and z apart), bin < 1, a negative count, ring_offset that does not run from 0 to
+ * n_vertices without decreasing, a ring_label outside [0, n_labels) or before its label's first ring, or the file cannot
+ * be written. */
+int bs_outlines_write_obj(const struct bs_outlines* o, int32_t bin, const int32_t* origin, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
