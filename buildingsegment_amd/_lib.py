@@ -36,7 +36,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_plane_fit_apply", "bs_solids_count_dev", "bs_solids_emit_dev", "bs_solids", "bs_solids_free",
            "bs_solids_write_obj", "bs_roof_facets_dev", "bs_roof_facets", "bs_roof_facets_free", "bs_roof_edge_kinds",
            "bs_roof_edges_write_obj", "bs_facet_outlines_count_dev", "bs_facet_outlines_emit_dev", "bs_facet_outlines",
-           "bs_outlines_free", "bs_outlines_write_obj"]
+           "bs_outlines_free", "bs_outlines_write_obj", "bs_simple_outlines_count_dev", "bs_simple_outlines_emit_dev",
+           "bs_simple_outlines", "bs_simple_outlines_free", "bs_simple_outlines_write_obj"]
 
 
 class Params(C.Structure):
@@ -177,6 +178,22 @@ class Outlines(C.Structure):
                 ("ring_offset", C.POINTER(C.c_int64)), ("label_ring_offset", C.POINTER(C.c_int64)),
                 ("xy", C.POINTER(C.c_int32)), ("z", C.POINTER(C.c_int32)), ("ms_halfedges", C.c_double),
                 ("ms_leaders", C.c_double), ("ms_rank", C.c_double), ("ms_rings", C.c_double), ("ms_emit", C.c_double)]
+
+
+class SimpleOutlines(C.Structure):
+    """bs_simple_outlines (include/bs_api.h): totals, per-ring arrays and (host-memory entry point) the kept vertices, host
+    memory owned by the library."""
+    _fields_ = ([("width", C.c_int32), ("height", C.c_int32), ("n_labels", C.c_int32), ("has_z", C.c_int32),
+                 ("tol_num", C.c_int32), ("tol_den", C.c_int32)] +
+                [(k, C.c_int64) for k in ("n_rings", "n_nodes", "n_junction_nodes", "n_arcs", "n_svertices", "rounds",
+                                          "max_arc_nodes")] +
+                [("ring_label", C.POINTER(C.c_int32)), ("ring_area2", C.POINTER(C.c_int64)),
+                 ("s_ring_vertices", C.POINTER(C.c_int64)), ("s_ring_area2", C.POINTER(C.c_int64)),
+                 ("s_ring_arcs", C.POINTER(C.c_int64)), ("s_ring_offset", C.POINTER(C.c_int64)),
+                 ("label_ring_offset", C.POINTER(C.c_int64)), ("sxy", C.POINTER(C.c_int32)), ("sz", C.POINTER(C.c_int32)),
+                 ("s_right", C.POINTER(C.c_int32)), ("s_flag", C.POINTER(C.c_uint8))] +
+                [(k, C.c_double) for k in ("ms_outlines", "ms_nodes", "ms_placing", "ms_arcs", "ms_rounds", "ms_rings",
+                                           "ms_emit")])
 
 
 class BsError(RuntimeError):
@@ -322,5 +339,13 @@ def load():
     L.bs_outlines_free.argtypes = [olp]
     L.bs_outlines_free.restype = None
     L.bs_outlines_write_obj.argtypes = [olp, C.c_int32, ip, C.c_char_p]
+    sop = C.POINTER(SimpleOutlines)
+    simple_args = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, sop, olp]
+    L.bs_simple_outlines_count_dev.argtypes = simple_args
+    L.bs_simple_outlines.argtypes = simple_args
+    L.bs_simple_outlines_emit_dev.argtypes = [vp, ip, ip, ip, vp]
+    L.bs_simple_outlines_free.argtypes = [sop]
+    L.bs_simple_outlines_free.restype = None
+    L.bs_simple_outlines_write_obj.argtypes = [sop, C.c_int32, ip, C.c_char_p]
     _LIB = L
     return L

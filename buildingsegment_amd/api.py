@@ -744,6 +744,51 @@ class Context:
         return self.facet_outlines(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets)
 
 
+    # ---- simplified outlines: shared arcs, exact Douglas-Peucker (bs_simple_outlines, include/bs_api.h) ----------------
+    def simplified_outlines(self, label, top=None, n_labels=None, num=0, den=1):
+        """The outlines of facet_outlines() cut into the arcs that two labels share, every arc simplified by an exact
+        Douglas-Peucker with the tolerance tol2 = num / den in lattice units squared (simplify_tolerance()).  Returns
+        (SimpleOutlines, the plain Outlines without vertices)."""
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        if label.ndim != 2 or label.size == 0:
+            raise ValueError("simplified_outlines: label must be [height][width]")
+        if top is not None:
+            top = np.ascontiguousarray(top, dtype=np.int32)
+            if top.shape != label.shape + (4,):
+                raise ValueError("simplified_outlines: top must be [height][width][4]")
+        h, w = label.shape
+        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        out, plain = _lib.SimpleOutlines(), _lib.Outlines()
+        self._check(self._L.bs_simple_outlines(self._h, label.ctypes.data, None if top is None else top.ctypes.data, w, h, nl,
+                                               int(num), int(den), C.byref(out), C.byref(plain)))
+        return _take_simple_outlines(self._L, out, True), _take_outlines(self._L, plain, False)
+
+    def simplified_outlines_dev(self, d_label, d_top, width, height, n_labels, num=0, den=1):
+        """Device-resident count (bs_simple_outlines_count_dev): d_label and d_top (0: no Z) are device pointers (ints).
+        Returns (SimpleOutlines with the vertex arrays None and the size n_svertices of the buffers
+        simplified_outlines_emit_dev fills, the plain Outlines without vertices)."""
+        out, plain = _lib.SimpleOutlines(), _lib.Outlines()
+        self._check(self._L.bs_simple_outlines_count_dev(self._h, d_label or None, d_top or None, width, height,
+                                                         int(n_labels), int(num), int(den), C.byref(out), C.byref(plain)))
+        return _take_simple_outlines(self._L, out, False), _take_outlines(self._L, plain, False)
+
+    def simplified_outlines_emit_dev(self, d_sxy, d_sz, d_right, d_flag):
+        """The kept vertices of the last simplified_outlines_dev on this context into device buffers (ints) of exactly
+        its sizes: d_sxy [n_svertices][2], d_sz [n_svertices] (0 iff the count had no top), d_right [n_svertices] int32,
+        d_flag [n_svertices] uint8."""
+        self._check(self._L.bs_simple_outlines_emit_dev(self._h, d_sxy or None, d_sz or None, d_right or None, d_flag or None))
+
+    def roof_polygons(self, roof_facets, solids, tolerance_mm=0, bin=None):
+        """simplified_outlines() of the facet image of roof_facets() / roof_structure() with the tops of solids(), at a
+        tolerance in millimetres (bin: the pixel edge, by default the Solids')."""
+        if roof_facets.facet is None:
+            raise ValueError("roof_polygons: the facet image is on the device: use simplified_outlines_dev")
+        if solids.top is None:
+            raise ValueError("roof_polygons: the Solids carry no top image (solids(top=True))")
+        num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
+        return self.simplified_outlines(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)
+
+
 @dataclass
 class PlaneVotes:
     """Entry p - 1 is plane p: the building that holds most of its points (-1: none), that building's count, the
@@ -1337,6 +1382,113 @@ def write_outlines_obj(outlines, path, bin, origin=None):
         raise ValueError("origin must be [3]")
     rc = _lib.load().bs_outlines_write_obj(C.byref(st), int(bin), org.ctypes.data if org is not None else None,
                                            str(path).encode())
+    if rc != 0:
+        raise BsError(rc, f"cannot write {path} (or the ring arrays do not fit each other)")
+
+
+@dataclass
+class SimpleOutlines:
+    """bs_simple_outlines: the totals, the per-ring arrays (s_ring_*, and ring_label / ring_area2 / label_ring_offset of the
+    plain outlines) and the kept vertices sxy / sz / s_right / s_flag (None after simplified_outlines_dev; sz None without
+    top) as include/bs_api.h names them.  Ring r has the vertices s_ring_offset[r] .. s_ring_offset[r + 1]."""
+    width: int
+    image_height: int
+    n_labels: int
+    tol_num: int
+    tol_den: int
+    n_rings: int
+    n_nodes: int
+    n_junction_nodes: int
+    n_arcs: int
+    n_svertices: int
+    rounds: int
+    max_arc_nodes: int
+    ring_label: np.ndarray
+    ring_area2: np.ndarray
+    s_ring_vertices: np.ndarray
+    s_ring_area2: np.ndarray
+    s_ring_arcs: np.ndarray
+    s_ring_offset: np.ndarray
+    label_ring_offset: np.ndarray
+    has_z: bool = False
+    info: dict = field(default_factory=dict)
+    sxy: np.ndarray | None = field(default=None, repr=False)
+    sz: np.ndarray | None = field(default=None, repr=False)
+    s_right: np.ndarray | None = field(default=None, repr=False)
+    s_flag: np.ndarray | None = field(default=None, repr=False)
+
+
+_SIMPLE_RING_ARRAYS = (("ring_label", np.int32), ("ring_area2", np.int64), ("s_ring_vertices", np.int64),
+                       ("s_ring_area2", np.int64), ("s_ring_arcs", np.int64))
+_SIMPLE_TOTALS = ("n_rings", "n_nodes", "n_junction_nodes", "n_arcs", "n_svertices", "rounds", "max_arc_nodes")
+
+
+def _take_simple_outlines(L, out, vertices) -> SimpleOutlines:
+    """Copy a bs_simple_outlines into numpy arrays and release it."""
+    try:
+        nr, nv = out.n_rings, out.n_svertices
+        arrs = {name: np.ctypeslib.as_array(getattr(out, name), (nr,)).copy() if nr else np.zeros(0, dt)
+                for name, dt in _SIMPLE_RING_ARRAYS}
+        arrs["s_ring_offset"] = np.ctypeslib.as_array(out.s_ring_offset, (nr + 1,)).copy()
+        arrs["label_ring_offset"] = np.ctypeslib.as_array(out.label_ring_offset, (out.n_labels + 1,)).copy()
+        v = dict(sxy=None, sz=None, s_right=None, s_flag=None)
+        if vertices:
+            v["sxy"] = np.ctypeslib.as_array(out.sxy, (nv, 2)).copy() if nv else np.zeros((0, 2), np.int32)
+            v["s_right"] = np.ctypeslib.as_array(out.s_right, (nv,)).copy() if nv else np.zeros(0, np.int32)
+            v["s_flag"] = np.ctypeslib.as_array(out.s_flag, (nv,)).copy() if nv else np.zeros(0, np.uint8)
+            if out.has_z:
+                v["sz"] = np.ctypeslib.as_array(out.sz, (nv,)).copy() if nv else np.zeros(0, np.int32)
+        info = {k: getattr(out, k) for k in ("ms_outlines", "ms_nodes", "ms_placing", "ms_arcs", "ms_rounds", "ms_rings",
+                                             "ms_emit")}
+        return SimpleOutlines(out.width, out.height, out.n_labels, out.tol_num, out.tol_den,
+                              *[getattr(out, k) for k in _SIMPLE_TOTALS], has_z=bool(out.has_z), info=info, **arrs, **v)
+    finally:
+        L.bs_simple_outlines_free(C.byref(out))
+
+
+def simplify_tolerance(tolerance_mm, bin):
+    """The tolerance of the simplified outlines for a distance in millimetres on a raster of `bin` millimetres per pixel:
+    tol2 = (tolerance_mm / bin)^2 as the reduced fraction (num, den) = (tolerance_mm^2, bin^2) / their gcd."""
+    import math
+    t, b = int(tolerance_mm), int(bin)
+    if t != tolerance_mm or b != bin or t < 0 or b < 1:
+        raise ValueError("simplify_tolerance: tolerance_mm must be a whole number >= 0 and bin a whole number >= 1")
+    g = math.gcd(t * t, b * b)
+    num, den = t * t // g, b * b // g
+    if num >= 1 << 31 or den >= 1 << 31:
+        raise ValueError("simplify_tolerance: the reduced fraction does not fit 31 bits")
+    return num, den
+
+
+def write_simple_outlines_obj(simple, path, bin, origin=None):
+    """The rings of a SimpleOutlines as an OBJ of closed polylines in millimetres through the library's writer
+    (bs_simple_outlines_write_obj; the format is written down in include/bs_api.h), one group per ring."""
+    if simple.sxy is None:
+        raise ValueError("write_simple_outlines_obj: the vertices are on the device")
+    st, keep = _lib.SimpleOutlines(), []
+    st.n_labels, st.n_rings, st.n_svertices = int(simple.n_labels), int(simple.n_rings), int(simple.n_svertices)
+    st.tol_num, st.tol_den = int(simple.tol_num), int(simple.tol_den)
+
+    def put(name, dt, n):
+        a = np.ascontiguousarray(getattr(simple, name), dtype=dt).reshape(-1)
+        if len(a) != n:
+            raise ValueError(f"SimpleOutlines.{name} must hold {n} values")
+        keep.append(a if len(a) else np.zeros(1, dt))
+        setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
+
+    put("ring_label", np.int32, st.n_rings)
+    put("ring_area2", np.int64, st.n_rings)
+    put("s_ring_offset", np.int64, st.n_rings + 1)
+    put("label_ring_offset", np.int64, st.n_labels + 1)
+    put("sxy", np.int32, 2 * st.n_svertices)
+    if simple.sz is not None:
+        put("sz", np.int32, st.n_svertices)
+        st.has_z = 1
+    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+    if org is not None and org.shape != (3,):
+        raise ValueError("origin must be [3]")
+    rc = _lib.load().bs_simple_outlines_write_obj(C.byref(st), int(bin), org.ctypes.data if org is not None else None,
+                                                  str(path).encode())
     if rc != 0:
         raise BsError(rc, f"cannot write {path} (or the ring arrays do not fit each other)")
 

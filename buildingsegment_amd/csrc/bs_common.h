@@ -255,9 +255,16 @@ struct bs_ctx {
   // (per half-edge: its number, its place in the vertex arrays or -1, its Z)
   bs::DevBuf ol[27];
   bool ol_valid = false, ol_has_z = false;
-  int32_t ol_w = 0;
+  int32_t ol_w = 0, ol_nr = 0;      // (ol_nr, ol_leader: the ring count and the leader of every half-edge, for bs_simplify.hip)
+  const int32_t* ol_leader = nullptr;
   int64_t ol_nhalf = 0, ol_nv = 0;
   double ol_ms_emit = 0;  // the last emit
+  // simplified outlines (bs_simplify.hip): scratch, and what bs_simple_outlines_count_dev leaves for
+  // bs_simple_outlines_emit_dev (the finished vertex arrays)
+  bs::DevBuf sp[40];
+  bool sp_valid = false, sp_has_z = false;
+  int64_t sp_nsv = 0;
+  double sp_ms_emit = 0;  // the last emit
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew

@@ -23,21 +23,11 @@
 #include <cstring>
 
 #include "bs_common.h"
+#include "bs_outline.h"
 #include "bs_segscan.h"
 
 namespace bs {
 namespace {
-
-constexpr int GRID_CAP = 4096;  // workgroups of the grid-stride pass over the image
-constexpr int32_t END = -1;
-// scratch of bs_ctx::ol
-enum { OL_FLAGS, OL_BASE, OL_TMP, OL_MISC, OL_HNUM, OL_SUCC, OL_VERT, OL_MN0, OL_MN1, OL_NX0, OL_NX1, OL_VAL0, OL_VAL1, OL_ZV,
-       OL_DEST, OL_SLOT, OL_KEYS, OL_KEYS2, OL_VALS, OL_VALS2, OL_RSLOT, OL_RING, OL_LRO, OL_IN_LABEL, OL_IN_TOP, OL_OUT_XY,
-       OL_OUT_Z, OL_COUNT };
-static_assert(OL_COUNT <= (int)(sizeof(bs_ctx::ol) / sizeof(DevBuf)), "bs_ctx::ol is too short");
-
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
-inline int grid_of(int64_t n) { return (int)std::min<int64_t>(nblk(n, 256), GRID_CAP); }
 
 // ---- half-edges ----------------------------------------------------------------------------------------------------------
 // flags[pixel]: bit k = side k is a half-edge (k = 0 north, 1 east, 2 south, 3 west: the neighbour p + delta[k] is outside
@@ -166,42 +156,6 @@ __global__ __launch_bounds__(256) void outline_min_kernel(const int32_t* __restr
   nxt2[i] = nxt[j];
 }
 
-// ---- rank ----------------------------------------------------------------------------------------------------------------
-// the cycle becomes a list that starts at its leader: the half-edge in front of the leader is the tail
-__global__ __launch_bounds__(256) void outline_cut_kernel(const int32_t* __restrict__ succ, const int32_t* __restrict__ leader,
-                                                          const uint8_t* __restrict__ vert, int32_t n, int32_t* __restrict__ nxt,
-                                                          int32_t* __restrict__ val)
-{
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= n)
-    return;
-  const int32_t s = succ[i];
-  nxt[i] = s == leader[i] ? END : s;
-  val[i] = vert[i];
-}
-
-// one Wyllie round: val = the vertex half-edges in [i, nxt)
-__global__ __launch_bounds__(256) void outline_jump_kernel(const int32_t* __restrict__ nxt, const int32_t* __restrict__ val,
-                                                           int32_t n, int32_t* __restrict__ nxt2, int32_t* __restrict__ val2,
-                                                           int* __restrict__ err)
-{
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= n)
-    return;
-  const int32_t j = nxt[i];
-  if (j == END) {
-    nxt2[i] = END;
-    val2[i] = val[i];
-  } else if ((uint32_t)j >= (uint32_t)n) {
-    atomicOr(err, 8);
-    nxt2[i] = END;
-    val2[i] = val[i];
-  } else {
-    nxt2[i] = nxt[j];
-    val2[i] = val[i] + val[j];
-  }
-}
-
 // ---- rings ---------------------------------------------------------------------------------------------------------------
 struct LeadFlag {  // a half-edge that is the lowest of its ring
   const int32_t* leader;
@@ -226,32 +180,6 @@ SlotFig slot_fig_at(void* p, size_t n)
   f.vertices = f.bbox + 4 * n;
   f.start = f.vertices + n;
   return f;
-}
-
-struct RingOut {  // per ring in the listed order, device
-  unsigned long long* length;
-  unsigned long long* area2;
-  int32_t* bbox;
-  int32_t* label;
-  int32_t* start;
-  int32_t* vertices;
-  int32_t* offset;   // [n_rings + 1]
-  int32_t* of_slot;  // [n_rings]: the ring of a slot
-};
-constexpr size_t RING_OUT_BYTES = 2 * 8 + 9 * 4;  // (+ 4 for the last offset)
-
-RingOut ring_out_at(void* p, size_t n)
-{
-  RingOut r;
-  r.length = (unsigned long long*)p;
-  r.area2 = r.length + n;
-  r.bbox = (int32_t*)(r.area2 + n);
-  r.label = r.bbox + 4 * n;
-  r.start = r.label + n;
-  r.vertices = r.start + n;
-  r.of_slot = r.vertices + n;
-  r.offset = r.of_slot + n;
-  return r;
 }
 
 __global__ __launch_bounds__(256) void outline_slot_init_kernel(SlotFig F, int32_t nr)
@@ -424,28 +352,6 @@ __global__ __launch_bounds__(256) void outline_emit_kernel(const int32_t* __rest
     z[d] = zv[i];
 }
 
-struct Events {
-  hipEvent_t e[10] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  double ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.0;
-  }
-};
-
-template <class T>
-bool alloc(T** p, size_t n)
-{
-  *p = (T*)calloc(std::max<size_t>(n, 1), sizeof(T));
-  return *p != nullptr;
-}
-
 struct Guard {  // frees a half-built result unless it is handed over
   struct bs_outlines* s;
   bool keep = false;
@@ -456,27 +362,8 @@ struct Guard {  // frees a half-built result unless it is handed over
   }
 };
 
-// (a half-edge is numbered 4 * pixel + side in 31 bits)
-bool bad_image(int32_t w, int32_t h) { return w < 1 || h < 1 || (int64_t)w * h >= (1ll << 29); }
-
 const char* const OUTLINES_INVALID = "facet outlines: null pointer, width or height < 1, width * height >= 2^29, n_labels < 0, "
                                      "or d_top not 16-byte aligned";
-
-int bits_of(int64_t n)  // bits that hold 0 .. n - 1 (at least 1)
-{
-  int b = 1;
-  while (b < 32 && (1ll << b) < n)
-    b++;
-  return b;
-}
-
-int rounds_of(int64_t n)  // the smallest R with 2^R >= n
-{
-  int r = 0;
-  while ((1ll << r) < n)
-    r++;
-  return r;
-}
 
 int internal(bs_ctx* ctx, int err)
 {
@@ -708,6 +595,8 @@ extern "C" int bs_facet_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   ctx->ol_nhalf = n_half;
   ctx->ol_nv = res.n_vertices;
   ctx->ol_w = w;
+  ctx->ol_nr = nr;
+  ctx->ol_leader = leader;
   ctx->ol_has_z = d_top != nullptr;
   ctx->ol_valid = true;
   *out = res;

@@ -1,6 +1,6 @@
 // bs_segscan.h -- reductions over the runs of equal key inside one wave of 64 lanes: the run heads come from one ballot,
 // the values from segmented scans with __shfl_up.  Used where a per-key figure is reduced before ONE set of global
-// atomics per run (bs_facet.hip, bs_outline.hip).
+// atomics per run (bs_facet.hip, bs_outline.hip, bs_simplify.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

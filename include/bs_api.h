@@ -1101,6 +1101,118 @@ void bs_outlines_free(struct bs_outlines* o);
  * be written. */
 int bs_outlines_write_obj(const struct bs_outlines* o, int32_t bin, const int32_t* origin, const char* path);
 
+/* ---- simplified outlines: the facet outlines cut into shared arcs, every arc simplified by an exact Douglas-Peucker ----
+ *
+ * Everything builds on "facet outlines" above: the label image, half-edges 4 * pixel + side, the successor rule, rings, h0
+ * and the ring order (label, h0) are the same, and so are the ring count and label_ring_offset.  "Outside" below means
+ * outside the image or a negative label; both count as the single label -1.
+ *
+ * Junctions.  The block of a lattice corner (X, Y) is the four pixels (X-1, Y-1), (X, Y-1), (X-1, Y), (X, Y).  A corner is
+ * a junction iff its block holds three or more distinct labels, or is the saddle a b / b a with a != b.  At every other
+ * corner that lies on a boundary exactly two labels meet along a simple curve, and the rings of both pass through it once,
+ * in opposite directions.  (A ring passes exactly one junction only at a saddle: its right label can change only at a
+ * junction and has to change back.)
+ *
+ * Nodes.  A half-edge is a node iff it is a vertex (the rule above) or its start corner is a junction; in the second case
+ * it is a junction node.  A junction can lie in the middle of a straight run (a a / b c seen from a).  A node's position is
+ * its start corner, its corner index Y * (width + 1) + X, its Z (with top) the top of its own pixel at that corner, its
+ * right label the label across the half-edge, -1 for outside.
+ *
+ * Arcs.  A ring with junction nodes is cut at each of them: an arc runs from one junction node to the next in walk order,
+ * both ends included.  A ring with exactly one junction node is one arc from that node round to itself.  A ring with no
+ * junction node is one arc that starts and ends at its node with the lowest corner index (such a ring visits no corner
+ * twice, so that node is unique).  The right label is constant along an arc.  An arc with right label B >= 0 is, corner for
+ * corner in reverse, an arc of B's rings with the ring's own label on its right; every choice below is symmetric under
+ * that reversal.
+ *
+ * Tolerance.  A rational tol2 = num / den in lattice units squared, 0 <= num < 2^31, 1 <= den < 2^31.  For a segment
+ * S -> E and a node P, c = cross(E - S, P - S) is twice the triangle's area, in int64; |c| <= 2 * width * height < 2^30.
+ * len2 = |E - S|^2.  P is farther than the tolerance iff c^2 * den > num * len2, evaluated exactly (the products reach 2^91:
+ * 128 bits on the device).
+ *
+ * Douglas-Peucker on an arc.  The end nodes are kept.  A split of a segment S -> E: among the nodes strictly between the
+ * ends take the one with the greatest c^2, ties to the lowest corner index; keep it and split both parts iff it is farther
+ * than the tolerance, otherwise drop all nodes in between.  If the end corner differs from the start corner the arc is
+ * split in this way, except that its FIRST split is made whatever the tolerance, provided its greatest c^2 is above 0.
+ * (Without this a ring with exactly two junction nodes -- two open arcs -- would become those two nodes beyond a tolerance
+ * of its width.  A rule per ring could not be symmetric under the reversal of a shared arc; this rule is per arc.  Its
+ * price is one vertex on every arc that is not straight, however small its deviation.)  If the end corner equals the start
+ * corner S (a ring without junctions or with one, or a lobe at a saddle): keep the node F with the greatest squared
+ * distance from S, ties to the lowest corner index; each of the two parts S..F and F..S makes its first split whatever the
+ * tolerance, provided its greatest c^2 is above 0; below that first split the tolerance decides as above.  So no ring
+ * collapses to a line: every ring keeps at least 3 vertices, and one pixel keeps its four corners.  With num = 0 exactly the nodes are kept, and s_ring_area2
+ * equals ring_area2.
+ *
+ * Result.  Per ring r of the plain outlines: s_ring_vertices, the kept nodes in walk order beginning with the first kept
+ * node at or after h0; s_ring_area2, the shoelace sum over them in int64; s_ring_arcs; s_ring_offset[n_rings + 1].  Per
+ * kept vertex: sxy[.][2]; sz (with top); s_right, the right label of the segment that starts there; s_flag, bit 0 junction
+ * node, bit 1 the arc start of a ring without junctions.  Totals: n_nodes, n_junction_nodes, n_arcs, n_svertices; rounds,
+ * the depth of the deepest split that kept a node (the device counts its synchronous rounds that kept something; the
+ * choice of F is no round); max_arc_nodes, the largest node count of an arc with both ends included (a whole ring counts
+ * its start twice).  ring_label, ring_area2 and label_ring_offset are copies of the plain outlines' for the writer.
+ *
+ * Promised: neighbouring facets share their simplified boundary exactly -- every segment with s_right = B >= 0 occurs
+ * exactly once more, reversed, in a ring of B with the first ring's label as its s_right.  Every ring keeps at least 3
+ * vertices.  The kept set at a larger tolerance is a subset of the kept set at a smaller one (where a segment splits does
+ * not depend on the tolerance, only whether it does).  NOT promised: that two different arcs
+ * never cross at a large tolerance; that is Douglas-Peucker's known limit, and a crossing check is a later piece of work. */
+struct bs_simple_outlines {
+  int32_t width, height;
+  int32_t n_labels;
+  int32_t has_z;            /* the count had a top image */
+  int32_t tol_num, tol_den; /* the tolerance of the call */
+  int64_t n_rings, n_nodes, n_junction_nodes, n_arcs, n_svertices, rounds, max_arc_nodes; /* totals */
+  /* per ring; host memory owned by the library */
+  int32_t* ring_label;      /* [n_rings], of the plain outlines */
+  int64_t* ring_area2;      /* [n_rings], of the plain outlines */
+  int64_t* s_ring_vertices; /* [n_rings] */
+  int64_t* s_ring_area2;    /* [n_rings] */
+  int64_t* s_ring_arcs;     /* [n_rings] */
+  int64_t* s_ring_offset;   /* [n_rings + 1] */
+  /* per label */
+  int64_t* label_ring_offset; /* [n_labels + 1], of the plain outlines */
+  /* the kept vertices, host memory owned by the library: filled by the host-memory entry point only (NULL after the count) */
+  int32_t* sxy;     /* [n_svertices][2] */
+  int32_t* sz;      /* [n_svertices], NULL without top */
+  int32_t* s_right; /* [n_svertices] */
+  uint8_t* s_flag;  /* [n_svertices] */
+  /* device time (HIP events on the context's stream) */
+  double ms_outlines; /* the plain count: the sum of its phases */
+  double ms_nodes;    /* junction test, node flag, right label, corner index, Z */
+  double ms_placing;  /* the cut and the Wyllie rounds with node counts, nodes per ring, their scan */
+  double ms_arcs;     /* ring figures, rotation, scatter, arc ids, segments, the closed pass */
+  double ms_rounds;   /* the rounds, the host's reads of the "kept something" words included */
+  double ms_rings;    /* kept scan, places, area2 */
+  double ms_emit;     /* the emit (host-memory entry point only) */
+};
+
+/* Counts, figures and sizes.  Runs bs_facet_outlines_count_dev on the same images first (its context state is replaced:
+ * bs_facet_outlines_emit_dev afterwards emits the plain vertices of these images) and hands its result to *plain unless
+ * plain is NULL (release it with bs_outlines_free).  The kept vertices stay in the context for the emit below.
+ * BS_ERR_INVALID: as bs_facet_outlines_count_dev, or num outside [0, 2^31), or den outside [1, 2^31).  BS_ERR_RANGE: a label
+ * >= n_labels.  On any error out and plain are left untouched, and the context stays usable.  Synchronises: the plain
+ * count's three times, once for n_nodes, once every four rounds, once for the result. */
+int bs_simple_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t width, int32_t height,
+                                 int32_t n_labels, int64_t num, int64_t den, struct bs_simple_outlines* out,
+                                 struct bs_outlines* plain);
+/* The kept vertices of the last successful count on this context into device buffers of exactly its sizes: d_sxy
+ * [n_svertices][2], d_sz [n_svertices] (NULL iff the count had no top), d_right [n_svertices], d_flag [n_svertices] bytes
+ * (with no vertex all may be NULL).  May be called more than once.  BS_ERR_INVALID: no successful count, a missing buffer,
+ * or d_sz given or missing against the count.  Synchronises. */
+int bs_simple_outlines_emit_dev(bs_ctx* ctx, int32_t* d_sxy, int32_t* d_sz, int32_t* d_right, uint8_t* d_flag);
+/* Host-memory twin: label and top (may be NULL) are host pointers; both steps, and the kept vertices come back in out's
+ * library-owned sxy, sz, s_right and s_flag. */
+int bs_simple_outlines(bs_ctx* ctx, const int32_t* label, const int32_t* top, int32_t width, int32_t height, int32_t n_labels,
+                       int64_t num, int64_t den, struct bs_simple_outlines* out, struct bs_outlines* plain);
+void bs_simple_outlines_free(struct bs_simple_outlines* o);
+
+/* The simplified rings as an OBJ of closed polylines in millimetres, in the format of bs_outlines_write_obj.  Host only.
+ *   "# simplified outlines: <n_labels> labels, <n_rings> rings, <n_svertices> vertices, tol2 <num>/<den>"
+ *   for every ring r: "g label_<l>_ring_<i>_<outer|hole>" by the sign of the plain ring's area2, its kept vertices, and
+ *   one closed polyline.
+ * BS_ERR_INVALID: as bs_outlines_write_obj. */
+int bs_simple_outlines_write_obj(const struct bs_simple_outlines* o, int32_t bin, const int32_t* origin, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
