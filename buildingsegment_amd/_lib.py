@@ -37,7 +37,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_solids_write_obj", "bs_roof_facets_dev", "bs_roof_facets", "bs_roof_facets_free", "bs_roof_edge_kinds",
            "bs_roof_edges_write_obj", "bs_facet_outlines_count_dev", "bs_facet_outlines_emit_dev", "bs_facet_outlines",
            "bs_outlines_free", "bs_outlines_write_obj", "bs_simple_outlines_count_dev", "bs_simple_outlines_emit_dev",
-           "bs_simple_outlines", "bs_simple_outlines_free", "bs_simple_outlines_write_obj"]
+           "bs_simple_outlines", "bs_simple_outlines_free", "bs_simple_outlines_write_obj", "bs_clean_outlines_count_dev",
+           "bs_clean_outlines_emit_dev", "bs_clean_outlines", "bs_clean_outlines_free", "bs_clean_outlines_write_obj"]
 
 
 class Params(C.Structure):
@@ -196,6 +197,22 @@ class SimpleOutlines(C.Structure):
                                            "ms_emit")])
 
 
+class CleanOutlines(C.Structure):
+    """bs_clean_outlines (include/bs_api.h): the simplified outlines' totals and arrays over the repaired kept set, and the
+    figures of the conflict check and repair."""
+    _fields_ = ([("width", C.c_int32), ("height", C.c_int32), ("n_labels", C.c_int32), ("has_z", C.c_int32),
+                 ("tol_num", C.c_int32), ("tol_den", C.c_int32), ("max_rounds", C.c_int32), ("cell_log2", C.c_int32)] +
+                [(k, C.c_int64) for k in ("n_rings", "n_nodes", "n_junction_nodes", "n_arcs", "n_svertices", "rounds",
+                                          "max_arc_nodes", "n_svertices_before", "n_marked_first", "n_marked_left", "n_forced",
+                                          "repair_rounds", "n_entries", "max_cell_entries")] +
+                [("ring_label", C.POINTER(C.c_int32)), ("ring_area2", C.POINTER(C.c_int64)),
+                 ("s_ring_vertices", C.POINTER(C.c_int64)), ("s_ring_area2", C.POINTER(C.c_int64)),
+                 ("s_ring_arcs", C.POINTER(C.c_int64)), ("s_ring_offset", C.POINTER(C.c_int64)),
+                 ("label_ring_offset", C.POINTER(C.c_int64)), ("sxy", C.POINTER(C.c_int32)), ("sz", C.POINTER(C.c_int32)),
+                 ("s_right", C.POINTER(C.c_int32)), ("s_flag", C.POINTER(C.c_uint8))] +
+                [(k, C.c_double) for k in ("ms_simplify", "ms_detect", "ms_repair", "ms_rings", "ms_emit")])
+
+
 class BsError(RuntimeError):
     def __init__(self, status, detail=""):
         self.status = status
@@ -347,5 +364,13 @@ def load():
     L.bs_simple_outlines_free.argtypes = [sop]
     L.bs_simple_outlines_free.restype = None
     L.bs_simple_outlines_write_obj.argtypes = [sop, C.c_int32, ip, C.c_char_p]
+    cop = C.POINTER(CleanOutlines)
+    clean_args = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int32, cop, sop, olp]
+    L.bs_clean_outlines_count_dev.argtypes = clean_args
+    L.bs_clean_outlines.argtypes = clean_args
+    L.bs_clean_outlines_emit_dev.argtypes = [vp, ip, ip, ip, vp]
+    L.bs_clean_outlines_free.argtypes = [cop]
+    L.bs_clean_outlines_free.restype = None
+    L.bs_clean_outlines_write_obj.argtypes = [cop, C.c_int32, ip, C.c_char_p]
     _LIB = L
     return L

@@ -778,15 +778,56 @@ class Context:
         d_flag [n_svertices] uint8."""
         self._check(self._L.bs_simple_outlines_emit_dev(self._h, d_sxy or None, d_sz or None, d_right or None, d_flag or None))
 
-    def roof_polygons(self, roof_facets, solids, tolerance_mm=0, bin=None):
+    def roof_polygons(self, roof_facets, solids, tolerance_mm=0, bin=None, clean=False):
         """simplified_outlines() of the facet image of roof_facets() / roof_structure() with the tops of solids(), at a
-        tolerance in millimetres (bin: the pixel edge, by default the Solids')."""
+        tolerance in millimetres (bin: the pixel edge, by default the Solids').  clean=True: clean_outlines() instead --
+        polygons whose segments meet only in shared end points -- as (CleanOutlines, the plain Outlines)."""
         if roof_facets.facet is None:
             raise ValueError("roof_polygons: the facet image is on the device: use simplified_outlines_dev")
         if solids.top is None:
             raise ValueError("roof_polygons: the Solids carry no top image (solids(top=True))")
         num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
+        if clean:
+            c, _, plain = self.clean_outlines(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)
+            return c, plain
         return self.simplified_outlines(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)
+
+    # ---- clean outlines: conflicts between simplified segments found and repaired (bs_clean_outlines, include/bs_api.h) --
+    def clean_outlines(self, label, top=None, n_labels=None, num=0, den=1, max_rounds=-1, cell_log2=0):
+        """The simplified outlines with every conflict between kept segments (cross, touch, overlap) repaired by keeping
+        further nodes.  max_rounds < 0: until clean; 0: check only (s_flag bit 3 and n_marked_first report the conflicts);
+        > 0: a cap.  cell_log2: the broad-phase cell edge, 0 = the default.  Returns (CleanOutlines, the SimpleOutlines
+        without vertices, the plain Outlines without vertices)."""
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        if label.ndim != 2 or label.size == 0:
+            raise ValueError("clean_outlines: label must be [height][width]")
+        if top is not None:
+            top = np.ascontiguousarray(top, dtype=np.int32)
+            if top.shape != label.shape + (4,):
+                raise ValueError("clean_outlines: top must be [height][width][4]")
+        h, w = label.shape
+        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        out, simple, plain = _lib.CleanOutlines(), _lib.SimpleOutlines(), _lib.Outlines()
+        self._check(self._L.bs_clean_outlines(self._h, label.ctypes.data, None if top is None else top.ctypes.data, w, h, nl,
+                                              int(num), int(den), int(max_rounds), int(cell_log2), C.byref(out),
+                                              C.byref(simple), C.byref(plain)))
+        return (_take_clean_outlines(self._L, out, True), _take_simple_outlines(self._L, simple, False),
+                _take_outlines(self._L, plain, False))
+
+    def clean_outlines_dev(self, d_label, d_top, width, height, n_labels, num=0, den=1, max_rounds=-1, cell_log2=0):
+        """Device-resident count (bs_clean_outlines_count_dev): d_label and d_top (0: no Z) are device pointers (ints).
+        Returns (CleanOutlines with the vertex arrays None, SimpleOutlines, Outlines)."""
+        out, simple, plain = _lib.CleanOutlines(), _lib.SimpleOutlines(), _lib.Outlines()
+        self._check(self._L.bs_clean_outlines_count_dev(self._h, d_label or None, d_top or None, width, height, int(n_labels),
+                                                        int(num), int(den), int(max_rounds), int(cell_log2), C.byref(out),
+                                                        C.byref(simple), C.byref(plain)))
+        return (_take_clean_outlines(self._L, out, False), _take_simple_outlines(self._L, simple, False),
+                _take_outlines(self._L, plain, False))
+
+    def clean_outlines_emit_dev(self, d_sxy, d_sz, d_right, d_flag):
+        """The kept vertices of the last clean_outlines_dev on this context into device buffers (ints) of exactly its
+        sizes, as simplified_outlines_emit_dev."""
+        self._check(self._L.bs_clean_outlines_emit_dev(self._h, d_sxy or None, d_sz or None, d_right or None, d_flag or None))
 
 
 @dataclass
@@ -1444,6 +1485,81 @@ def _take_simple_outlines(L, out, vertices) -> SimpleOutlines:
                               *[getattr(out, k) for k in _SIMPLE_TOTALS], has_z=bool(out.has_z), info=info, **arrs, **v)
     finally:
         L.bs_simple_outlines_free(C.byref(out))
+
+
+@dataclass
+class CleanOutlines(SimpleOutlines):
+    """bs_clean_outlines: a SimpleOutlines over the repaired kept set (s_flag bit 2: kept by the repair, bit 3: still
+    marked) with the figures of the conflict check and repair as include/bs_api.h names them."""
+    max_rounds: int = -1
+    cell_log2: int = 0
+    n_svertices_before: int = 0
+    n_marked_first: int = 0
+    n_marked_left: int = 0
+    n_forced: int = 0
+    repair_rounds: int = 0
+    n_entries: int = 0
+    max_cell_entries: int = 0
+
+
+_CLEAN_TOTALS = ("max_rounds", "cell_log2", "n_svertices_before", "n_marked_first", "n_marked_left", "n_forced", "repair_rounds",
+                 "n_entries", "max_cell_entries")
+
+
+def _take_clean_outlines(L, out, vertices) -> CleanOutlines:
+    """Copy a bs_clean_outlines into numpy arrays and release it."""
+    try:
+        nr, nv = out.n_rings, out.n_svertices
+        arrs = {name: np.ctypeslib.as_array(getattr(out, name), (nr,)).copy() if nr else np.zeros(0, dt)
+                for name, dt in _SIMPLE_RING_ARRAYS}
+        arrs["s_ring_offset"] = np.ctypeslib.as_array(out.s_ring_offset, (nr + 1,)).copy()
+        arrs["label_ring_offset"] = np.ctypeslib.as_array(out.label_ring_offset, (out.n_labels + 1,)).copy()
+        v = dict(sxy=None, sz=None, s_right=None, s_flag=None)
+        if vertices:
+            v["sxy"] = np.ctypeslib.as_array(out.sxy, (nv, 2)).copy() if nv else np.zeros((0, 2), np.int32)
+            v["s_right"] = np.ctypeslib.as_array(out.s_right, (nv,)).copy() if nv else np.zeros(0, np.int32)
+            v["s_flag"] = np.ctypeslib.as_array(out.s_flag, (nv,)).copy() if nv else np.zeros(0, np.uint8)
+            if out.has_z:
+                v["sz"] = np.ctypeslib.as_array(out.sz, (nv,)).copy() if nv else np.zeros(0, np.int32)
+        info = {k: getattr(out, k) for k in ("ms_simplify", "ms_detect", "ms_repair", "ms_rings", "ms_emit")}
+        return CleanOutlines(out.width, out.height, out.n_labels, out.tol_num, out.tol_den,
+                             *[getattr(out, k) for k in _SIMPLE_TOTALS], has_z=bool(out.has_z), info=info, **arrs, **v,
+                             **{k: getattr(out, k) for k in _CLEAN_TOTALS})
+    finally:
+        L.bs_clean_outlines_free(C.byref(out))
+
+
+def write_clean_outlines_obj(clean, path, bin, origin=None):
+    """The rings of a CleanOutlines as an OBJ through the library's writer (bs_clean_outlines_write_obj)."""
+    if clean.sxy is None:
+        raise ValueError("write_clean_outlines_obj: the vertices are on the device")
+    st, keep = _lib.CleanOutlines(), []
+    st.n_labels, st.n_rings, st.n_svertices = int(clean.n_labels), int(clean.n_rings), int(clean.n_svertices)
+    st.tol_num, st.tol_den = int(clean.tol_num), int(clean.tol_den)
+    st.repair_rounds, st.n_forced = int(clean.repair_rounds), int(clean.n_forced)
+
+    def put(name, dt, n):
+        a = np.ascontiguousarray(getattr(clean, name), dtype=dt).reshape(-1)
+        if len(a) != n:
+            raise ValueError(f"CleanOutlines.{name} must hold {n} values")
+        keep.append(a if len(a) else np.zeros(1, dt))
+        setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
+
+    put("ring_label", np.int32, st.n_rings)
+    put("ring_area2", np.int64, st.n_rings)
+    put("s_ring_offset", np.int64, st.n_rings + 1)
+    put("label_ring_offset", np.int64, st.n_labels + 1)
+    put("sxy", np.int32, 2 * st.n_svertices)
+    if clean.sz is not None:
+        put("sz", np.int32, st.n_svertices)
+        st.has_z = 1
+    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+    if org is not None and org.shape != (3,):
+        raise ValueError("origin must be [3]")
+    rc = _lib.load().bs_clean_outlines_write_obj(C.byref(st), int(bin), org.ctypes.data if org is not None else None,
+                                                 str(path).encode())
+    if rc != 0:
+        raise BsError(rc, f"cannot write {path} (or the ring arrays do not fit each other)")
 
 
 def simplify_tolerance(tolerance_mm, bin):

@@ -265,6 +265,24 @@ struct bs_ctx {
   bool sp_valid = false, sp_has_z = false;
   int64_t sp_nsv = 0;
   double sp_ms_emit = 0;  // the last emit
+  // what the last successful bs_simple_outlines_count_dev leaves for the clean outlines (bs_uncross.hip): the node arrays
+  // in the rotated order, the kept flags (seg[cur].x == -1), the round buffers and the ring figures, all inside sp
+  struct SimplifyState {
+    int32_t N = 0, nr = 0, cur = 0;
+    int2* seg[2] = {nullptr, nullptr};
+    unsigned long long* best[2] = {nullptr, nullptr};
+    unsigned long long* tie[2] = {nullptr, nullptr};
+    unsigned long long* c2 = nullptr;
+    uint8_t* forced = nullptr;
+    const int2* xy = nullptr;
+    const int32_t *cidx = nullptr, *z = nullptr, *right = nullptr, *ring = nullptr, *noff = nullptr, *rot = nullptr;
+    const uint8_t* flag = nullptr;
+  } sp_state;
+  // clean outlines (bs_uncross.hip): scratch, and what bs_clean_outlines_count_dev leaves for bs_clean_outlines_emit_dev
+  bs::DevBuf uc[32];
+  bool uc_valid = false, uc_has_z = false;
+  int64_t uc_nsv = 0;
+  double uc_ms_emit = 0;
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew
@@ -291,6 +309,11 @@ int fail(bs_ctx* ctx, int status, const char* what, hipError_t e = hipSuccess);
       return bs::fail((ctx), BS_ERR_HIP, #call, _e);          \
   } while (0)
 
+// simplify.hip: one Douglas-Peucker round in which every segment whose left end `forced` marks splits at its choice
+// whatever the tolerance (bs_uncross.hip activates only the nodes of marked segments, and marks all of those)
+void simplify_forced_round(hipStream_t st, int32_t N, const int2* seg, const int2* xy, const int32_t* cidx,
+                           unsigned long long* c2, unsigned long long* best, unsigned long long* tie, const uint8_t* forced,
+                           int2* seg2, unsigned long long* best2, unsigned long long* tie2, int* changed, int* err);
 // grid.hip
 int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t n, double radius,
                int k, int cell_hint, GridDev* out);

@@ -636,6 +636,15 @@ void launch_round(hipStream_t st, int32_t N, const int2* seg, const NodeArrays& 
 }
 
 }  // namespace
+
+void simplify_forced_round(hipStream_t st, int32_t N, const int2* seg, const int2* xy, const int32_t* cidx,
+                           unsigned long long* c2, unsigned long long* best, unsigned long long* tie, const uint8_t* forced,
+                           int2* seg2, unsigned long long* best2, unsigned long long* tie2, int* changed, int* err)
+{
+  const NodeArrays A{const_cast<int2*>(xy), const_cast<int32_t*>(cidx), nullptr, nullptr, nullptr, nullptr};
+  launch_round<false>(st, N, seg, A, c2, best, tie, forced, 0, 1, seg2, best2, tie2, nullptr, changed, err);
+}
+
 }  // namespace bs
 
 using namespace bs;
@@ -707,6 +716,7 @@ extern "C" int bs_simple_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label,
     return BS_OK;
   };
   if (pl.n_half == 0) {  // no labelled pixel: no ring, every offset 0
+    ctx->sp_state.N = ctx->sp_state.nr = 0;
     ctx->sp_nsv = 0;
     ctx->sp_has_z = has_z;
     ctx->sp_valid = true;
@@ -894,6 +904,16 @@ extern "C" int bs_simple_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label,
   res.ms_arcs = ev.ms(2, 3);
   res.ms_rounds = ev.ms(3, 4);
   res.ms_rings = ev.ms(4, 5);
+  bs_ctx::SimplifyState& S = ctx->sp_state;  // for bs_uncross.hip
+  S.N = N;
+  S.nr = nr;
+  S.cur = cur;
+  for (int j = 0; j < 2; j++)
+    S.seg[j] = seg[j], S.best[j] = best[j], S.tie[j] = tie[j];
+  S.c2 = c2;
+  S.forced = forced;
+  S.xy = A.xy, S.cidx = A.cidx, S.z = A.z, S.right = A.right, S.ring = A.ring, S.flag = A.flag;
+  S.noff = F.noff, S.rot = F.rot;
   ctx->sp_nsv = res.n_svertices;
   ctx->sp_has_z = has_z;
   ctx->sp_valid = true;

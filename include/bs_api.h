@@ -1155,7 +1155,7 @@ int bs_outlines_write_obj(const struct bs_outlines* o, int32_t bin, const int32_
  * exactly once more, reversed, in a ring of B with the first ring's label as its s_right.  Every ring keeps at least 3
  * vertices.  The kept set at a larger tolerance is a subset of the kept set at a smaller one (where a segment splits does
  * not depend on the tolerance, only whether it does).  NOT promised: that two different arcs
- * never cross at a large tolerance; that is Douglas-Peucker's known limit, and a crossing check is a later piece of work. */
+ * never cross at a large tolerance; that is Douglas-Peucker's known limit: "clean outlines" below check and repair it. */
 struct bs_simple_outlines {
   int32_t width, height;
   int32_t n_labels;
@@ -1212,6 +1212,89 @@ void bs_simple_outlines_free(struct bs_simple_outlines* o);
  *   one closed polyline.
  * BS_ERR_INVALID: as bs_outlines_write_obj. */
 int bs_simple_outlines_write_obj(const struct bs_simple_outlines* o, int32_t bin, const int32_t* origin, const char* path);
+
+/* ---- clean outlines: the simplified outlines with every conflict between kept segments found and repaired ----
+ *
+ * Everything builds on "simplified outlines" above: nodes, arcs, the split choice, the rings and their order.
+ *
+ * Segments.  A segment is every pair of consecutive kept nodes of a ring (the last and the first included).  It carries the
+ * ring's label on its left and s_right of its first node on its right.
+ * Twins.  Two segments are twins iff their end corners are equal in reverse and their (left, right) labels are swapped.
+ * Twins never conflict with each other.
+ * Conflict.  Two segments that are not twins conflict iff their closed segments have a common point that is not an end
+ * point of both: a proper crossing (cross), an end point of one in the open interior of the other (touch), or collinear
+ * segments with more than a point in common (overlap; also between two segments that share an end corner and run the same
+ * way).  All of it is evaluated with orientation tests in int64; the coordinates are lattice corners, so |cross| < 2^31.
+ * Marked.  A segment is marked iff it conflicts with at least one other segment.
+ * Repair round.  Every marked segment that has nodes strictly between its ends keeps its Douglas-Peucker choice -- the
+ * greatest c^2, ties to the lowest corner index -- whatever the tolerance; the two halves are not simplified further and
+ * keep no other node.  A marked segment without interior nodes stays as it is.  Rounds repeat until a round marks nothing.
+ * Symmetry.  A twin is the same geometric segment: it conflicts with the same segments, is marked in the same round and
+ * picks the same node, so neighbouring facets still share their boundary vertex for vertex.
+ * Termination.  Interior nodes of an arc are vertices of a staircase, so a segment with interior nodes always has a greatest
+ * c^2 > 0.  With every node kept (num = 0) no two segments conflict: junction nodes are arc ends and always kept, and runs
+ * between adjacent nodes meet only in nodes.  Hence in every round with a conflict at least one marked segment has an
+ * interior node, and the kept set grows.  Hence repair_rounds < n_nodes; more rounds than nodes is BS_ERR_INTERNAL.
+ *
+ * Result.  The per-ring and per-vertex arrays of the simplified outlines recomputed over the larger kept set.  s_flag gains
+ * bit 2, kept by the repair, and bit 3, the segment that starts here is still marked (possible only when max_rounds stopped
+ * the loop).  n_svertices_before: the vertex count of the plain simplification; n_marked_first: its marked segments, twins
+ * counted each; n_marked_left: 0 unless stopped by max_rounds; n_forced: vertices added; repair_rounds.  Of the broad
+ * phase (they depend on cell_log2, nothing else does): n_entries, the (cell, segment) entries of the first detection, and
+ * max_cell_entries, the most entries of one cell in any detection. */
+struct bs_clean_outlines {
+  int32_t width, height;
+  int32_t n_labels;
+  int32_t has_z;
+  int32_t tol_num, tol_den;
+  int32_t max_rounds, cell_log2; /* of the call; cell_log2 as used (the default resolved) */
+  int64_t n_rings, n_nodes, n_junction_nodes, n_arcs, n_svertices, rounds, max_arc_nodes; /* as bs_simple_outlines */
+  int64_t n_svertices_before, n_marked_first, n_marked_left, n_forced, repair_rounds, n_entries, max_cell_entries;
+  /* per ring, per label and per kept vertex: as bs_simple_outlines, host memory owned by the library */
+  int32_t* ring_label;
+  int64_t* ring_area2;
+  int64_t* s_ring_vertices;
+  int64_t* s_ring_area2;
+  int64_t* s_ring_arcs;
+  int64_t* s_ring_offset;
+  int64_t* label_ring_offset;
+  int32_t* sxy;
+  int32_t* sz;
+  int32_t* s_right;
+  uint8_t* s_flag;
+  /* device time (HIP events on the context's stream) */
+  double ms_simplify; /* the simplified count: the sum of its phases, the plain count included */
+  double ms_detect;   /* all detections: segments, cells, scan, fill, sort, pair tests, the host's reads included */
+  double ms_repair;   /* all repair rounds */
+  double ms_rings;    /* places, flags, area2 */
+  double ms_emit;     /* the emit (host-memory entry point only) */
+};
+
+#define BS_CLEAN_DEFAULT_CELL_LOG2 4 /* cells of 16 x 16 corners: the fastest on urban_50m ("Clean outlines") */
+
+/* Counts, figures and sizes.  Runs bs_simple_outlines_count_dev on the same images first (its context state and the plain
+ * count's are replaced) and hands its results to *simple and *plain unless they are NULL.  max_rounds < 0: repair until
+ * clean; 0: check only (the kept set equals the simplified outlines', bit 3 and n_marked_first report the conflicts);
+ * > 0: a cap.  cell_log2: the broad-phase cell edge as a power of two in lattice units, 0 = the library's default, 1..30
+ * valid, 30 puts everything into one cell; no result but n_entries and max_cell_entries depends on it.
+ * Errors as bs_simple_outlines_count_dev; also BS_ERR_INVALID for cell_log2 outside 0..30, or where a detection would list more
+ * than 2^31 - 1 (cell, segment) entries (take a larger cell_log2).  On any error the outputs are
+ * left untouched.  Synchronises: the simplified count's times, then twice per detection (the entry count; the marked
+ * count and the error word) -- one detection more than repair rounds -- and once for the result. */
+int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t width, int32_t height,
+                                int32_t n_labels, int64_t num, int64_t den, int32_t max_rounds, int32_t cell_log2,
+                                struct bs_clean_outlines* out, struct bs_simple_outlines* simple, struct bs_outlines* plain);
+/* The kept vertices of the last successful clean count on this context; buffers and errors as bs_simple_outlines_emit_dev. */
+int bs_clean_outlines_emit_dev(bs_ctx* ctx, int32_t* d_sxy, int32_t* d_sz, int32_t* d_right, uint8_t* d_flag);
+/* Host-memory twin: label and top (may be NULL) are host pointers; both steps. */
+int bs_clean_outlines(bs_ctx* ctx, const int32_t* label, const int32_t* top, int32_t width, int32_t height, int32_t n_labels,
+                      int64_t num, int64_t den, int32_t max_rounds, int32_t cell_log2, struct bs_clean_outlines* out,
+                      struct bs_simple_outlines* simple, struct bs_outlines* plain);
+void bs_clean_outlines_free(struct bs_clean_outlines* o);
+/* The clean rings as an OBJ in the format of bs_simple_outlines_write_obj, with the first line
+ *   "# clean outlines: <n_labels> labels, <n_rings> rings, <n_svertices> vertices, tol2 <num>/<den>, repair_rounds <r>,
+ *    n_forced <f>" (one line).  Host only. */
+int bs_clean_outlines_write_obj(const struct bs_clean_outlines* o, int32_t bin, const int32_t* origin, const char* path);
 
 #ifdef __cplusplus
 }
