@@ -38,7 +38,9 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_roof_edges_write_obj", "bs_facet_outlines_count_dev", "bs_facet_outlines_emit_dev", "bs_facet_outlines",
            "bs_outlines_free", "bs_outlines_write_obj", "bs_simple_outlines_count_dev", "bs_simple_outlines_emit_dev",
            "bs_simple_outlines", "bs_simple_outlines_free", "bs_simple_outlines_write_obj", "bs_clean_outlines_count_dev",
-           "bs_clean_outlines_emit_dev", "bs_clean_outlines", "bs_clean_outlines_free", "bs_clean_outlines_write_obj"]
+           "bs_clean_outlines_emit_dev", "bs_clean_outlines", "bs_clean_outlines_free", "bs_clean_outlines_write_obj",
+           "bs_outline_triangles_count_dev", "bs_outline_triangles_emit_dev", "bs_outline_triangles",
+           "bs_outline_triangles_free", "bs_outline_triangles_write_obj"]
 
 
 class Params(C.Structure):
@@ -213,6 +215,22 @@ class CleanOutlines(C.Structure):
                 [(k, C.c_double) for k in ("ms_simplify", "ms_detect", "ms_repair", "ms_rings", "ms_emit")])
 
 
+TRI_STATUS = {0: "BS_TRI_OK", 1: "BS_TRI_NO_BRIDGE", 2: "BS_TRI_STALLED", 3: "BS_TRI_EMPTY"}
+TRI_WAVE_CAP, TRI_LDS_CAP = 64, 1024  # BS_TRI_WAVE_CAP, BS_TRI_LDS_CAP of include/bs_api.h
+
+
+class OutlineTriangles(C.Structure):
+    """bs_outline_triangles (include/bs_api.h): totals, per-label and per-ring arrays and (host-memory entry point) the
+    triangles, host memory owned by the library."""
+    _fields_ = ([("n_labels", C.c_int32), ("wave_cap", C.c_int32), ("lds_cap", C.c_int32), ("reserved", C.c_int32)] +
+                [(k, C.c_int64) for k in ("n_rings", "n_svertices", "n_triangles", "n_failed_labels", "n_bridges", "n_tests",
+                                          "max_label_occurrences", "n_labels_wave", "n_labels_lds", "n_labels_global")] +
+                [("tri_offset", C.POINTER(C.c_int64)), ("label_status", C.POINTER(C.c_int32)),
+                 ("label_area2", C.POINTER(C.c_int64)), ("label_tests", C.POINTER(C.c_int64)),
+                 ("bridge", C.POINTER(C.c_int32)), ("tri", C.POINTER(C.c_int32))] +
+                [(k, C.c_double) for k in ("ms_clean", "ms_prologue", "ms_wave", "ms_lds", "ms_global", "ms_emit")])
+
+
 class BsError(RuntimeError):
     def __init__(self, status, detail=""):
         self.status = status
@@ -372,5 +390,13 @@ def load():
     L.bs_clean_outlines_free.argtypes = [cop]
     L.bs_clean_outlines_free.restype = None
     L.bs_clean_outlines_write_obj.argtypes = [cop, C.c_int32, ip, C.c_char_p]
+    otp = C.POINTER(OutlineTriangles)
+    tri_args = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, otp, cop, sop, olp]
+    L.bs_outline_triangles_count_dev.argtypes = tri_args
+    L.bs_outline_triangles.argtypes = tri_args
+    L.bs_outline_triangles_emit_dev.argtypes = [vp, ip]
+    L.bs_outline_triangles_free.argtypes = [otp]
+    L.bs_outline_triangles_free.restype = None
+    L.bs_outline_triangles_write_obj.argtypes = [otp, cop, C.c_int32, ip, C.c_char_p]
     _LIB = L
     return L

@@ -829,6 +829,54 @@ class Context:
         sizes, as simplified_outlines_emit_dev."""
         self._check(self._L.bs_clean_outlines_emit_dev(self._h, d_sxy or None, d_sz or None, d_right or None, d_flag or None))
 
+    # ---- outline triangles: the clean rings of every label, holes included, as triangles (bs_outline_triangles) ----------
+    def outline_triangles(self, label, top=None, n_labels=None, num=0, den=1, cell_log2=0):
+        """Every label's clean rings as triangles over the clean vertices (include/bs_api.h, "outline triangles").
+        Returns (OutlineTriangles, the CleanOutlines with their vertices, the SimpleOutlines without vertices, the plain
+        Outlines without vertices)."""
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        if label.ndim != 2 or label.size == 0:
+            raise ValueError("outline_triangles: label must be [height][width]")
+        if top is not None:
+            top = np.ascontiguousarray(top, dtype=np.int32)
+            if top.shape != label.shape + (4,):
+                raise ValueError("outline_triangles: top must be [height][width][4]")
+        h, w = label.shape
+        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        out, clean, simple, plain = _lib.OutlineTriangles(), _lib.CleanOutlines(), _lib.SimpleOutlines(), _lib.Outlines()
+        self._check(self._L.bs_outline_triangles(self._h, label.ctypes.data, None if top is None else top.ctypes.data, w, h, nl,
+                                                 int(num), int(den), int(cell_log2), C.byref(out), C.byref(clean),
+                                                 C.byref(simple), C.byref(plain)))
+        return (_take_outline_triangles(self._L, out, True), _take_clean_outlines(self._L, clean, True),
+                _take_simple_outlines(self._L, simple, False), _take_outlines(self._L, plain, False))
+
+    def outline_triangles_dev(self, d_label, d_top, width, height, n_labels, num=0, den=1, cell_log2=0):
+        """Device-resident count (bs_outline_triangles_count_dev): d_label and d_top (0: no Z) are device pointers (ints).
+        Returns (OutlineTriangles with tri None, CleanOutlines with the vertex arrays None, SimpleOutlines, Outlines)."""
+        out, clean, simple, plain = _lib.OutlineTriangles(), _lib.CleanOutlines(), _lib.SimpleOutlines(), _lib.Outlines()
+        self._check(self._L.bs_outline_triangles_count_dev(self._h, d_label or None, d_top or None, width, height,
+                                                           int(n_labels), int(num), int(den), int(cell_log2), C.byref(out),
+                                                           C.byref(clean), C.byref(simple), C.byref(plain)))
+        return (_take_outline_triangles(self._L, out, False), _take_clean_outlines(self._L, clean, False),
+                _take_simple_outlines(self._L, simple, False), _take_outlines(self._L, plain, False))
+
+    def outline_triangles_emit_dev(self, d_tri):
+        """The triangles of the last outline_triangles_dev on this context into a device buffer (int) of
+        [n_triangles][3] int32."""
+        self._check(self._L.bs_outline_triangles_emit_dev(self._h, d_tri or None))
+
+    def roof_mesh(self, roof_facets, solids, tolerance_mm=0, bin=None):
+        """outline_triangles() of the facet image of roof_facets() / roof_structure() with the tops of solids(), at a
+        tolerance in millimetres (bin: the pixel edge, by default the Solids'), beside roof_polygons(clean=True): returns
+        (OutlineTriangles, CleanOutlines, the plain Outlines)."""
+        if roof_facets.facet is None:
+            raise ValueError("roof_mesh: the facet image is on the device: use outline_triangles_dev")
+        if solids.top is None:
+            raise ValueError("roof_mesh: the Solids carry no top image (solids(top=True))")
+        num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
+        t, c, _, plain = self.outline_triangles(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)
+        return t, c, plain
+
 
 @dataclass
 class PlaneVotes:
@@ -1560,6 +1608,87 @@ def write_clean_outlines_obj(clean, path, bin, origin=None):
                                                  str(path).encode())
     if rc != 0:
         raise BsError(rc, f"cannot write {path} (or the ring arrays do not fit each other)")
+
+
+@dataclass
+class OutlineTriangles:
+    """bs_outline_triangles: the triangles of every label over the clean vertices, tri_offset per label, the status, area
+    and ear tests of every label, the bridge (M, V) of every hole, and the totals as include/bs_api.h names them."""
+    n_labels: int
+    n_rings: int
+    n_svertices: int
+    n_triangles: int
+    n_failed_labels: int
+    n_bridges: int
+    n_tests: int
+    max_label_occurrences: int
+    n_labels_wave: int
+    n_labels_lds: int
+    n_labels_global: int
+    wave_cap: int
+    lds_cap: int
+    tri_offset: np.ndarray
+    label_status: np.ndarray
+    label_area2: np.ndarray
+    label_tests: np.ndarray
+    bridge: np.ndarray
+    info: dict = field(default_factory=dict)
+    tri: np.ndarray | None = field(default=None, repr=False)
+
+
+_TRI_TOTALS = ("n_labels", "n_rings", "n_svertices", "n_triangles", "n_failed_labels", "n_bridges", "n_tests",
+               "max_label_occurrences", "n_labels_wave", "n_labels_lds", "n_labels_global", "wave_cap", "lds_cap")
+
+
+def _take_outline_triangles(L, out, triangles) -> OutlineTriangles:
+    """Copy a bs_outline_triangles into numpy arrays and release it."""
+    try:
+        nl, nr, nt = out.n_labels, out.n_rings, out.n_triangles
+        arr = lambda p, n, dt: np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, dt)  # noqa: E731
+        tri = None
+        if triangles:
+            tri = np.ctypeslib.as_array(out.tri, (nt, 3)).copy() if nt else np.zeros((0, 3), np.int32)
+        info = {k: getattr(out, k) for k in ("ms_clean", "ms_prologue", "ms_wave", "ms_lds", "ms_global", "ms_emit")}
+        return OutlineTriangles(*[getattr(out, k) for k in _TRI_TOTALS],
+                                tri_offset=np.ctypeslib.as_array(out.tri_offset, (nl + 1,)).copy(),
+                                label_status=arr(out.label_status, nl, np.int32), label_area2=arr(out.label_area2, nl, np.int64),
+                                label_tests=arr(out.label_tests, nl, np.int64),
+                                bridge=arr(out.bridge, 2 * nr, np.int32).reshape(-1, 2), info=info, tri=tri)
+    finally:
+        L.bs_outline_triangles_free(C.byref(out))
+
+
+def write_outline_triangles_obj(tri, clean, path, bin, origin=None):
+    """The mesh of an OutlineTriangles over the vertices of its CleanOutlines as an OBJ through the library's writer
+    (bs_outline_triangles_write_obj)."""
+    if tri.tri is None or clean.sxy is None:
+        raise ValueError("write_outline_triangles_obj: the triangles or the vertices are on the device")
+    st, cl, keep = _lib.OutlineTriangles(), _lib.CleanOutlines(), []
+    st.n_labels, st.n_svertices, st.n_triangles = int(tri.n_labels), int(tri.n_svertices), int(tri.n_triangles)
+    st.n_failed_labels, st.n_bridges = int(tri.n_failed_labels), int(tri.n_bridges)
+    cl.n_svertices = int(clean.n_svertices)
+
+    def put(struct, src, name, dt, n):
+        a = np.ascontiguousarray(getattr(src, name), dtype=dt).reshape(-1)
+        if len(a) != n:
+            raise ValueError(f"{type(src).__name__}.{name} must hold {n} values")
+        keep.append(a if len(a) else np.zeros(1, dt))
+        setattr(struct, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
+
+    put(st, tri, "tri_offset", np.int64, st.n_labels + 1)
+    put(st, tri, "label_status", np.int32, st.n_labels)
+    put(st, tri, "tri", np.int32, 3 * st.n_triangles)
+    put(cl, clean, "sxy", np.int32, 2 * cl.n_svertices)
+    if clean.sz is not None:
+        put(cl, clean, "sz", np.int32, cl.n_svertices)
+        cl.has_z = 1
+    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+    if org is not None and org.shape != (3,):
+        raise ValueError("origin must be [3]")
+    rc = _lib.load().bs_outline_triangles_write_obj(C.byref(st), C.byref(cl), int(bin),
+                                                    org.ctypes.data if org is not None else None, str(path).encode())
+    if rc != 0:
+        raise BsError(rc, f"cannot write {path} (or the arrays do not fit each other)")
 
 
 def simplify_tolerance(tolerance_mm, bin):

@@ -283,6 +283,16 @@ struct bs_ctx {
   bool uc_valid = false, uc_has_z = false;
   int64_t uc_nsv = 0;
   double uc_ms_emit = 0;
+  // what the last successful bs_clean_outlines_count_dev leaves for the outline triangles (bs_triangulate.hip), all inside
+  // uc: the clean vertices, the ring of every vertex, the first vertex of every ring
+  const int2* uc_xy = nullptr;
+  const int32_t *uc_ring = nullptr, *uc_soff = nullptr;
+  // outline triangles (bs_triangulate.hip): scratch, and what bs_outline_triangles_count_dev leaves for
+  // bs_outline_triangles_emit_dev (the triangles)
+  bs::DevBuf tr[16];
+  bool tr_valid = false;
+  int64_t tr_ntri = 0;
+  double tr_ms_emit = 0;
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew

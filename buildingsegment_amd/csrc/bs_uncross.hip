@@ -644,6 +644,9 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
     guard.keep = true;
     ctx->uc_nsv = res.n_svertices;
     ctx->uc_has_z = has_z;
+    ctx->uc_xy = ctx->uc[UC_FXY].as<int2>();  // (for bs_triangulate.hip)
+    ctx->uc_ring = ctx->uc[UC_FRING].as<int32_t>();
+    ctx->uc_soff = ctx->uc[UC_SOFF].as<int32_t>();
     ctx->uc_valid = true;
     return BS_OK;
   };

@@ -1296,6 +1296,105 @@ void bs_clean_outlines_free(struct bs_clean_outlines* o);
  *    n_forced <f>" (one line).  Host only. */
 int bs_clean_outlines_write_obj(const struct bs_clean_outlines* o, int32_t bin, const int32_t* origin, const char* path);
 
+/* ---- outline triangles: every label's clean rings, holes included, as triangles over the clean vertices ----
+ *
+ * Input.  The result of bs_clean_outlines_count_dev with max_rounds = -1 on the same images and tolerance: the rings in the
+ * order (label, h0), s_ring_offset and sxy as that stage leaves them, ring_area2 the plain outlines'.  A ring is outer iff its
+ * plain ring_area2 > 0, else a hole.  A label may have several outer rings (a general label image); a facet image has exactly
+ * one per label.  A vertex is an index into the clean vertex arrays; an occurrence is one visit of a vertex by a cyclic list.
+ * A ring's label lies on the left of every segment, holes included.  No vertex is created: neighbouring labels that share a
+ * segment vertex for vertex share it as a mesh edge.
+ * Exact predicates.  orient(a, b, c) = (b - a) x (c - a) in int64 is the only arithmetic; the coordinates are lattice corners.
+ * Cone.  At an occurrence v with predecessor p and successor n in its list a direction d lies in the cone
+ *   if orient(p, v, n) > 0: iff (n - v) x d > 0 and d x (p - v) > 0;
+ *   otherwise: iff not ((p - v) x d >= 0 and d x (n - v) >= 0).
+ * Blocks.  A segment s-e blocks M-V iff the two cross properly, or an end of s-e that is at neither M's nor V's position lies
+ * on the closed M-V, or M or V lies on s-e without being at one of its ends.
+ * Bridges, per label.  The cyclic lists start as the label's outer rings in ring order.  The holes are taken in ascending
+ * order of (x, y, vertex) of their leftmost vertex M (a ring that visits that position twice takes the lower vertex).
+ * Candidates are all occurrences of all the label's lists whose position differs from M's.  An occurrence of vertex V is
+ * valid iff M - V is in the cone at that occurrence, V - M is in the cone at M taken in its own ring, no segment of any ring
+ * of the label blocks M-V (the holes not yet merged and M's own hole included), and no earlier bridge of the label blocks
+ * M-V.  The bridge goes to the valid occurrence with the least (|V - M|^2, V); two occurrences of one vertex have disjoint
+ * cones, so at most one of them is valid.  The list becomes ... V, M, (the hole from M round), M', V', ...: two occurrences
+ * more.  A hole without a valid occurrence gives the label the status BS_TRI_NO_BRIDGE and no triangles: such a hole lies
+ * outside its outer ring, which the clean outlines do not notice when a chord sweeps over a whole ring without touching it
+ * ("Outline triangles").
+ * Ears, scanned as earcut scans, per list in the order of the outer rings.  stop = cursor = the outer ring's first
+ * occurrence.  While more than 3 occurrences remain: b = cursor, a its predecessor, c its successor; b is an ear iff
+ * orient(a, b, c) > 0 and no other occurrence q of the current list whose position differs from those of a, b and c has
+ * orient(a, b, q) >= 0, orient(b, c, q) >= 0 and orient(c, a, q) >= 0.  An ear emits (a, b, c) as vertices, unlinks b and
+ * sets cursor = stop = succ(c); otherwise cursor = succ(cursor), and if the cursor comes back to stop the label gets the
+ * status BS_TRI_STALLED and no triangles.  The last three occurrences are emitted as (pred, cursor, succ).
+ *
+ * Result.  tri [n_triangles][3]: indices into the clean vertex arrays.  tri_offset [n_labels + 1] is known before anything
+ * is clipped: a label has V + 2 H - 2 O triangles (V kept vertices, H holes, O outer rings), within a label the triangles
+ * follow the outer rings in order, each in clip order; the slots of a label whose status is not BS_TRI_OK are all -1.
+ * label_status; label_area2, the sum of orient over the label's triangles (0 unless OK); label_tests, the ear tests made
+ * (every evaluation of "b is an ear").  bridge [n_rings][2] = (M, V), or (-1, -1) for outer rings and the holes of failed
+ * labels.  Totals: n_triangles (all slots), n_failed_labels (NO_BRIDGE or STALLED), n_bridges, n_tests,
+ * max_label_occurrences (the most V + 2 H of one label), and the labels that took each kernel path.
+ * Promised for every OK label: every triangle has orient > 0; label_area2 equals the sum of s_ring_area2 over the label's
+ * rings; every ring segment (i, next i) is a directed triangle edge exactly once; every other directed triangle edge occurs
+ * exactly once and so does its reverse.  Hence the triangles tile the polygon. */
+#define BS_TRI_OK 0
+#define BS_TRI_NO_BRIDGE 1
+#define BS_TRI_STALLED 2
+#define BS_TRI_EMPTY 3 /* a label without a ring */
+#define BS_TRI_WAVE_CAP 64  /* up to this many occurrences (V + 2 H) a label is one wave's work item */
+#define BS_TRI_LDS_CAP 1024 /* up to this many a workgroup's, with its lists in LDS; beyond, in a global workspace */
+
+struct bs_outline_triangles {
+  int32_t n_labels;
+  int32_t wave_cap, lds_cap; /* BS_TRI_WAVE_CAP, BS_TRI_LDS_CAP of the library */
+  int32_t reserved;
+  int64_t n_rings, n_svertices; /* of the clean outlines */
+  int64_t n_triangles, n_failed_labels, n_bridges, n_tests, max_label_occurrences;
+  int64_t n_labels_wave, n_labels_lds, n_labels_global; /* labels by kernel path (labels without a ring take none) */
+  /* host memory owned by the library */
+  int64_t* tri_offset;   /* [n_labels + 1] */
+  int32_t* label_status; /* [n_labels] */
+  int64_t* label_area2;  /* [n_labels] */
+  int64_t* label_tests;  /* [n_labels] */
+  int32_t* bridge;       /* [n_rings][2] */
+  int32_t* tri;          /* [n_triangles][3]: host-memory entry point only, else NULL */
+  /* device time (HIP events on the context's stream) */
+  double ms_clean;    /* the clean count: the sum of its phases */
+  double ms_prologue; /* uploads, the leftmost vertex of every hole */
+  double ms_wave, ms_lds, ms_global; /* the three kernels */
+  double ms_emit;     /* the emit (host-memory entry point only) */
+};
+
+/* Counts, triangulates and sizes.  Runs bs_clean_outlines_count_dev with max_rounds = -1 on the same images first (its
+ * context state and that of the stages below it are replaced) and hands its results to *clean, *simple and *plain unless
+ * they are NULL.  The triangles stay in the context for the emit below.  Errors as bs_clean_outlines_count_dev; also
+ * BS_ERR_INVALID for n_svertices >= 2^31 or a label of 2^29 occurrences or more, BS_ERR_INTERNAL where an index read from
+ * memory left its range.  On any error the outputs are left untouched.  Synchronises: the clean count's times, then once
+ * for the result. */
+int bs_outline_triangles_count_dev(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t width, int32_t height,
+                                   int32_t n_labels, int64_t num, int64_t den, int32_t cell_log2,
+                                   struct bs_outline_triangles* out, struct bs_clean_outlines* clean,
+                                   struct bs_simple_outlines* simple, struct bs_outlines* plain);
+/* The triangles of the last successful count on this context into a device buffer d_tri [n_triangles][3] (may be NULL with
+ * no triangle).  May be called more than once.  BS_ERR_INVALID: no successful count, or a missing buffer.  Synchronises. */
+int bs_outline_triangles_emit_dev(bs_ctx* ctx, int32_t* d_tri);
+/* Host-memory twin: label and top (may be NULL) are host pointers; both steps; the triangles come back in out's
+ * library-owned tri, and *clean (unless NULL) carries the clean vertices as bs_clean_outlines returns them. */
+int bs_outline_triangles(bs_ctx* ctx, const int32_t* label, const int32_t* top, int32_t width, int32_t height, int32_t n_labels,
+                         int64_t num, int64_t den, int32_t cell_log2, struct bs_outline_triangles* out,
+                         struct bs_clean_outlines* clean, struct bs_simple_outlines* simple, struct bs_outlines* plain);
+void bs_outline_triangles_free(struct bs_outline_triangles* o);
+/* The mesh as an OBJ in millimetres.  Host only: tri->tri and clean->sxy (and sz, else Z = 0) must be present.
+ *   "# outline triangles: <n_labels> labels, <n_svertices> vertices, <n_triangles> triangles, <n_failed_labels> failed
+ *    labels, <n_bridges> bridges" (one line)
+ *   every clean vertex as "v X*bin+origin[0] Y*bin+origin[1] Z+origin[2]"
+ *   for every label l with status BS_TRI_OK: "g label_<l>" and its triangles as "f i j k" (indices from 1).
+ * Every number is a decimal integer, every line ends with \n.  origin may be NULL (zeros).  BS_ERR_INVALID: a null pointer,
+ * bin < 1, counts or offsets that do not fit each other, a vertex index outside the vertices, or a file that cannot be
+ * written. */
+int bs_outline_triangles_write_obj(const struct bs_outline_triangles* tri, const struct bs_clean_outlines* clean, int32_t bin,
+                                   const int32_t* origin, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
