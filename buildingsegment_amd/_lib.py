@@ -40,7 +40,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_simple_outlines", "bs_simple_outlines_free", "bs_simple_outlines_write_obj", "bs_clean_outlines_count_dev",
            "bs_clean_outlines_emit_dev", "bs_clean_outlines", "bs_clean_outlines_free", "bs_clean_outlines_write_obj",
            "bs_outline_triangles_count_dev", "bs_outline_triangles_emit_dev", "bs_outline_triangles",
-           "bs_outline_triangles_free", "bs_outline_triangles_write_obj"]
+           "bs_outline_triangles_free", "bs_outline_triangles_write_obj", "bs_poly_solids_count_dev",
+           "bs_poly_solids_emit_dev", "bs_poly_solids", "bs_poly_solids_free"]
 
 
 class Params(C.Structure):
@@ -231,6 +232,26 @@ class OutlineTriangles(C.Structure):
                 [(k, C.c_double) for k in ("ms_clean", "ms_prologue", "ms_wave", "ms_lds", "ms_global", "ms_emit")])
 
 
+POLY_FIG_CAP = 1024  # BS_POLY_FIG_CAP of include/bs_api.h
+POLY_FIGURES = (("status", C.c_int32), ("labels", C.c_int64), ("vertices", C.c_int64), ("faces", C.c_int64),
+                ("roof_faces", C.c_int64), ("wall_faces", C.c_int64), ("crossing_walls", C.c_int64),
+                ("max_wall_vertices", C.c_int64), ("z_min", C.c_int32), ("z_max", C.c_int32), ("area2", C.c_int64),
+                ("volume6", C.c_int64))
+POLY_TOTALS = ("n_open_buildings", "n_vertices", "n_faces", "n_indices", "n_roof_faces", "n_wall_faces", "n_crossing_walls",
+               "max_wall_vertices_all", "total_area2", "total_volume6")
+POLY_MS = ("ms_triangles", "ms_twins", "ms_vertices", "ms_count", "ms_emit_vertices", "ms_emit_faces")
+
+
+class PolySolids(C.Structure):
+    """bs_poly_solids (include/bs_api.h): totals, per-building figures and (host-memory entry point) the mesh, host memory
+    owned by the library."""
+    _fields_ = ([(k, C.c_int32) for k in ("n_buildings", "n_labels", "bin", "base_z", "fig_cap", "reserved")] +
+                [(k, C.c_int64) for k in POLY_TOTALS] + [(k, C.POINTER(t)) for k, t in POLY_FIGURES] +
+                [("vertex", C.POINTER(C.c_int32)), ("face_offset", C.POINTER(C.c_int32)), ("face_index", C.POINTER(C.c_int32)),
+                 ("face_building", C.POINTER(C.c_int32)), ("face_kind", C.POINTER(C.c_uint8))] +
+                [(k, C.c_double) for k in POLY_MS])
+
+
 class BsError(RuntimeError):
     def __init__(self, status, detail=""):
         self.status = status
@@ -398,5 +419,13 @@ def load():
     L.bs_outline_triangles_free.argtypes = [otp]
     L.bs_outline_triangles_free.restype = None
     L.bs_outline_triangles_write_obj.argtypes = [otp, cop, C.c_int32, ip, C.c_char_p]
+    psp = C.POINTER(PolySolids)
+    poly_args = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int32, C.c_int32, C.c_int32,
+                 psp, otp, cop, sop, olp]
+    L.bs_poly_solids_count_dev.argtypes = poly_args
+    L.bs_poly_solids.argtypes = poly_args
+    L.bs_poly_solids_emit_dev.argtypes = [vp, ip, ip, ip, ip, vp]
+    L.bs_poly_solids_free.argtypes = [psp]
+    L.bs_poly_solids_free.restype = None
     _LIB = L
     return L

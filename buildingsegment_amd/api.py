@@ -877,6 +877,73 @@ class Context:
         t, c, _, plain = self.outline_triangles(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)
         return t, c, plain
 
+    # ---- polygon solids: a closed mesh per building over the clean vertices and the triangles (bs_poly_solids) ------------
+    def poly_solids(self, label, top, label_building, n_labels=None, n_buildings=None, num=0, den=1, bin=1, base_z=0,
+                    cell_log2=0):
+        """Roof, floor and walls of every building as one closed mesh over the clean vertices (include/bs_api.h, "polygon
+        solids").  label is [height][width], top [height][width][4] as Solids.top, label_building [n_labels] the building
+        of every label.  n_labels defaults to label.max() + 1, n_buildings to label_building.max() + 1.  Returns
+        (PolySolids, OutlineTriangles, the CleanOutlines with their vertices, the SimpleOutlines without vertices, the
+        plain Outlines without vertices)."""
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        if label.ndim != 2 or label.size == 0:
+            raise ValueError("poly_solids: label must be [height][width]")
+        if top is None:
+            raise ValueError("poly_solids: the stage needs a top image")
+        top = np.ascontiguousarray(top, dtype=np.int32)
+        if top.shape != label.shape + (4,):
+            raise ValueError("poly_solids: top must be [height][width][4]")
+        h, w = label.shape
+        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        lb = np.ascontiguousarray(label_building, dtype=np.int32).reshape(-1)
+        if len(lb) != nl:
+            raise ValueError("poly_solids: label_building must have one entry per label")
+        nb = (int(lb.max()) + 1 if nl else 0) if n_buildings is None else int(n_buildings)
+        out, tri, clean = _lib.PolySolids(), _lib.OutlineTriangles(), _lib.CleanOutlines()
+        simple, plain = _lib.SimpleOutlines(), _lib.Outlines()
+        self._check(self._L.bs_poly_solids(self._h, label.ctypes.data, top.ctypes.data, w, h, nl, int(num), int(den),
+                                           int(cell_log2), lb.ctypes.data if nl else None, nb, int(bin), int(base_z),
+                                           C.byref(out), C.byref(tri), C.byref(clean), C.byref(simple), C.byref(plain)))
+        return (_take_poly_solids(self._L, out, True), _take_outline_triangles(self._L, tri, True),
+                _take_clean_outlines(self._L, clean, True), _take_simple_outlines(self._L, simple, False),
+                _take_outlines(self._L, plain, False))
+
+    def poly_solids_dev(self, d_label, d_top, width, height, n_labels, d_label_building, n_buildings, num=0, den=1, bin=1,
+                        base_z=0, cell_log2=0):
+        """Device-resident count (bs_poly_solids_count_dev): d_label, d_top and d_label_building are device pointers
+        (ints).  Returns (PolySolids with the mesh None and the sizes n_vertices / n_faces / n_indices of the buffers
+        poly_solids_emit_dev fills, OutlineTriangles, CleanOutlines, SimpleOutlines, Outlines, all without their arrays
+        of the emits)."""
+        out, tri, clean = _lib.PolySolids(), _lib.OutlineTriangles(), _lib.CleanOutlines()
+        simple, plain = _lib.SimpleOutlines(), _lib.Outlines()
+        self._check(self._L.bs_poly_solids_count_dev(self._h, d_label or None, d_top or None, width, height, int(n_labels),
+                                                     int(num), int(den), int(cell_log2), d_label_building or None,
+                                                     int(n_buildings), int(bin), int(base_z), C.byref(out), C.byref(tri),
+                                                     C.byref(clean), C.byref(simple), C.byref(plain)))
+        return (_take_poly_solids(self._L, out, False), _take_outline_triangles(self._L, tri, False),
+                _take_clean_outlines(self._L, clean, False), _take_simple_outlines(self._L, simple, False),
+                _take_outlines(self._L, plain, False))
+
+    def poly_solids_emit_dev(self, d_vertex, d_face_offset, d_face_index, d_face_building, d_face_kind):
+        """The mesh of the last poly_solids_dev on this context into device buffers (ints) of exactly its sizes."""
+        self._check(self._L.bs_poly_solids_emit_dev(self._h, d_vertex or None, d_face_offset or None, d_face_index or None,
+                                                    d_face_building or None, d_face_kind or None))
+
+    def building_model(self, roof_facets, solids, tolerance_mm=0, bin=None):
+        """poly_solids() of the facet image and facet_building of roof_facets() / roof_structure() with the tops, bin and
+        base_z of solids(), at a tolerance in millimetres, beside roof_mesh(): returns (PolySolids, OutlineTriangles,
+        CleanOutlines, the plain Outlines)."""
+        if roof_facets.facet is None:
+            raise ValueError("building_model: the facet image is on the device: use poly_solids_dev")
+        if solids.top is None:
+            raise ValueError("building_model: the Solids carry no top image (solids(top=True))")
+        b = solids.bin if bin is None else bin
+        num, den = simplify_tolerance(tolerance_mm, b)
+        p, t, c, _, plain = self.poly_solids(roof_facets.facet, solids.top, roof_facets.facet_building,
+                                             n_labels=roof_facets.n_facets, n_buildings=solids.n_buildings, num=num, den=den,
+                                             bin=b, base_z=solids.base_z)
+        return p, t, c, plain
+
 
 @dataclass
 class PlaneVotes:
@@ -1689,6 +1756,67 @@ def write_outline_triangles_obj(tri, clean, path, bin, origin=None):
                                                     org.ctypes.data if org is not None else None, str(path).encode())
     if rc != 0:
         raise BsError(rc, f"cannot write {path} (or the arrays do not fit each other)")
+
+
+@dataclass
+class PolySolids:
+    """bs_poly_solids: the totals, the per-building figures (status 0 closed / 1 open, labels, vertices, faces, roof_faces,
+    wall_faces, crossing_walls, max_wall_vertices, z_min, z_max, area2, volume6) and the mesh in the layout of Solids (None
+    after poly_solids_dev: it is written by poly_solids_emit_dev), which write_solids_obj writes.  The volume of building c
+    in mm^3 is volume6[c] * bin^2 / 6."""
+    n_buildings: int
+    n_labels: int
+    bin: int
+    base_z: int
+    fig_cap: int
+    n_open_buildings: int
+    n_vertices: int
+    n_faces: int
+    n_indices: int
+    n_roof_faces: int
+    n_wall_faces: int
+    n_crossing_walls: int
+    max_wall_vertices_all: int
+    total_area2: int
+    total_volume6: int
+    status: np.ndarray
+    labels: np.ndarray
+    vertices: np.ndarray
+    faces: np.ndarray
+    roof_faces: np.ndarray
+    wall_faces: np.ndarray
+    crossing_walls: np.ndarray
+    max_wall_vertices: np.ndarray
+    z_min: np.ndarray
+    z_max: np.ndarray
+    area2: np.ndarray
+    volume6: np.ndarray
+    info: dict = field(default_factory=dict)
+    vertex: np.ndarray | None = field(default=None, repr=False)
+    face_offset: np.ndarray | None = field(default=None, repr=False)
+    face_index: np.ndarray | None = field(default=None, repr=False)
+    face_building: np.ndarray | None = field(default=None, repr=False)
+    face_kind: np.ndarray | None = field(default=None, repr=False)
+
+
+def _take_poly_solids(L, out, mesh) -> PolySolids:
+    """Copy a bs_poly_solids into numpy arrays and release it."""
+    n = out.n_buildings
+    try:
+        arrs = {name: (np.ctypeslib.as_array(getattr(out, name), (n,)).copy() if n else np.zeros(0, np.dtype(ct)))
+                for name, ct in _lib.POLY_FIGURES}
+        if mesh:
+            nv, nf, ni = out.n_vertices, out.n_faces, out.n_indices
+            arrs["vertex"] = np.ctypeslib.as_array(out.vertex, (nv, 4)).copy() if nv else np.zeros((0, 4), np.int32)
+            arrs["face_offset"] = np.ctypeslib.as_array(out.face_offset, (nf + 1,)).copy()
+            arrs["face_index"] = np.ctypeslib.as_array(out.face_index, (ni,)).copy() if ni else np.zeros(0, np.int32)
+            arrs["face_building"] = np.ctypeslib.as_array(out.face_building, (nf,)).copy() if nf else np.zeros(0, np.int32)
+            arrs["face_kind"] = np.ctypeslib.as_array(out.face_kind, (nf,)).copy() if nf else np.zeros(0, np.uint8)
+        info = {k: getattr(out, k) for k in _lib.POLY_MS}
+        return PolySolids(n, out.n_labels, out.bin, out.base_z, out.fig_cap, *[getattr(out, k) for k in _lib.POLY_TOTALS],
+                          info=info, **arrs)
+    finally:
+        L.bs_poly_solids_free(C.byref(out))
 
 
 def simplify_tolerance(tolerance_mm, bin):

@@ -249,6 +249,8 @@ void bs_destroy(bs_ctx* c)
     b.release();
   for (auto& b : c->tr)
     b.release();
+  for (auto& b : c->ps)
+    b.release();
   for (auto& b : c->bt)
     b.release();
   c->tile_desc.release();

@@ -287,12 +287,22 @@ struct bs_ctx {
   // uc: the clean vertices, the ring of every vertex, the first vertex of every ring
   const int2* uc_xy = nullptr;
   const int32_t *uc_ring = nullptr, *uc_soff = nullptr;
+  const int32_t *uc_z = nullptr, *uc_right = nullptr;  // (their Z and right labels, for bs_polysolid.hip)
   // outline triangles (bs_triangulate.hip): scratch, and what bs_outline_triangles_count_dev leaves for
   // bs_outline_triangles_emit_dev (the triangles)
   bs::DevBuf tr[16];
   bool tr_valid = false;
   int64_t tr_ntri = 0;
   double tr_ms_emit = 0;
+  const int32_t* tr_tri = nullptr;  // (the triangles of the last count, inside tr, for bs_polysolid.hip)
+  // polygon solids (bs_polysolid.hip): scratch, and what bs_poly_solids_count_dev leaves for bs_poly_solids_emit_dev (the
+  // twins, the vertex numbers, the offsets); the emit also reads the clean vertices and the triangles, so a later clean
+  // count on this context ends its validity
+  bs::DevBuf ps[36];
+  bool ps_valid = false;
+  int32_t ps_bin = 0, ps_base = 0, ps_nl = 0, ps_nr = 0, ps_nsv = 0;
+  int64_t ps_nv = 0, ps_nf = 0, ps_ni = 0, ps_ntri = 0;
+  double ps_ms_emit[2] = {0, 0};  // vertex pass, face passes of the last emit
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew

@@ -584,6 +584,7 @@ int triangulate(bs_ctx* ctx, const struct bs_clean_outlines& c, struct bs_outlin
   for (int64_t r = 0; r < 2 * (int64_t)nr; r++)
     res.bridge[r] = -1;
   ctx->tr_ntri = ntri;
+  ctx->tr_tri = nullptr;
   if (nr == 0)
     return BS_OK;
   BS_HIP(ctx, hipSetDevice(ctx->device));
@@ -610,6 +611,7 @@ int triangulate(bs_ctx* ctx, const struct bs_clean_outlines& c, struct bs_outlin
   uint8_t* d_outer = B[TR_OUTER].as<uint8_t>();
   unsigned long long* rkey = B[TR_RKEY].as<unsigned long long>();
   int32_t* rm = B[TR_RM].as<int32_t>();
+  ctx->tr_tri = B[TR_TRI].as<int32_t>();  // (for bs_polysolid.hip)
   const TriArgs args{B[TR_DESC].as<LabelDesc>(), B[TR_LIST].as<int32_t>(), ctx->uc_xy, ctx->uc_ring, ctx->uc_soff, d_outer, rm,
                      B[TR_TRI].as<int32_t>(), B[TR_LOUT].as<LabelOut>(), B[TR_BRIDGE].as<int2>(), B[TR_WS].as<int32_t>(), ws_total,
                      ntri, nr, nsv, nl, 0, d_err};

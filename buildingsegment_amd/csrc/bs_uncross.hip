@@ -591,6 +591,7 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   if (!ctx)
     return BS_ERR_INVALID;
   ctx->uc_valid = false;
+  ctx->ps_valid = false;  // (the polygon solids' emit reads the clean vertices)
   if (!out || cell_log2 < 0 || cell_log2 > 30)
     return fail(ctx, BS_ERR_INVALID, "clean outlines: null pointer or cell_log2 outside 0 .. 30");
   struct bs_simple_outlines sm;
@@ -647,6 +648,8 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
     ctx->uc_xy = ctx->uc[UC_FXY].as<int2>();  // (for bs_triangulate.hip)
     ctx->uc_ring = ctx->uc[UC_FRING].as<int32_t>();
     ctx->uc_soff = ctx->uc[UC_SOFF].as<int32_t>();
+    ctx->uc_z = ctx->uc[UC_FZ].as<int32_t>();  // (for bs_polysolid.hip)
+    ctx->uc_right = ctx->uc[UC_FRIGHT].as<int32_t>();
     ctx->uc_valid = true;
     return BS_OK;
   };

@@ -1395,6 +1395,122 @@ void bs_outline_triangles_free(struct bs_outline_triangles* o);
 int bs_outline_triangles_write_obj(const struct bs_outline_triangles* tri, const struct bs_clean_outlines* clean, int32_t bin,
                                    const int32_t* origin, const char* path);
 
+/* ---- polygon solids: a closed mesh per building (roof, floor, walls) over the clean vertices and the outline triangles ----
+ *
+ * The LoD2-style counterpart of "solids": the face count follows the simplified polygons, not the pixels.  Step 3 of "solids"
+ * is followed so closely that the wall polygon is the same formula.  No vertex position is invented; every figure is an exact
+ * integer.
+ *
+ * Input.  The state of a successful bs_outline_triangles_count_dev with a top image (d_top == NULL is BS_ERR_INVALID): the
+ * clean vertices i with position sxy[i], height sz[i], s_right[i] and next(i) within their ring, the rings' labels, tri,
+ * tri_offset and label_status.  And: a device table label_building[n_labels] (int32), each entry in 0 .. n_buildings - 1;
+ * n_buildings; bin >= 1; base_z.  Nothing is assumed about sz against base_z: walls in both directions work.
+ *
+ * Open buildings.  A building is OPEN iff one of its labels has status BS_TRI_NO_BRIDGE or BS_TRI_STALLED.  An open building
+ * contributes no vertex and no face and is counted.  BS_TRI_EMPTY labels contribute nothing and open nothing.
+ *
+ * Vertices.  Every clean vertex i of a label of a building c that is not open names two mesh vertices: (c, X, Y, sz[i]) and
+ * (c, X, Y, base_z).  The mesh has one vertex per distinct quadruple: int32 [4] {X * bin, Y * bin, Z, c}, ordered by ascending
+ * (c, Y, X, Z).  In this order bs_solids_write_obj writes the mesh unchanged, and the vertices of one (c, corner) -- a column
+ * -- are consecutive by height.
+ *
+ * Faces.  Take the labels l in ascending order whose building c is not open and whose status is BS_TRI_OK.  For each label:
+ *   1. roof, kind 0: every triangle (a, b, d) of l, in tri order, at the vertices (c, position, sz);
+ *   2. floor, kind 1: the same triangles as (d, b, a) at base_z;
+ *   3. walls, kind 2: every clean vertex s of l's rings in ascending order, with e = next(s), a_s = sz[s], a_e = sz[e] and
+ *      R = s_right[s].
+ *      If R >= 0 and label_building[R] == c, the segment has a twin t in a ring of R: the same two corners reversed and
+ *      s_right[t] == l, which "simplified outlines" promise.  Then b_e = sz[t] and b_s = sz[next(t)], and only the smaller
+ *      of the two labels emits the wall.  Otherwise b_s = b_e = base_z.
+ *      The wall exists iff (a_s, a_e) != (b_s, b_e).  It is the polygon
+ *        (e, a_e), (s, a_s), the vertices of (c, s) strictly between a_s and b_s walking from a_s, (s, b_s), (e, b_e), the
+ *        vertices of (c, e) strictly between b_e and a_e walking from b_e
+ *      with (s, b_s) left out when b_s == a_s and (e, b_e) when b_e == a_e: at least 3 vertices.
+ *      A wall is CROSSING iff (a_s - b_s) * (a_e - b_e) < 0; it is emitted as that one polygon (a bow-tie in a vertical
+ *      plane) and counted.
+ * face_offset int32 [n_faces + 1], face_index int32 [n_indices] (vertex numbers from 0), face_building int32 [n_faces],
+ * face_kind uint8 [n_faces], exactly as in struct bs_solids.  No new OBJ writer is needed: the five mesh arrays have the layout
+ * that bs_solids_write_obj reads.
+ *
+ * Figures per building: status (0 closed, 1 open); labels (all labels the table maps to it); vertices; faces; roof_faces;
+ * wall_faces; crossing_walls; max_wall_vertices; z_min / z_max over the sz of its clean vertices (INT32_MAX / INT32_MIN without
+ * one); area2, the sum of orient over its roof triangles; volume6, the sum over its roof triangles of
+ * orient(a, b, d) * (sz[a] + sz[b] + sz[d] - 3 * base_z) in int64.  The volume in mm^3 is volume6 * bin^2 / 6.  All but status
+ * and labels are 0 (z_min / z_max: the values without a vertex) for an open building.  And the totals of these figures,
+ * n_indices and n_open_buildings.
+ *
+ * Errors.  BS_ERR_RANGE: a clean vertex (of any label) with |sz - base_z| >= 2^24 (which keeps volume6 inside int64), a
+ * label_building value outside its range, or 2^31 or more vertices or indices.  BS_ERR_INTERNAL: a twin that is missing or has
+ * the wrong labels.  On any error the outputs are untouched and the context stays usable.
+ *
+ * Promised.  Per closed building every directed edge of the mesh occurs exactly as often as its reverse.  The sum over the fan
+ * triangles of all its faces of det[(X, Y, Z)] in lattice units (X, Y not multiplied by bin) equals volume6.  NOT promised:
+ * that the mesh is manifold or free of self-intersection -- crossing walls are bow-ties, and a chord may sweep over a foreign
+ * building's ring ("Polygon solids"). */
+#define BS_POLY_FIG_CAP 1024 /* buildings below this number have their figures reduced in LDS, the rest by global atomics */
+
+struct bs_poly_solids {
+  int32_t n_buildings, n_labels;
+  int32_t bin, base_z;
+  int32_t fig_cap; /* BS_POLY_FIG_CAP of the library */
+  int32_t reserved;
+  int64_t n_open_buildings, n_vertices, n_faces, n_indices, n_roof_faces, n_wall_faces, n_crossing_walls;
+  int64_t max_wall_vertices_all, total_area2, total_volume6; /* totals (max_wall_vertices_all: the maximum) */
+  /* per building; host memory owned by the library */
+  int32_t* status;            /* [n_buildings] */
+  int64_t* labels;            /* [n_buildings] */
+  int64_t* vertices;          /* [n_buildings] */
+  int64_t* faces;             /* [n_buildings] */
+  int64_t* roof_faces;        /* [n_buildings] */
+  int64_t* wall_faces;        /* [n_buildings] */
+  int64_t* crossing_walls;    /* [n_buildings] */
+  int64_t* max_wall_vertices; /* [n_buildings] */
+  int32_t* z_min;             /* [n_buildings] */
+  int32_t* z_max;             /* [n_buildings] */
+  int64_t* area2;             /* [n_buildings] */
+  int64_t* volume6;           /* [n_buildings] */
+  /* the mesh, host memory owned by the library: filled by the host-memory entry point only (NULL after the count) */
+  int32_t* vertex;        /* [n_vertices][4] */
+  int32_t* face_offset;   /* [n_faces + 1] */
+  int32_t* face_index;    /* [n_indices] */
+  int32_t* face_building; /* [n_faces] */
+  uint8_t* face_kind;     /* [n_faces] */
+  /* device time (HIP events on the context's stream) */
+  double ms_triangles; /* the triangle count: the sum of its phases, the clean count included */
+  double ms_twins;     /* uploads, keys, the sort of the segments, the pairing */
+  double ms_vertices;  /* the two sorts of the entries, head flags, their sum, the numbers */
+  double ms_count;     /* walls, triangles, the two sums */
+  double ms_emit_vertices, ms_emit_faces; /* the passes of the emit (host-memory entry point only) */
+};
+
+/* Counts, figures and sizes.  Runs bs_outline_triangles_count_dev on the same images first (its context state and that of the
+ * stages below it are replaced) and hands its results to *tri, *clean, *simple and *plain unless they are NULL.
+ * d_label_building is a device pointer (read once, not kept).  The twins, the vertex numbers and the offsets stay in the
+ * context for the emit below; out's per-building arrays are host memory owned by the library (bs_poly_solids_free, which
+ * accepts a zeroed struct).  An image without a labelled pixel is valid: an empty mesh.
+ * BS_ERR_INVALID: a null pointer (d_top included; d_label_building may be NULL with n_labels == 0), n_buildings < 0, bin < 1,
+ * or what bs_outline_triangles_count_dev refuses.  BS_ERR_RANGE and BS_ERR_INTERNAL as above.  On any error the outputs are
+ * left untouched.  Synchronises: the triangle count's times, once for the table, once for the result. */
+int bs_poly_solids_count_dev(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t width, int32_t height,
+                             int32_t n_labels, int64_t num, int64_t den, int32_t cell_log2, const int32_t* d_label_building,
+                             int32_t n_buildings, int32_t bin, int32_t base_z, struct bs_poly_solids* out,
+                             struct bs_outline_triangles* tri, struct bs_clean_outlines* clean,
+                             struct bs_simple_outlines* simple, struct bs_outlines* plain);
+/* The mesh of the last successful count on this context into device buffers of exactly its sizes: d_vertex [n_vertices][4]
+ * (16-byte aligned), d_face_offset [n_faces + 1], d_face_index [n_indices], d_face_building and d_face_kind [n_faces] (a
+ * pointer to an array of no element may be NULL; an empty mesh writes face_offset[0] alone).  May be called more than once.
+ * The emit reads the clean vertices and the triangles of the count: a later count of the clean outlines or of a stage built on
+ * them on this context ends its validity.  BS_ERR_INVALID: null pointer, or no successful count.  Synchronises. */
+int bs_poly_solids_emit_dev(bs_ctx* ctx, int32_t* d_vertex, int32_t* d_face_offset, int32_t* d_face_index,
+                            int32_t* d_face_building, uint8_t* d_face_kind);
+/* Host-memory twin: label, top and label_building are host pointers; both steps; the mesh comes back in out's library-owned
+ * arrays, *tri and *clean (unless NULL) as bs_outline_triangles returns them. */
+int bs_poly_solids(bs_ctx* ctx, const int32_t* label, const int32_t* top, int32_t width, int32_t height, int32_t n_labels,
+                   int64_t num, int64_t den, int32_t cell_log2, const int32_t* label_building, int32_t n_buildings, int32_t bin,
+                   int32_t base_z, struct bs_poly_solids* out, struct bs_outline_triangles* tri, struct bs_clean_outlines* clean,
+                   struct bs_simple_outlines* simple, struct bs_outlines* plain);
+void bs_poly_solids_free(struct bs_poly_solids* s);
+
 #ifdef __cplusplus
 }
 #endif
