@@ -164,7 +164,7 @@ inline int grid_blocks(int64_t n, int bs) { return (int)((n + bs - 1) / bs); }
 
 }  // namespace
 
-// Occupied-cell count at a trial cell size (keys only).  (Counting by insertion into an open-addressing table instead
+// Occupied-cell count at a trial cell size (keys only, or pairs: see sort_count_keys).  (Counting by insertion into an open-addressing table instead
 // of sorting was measured: the points arrive in the caller's order, 50 M random probes into a 1 GB table take 4.5 ms
 // against 2.7 ms for the radix sort -- grid stage 19.7 instead of 11.0 ms.)
 // Bits a Morton cell key occupies when the longest axis has ext / cell + 1 cells: the radix sorts run over these only
@@ -177,16 +177,26 @@ static int morton_key_bits(int64_t ext, int cell)
   return std::min(63, 3 * bits);
 }
 
-// sort the keys in keys_in over [0, end_bit) and count the distinct ones (synchronises)
-static int sort_count_keys(bs_ctx* ctx, int64_t n, int end_bit, int64_t* ncell)
+// sort the keys in keys_in over [0, end_bit) and count the distinct ones (synchronises).  pairs: vals_in goes along
+// into vals_out, which is then what step 3 of build_grid would produce at this cell size (the same keys, the same
+// stable sort) -- an accepted trial is the grid's sort.
+static int sort_count_keys(bs_ctx* ctx, int64_t n, int end_bit, int64_t* ncell, bool pairs)
 {
   hipStream_t st = ctx->stream;
   uint64_t* kin = ctx->keys_in.as<uint64_t>();
   uint64_t* kout = ctx->keys_out.as<uint64_t>();
+  int32_t* vin = ctx->vals_in.as<int32_t>();
+  int32_t* vout = ctx->vals_out.as<int32_t>();
   size_t tb = 0;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, kin, kout, (int)n, 0, end_bit, st));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(ctx->cub_tmp.p, tb, kin, kout, (int)n, 0, end_bit, st));
+  if (pairs) {
+    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+    BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
+    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+  } else {
+    BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, kin, kout, (int)n, 0, end_bit, st));
+    BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
+    BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(ctx->cub_tmp.p, tb, kin, kout, (int)n, 0, end_bit, st));
+  }
   unsigned long long* cnt = ctx->misc.as<unsigned long long>() + 8;
   BS_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st));
   count_heads_kernel<<<std::min(grid_blocks(n, 256), 1024), 256, 0, st>>>(kout, n, cnt);
@@ -198,11 +208,19 @@ static int sort_count_keys(bs_ctx* ctx, int64_t n, int end_bit, int64_t* ncell)
 }
 
 static int count_cells(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, const int mn[3], int cell, int64_t ext,
-                       int64_t* ncell)
+                       int64_t* ncell, bool pairs)
 {
   cellkey_kernel<<<grid_blocks(n, 256), 256, 0, ctx->stream>>>(d_xyz, n, mn[0], mn[1], mn[2], cell, 1,
-                                                               ctx->keys_in.as<uint64_t>(), nullptr);
-  return sort_count_keys(ctx, n, morton_key_bits(ext, cell), ncell);
+                                                               ctx->keys_in.as<uint64_t>(),
+                                                               pairs ? ctx->vals_in.as<int32_t>() : nullptr);
+  return sort_count_keys(ctx, n, morton_key_bits(ext, cell), ncell, pairs);
+}
+
+// BS_GRID_REUSE=0 (read in every call): no trial sorts pairs, step 3 always sorts again
+static bool grid_reuse_on()
+{
+  const char* e = getenv("BS_GRID_REUSE");
+  return !e || atoi(e) != 0;
 }
 
 int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t n, double radius,
@@ -237,15 +255,26 @@ int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t
   int64_t ext = 1;
   for (int a = 0; a < 3; a++)
     ext = std::max<int64_t>(ext, (int64_t)bb[3 + a] - bb[a] + 1);
+  static const int morton = []() {
+    const char* e = getenv("BS_GRID_ORDER");  // developer A/B switch: "raster" restores the x-fastest cell order
+    return (e && e[0] == 'r') ? 0 : 1;
+  }();
+  // The first trial is usually rejected and sorts keys only.  Every later trial writes the values and sorts pairs: if
+  // its cell size is the one the rule ends on, its output IS step 3's (Morton keys, the same stable sort) and step 3
+  // is skipped.  sorted_cell: the cell size whose sorted pairs are in keys_out / vals_out, 0 = none.
+  const bool reuse = morton && grid_reuse_on();
+  int sorted_cell = 0;
   int cell = cell_hint > 0 ? cell_hint : (int)std::max(1.0, std::ceil(radius));
   if (cell_hint <= 0) {
     const double target = std::max(4.0, 0.5 * k);
     const int cmin = cell;
     for (int it = 0; it < 4; it++) {
       int64_t nc = 0;
-      int rc = count_cells(ctx, d_xyz, n, bb, cell, ext, &nc);
+      const bool pairs = reuse && it >= 1;
+      int rc = count_cells(ctx, d_xyz, n, bb, cell, ext, &nc, pairs);
       if (rc != BS_OK)
         return rc;
+      sorted_cell = pairs ? cell : 0;
       double occ = (double)n / (double)std::max<int64_t>(nc, 1);
       if (occ >= 0.7 * target && occ <= 1.6 * target)
         break;
@@ -261,21 +290,19 @@ int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t
   while (ext / cell + 1 >= (1 << 21))
     cell *= 2;
 
-  // 3. keys + sort
+  // 3. keys + sort (unless the last trial did both at this cell size)
   uint64_t* kin = ctx->keys_in.as<uint64_t>();
   uint64_t* kout = ctx->keys_out.as<uint64_t>();
   int32_t* vin = ctx->vals_in.as<int32_t>();
   int32_t* vout = ctx->vals_out.as<int32_t>();
-  static const int morton = []() {
-    const char* e = getenv("BS_GRID_ORDER");  // developer A/B switch: "raster" restores the x-fastest cell order
-    return (e && e[0] == 'r') ? 0 : 1;
-  }();
-  cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, bb[0], bb[1], bb[2], cell, morton, kin, vin);
   size_t tb = 0;
-  const int end_bit = morton ? morton_key_bits(ext, cell) : 63;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+  if (sorted_cell != cell) {
+    cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, bb[0], bb[1], bb[2], cell, morton, kin, vin);
+    const int end_bit = morton ? morton_key_bits(ext, cell) : 63;
+    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+    BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
+    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+  }
 
   // 4. unique cells (run-length encode), starts (exclusive scan)
   BS_HIP(ctx, ctx->uniq_keys.reserve(sizeof(uint64_t) * n));
@@ -566,19 +593,24 @@ int build_grid_tiled(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_off, co
   BS_HIP(ctx, upload_desc(1));  // (the keys read only the minima)
   const TileDesc* d_desc = ctx->bt[BT_DESC].as<TileDesc>();
 
-  // 2. cell size (build_grid's rule, counted with the tiled keys)
+  // 2. cell size (build_grid's rule, counted with the tiled keys; the keys are always Morton keys here)
+  const bool reuse = grid_reuse_on();
+  int sorted_cell = 0;
   int cell = cell_hint > 0 ? cell_hint : (int)std::max(1.0, std::ceil(radius));
   if (cell_hint <= 0) {
     const double target = std::max(4.0, 0.5 * k);
     const int cmin = cell;
     for (int it = 0; it < 4 && fits(cell); it++) {
       const int mb = morton_key_bits(ext, cell);
+      const bool pairs = reuse && it >= 1;  // (as in build_grid)
       tiled_cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, d_off, nt, d_desc, cell, mb,
-                                                                ctx->keys_in.as<uint64_t>(), nullptr);
+                                                                ctx->keys_in.as<uint64_t>(),
+                                                                pairs ? ctx->vals_in.as<int32_t>() : nullptr);
       int64_t nc = 0;
-      rc = sort_count_keys(ctx, n, tbits + mb, &nc);
+      rc = sort_count_keys(ctx, n, tbits + mb, &nc, pairs);
       if (rc != BS_OK)
         return rc;
+      sorted_cell = pairs ? cell : 0;
       double occ = (double)n / (double)std::max<int64_t>(nc, 1);
       if (occ >= 0.7 * target && occ <= 1.6 * target)
         break;
@@ -596,17 +628,19 @@ int build_grid_tiled(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_off, co
   const int mbits = morton_key_bits(ext, cell);
   BS_HIP(ctx, upload_desc(cell));
 
-  // 3. keys + sort: (tile, Morton cell)
+  // 3. keys + sort: (tile, Morton cell), unless the last trial did both at this cell size
   uint64_t* kin = ctx->keys_in.as<uint64_t>();
   uint64_t* kout = ctx->keys_out.as<uint64_t>();
   int32_t* vin = ctx->vals_in.as<int32_t>();
   int32_t* vout = ctx->vals_out.as<int32_t>();
-  tiled_cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, d_off, nt, d_desc, cell, mbits, kin, vin);
   size_t tb = 0;
-  const int end_bit = tbits + mbits;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+  if (sorted_cell != cell) {
+    tiled_cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, d_off, nt, d_desc, cell, mbits, kin, vin);
+    const int end_bit = tbits + mbits;
+    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+    BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
+    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+  }
 
   // 4. unique cells, starts
   BS_HIP(ctx, ctx->uniq_keys.reserve(sizeof(uint64_t) * n));

@@ -20,6 +20,9 @@
 // rings, or whose r-ball holds more than max_nn points (needs a top-max_nn
 // selection), are appended to a work list and finished by knn_general_kernel,
 // which keeps explicit sorted lists in scratch and falls back to a full scan.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -277,15 +280,37 @@ __global__ __launch_bounds__(256) void knn_fast_kernel(GridOf<TILED> g, int64_t 
 #define BS_KNN_CAP4 0
 #endif
 constexpr int KBUF = 8;  // waiting candidates per thread of knn_fast2_kernel
+// cells of a ring-1 slab whose first hash probes are in flight together in the STREAM instances (1, 3 or 9; the
+// register count is the same with 3 and 9)
+#ifndef BS_KNN_PROBE_GROUP
+#define BS_KNN_PROBE_GROUP 3
+#endif
+#ifdef BS_PROBE
+__device__ unsigned long long g_knn_probe[8];  // developer build: see the end of knn_fast2_kernel's ring loop
+#endif
 
 // REL32: the moment sums of the d^2 < r^2 ball are kept RELATIVE to the query in 32-bit registers (r <= 181 mm: every
 // product is below 2^15, a ball the fast path accepts holds at most max_nn <= 64 points) and turned into the absolute
 // 64-bit sums at the end -- exactly: sum x = n q + sum e, sum x^2 = n q^2 + 2 q sum e + sum e^2, sum xy = n qx qy +
 // qx sum ey + qy sum ex + sum ex ey.  Ten registers instead of nineteen and 24-bit multiplies instead of 64-bit
 // multiply-adds: the kernel drops below 128 registers (4 waves per SIMD instead of 3).
-template <int KC, bool REL32, bool TILED = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 && REL32 && BS_KNN_CAP4 ? 4 : 2))) void knn_fast2_kernel(GridOf<TILED> g, int64_t q_begin, int64_t q_end, int K,
-                                                       int max_nn, double r2, int32_t* __restrict__ neigh,
+//
+// STREAM: ring 1 (26 cells, where nearly every query is settled) is walked as ONE candidate stream per lane instead of
+// one loop per cell.  With a loop per cell the wave runs, for its u-th cell, as many batches as the fullest u-th cell
+// of any of its 64 lanes, while the lanes whose u-th cell is empty or short sit out: the sum over the cells of the
+// per-cell maxima.  With a stream per lane it runs as many batches as its longest lane needs.  Per slab of dz (9, 8 and
+// 9 cells) the cells are probed first and the occupied cells' [start, end) go to the lane's column of an LDS array; a
+// batch takes its four candidates from the range the lane is in and, where that ends inside the batch, goes on in the
+// next one.  The multiset of candidates of a lane is the same as with the loops, only the moments at which the waiting
+// candidates are merged differ: the k-list is the K smallest of unique keys, the moment sums are integers, the
+// runner-up is a minimum and the admission bound is never below the true one -- none depends on the order.
+// (STREAM = false: the loops, BS_KNN_STREAM=0.)
+//
+// r2le = ceil(r^2) - 1, saturated at 2^32 - 1: d^2 is an integer, so d2 <= r2le is (double)d2 < r2 without the f64
+// conversion and compare in every slot.
+template <int KC, bool REL32, bool TILED = false, bool STREAM = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 && REL32 && BS_KNN_CAP4 ? 4 : (KC == 16 && REL32 && STREAM ? 3 : 2)))) void knn_fast2_kernel(GridOf<TILED> g, int64_t q_begin, int64_t q_end, int K,
+                                                       int max_nn, double r2, uint32_t r2le, int32_t* __restrict__ neigh,
                                                        double* __restrict__ normals,
                                                        int32_t* __restrict__ fb_list,
                                                        int32_t* __restrict__ fb_count, uint64_t cert_r2,
@@ -314,6 +339,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 &&
   // candidates that beat the list's last entry wait in LDS (KBUF per thread, slot-major: conflict-free) ...
   __shared__ uint32_t blo[KBUF][256], bhi[KBUF][256];
   __shared__ int bps[KBUF][256];
+  // STREAM: [start, end) of the occupied cells of the ring-1 slab a lane is walking, slot-major like the wait buffers
+  // (9 + 9 registers per lane do not fit beside the lists at three waves per SIMD; 42 KB per block in all, three
+  // blocks in a CU's 160 KB)
+  __shared__ int srs[STREAM ? 9 : 1][STREAM ? 256 : 1], sre[STREAM ? 9 : 1][STREAM ? 256 : 1];
   int nbuf = 0;
   uint64_t best[KC];
   // cell-sorted POSITION of every kept candidate, carried through the insertion network as a payload:
@@ -332,7 +361,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 &&
   // compare-exchanges) and merges them into its list (reverse, lower half, bitonic merge: KBUF + KC/2 log2 KC more).
   // The per-candidate insertion network this replaces (KC compare-exchanges, run by the WHOLE wave whenever ONE of its
   // 64 queries admits a candidate -- nearly always) cost 3x as many instructions per query.
-  auto flush = [&]() {
+  auto flush = [&]() __attribute__((always_inline)) {
     uint64_t bk[KBUF];
     int bp[KBUF];
 #pragma unroll
@@ -375,8 +404,167 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 &&
     }
 #undef BS_CE
   };
+  // one candidate slot: the point c at sorted position t (real = false: padding, a repeated point that counts for nothing)
+  auto cand_slot = [&](const int4 c, const int t, const bool real) __attribute__((always_inline)) {
+    const int ex = c.x - q[0], ey = c.y - q[1], ez = c.z - q[2];
+    // (d2 from __mul24 products -- exact here, every offset fits 24 bits -- was measured: 12.33 k instead of 12.06 k
+    // vector instructions per wave at 50 M points, not kept)
+    const uint32_t d2 = (uint32_t)(ex * ex) + (uint32_t)(ey * ey) + (uint32_t)(ez * ez);
+    const uint64_t key = ((uint64_t)d2 << 32) | (uint32_t)c.w;
+    if (real && key < best[KC - 1]) {  // (the list's last entry as of the last merge: never below the true bound)
+      blo[nbuf][threadIdx.x] = (uint32_t)key;
+      bhi[nbuf][threadIdx.x] = d2;
+      bps[nbuf][threadIdx.x] = t;
+      nbuf++;
+    } else if (real) {
+      runner = key < runner ? key : runner;  // not admitted
+    }
+    if (__ballot(nbuf == KBUF))
+      flush();
+    if (real && d2 <= r2le) {
+      if constexpr (REL32) {
+        rsx += ex;
+        rsy += ey;
+        rsz += ez;
+        rsxx += __mul24(ex, ex);
+        rsyy += __mul24(ey, ey);
+        rszz += __mul24(ez, ez);
+        rsxy += __mul24(ex, ey);
+        rsxz += __mul24(ex, ez);
+        rsyz += __mul24(ey, ez);
+        rn += 1;
+      } else {
+        moments_add(m, c.x, c.y, c.z);
+      }
+    }
+  };
+#ifdef BS_PROBE
+  // developer build (-DBS_PROBE): batches the wave executed in rings 0 and 1 against what its lanes need
+  int probe_exec = 0, probe_cand = 0;
+#define BS_PROBE_BATCH()                                                         \
+  do {                                                                           \
+    if (rho <= 1 && (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) \
+      probe_exec++;                                                              \
+  } while (0)
+#define BS_PROBE_CELL(cnt) \
+  do {                     \
+    if (rho <= 1)          \
+      probe_cand += (cnt); \
+  } while (0)
+#else
+#define BS_PROBE_BATCH() \
+  do {                   \
+  } while (0)
+#define BS_PROBE_CELL(cnt) \
+  do {                     \
+  } while (0)
+#endif
   for (int rho = 0; rho <= BS_FAST_RINGS && !done; rho++) {
-    for (int dz = -rho; dz <= rho; dz++) {
+    const bool streamed = STREAM && rho == 1;
+    if (streamed) {
+#pragma unroll 1
+      for (int dz = -1; dz <= 1; dz++) {
+        const int cz = ci[2] + dz;
+        const bool zok = cz >= 0 && cz < g.dim[2];
+        // The occupied cells' ranges go to the lane's column of srs / sre, in the loops' order.  The first probes of GP
+        // cells are issued together (a cell that is not wanted probes the query's own).
+        int cnt = 0;
+        constexpr int GP = BS_KNN_PROBE_GROUP;
+        static_assert(9 % GP == 0, "probe groups tile the slab");
+#pragma unroll
+        for (int u0 = 0; u0 < 9; u0 += GP) {
+          int4 raw[GP];
+          uint64_t ck[GP];
+          uint32_t hh[GP];
+          bool want[GP];
+#pragma unroll
+          for (int w = 0; w < GP; w++) {
+            const int u = u0 + w;
+            const int cy = ci[1] + u / 3 - 1, cx = ci[0] + u % 3 - 1;
+            want[w] = zok && cy >= 0 && cy < g.dim[1] && cx >= 0 && cx < g.dim[0] && !(dz == 0 && u == 4);
+            ck[w] = cell_key<TILED>((uint32_t)(want[w] ? cx : ci[0]), (uint32_t)(want[w] ? cy : ci[1]),
+                                    (uint32_t)(want[w] ? cz : ci[2]), kbase);
+            hh[w] = hash_cell(ck[w]) & g.hmask;
+            raw[w] = *reinterpret_cast<const int4*>(&g.table[hh[w]]);
+          }
+#pragma unroll
+          for (int w = 0; w < GP; w++) {
+            int cs = 0, ce = 0;
+            if (want[w]) {
+              for (;;) {  // (linear probing: the first probe is nearly always the cell or an empty slot)
+                const uint64_t ek = (uint64_t)(uint32_t)raw[w].x | ((uint64_t)(uint32_t)raw[w].y << 32);
+                if (ek == ck[w]) {
+                  cs = raw[w].z;
+                  ce = raw[w].w;
+                  break;
+                }
+                if (ek == ~0ull)
+                  break;
+                hh[w] = (hh[w] + 1) & g.hmask;
+                raw[w] = *reinterpret_cast<const int4*>(&g.table[hh[w]]);
+              }
+            }
+            BS_PROBE_CELL(ce - cs);
+            if (cs < ce) {  // (cnt <= u0 + w <= 8)
+              srs[cnt][threadIdx.x] = cs;
+              sre[cnt][threadIdx.x] = ce;
+              cnt++;
+            }
+          }
+        }
+        // [t0, e0): what is left of the range the lane is in, [s1, e1): the range after it ({0, 0}: none), cur: the
+        // index of the former.  Nobody but the lane itself reads its column: no barrier.
+        int cur = 0;
+        int t0 = cnt > 0 ? srs[0][threadIdx.x] : 0, e0 = cnt > 0 ? sre[0][threadIdx.x] : 0;
+        int s1 = cnt > 1 ? srs[1][threadIdx.x] : 0, e1 = cnt > 1 ? sre[1][threadIdx.x] : 0;
+        // Bounded by the slab's candidates: a batch takes at least one.  A lane leaves when it is through, as it leaves
+        // the loop of a cell: the wave runs as many batches as its longest lane needs.
+        while (t0 < e0) {
+          BS_PROBE_BATCH();
+          const int rem = e0 - t0;  // (> 0)
+          int ta[4];
+          bool rl[4];
+          int4 cc[4];
+#pragma unroll
+          for (int v = 0; v < 4; v++) {
+            const int t1 = s1 + (v - rem);  // (meaningful only where v >= rem: the batch goes on in the next range)
+            rl[v] = v < rem || t1 < e1;
+            ta[v] = v < rem ? t0 + v : t1;
+            cc[v] = g.spts[rl[v] ? ta[v] : (int)s];  // (padding repeats the query's own point)
+          }
+#pragma unroll
+          for (int v = 0; v < 4; v++)
+            cand_slot(cc[v], ta[v], rl[v]);
+          // The range ends with this batch: the next one takes its place, less what the batch took of it -- and if
+          // that was all of it, the one after it, of which nothing was taken.  (Selects under branches the whole wave
+          // takes; srs / sre are read at index <= 8 whatever cur is.)
+          const bool pop1 = rem <= 4;
+          t0 += pop1 ? 0 : 4;
+          if (__ballot(pop1)) {
+            const bool more1 = pop1 && cur + 2 < cnt;
+            const int i2 = min(cur + 2, 8);
+            const int s2 = more1 ? srs[i2][threadIdx.x] : 0, e2 = more1 ? sre[i2][threadIdx.x] : 0;
+            t0 = pop1 ? s1 + (4 - rem) : t0;
+            e0 = pop1 ? e1 : e0;
+            s1 = pop1 ? s2 : s1;
+            e1 = pop1 ? e2 : e1;
+            cur += pop1 ? 1 : 0;
+            const bool pop2 = pop1 && e0 != 0 && t0 >= e0;
+            if (__ballot(pop2)) {
+              const bool more2 = pop2 && cur + 2 < cnt;
+              const int i3 = min(cur + 2, 8);
+              const int s3 = more2 ? srs[i3][threadIdx.x] : 0, e3 = more2 ? sre[i3][threadIdx.x] : 0;
+              t0 = pop2 ? s1 : t0;
+              e0 = pop2 ? e1 : e0;
+              s1 = pop2 ? s3 : s1;
+              e1 = pop2 ? e3 : e1;
+              cur += pop2 ? 1 : 0;
+            }
+          }
+        }
+      }
+    }
+    for (int dz = -rho; !streamed && dz <= rho; dz++) {
       const int cz = ci[2] + dz;
       if (cz < 0 || cz >= g.dim[2])
         continue;
@@ -386,9 +574,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 &&
           continue;
         const bool face = (dz == -rho || dz == rho || dy == -rho || dy == rho);
         const int step = face ? 1 : (rho > 0 ? 2 * rho : 1);
-        // The kernel is bound by latency, not by arithmetic (108-128 registers: 4 waves per SIMD, and every hash
-        // probe and every candidate used to be ONE load followed by its use): the first probes of up to three cells
-        // of a row are issued together, and the candidates of a cell are fetched four at a time.
+        // Every hash probe and every candidate used to be ONE load followed by its use: the first probes of up to
+        // three cells of a row are issued together, and the candidates of a cell are fetched four at a time.  (What
+        // bounds the kernel since: see the counters at launch_knn.)
         for (int dx0 = -rho; dx0 <= rho; dx0 += 3 * step) {
           int4 raw[3];
           uint64_t ck[3];
@@ -428,46 +616,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 &&
           for (int u = 0; u < 3; u++) {
             const int cs = u == 0 ? cs3[0] : (u == 1 ? cs3[1] : cs3[2]);
             const int ce = u == 0 ? ce3[0] : (u == 1 ? ce3[1] : ce3[2]);
+            BS_PROBE_CELL(ce - cs);
             for (int t0 = cs; t0 < ce; t0 += 4) {
+              BS_PROBE_BATCH();
               int4 cc[4];
 #pragma unroll
               for (int v = 0; v < 4; v++)
                 cc[v] = g.spts[t0 + v < ce ? t0 + v : ce - 1];
 #pragma unroll
-              for (int v = 0; v < 4; v++) {
-                const int t = t0 + v;
-                const int4 c = cc[v];
-                const int ex = c.x - q[0], ey = c.y - q[1], ez = c.z - q[2];
-                const uint32_t d2 = (uint32_t)(ex * ex) + (uint32_t)(ey * ey) + (uint32_t)(ez * ez);
-                const uint64_t key = ((uint64_t)d2 << 32) | (uint32_t)c.w;
-                const bool real = t < ce;  // (the last batch of a cell repeats its last point)
-                if (real && key < best[KC - 1]) {  // (the list's last entry as of the last merge: never below the true bound)
-                  blo[nbuf][threadIdx.x] = (uint32_t)key;
-                  bhi[nbuf][threadIdx.x] = d2;
-                  bps[nbuf][threadIdx.x] = t;
-                  nbuf++;
-                } else if (real) {
-                  runner = key < runner ? key : runner;  // not admitted
-                }
-                if (__ballot(nbuf == KBUF))
-                  flush();
-                if (real && (double)d2 < r2) {
-                  if constexpr (REL32) {
-                    rsx += ex;
-                    rsy += ey;
-                    rsz += ez;
-                    rsxx += __mul24(ex, ex);
-                    rsyy += __mul24(ey, ey);
-                    rszz += __mul24(ez, ez);
-                    rsxy += __mul24(ex, ey);
-                    rsxz += __mul24(ex, ez);
-                    rsyz += __mul24(ey, ez);
-                    rn += 1;
-                  } else {
-                    moments_add(m, c.x, c.y, c.z);
-                  }
-                }
-              }
+              for (int v = 0; v < 4; v++)
+                cand_slot(cc[v], t0 + v, t0 + v < ce);  // (the last batch of a cell repeats its last point)
             }
           }
         }
@@ -489,6 +647,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KC == 16 &&
       done = knn_ok && nrm_ok;
     }
   }
+#undef BS_PROBE_BATCH
+#undef BS_PROBE_CELL
+#ifdef BS_PROBE
+  {  // per wave: executed batches, the largest and the summed ceil(T_lane / 4) of its lanes, lanes, waves
+    const unsigned long long act = __ballot(1);
+    const int lane = threadIdx.x & 63;
+    const int need = (probe_cand + 3) / 4;
+    int ex_sum = probe_exec, nd_max = need, nd_sum = need, ln = 1;
+    for (int o = 32; o > 0; o >>= 1) {
+      const int a = __shfl_xor(ex_sum, o), b = __shfl_xor(nd_max, o), c = __shfl_xor(nd_sum, o), d = __shfl_xor(ln, o);
+      const bool ok = (act >> (lane ^ o)) & 1;
+      ex_sum += ok ? a : 0;
+      nd_max = ok && b > nd_max ? b : nd_max;
+      nd_sum += ok ? c : 0;
+      ln += ok ? d : 0;
+    }
+    if (lane == __ffsll((long long)act) - 1) {
+      atomicAdd(&g_knn_probe[0], (unsigned long long)ex_sum);
+      atomicAdd(&g_knn_probe[1], (unsigned long long)nd_max);
+      atomicAdd(&g_knn_probe[2], (unsigned long long)nd_sum);
+      atomicAdd(&g_knn_probe[3], (unsigned long long)ln);
+      atomicAdd(&g_knn_probe[4], 1ull);
+    }
+  }
+#endif
   uint64_t kth_final = ~0ull;
 #pragma unroll
   for (int j = 0; j < KC; j++)
@@ -941,20 +1124,37 @@ static int launch_knn(bs_ctx* ctx, const GridOf<TILED>& g, int64_t q_begin, int6
     // instead of 16.0 k vector instructions per wave, but 135 instead of 108 registers (3 instead of 4 waves per
     // SIMD) -- capped to 128 registers the spills (140 bytes of scratch) cost more than the fourth wave brings
     // (66 ms).  BS_KNN_BUFFERED=0 selects the first kernel.
+    // What bounds knn_fast2_kernel (urban 50 M, rocprofv3 --pmc, profiles/knn_stream_ab.txt): 12.2 k vector and 265
+    // memory instructions per wave, SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES = 0.23 -- at three waves per SIMD the vector
+    // ALU is busy two thirds of the time: arithmetic is the larger half, latency the smaller.  With a loop per cell a
+    // wave ran 29.7 batches in rings 0 and 1 where its longest lane needs 20.1; with ring 1 as one stream per lane
+    // (STREAM) it runs 22.4, 12.0 k vector and 236 memory instructions, and waits 6 % less: 27.4 -> 26.3 ms.
     const bool buffered = getenv("BS_KNN_BUFFERED") ? atoi(getenv("BS_KNN_BUFFERED")) != 0 : true;
     const bool rel32 = r2 <= 32761.0 && !getenv("BS_KNN_MOMENTS64");  // r <= 181 mm (see REL32)
+    // ring 1 as one candidate stream per lane (see STREAM); BS_KNN_STREAM=0 selects the loop per cell
+    // (not for the batched <16, 64-bit moments> instance: 178 registers, two waves per SIMD instead of the loops' three)
+    const bool stream = (getenv("BS_KNN_STREAM") ? atoi(getenv("BS_KNN_STREAM")) != 0 : true) && !(TILED && p.k <= 16 && !rel32);
+    const uint32_t r2le = (uint32_t)(std::min(std::ceil(r2), 4294967296.0) - 1.0);  // (radius > 0: ceil(r2) >= 1)
+#define BS_FAST2(KC_, REL_)                                                                                              \
+  do {                                                                                                                   \
+    if (stream)                                                                                                          \
+      knn_fast2_kernel<KC_, REL_, TILED, true><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, r2le, d_neigh, \
+                                                                        d_normals, fb_list, fb_count, cert_r2, uncert,  \
+                                                                        d_npos, tie_rows);                              \
+    else                                                                                                                 \
+      knn_fast2_kernel<KC_, REL_, TILED, false><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, r2le, d_neigh, \
+                                                                         d_normals, fb_list, fb_count, cert_r2, uncert, \
+                                                                         d_npos, tie_rows);                             \
+  } while (0)
     if (buffered && p.k <= 16 && rel32)
-      knn_fast2_kernel<16, true, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
-                                                         fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
+      BS_FAST2(16, true);
     else if (buffered && p.k <= 16)
-      knn_fast2_kernel<16, false, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
-                                                          fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
+      BS_FAST2(16, false);
     else if (buffered && rel32)
-      knn_fast2_kernel<32, true, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
-                                                         fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
+      BS_FAST2(32, true);
     else if (buffered)
-      knn_fast2_kernel<32, false, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
-                                                          fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
+      BS_FAST2(32, false);
+#undef BS_FAST2
     else if (p.k <= 16)
       knn_fast_kernel<16, TILED><<<xblocks, 256, 0, st>>>(g, q_begin, q_end, p.k, p.max_nn, r2, d_neigh, d_normals,
                                                   fb_list, fb_count, cert_r2, uncert, d_npos, tie_rows);
@@ -981,6 +1181,18 @@ static int launch_knn(bs_ctx* ctx, const GridOf<TILED>& g, int64_t q_begin, int6
   BS_HIP(ctx, hipMemcpyAsync(&hu, uncert, sizeof hu, hipMemcpyDeviceToHost, st));
   BS_HIP(ctx, hipMemcpyAsync(&ht, tie_rows, sizeof ht, hipMemcpyDeviceToHost, st));
   BS_HIP(ctx, hipStreamSynchronize(st));
+#ifdef BS_PROBE
+  {
+    unsigned long long pr[8] = {};
+    BS_HIP(ctx, hipMemcpyFromSymbol(pr, HIP_SYMBOL(g_knn_probe), sizeof pr));
+    if (pr[4])
+      fprintf(stderr, "knn probe: waves %llu lanes %llu executed batches/wave %.2f largest need/wave %.2f mean need/lane %.2f "
+                      "executed/largest %.3f\n", pr[4], pr[3], (double)pr[0] / pr[4], (double)pr[1] / pr[4],
+              (double)pr[2] / pr[3], (double)pr[0] / (double)pr[1]);
+    const unsigned long long zero[8] = {};
+    BS_HIP(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_knn_probe), zero, sizeof zero));
+  }
+#endif
   ctx->tm.n_fallback_queries = hb[0];
   ctx->tm.tie_rows = (int64_t)ht;
   if (n_uncertified)
