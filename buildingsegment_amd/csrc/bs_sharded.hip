@@ -367,28 +367,57 @@ int rccl_all_to_all_v(void* h, const void* d_send, const int64_t* sb, void* d_re
 // ---- in-process communicator: the ranks are threads of one process ---------------------------------------------
 // (one host thread per GPU without a launcher, or several ranks sharing one GPU in the tests).  Buffers are
 // exchanged by device-to-device copies between the ranks' allocations, synchronised by a host barrier.
+//
+// Every wait of the barrier has a deadline.  A rank that leaves bs_segment_sharded between two collectives (an error
+// only it met) would otherwise leave its peers waiting for ever.  On expiry the communicator is marked broken and
+// everybody is woken: the collective in progress and every later one on this communicator return non-zero on every
+// rank, and each rank leaves bs_segment_sharded with BS_ERR_INTERNAL.
+// Default: the longest legitimate wait is a peer's whole pass while several ranks share one GPU.  The largest pass in
+// profiles/r03_sharded_thread_ranks_one_gpu.txt is 2.31 s (rank 0 of 2, 50 M points, of which 0.85 s growth); twenty
+// times that is 46 s, and the default is 120 s.  Waits on a real multi-GPU node have not been measured.
+// BS_COMM_LOCAL_TIMEOUT_S (seconds, > 0) overrides it; read in bs_comm_local_create.
+constexpr double LOCAL_BARRIER_TIMEOUT_S = 120.0;
+
 struct LocalShared {
   int world;
   std::mutex mu;
   std::condition_variable cv;
   int arrived = 0;
   uint64_t epoch = 0;
+  bool broken = false;
+  double timeout_s = LOCAL_BARRIER_TIMEOUT_S;
   std::vector<const void*> ptr;
   std::vector<const int64_t*> cnt;
   std::vector<int> dev;
   std::atomic<int> refs;
   explicit LocalShared(int w) : world(w), ptr(w), cnt(w), dev(w), refs(w) {}
-  void barrier()
+  // 0: every rank arrived; 1: the communicator is broken (now or before)
+  int barrier()
   {
     std::unique_lock<std::mutex> lk(mu);
+    if (broken)
+      return 1;
     const uint64_t e = epoch;
     if (++arrived == world) {
       arrived = 0;
       epoch++;
       cv.notify_all();
-    } else {
-      cv.wait(lk, [&] { return epoch != e; });
+      return 0;
     }
+    const bool woken = cv.wait_for(lk, std::chrono::duration<double>(timeout_s), [&] { return epoch != e || broken; });
+    if (woken && epoch != e)
+      return 0;
+    broken = true;  // the deadline passed, or a peer gave up
+    cv.notify_all();
+    return 1;
+  }
+  // a rank that cannot take part in a collective: its peers must not wait for it
+  int give_up()
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    broken = true;
+    cv.notify_all();
+    return 1;
   }
 };
 
@@ -403,9 +432,10 @@ int local_all_reduce(void* h, void* d_buf, int64_t count, int dtype, int op, voi
   LocalShared* S = c->sh;
   hipStream_t st = (hipStream_t)stream;
   if (hipStreamSynchronize(st) != hipSuccess)
-    return 1;
+    return S->give_up();
   S->ptr[c->rank] = d_buf;
-  S->barrier();
+  if (S->barrier())
+    return 1;
   int rc = 0;
   if (c->rank == 0) {  // rank 0 folds every peer's buffer into its own ...
     for (int r = 1; r < S->world && !rc; r++) {
@@ -416,12 +446,14 @@ int local_all_reduce(void* h, void* d_buf, int64_t count, int dtype, int op, voi
     }
     rc = hipStreamSynchronize(st) != hipSuccess;
   }
-  S->barrier();
+  if (S->barrier())
+    return 1;
   if (c->rank != 0) {  // ... and the peers copy the result
     const size_t bytes = (size_t)count * (dtype == BS_I64 ? 8 : 4);
     rc = hipMemcpyAsync(d_buf, S->ptr[0], bytes, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess;
   }
-  S->barrier();
+  if (S->barrier())
+    return 1;
   return rc;
 }
 
@@ -431,15 +463,17 @@ int local_all_gather(void* h, const void* d_send, void* d_recv, int64_t bytes, v
   LocalShared* S = c->sh;
   hipStream_t st = (hipStream_t)stream;
   if (hipStreamSynchronize(st) != hipSuccess)
-    return 1;
+    return S->give_up();
   S->ptr[c->rank] = d_send;
-  S->barrier();
+  if (S->barrier())
+    return 1;
   int rc = 0;
   for (int r = 0; r < S->world && !rc; r++)
     if (bytes > 0)
       rc = hipMemcpyAsync((char*)d_recv + (size_t)r * bytes, S->ptr[r], (size_t)bytes, hipMemcpyDeviceToDevice, st) != hipSuccess;
   rc = rc || hipStreamSynchronize(st) != hipSuccess;
-  S->barrier();
+  if (S->barrier())
+    return 1;
   return rc;
 }
 
@@ -449,10 +483,11 @@ int local_all_to_all_v(void* h, const void* d_send, const int64_t* sb, void* d_r
   LocalShared* S = c->sh;
   hipStream_t st = (hipStream_t)stream;
   if (hipStreamSynchronize(st) != hipSuccess)
-    return 1;
+    return S->give_up();
   S->ptr[c->rank] = d_send;
   S->cnt[c->rank] = sb;
-  S->barrier();
+  if (S->barrier())
+    return 1;
   int rc = 0;
   int64_t ro = 0;
   for (int r = 0; r < S->world && !rc; r++) {
@@ -466,7 +501,8 @@ int local_all_to_all_v(void* h, const void* d_send, const int64_t* sb, void* d_r
     ro += rb[r];
   }
   rc = rc || hipStreamSynchronize(st) != hipSuccess;
-  S->barrier();
+  if (S->barrier())
+    return 1;
   return rc;
 }
 
@@ -667,8 +703,10 @@ int sort_keys(bs_ctx* ctx, const K* kin, K* kout, int64_t n)
 }
 
 int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, const int32_t* d_gidx, int64_t m, int64_t n_total,
-                 const bs_params& p, double halo, int32_t* d_plane_idx, bs_shard_info* info)
+                 const bs_params& p, double halo, int32_t* d_plane_idx, bs_shard_info* info, const char* bad_share)
 {
+  // bad_share: this rank's own share is unusable (see bs_segment_sharded); it takes part as a rank without input until
+  // the first all-reduce has told everybody
   // BS_SHARD_FORCE_COMM=1: issue every collective even at world size 1 (the RCCL calls on a one-GPU box)
   const bool use_comm = comm && (comm->world > 1 || getenv("BS_SHARD_FORCE_COMM") != nullptr);
   Pass P{ctx, use_comm ? comm : nullptr, ctx->stream, comm ? comm->rank : 0, comm ? comm->world : 1};
@@ -697,14 +735,19 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
   int rc = bbox_dev(ctx, d_xyz, m, bb);
   if (rc != BS_OK)
     return rc;
-  int64_t mnmx[6];
+  int64_t mnmx[7];
   for (int a = 0; a < 3; a++) {
     mnmx[a] = m > 0 ? bb[a] : ((int64_t)1 << 40);
     mnmx[3 + a] = m > 0 ? -(int64_t)bb[3 + a] : ((int64_t)1 << 40);  // max as min of the negation: ONE all-reduce
   }
-  rc = P.all_reduce_host(mnmx, 6, BS_MIN);
+  mnmx[6] = bad_share ? -1 : 0;  // (the agreement on the shares rides along)
+  rc = P.all_reduce_host(mnmx, 7, BS_MIN);
   if (rc != BS_OK)
     return rc;
+  if (bad_share)
+    return fail(ctx, BS_ERR_INVALID, bad_share);
+  if (mnmx[6] < 0)
+    return fail(ctx, BS_ERR_INTERNAL, "bs_segment_sharded: another rank passed bad arguments");
   const I3 origin = {mnmx[0], mnmx[1], mnmx[2]};
   int64_t ext = 0;
   for (int a = 0; a < 3; a++)
@@ -1231,6 +1274,11 @@ int bs_comm_local_create(int32_t world, bs_comm_ops* out /* [world] */)
   auto* S = new (std::nothrow) LocalShared(world);
   if (!S)
     return BS_ERR_NOMEM;
+  if (const char* e = getenv("BS_COMM_LOCAL_TIMEOUT_S")) {
+    const double v = atof(e);
+    if (v > 0)
+      S->timeout_s = v;
+  }
   for (int r = 0; r < world; r++) {
     out[r].handle = new LocalHandle{S, r};
     out[r].rank = r;
@@ -1259,17 +1307,22 @@ int bs_segment_sharded(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xy
 {
   if (!ctx)
     return BS_ERR_INVALID;
-  if (!p || !d_plane_idx || m < 0 || (m > 0 && !d_xyz) || n_total <= 0 || n_total >= (int64_t)INT32_MAX - 64 || m > n_total)
+  if (!p || !d_plane_idx || n_total <= 0 || n_total >= (int64_t)INT32_MAX - 64)
     return fail(ctx, BS_ERR_INVALID, "bs_segment_sharded: bad arguments");
   if (comm && (comm->world < 1 || comm->rank < 0 || comm->rank >= comm->world || !comm->all_reduce || !comm->all_gather ||
                !comm->all_to_all_v))
     return fail(ctx, BS_ERR_INVALID, "bs_segment_sharded: incomplete bs_comm_ops");
-  if (comm && comm->world > 1 && !d_gidx && m > 0)
-    return fail(ctx, BS_ERR_INVALID, "bs_segment_sharded: d_gidx is required when the cloud is spread over several ranks");
   if (p->k < 2 || p->k > 32 || n_total < p->k)
     return fail(ctx, BS_ERR_INVALID, "bs_segment_sharded: k out of range or n_total < k");
+  // What describes this rank's own share differs from rank to rank: a rank that returned here would leave its peers
+  // in the first collective.  It goes on without input, and every rank leaves after the first all-reduce.
+  const char* bad_share = nullptr;
+  if (m < 0 || (m > 0 && !d_xyz) || m > n_total)
+    bad_share = "bs_segment_sharded: bad arguments";
+  else if (comm && comm->world > 1 && !d_gidx && m > 0)
+    bad_share = "bs_segment_sharded: d_gidx is required when the cloud is spread over several ranks";
   BS_HIP(ctx, hipSetDevice(ctx->device));
-  return sharded_impl(ctx, comm, d_xyz, d_gidx, m, n_total, *p, halo, d_plane_idx, info);
+  return sharded_impl(ctx, comm, d_xyz, d_gidx, bad_share ? 0 : m, n_total, *p, halo, d_plane_idx, info, bad_share);
 }
 
 int bs_sharded_planes_fetch(bs_ctx* ctx, bs_planes* out)

@@ -417,7 +417,13 @@ int bs_comm_rccl_destroy(void* nccl_comm);
 /* In-process communicator: the `world` ranks are THREADS of one process (one host thread per GPU without a
  * launcher; several ranks sharing one GPU in the tests).  Fills out[0..world-1]; every rank's buffers must be
  * reachable from the others' devices (same device, or peer access enabled by the host).  Collectives are device
- * copies between the ranks' buffers behind a host barrier -- functional, not tuned: use bs_comm_rccl across GPUs. */
+ * copies between the ranks' buffers behind a host barrier -- functional, not tuned: use bs_comm_rccl across GPUs.
+ * Every wait of that barrier has a deadline: 120 s by default, or BS_COMM_LOCAL_TIMEOUT_S seconds (environment,
+ * a number > 0, read by bs_comm_local_create).  When a rank does not arrive in time (it left bs_segment_sharded
+ * with an error of its own, or its thread died) the communicator is broken for good: the collective in progress
+ * and every later one return non-zero on every rank, so bs_segment_sharded returns BS_ERR_INTERNAL instead of
+ * waiting for ever.  Destroy a broken communicator and create a new one.  The default is about fifty times the
+ * longest pass measured with thread-ranks sharing one GPU; waits on a real multi-GPU node have not been measured. */
 int bs_comm_local_create(int32_t world, bs_comm_ops* out /* [world] */);
 void bs_comm_local_destroy(bs_comm_ops* ops /* one entry of the array; call for every rank */);
 
@@ -433,7 +439,12 @@ typedef struct bs_shard_info {
 } bs_shard_info;
 
 /* halo: initial halo width in mm (0 = 2 * radius); doubled until every k-list is certified.  d_gidx may be NULL
- * only at world 1 (identity).  info is optional. */
+ * only at world 1 (identity).  info is optional.
+ * Errors reach every rank: a rank whose own share is unusable (m < 0, m > n_total, a missing d_xyz or d_gidx)
+ * returns BS_ERR_INVALID and its peers BS_ERR_INTERNAL after the first all-reduce; shares that do not cover
+ * 0..n_total-1 exactly once give BS_ERR_INVALID and a halo that cannot be certified within six doublings
+ * BS_ERR_UNCERTIFIED on every rank.  The contexts and the communicator stay usable after these.  Every d_gidx value
+ * must lie in 0..n_total-1: it is used as a subscript before the shares are checked. */
 int bs_segment_sharded(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, const int32_t* d_gidx, int64_t m,
                        int64_t n_total, const bs_params* p, double halo, int32_t* d_plane_idx, bs_shard_info* info);
 /* The planes THIS rank grew in the last bs_segment_sharded, with global ids (1-based rank of the seed among all

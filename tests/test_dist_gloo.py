@@ -16,6 +16,8 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "shard_ref"))
+import scenarios as S  # noqa: E402
 
 
 class OracleBackend:
@@ -105,10 +107,12 @@ def _params(k=15):
 
 def _cloud(name):
     from buildingsegment_amd import synth
+    if name in S.BY_NAME:  # a cloud of the scenario table (tests/shard_ref/scenarios.py)
+        return np.array(S.cloud(S.BY_NAME[name]))
     return synth.plane_cube()[:24000].copy() if name == "plane_cube" else synth.boxes()
 
 
-def _worker(rank, world, port, halo, out, cloud, fail_rank):
+def _worker(rank, world, port, halo, out, cloud, fail_rank, rule=None):
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -119,6 +123,9 @@ def _worker(rank, world, port, halo, out, cloud, fail_rank):
     b = bsd.slab_bounds(n, world)  # the input split is arbitrary: a contiguous 1/N of the input order
     d_xyz = torch.from_numpy(xyz[b[rank]:b[rank + 1]])
     d_gidx = torch.arange(b[rank], b[rank + 1], dtype=torch.int32)
+    if rule is not None:  # ... or any other 1/N: a share rule of the scenario table
+        idx = S.shares(rule, n, world)[rank]
+        d_xyz, d_gidx = torch.from_numpy(np.ascontiguousarray(xyz[idx])), torch.from_numpy(idx.copy())
     try:
         labels, info = bsd.segment_sharded_dev(OracleBackend(fail_rank), d_xyz, d_gidx, n, _params(), halo=halo, want_planes=True)
     except bsd.ShardError as e:
@@ -169,6 +176,46 @@ def test_sharded_run_equals_single_process(oracle, tmp_path, world, halo, cloud)
     assert sum(grown) == len(xyz)                         # stage 3: every point grown by exactly one rank
     if cloud == "boxes":
         assert int(g["components"]) == 6 and sum(1 for v in grown if v > 0) >= min(world, 2)  # the boxes are spread
+
+
+def _dist_start_halo(halo, radius):
+    """the starting halo of dist.segment_sharded_dev, restated: halo if halo > 0 else 2 * radius, at least radius"""
+    h = float(halo) if halo > 0 else 2.0 * radius
+    return max(h, radius)
+
+
+@pytest.mark.parametrize("name,world,rule", [("boxes3_contiguous_w2", 3, "interleaved"), ("boxes3_contiguous_w2", 2, "random"),
+                                             ("disc_retry1_w3", 3, "random"), ("tiny40_w3", 3, "interleaved")])
+def test_scenario_table_through_the_python_orchestration(oracle, tmp_path, name, world, rule):
+    """Share rules that are no index ranges, one component across every slab (all of it grows on one rank) and the
+    cloud whose slabs cannot fill a k-list, through dist.segment_sharded_dev with k = 15.  The retry count follows from
+    the oracle's largest k-th distance and dist.py's own starting halo."""
+    import dataclasses
+    sc = dataclasses.replace(S.BY_NAME[name], k=15)
+    f = S.facts(oracle, sc)
+    xyz, n = f["xyz"], len(f["xyz"])
+    h0 = _dist_start_halo(sc.halo, _params().radius)
+    assert S.retry_margin(f["max_kth"], h0) > 1.0
+    retries = S.expected_retries(f["max_kth"], h0)
+    out = str(tmp_path / "r%d.npz")
+    mp.spawn(_worker, args=(world, _free_port(), sc.halo, out, name, None, rule), nprocs=world, join=True)
+    pl = f["planes"]
+    seen = np.zeros(n, int)
+    grown = []
+    for r in range(world):
+        g = np.load(out % r)
+        assert np.array_equal(g["ng"], f["neigh"][g["idx"]]) and np.array_equal(g["nr"], f["normals"][g["idx"]])
+        assert np.array_equal(g["labels"], f["labels"])
+        assert np.array_equal(g["pid"], pl["id"])
+        assert np.array_equal(g["poff"], pl["offset"]) and np.array_equal(g["pidx"], pl["point_idx"])
+        assert np.array_equal(g["pcenter"], pl["center"])
+        assert np.array_equal(g["pnormal"].view(np.int64), pl["normal"].view(np.int64))
+        assert int(g["retries"]) == retries and int(g["components"]) == f["components"]
+        seen[g["idx"]] += 1
+        grown.append(int(g["n_grow"]))
+    assert (seen == 1).all() and sum(grown) == n
+    if f["components"] == 1:
+        assert sorted(grown) == [0] * (world - 1) + [n] and int(g["cc_iterations"]) >= 2
 
 
 def test_failure_on_one_rank_is_raised_on_every_rank(tmp_path):

@@ -6,11 +6,9 @@
   * world 1 through bs_comm_rccl with BS_SHARD_FORCE_COMM=1: the RCCL calls themselves (ncclAllReduce,
     ncclAllGather, grouped ncclSend / ncclRecv) on a communicator created from bs_comm_rccl_unique_id/_init.
 Labels and plane records must equal the single-process CPU oracle bit for bit."""
-import ctypes as C
 import os
 import subprocess
 import sys
-import threading
 
 import numpy as np
 import pytest
@@ -19,57 +17,26 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _expected(oracle, xyz, k):
-    ng, nr = oracle.knn_normals(xyz, k=k)
-    pi, pl = oracle.region_grow(xyz, nr, ng)
-    return pi, pl
-
-
-def _check_planes(all_planes, pl):
-    all_planes = sorted(all_planes, key=lambda q: q.id)
-    assert [q.id for q in all_planes] == pl["id"].tolist()
-    off = pl["offset"]
-    for i, q in enumerate(all_planes):
-        assert np.array_equal(q.pointIdx, pl["point_idx"][off[i]:off[i + 1]])
-        assert np.array_equal(q.center, pl["center"][i])
-        assert np.array_equal(q.normal.view(np.int64), pl["normal"][i].view(np.int64))
+sys.path.insert(0, os.path.join(ROOT, "tests", "shard_ref"))
+from thread_ranks import Comm, check_planes as _check_planes, expected as _expected, run_ranks  # noqa: E402
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_threads_as_ranks_on_one_gpu(oracle, gpu_ctx, world):
-    import torch
-    from buildingsegment_amd import _lib, api, synth
-    L = _lib.load()
+    from buildingsegment_amd import api, synth
     xyz = synth.boxes()
     n = len(xyz)
     k = 16
-    dev = torch.device("cuda", 0)
-    ops = (_lib.CommOps * world)()
-    assert L.bs_comm_local_create(world, ops) == 0
     bounds = [(n * r) // world for r in range(world + 1)]
-    res = [None] * world
-
-    def run(r):
-        try:
-            ctx = api.Context(0)
-            d_xyz = torch.from_numpy(xyz[bounds[r]:bounds[r + 1]]).to(dev)
-            d_g = torch.arange(bounds[r], bounds[r + 1], dtype=torch.int32, device=dev)
-            d_lab = torch.empty(n, dtype=torch.int32, device=dev)
-            torch.cuda.synchronize()
-            info = ctx.segment_sharded(ops[r], d_xyz.data_ptr(), d_g.data_ptr(), len(d_xyz), n, d_lab.data_ptr(),
-                                       api.default_params(k=k), halo=250.0)
-            res[r] = (d_lab.cpu().numpy(), info, ctx.sharded_planes_fetch())
-            ctx.close()
-        except Exception as e:  # noqa: BLE001
-            res[r] = e
-
-    ts = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for t in ts:
-        t.start()
-    for t in ts:
-        t.join(timeout=600)
-    for r in range(world):
-        L.bs_comm_local_destroy(C.byref(ops[r]))
+    parts = [np.arange(bounds[r], bounds[r + 1], dtype=np.int32) for r in range(world)]
+    comm = Comm(world)
+    ctxs = [api.Context(0) for _ in range(world)]
+    try:
+        res = run_ranks(ctxs, comm, xyz, parts, api.default_params(k=k), 250.0, join_s=600)
+    finally:
+        for c in ctxs:
+            c.close()
+        comm.close()
     for r in range(world):
         assert not isinstance(res[r], Exception), res[r]
     pi, pl = _expected(oracle, xyz, k)
