@@ -41,7 +41,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_clean_outlines_emit_dev", "bs_clean_outlines", "bs_clean_outlines_free", "bs_clean_outlines_write_obj",
            "bs_outline_triangles_count_dev", "bs_outline_triangles_emit_dev", "bs_outline_triangles",
            "bs_outline_triangles_free", "bs_outline_triangles_write_obj", "bs_poly_solids_count_dev",
-           "bs_poly_solids_emit_dev", "bs_poly_solids", "bs_poly_solids_free"]
+           "bs_poly_solids_emit_dev", "bs_poly_solids", "bs_poly_solids_free", "bs_model_raster_dev", "bs_model_raster",
+           "bs_model_raster_free"]
 
 
 class Params(C.Structure):
@@ -252,6 +253,23 @@ class PolySolids(C.Structure):
                 [(k, C.c_double) for k in POLY_MS])
 
 
+MRASTER_FIG_CAP = 512  # BS_MRASTER_FIG_CAP of include/bs_api.h
+MRASTER_CHUNK = 256    # BS_MRASTER_CHUNK
+MRASTER_FIG_GRID = 2048  # BS_MRASTER_FIG_GRID
+MRASTER_FIGURES = ("pixels", "model_pixels", "kept", "multi", "err_pixels", "sum_abs_e2", "max_abs_e2", "sq_lo", "sq_hi")
+MRASTER_TOTALS = ("n_triangles", "total_pixels", "total_model_pixels", "total_kept", "total_err_pixels", "total_sum_abs_e2",
+                  "max_abs_e2_all", "total_sq_lo", "total_sq_hi", "n_uncovered", "n_spill", "n_moved", "n_multi", "sum_cover",
+                  "n_rows", "n_items", "n_empty_spans", "max_span")
+MRASTER_MS = ("ms_rows", "ms_spans", "ms_pixels", "ms_figures")
+
+
+class ModelRaster(C.Structure):
+    """bs_model_raster (include/bs_api.h): totals and per-label figures, host memory owned by the library."""
+    _fields_ = ([(k, C.c_int32) for k in ("width", "height", "n_labels", "fig_cap", "chunk", "reserved")] +
+                [(k, C.c_int64) for k in MRASTER_TOTALS] + [(k, C.POINTER(C.c_int64)) for k in MRASTER_FIGURES] +
+                [(k, C.c_double) for k in MRASTER_MS])
+
+
 class BsError(RuntimeError):
     def __init__(self, status, detail=""):
         self.status = status
@@ -427,5 +445,11 @@ def load():
     L.bs_poly_solids_emit_dev.argtypes = [vp, ip, ip, ip, ip, vp]
     L.bs_poly_solids_free.argtypes = [psp]
     L.bs_poly_solids_free.restype = None
+    mrp = C.POINTER(ModelRaster)
+    L.bs_model_raster_dev.argtypes = [vp, ip, ip, C.c_int32, C.c_int32, ip, ip, ip, mrp]
+    L.bs_model_raster.argtypes = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, ip, ip, ip, mrp,
+                                  otp, cop, sop, olp]
+    L.bs_model_raster_free.argtypes = [mrp]
+    L.bs_model_raster_free.restype = None
     _LIB = L
     return L

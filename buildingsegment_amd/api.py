@@ -944,6 +944,54 @@ class Context:
                                              bin=b, base_z=solids.base_z)
         return p, t, c, plain
 
+    # ---- model raster: the outline triangles back on the lattice, and the model's error (bs_model_raster) -----------------
+    def model_raster(self, label, top, n_labels=None, num=0, den=1, cell_log2=0, images=True):
+        """The outline triangles of the images rasterised back onto the pixel lattice (include/bs_api.h, "model raster").
+        label is [height][width], top [height][width][4] as Solids.top.  images=False leaves the three images out (None)
+        and computes the figures alone.  Returns (ModelRaster, OutlineTriangles, the CleanOutlines with their vertices, the
+        SimpleOutlines without vertices, the plain Outlines without vertices)."""
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        if label.ndim != 2 or label.size == 0:
+            raise ValueError("model_raster: label must be [height][width]")
+        if top is None:
+            raise ValueError("model_raster: the stage needs a top image")
+        top = np.ascontiguousarray(top, dtype=np.int32)
+        if top.shape != label.shape + (4,):
+            raise ValueError("model_raster: top must be [height][width][4]")
+        h, w = label.shape
+        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        img = [np.empty((h, w), np.int32) for _ in range(3)] if images else [None] * 3
+        out, tri, clean = _lib.ModelRaster(), _lib.OutlineTriangles(), _lib.CleanOutlines()
+        simple, plain = _lib.SimpleOutlines(), _lib.Outlines()
+        self._check(self._L.bs_model_raster(self._h, label.ctypes.data, top.ctypes.data, w, h, nl, int(num), int(den),
+                                            int(cell_log2), *[a.ctypes.data if a is not None else None for a in img],
+                                            C.byref(out), C.byref(tri), C.byref(clean), C.byref(simple), C.byref(plain)))
+        return (_take_model_raster(self._L, out, *img), _take_outline_triangles(self._L, tri, True),
+                _take_clean_outlines(self._L, clean, True), _take_simple_outlines(self._L, simple, False),
+                _take_outlines(self._L, plain, False))
+
+    def model_raster_dev(self, d_label, d_top, width, height, d_model=0, d_cover=0, d_mz2=0):
+        """Device-resident raster (bs_model_raster_dev) of the triangles that the last outline_triangles_dev or
+        poly_solids_dev left on this context, which it does not change: d_label and d_top are device pointers (ints) to
+        images of the size of that count; d_model, d_cover, d_mz2 device pointers to int32 [height][width] or 0.  Returns
+        the ModelRaster with its images None."""
+        out = _lib.ModelRaster()
+        self._check(self._L.bs_model_raster_dev(self._h, d_label or None, d_top or None, int(width), int(height),
+                                                d_model or None, d_cover or None, d_mz2 or None, C.byref(out)))
+        return _take_model_raster(self._L, out)
+
+    def model_fidelity(self, roof_facets, solids, tolerance_mm=0, bin=None):
+        """What the polygon model of building_model() at this tolerance costs, per building: model_raster() of the facet
+        image of roof_facets() / roof_structure() with the tops of solids(), its per-label figures added up by
+        facet_building.  Returns (ModelFidelity, ModelRaster)."""
+        if roof_facets.facet is None:
+            raise ValueError("model_fidelity: the facet image is on the device: use model_raster_dev")
+        if solids.top is None:
+            raise ValueError("model_fidelity: the Solids carry no top image (solids(top=True))")
+        num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
+        r = self.model_raster(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)[0]
+        return model_fidelity_of(r, roof_facets.facet_building, solids.n_buildings), r
+
 
 @dataclass
 class PlaneVotes:
@@ -1817,6 +1865,106 @@ def _take_poly_solids(L, out, mesh) -> PolySolids:
                           info=info, **arrs)
     finally:
         L.bs_poly_solids_free(C.byref(out))
+
+
+@dataclass
+class ModelRaster:
+    """bs_model_raster: the totals, the per-label figures (pixels, model_pixels, kept, multi, err_pixels, sum_abs_e2,
+    max_abs_e2, sq_lo, sq_hi; the sum of e2 squared of label l is sq_hi[l] * 2^32 + sq_lo[l]) and the three images: model
+    (the label the model puts on the pixel, -1: none), cover (the triangles that cover its centre), mz2 (twice the model's
+    height at the centre, INT32_MIN where none).  The images are None after model_raster_dev."""
+    width: int
+    height: int
+    n_labels: int
+    fig_cap: int
+    chunk: int
+    n_triangles: int
+    total_pixels: int
+    total_model_pixels: int
+    total_kept: int
+    total_err_pixels: int
+    total_sum_abs_e2: int
+    max_abs_e2_all: int
+    total_sq_lo: int
+    total_sq_hi: int
+    n_uncovered: int
+    n_spill: int
+    n_moved: int
+    n_multi: int
+    sum_cover: int
+    n_rows: int
+    n_items: int
+    n_empty_spans: int
+    max_span: int
+    pixels: np.ndarray
+    model_pixels: np.ndarray
+    kept: np.ndarray
+    multi: np.ndarray
+    err_pixels: np.ndarray
+    sum_abs_e2: np.ndarray
+    max_abs_e2: np.ndarray
+    sq_lo: np.ndarray
+    sq_hi: np.ndarray
+    info: dict = field(default_factory=dict)
+    model: np.ndarray | None = field(default=None, repr=False)
+    cover: np.ndarray | None = field(default=None, repr=False)
+    mz2: np.ndarray | None = field(default=None, repr=False)
+
+
+def _take_model_raster(L, out, model=None, cover=None, mz2=None) -> ModelRaster:
+    """Copy a bs_model_raster into numpy arrays and release it."""
+    n = out.n_labels
+    try:
+        arrs = {k: (np.ctypeslib.as_array(getattr(out, k), (n,)).copy() if n else np.zeros(0, np.int64))
+                for k in _lib.MRASTER_FIGURES}
+        info = {k: getattr(out, k) for k in _lib.MRASTER_MS}
+        return ModelRaster(out.width, out.height, n, out.fig_cap, out.chunk, *[getattr(out, k) for k in _lib.MRASTER_TOTALS],
+                           info=info, model=model, cover=cover, mz2=mz2, **arrs)
+    finally:
+        L.bs_model_raster_free(C.byref(out))
+
+
+@dataclass
+class ModelFidelity:
+    """Per building, from a ModelRaster and the building of every label.  lost: pixels of its labels that the model does
+    not give to the same label; gained: pixels the model gives to one of its labels that the image does not; twice: pixels
+    of its labels in the model that more than one triangle covers (an overlap in plan).  Over the pixels that are labelled
+    in both (err_pixels): the mean and the maximum absolute height error and the RMSE, in the unit of top (millimetres)."""
+    n_buildings: int
+    pixels: np.ndarray
+    lost: np.ndarray
+    gained: np.ndarray
+    twice: np.ndarray
+    err_pixels: np.ndarray
+    mean_abs_mm: np.ndarray
+    max_abs_mm: np.ndarray
+    rmse_mm: np.ndarray
+
+
+def model_fidelity_of(raster, label_building, n_buildings=None) -> ModelFidelity:
+    """The per-label figures of a ModelRaster added up by building (host only; Python integers for the sum of squares)."""
+    lb = np.ascontiguousarray(label_building, dtype=np.int64).reshape(-1)
+    if len(lb) != raster.n_labels:
+        raise ValueError("model_fidelity_of: label_building must have one entry per label")
+    nb = (int(lb.max()) + 1 if len(lb) else 0) if n_buildings is None else int(n_buildings)
+    if len(lb) and (lb.min() < 0 or lb.max() >= nb):
+        raise ValueError("model_fidelity_of: a label_building value outside 0 .. n_buildings - 1")
+
+    def add(v):
+        s = np.zeros(nb, np.int64)
+        np.add.at(s, lb, v)
+        return s
+
+    pixels, kept, errp = add(raster.pixels), add(raster.kept), add(raster.err_pixels)
+    mx = np.zeros(nb, np.int64)
+    np.maximum.at(mx, lb, raster.max_abs_e2)
+    sq = [0] * nb
+    for l, c in enumerate(lb.tolist()):
+        sq[c] += (int(raster.sq_hi[l]) << 32) + int(raster.sq_lo[l])
+    n = np.maximum(errp, 1)
+    rmse = np.array([(sq[c] / 4 / int(n[c])) ** 0.5 for c in range(nb)], np.float64)
+    return ModelFidelity(nb, pixels, pixels - kept, add(raster.model_pixels) - kept, add(raster.multi), errp,
+                         add(raster.sum_abs_e2) / 2.0 / n, mx / 2.0, rmse)
 
 
 def simplify_tolerance(tolerance_mm, bin):

@@ -295,6 +295,10 @@ struct bs_ctx {
   int64_t tr_ntri = 0;
   double tr_ms_emit = 0;
   const int32_t* tr_tri = nullptr;  // (the triangles of the last count, inside tr, for bs_polysolid.hip)
+  // (for bs_modelraster.hip: tri_offset [tr_nl + 1] of the last count on the device, inside tr, nullptr without a ring; the
+  // label count and the image size of that count)
+  const long long* tr_toff = nullptr;
+  int32_t tr_nl = 0, tr_w = 0, tr_h = 0;
   // polygon solids (bs_polysolid.hip): scratch, and what bs_poly_solids_count_dev leaves for bs_poly_solids_emit_dev (the
   // twins, the vertex numbers, the offsets); the emit also reads the clean vertices and the triangles, so a later clean
   // count on this context ends its validity
@@ -303,6 +307,7 @@ struct bs_ctx {
   int32_t ps_bin = 0, ps_base = 0, ps_nl = 0, ps_nr = 0, ps_nsv = 0;
   int64_t ps_nv = 0, ps_nf = 0, ps_ni = 0, ps_ntri = 0;
   double ps_ms_emit[2] = {0, 0};  // vertex pass, face passes of the last emit
+  bs::DevBuf mr[20];  // scratch of the model raster (bs_modelraster.hip); it keeps no state between calls
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew

@@ -34,7 +34,7 @@ namespace bs {
 namespace {
 
 // scratch of bs_ctx::tr
-enum { TR_MISC, TR_ARGS, TR_DESC, TR_LIST, TR_OUTER, TR_RKEY, TR_RM, TR_LOUT, TR_BRIDGE, TR_TRI, TR_WS, TR_OUT, TR_COUNT };
+enum { TR_MISC, TR_ARGS, TR_DESC, TR_LIST, TR_OUTER, TR_RKEY, TR_RM, TR_LOUT, TR_BRIDGE, TR_TRI, TR_WS, TR_OUT, TR_TOFF, TR_COUNT };
 static_assert(TR_COUNT <= (int)(sizeof(bs_ctx::tr) / sizeof(DevBuf)), "bs_ctx::tr is too short");
 
 constexpr int SWEEP_CAP = 1024;
@@ -585,6 +585,10 @@ int triangulate(bs_ctx* ctx, const struct bs_clean_outlines& c, struct bs_outlin
     res.bridge[r] = -1;
   ctx->tr_ntri = ntri;
   ctx->tr_tri = nullptr;
+  ctx->tr_toff = nullptr;  // (for bs_modelraster.hip)
+  ctx->tr_nl = nl;
+  ctx->tr_w = c.width;
+  ctx->tr_h = c.height;
   if (nr == 0)
     return BS_OK;
   BS_HIP(ctx, hipSetDevice(ctx->device));
@@ -607,6 +611,7 @@ int triangulate(bs_ctx* ctx, const struct bs_clean_outlines& c, struct bs_outlin
   BS_HIP(ctx, B[TR_BRIDGE].reserve(8 * (size_t)nr));
   BS_HIP(ctx, B[TR_TRI].reserve(12 * (size_t)std::max<long long>(ntri, 1)));
   BS_HIP(ctx, B[TR_WS].reserve(20 * (size_t)std::max<long long>(ws_total, 1)));
+  BS_HIP(ctx, B[TR_TOFF].reserve(8 * ((size_t)nl + 1)));
   int* d_err = B[TR_MISC].as<int>();
   uint8_t* d_outer = B[TR_OUTER].as<uint8_t>();
   unsigned long long* rkey = B[TR_RKEY].as<unsigned long long>();
@@ -626,6 +631,8 @@ int triangulate(bs_ctx* ctx, const struct bs_clean_outlines& c, struct bs_outlin
   BS_HIP(ctx, hipMemcpyAsync(B[TR_LIST].p, list.data(), 4 * list.size(), hipMemcpyHostToDevice, st));
   BS_HIP(ctx, hipMemcpyAsync(d_outer, outer.data(), (size_t)nr, hipMemcpyHostToDevice, st));
   BS_HIP(ctx, hipMemcpyAsync(B[TR_LOUT].p, lout.data(), sizeof(LabelOut) * (size_t)nl, hipMemcpyHostToDevice, st));
+  BS_HIP(ctx, hipMemcpyAsync(B[TR_TOFF].p, res.tri_offset, 8 * ((size_t)nl + 1), hipMemcpyHostToDevice, st));
+  ctx->tr_toff = B[TR_TOFF].as<long long>();
   tri_ring_init_kernel<<<sweep(nr), 256, 0, st>>>(nr, rkey, rm);
   tri_ring_left_kernel<0><<<sweep(nsv), 256, 0, st>>>(args.xy, args.ring, d_outer, nsv, nr, rkey, rm, d_err);
   tri_ring_left_kernel<1><<<sweep(nsv), 256, 0, st>>>(args.xy, args.ring, d_outer, nsv, nr, rkey, rm, d_err);

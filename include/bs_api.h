@@ -1522,6 +1522,94 @@ int bs_poly_solids(bs_ctx* ctx, const int32_t* label, const int32_t* top, int32_
                    struct bs_simple_outlines* simple, struct bs_outlines* plain);
 void bs_poly_solids_free(struct bs_poly_solids* s);
 
+/* ---- model raster: the outline triangles back on the pixel lattice, and the model's error against the images ----
+ *
+ * The inverse of the chain facets -> outlines -> simplified -> clean -> triangles.  Per pixel: the label the model puts there,
+ * how many triangles cover it, and the model's height at the pixel centre.  Per label: exact fidelity figures against the label
+ * image and top.  Everything is an exact integer.  It reports overlaps and swept holes; it repairs nothing.
+ *
+ * Input.  The state of a successful bs_outline_triangles_count_dev on the context, counted with a top image
+ * (bs_poly_solids_count_dev runs that count, so its state serves as well): the clean vertices sxy, sz; tri, tri_offset,
+ * label_status.  A label image d_label [height][width] and d_top [height][width][4] of the size of the count -- normally the
+ * images of the count; the stage does not require it.  n_labels is the count's.  L(p) is label[p] if it lies in
+ * 0 .. n_labels - 1, else -1.
+ *
+ * Coverage, in doubled lattice units.  The centre of pixel (x, y) is P = (2 x + 1, 2 y + 1).  A triangle slot t with vertices
+ * a, b, c (not -1) has the doubled positions A, B, C and the weights w_a = orient(P, B, C), w_b = orient(P, C, A),
+ * w_c = orient(P, A, B) in int64.  Each weight belongs to an edge u -> v: B -> C, C -> A, A -> B.  t covers the pixel iff every
+ * weight is > 0, or is == 0 and its edge has v.y > u.y.  A centre never lies on a vertex or on an axis-parallel edge (its
+ * coordinates are odd, theirs even), and the shared edge of two triangles runs in opposite directions in the two, so exactly
+ * one of them owns a centre on it.  cover[p] is the number of slots covering p; win[p] the lowest covering slot, -1 if none;
+ * M(p) the label of win[p] by tri_offset, -1 if none.
+ *
+ * Height.  For win[p] = t: D = w_a + w_b + w_c (> 0), N = w_a sz[a] + w_b sz[b] + w_c sz[c], and
+ * mz2[p] = floor((4 N + D) / (2 D)): the model height at the centre times two, rounded half up; INT32_MIN where win[p] < 0.
+ * The pixel-exact surface at the centre lies on the diagonal 00-11 of both top triangles; its doubled height is t00 + t11
+ * (top[p][0] + top[p][3]).  Where L(p) >= 0 and M(p) >= 0: e2[p] = mz2[p] - (t00 + t11).  top is read nowhere else.  With
+ * (width + 1)(height + 1) < 2^31 and |sz| < 2^24, 4 N + D stays below 2^61.
+ *
+ * Figures per label l, all int64: pixels = #{L = l}; model_pixels = #{M = l}; kept = #{L = l and M = l};
+ * multi = #{M = l and cover > 1}; and over the pixels with M = l and L >= 0: err_pixels, sum_abs_e2, max_abs_e2,
+ * sq_lo = sum of (e2^2 mod 2^32) and sq_hi = sum of (e2^2 div 2^32) -- both are order-free and cannot overflow; the sum of
+ * squares is sq_hi * 2^32 + sq_lo.
+ * Totals: the sums of the per-label figures (max_abs_e2_all: the maximum); n_uncovered = #{L >= 0, M < 0};
+ * n_spill = #{L < 0, M >= 0}; n_moved = #{L >= 0, M >= 0, L != M}; n_multi = #{cover > 1}; sum_cover.  And of the
+ * implementation ("Model raster"): n_rows and n_items, its row and pixel work items; n_empty_spans, the rows
+ * without a candidate pixel; max_span, the longest span.
+ *
+ * Promised.  sum pixels = sum kept + n_moved + n_uncovered.  sum model_pixels = sum kept + n_moved + n_spill.  If every label
+ * is BS_TRI_OK or BS_TRI_EMPTY and the tolerance is 0: M = L on every pixel and cover = [L >= 0].
+ *
+ * Errors.  BS_ERR_INVALID: no valid triangle state, that state's count had no top image, a null d_label or d_top or out, or a
+ * size that differs from the count's.  BS_ERR_RANGE: a vertex of a triangle with |sz| >= 2^24, or |t00 + t11| >= 2^25 on a
+ * pixel where e2 is formed.  On any error the outputs are untouched and the context stays usable. */
+#define BS_MRASTER_FIG_CAP 512 /* labels below this number have their figures reduced in LDS, the rest by global atomics */
+#define BS_MRASTER_CHUNK 256   /* the pixel items of one workgroup */
+#define BS_MRASTER_FIG_GRID 2048 /* workgroups of 256 of the pass over the pixels: beyond 524 288 pixels a thread takes several */
+
+struct bs_model_raster {
+  int32_t width, height, n_labels;
+  int32_t fig_cap, chunk; /* BS_MRASTER_FIG_CAP, BS_MRASTER_CHUNK of the library */
+  int32_t reserved;
+  int64_t n_triangles; /* all slots of the triangle state */
+  int64_t total_pixels, total_model_pixels, total_kept, total_err_pixels, total_sum_abs_e2, max_abs_e2_all, total_sq_lo,
+      total_sq_hi;
+  int64_t n_uncovered, n_spill, n_moved, n_multi, sum_cover;
+  int64_t n_rows, n_items, n_empty_spans, max_span;
+  /* per label; host memory owned by the library */
+  int64_t* pixels;       /* [n_labels] */
+  int64_t* model_pixels; /* [n_labels] */
+  int64_t* kept;         /* [n_labels] */
+  int64_t* multi;        /* [n_labels] */
+  int64_t* err_pixels;   /* [n_labels] */
+  int64_t* sum_abs_e2;   /* [n_labels] */
+  int64_t* max_abs_e2;   /* [n_labels] */
+  int64_t* sq_lo;        /* [n_labels] */
+  int64_t* sq_hi;        /* [n_labels] */
+  /* device time (HIP events on the context's stream) */
+  double ms_rows;    /* clearing the images, the rows of every slot, their sum, the host's read of n_rows */
+  double ms_spans;   /* the span of every row, their sum, the host's read of n_items */
+  double ms_pixels;  /* the pixel items: weights, win and cover */
+  double ms_figures; /* the pass over the pixels: M, mz2, the figures; the host's read of the result; the copies into the
+                        caller's images */
+};
+
+/* Rasterises the triangles of the last successful bs_outline_triangles_count_dev (or bs_poly_solids_count_dev) on this context
+ * where they lie and changes none of that state: bs_outline_triangles_emit_dev and bs_poly_solids_emit_dev stay valid.
+ * d_model, d_cover, d_mz2: device images int32 [height][width] for M, cover and mz2; each may be NULL.  The figures are
+ * always computed; out's per-label arrays are host memory owned by the library (bs_model_raster_free, which accepts a zeroed
+ * struct).  Synchronises: once for n_rows, once for n_items, once for the result, once for the copies. */
+int bs_model_raster_dev(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t width, int32_t height,
+                        int32_t* d_model, int32_t* d_cover, int32_t* d_mz2, struct bs_model_raster* out);
+/* Host-memory twin: label, top and the three images (each may be NULL) are host pointers.  Runs bs_outline_triangles on the
+ * images, then the raster; hands the results of the stages before to *tri, *clean, *simple and *plain unless they are NULL, as
+ * bs_outline_triangles returns them.  Errors of both. */
+int bs_model_raster(bs_ctx* ctx, const int32_t* label, const int32_t* top, int32_t width, int32_t height, int32_t n_labels,
+                    int64_t num, int64_t den, int32_t cell_log2, int32_t* model, int32_t* cover, int32_t* mz2,
+                    struct bs_model_raster* out, struct bs_outline_triangles* tri, struct bs_clean_outlines* clean,
+                    struct bs_simple_outlines* simple, struct bs_outlines* plain);
+void bs_model_raster_free(struct bs_model_raster* r);
+
 #ifdef __cplusplus
 }
 #endif
