@@ -39,6 +39,7 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_outlines_free", "bs_outlines_write_obj", "bs_simple_outlines_count_dev", "bs_simple_outlines_emit_dev",
            "bs_simple_outlines", "bs_simple_outlines_free", "bs_simple_outlines_write_obj", "bs_clean_outlines_count_dev",
            "bs_clean_outlines_emit_dev", "bs_clean_outlines", "bs_clean_outlines_free", "bs_clean_outlines_write_obj",
+           "bs_set_outline_sweeps", "bs_get_outline_sweeps",
            "bs_outline_triangles_count_dev", "bs_outline_triangles_emit_dev", "bs_outline_triangles",
            "bs_outline_triangles_free", "bs_outline_triangles_write_obj", "bs_poly_solids_count_dev",
            "bs_poly_solids_emit_dev", "bs_poly_solids", "bs_poly_solids_free", "bs_model_raster_dev", "bs_model_raster",
@@ -215,6 +216,18 @@ class CleanOutlines(C.Structure):
                  ("label_ring_offset", C.POINTER(C.c_int64)), ("sxy", C.POINTER(C.c_int32)), ("sz", C.POINTER(C.c_int32)),
                  ("s_right", C.POINTER(C.c_int32)), ("s_flag", C.POINTER(C.c_uint8))] +
                 [(k, C.c_double) for k in ("ms_simplify", "ms_detect", "ms_repair", "ms_rings", "ms_emit")])
+
+
+SWEEP_WAVE_CAP = 64  # BS_SWEEP_WAVE_CAP of include/bs_api.h
+SWEEP_FIGURES = ("n_lens_segments_first", "n_sweeping_first", "n_sweeping_only_first", "n_swept_pairs_first", "max_abs_winding",
+                 "sweep_rounds", "n_sweeping_left", "n_items_first", "n_items_swapped_first", "n_candidates_first",
+                 "n_exact_first", "n_exact_wave_first", "n_rejected_first")
+
+
+class OutlineSweeps(C.Structure):
+    """bs_outline_sweeps (include/bs_api.h): the figures of the sweep detection of the last clean count."""
+    _fields_ = ([("mode", C.c_int32), ("wave_cap", C.c_int32)] + [(k, C.c_int64) for k in SWEEP_FIGURES] +
+                [("ms_sweep", C.c_double)])
 
 
 TRI_STATUS = {0: "BS_TRI_OK", 1: "BS_TRI_NO_BRIDGE", 2: "BS_TRI_STALLED", 3: "BS_TRI_EMPTY"}
@@ -429,6 +442,8 @@ def load():
     L.bs_clean_outlines_free.argtypes = [cop]
     L.bs_clean_outlines_free.restype = None
     L.bs_clean_outlines_write_obj.argtypes = [cop, C.c_int32, ip, C.c_char_p]
+    L.bs_set_outline_sweeps.argtypes = [vp, C.c_int32]
+    L.bs_get_outline_sweeps.argtypes = [vp, C.POINTER(OutlineSweeps)]
     otp = C.POINTER(OutlineTriangles)
     tri_args = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, otp, cop, sop, olp]
     L.bs_outline_triangles_count_dev.argtypes = tri_args

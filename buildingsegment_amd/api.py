@@ -12,6 +12,7 @@ library; nothing is computed in Python and there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -778,26 +779,55 @@ class Context:
         d_flag [n_svertices] uint8."""
         self._check(self._L.bs_simple_outlines_emit_dev(self._h, d_sxy or None, d_sz or None, d_right or None, d_flag or None))
 
-    def roof_polygons(self, roof_facets, solids, tolerance_mm=0, bin=None, clean=False):
+    def roof_polygons(self, roof_facets, solids, tolerance_mm=0, bin=None, clean=False, sweeps=None):
         """simplified_outlines() of the facet image of roof_facets() / roof_structure() with the tops of solids(), at a
         tolerance in millimetres (bin: the pixel edge, by default the Solids').  clean=True: clean_outlines() instead --
-        polygons whose segments meet only in shared end points -- as (CleanOutlines, the plain Outlines)."""
+        polygons whose segments meet only in shared end points -- as (CleanOutlines, the plain Outlines); sweeps: the sweep
+        mode of that clean count (set_outline_sweeps), None = the context's."""
         if roof_facets.facet is None:
             raise ValueError("roof_polygons: the facet image is on the device: use simplified_outlines_dev")
         if solids.top is None:
             raise ValueError("roof_polygons: the Solids carry no top image (solids(top=True))")
         num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
         if clean:
-            c, _, plain = self.clean_outlines(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)
+            c, _, plain = self.clean_outlines(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den,
+                                              sweeps=sweeps)
             return c, plain
         return self.simplified_outlines(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)
 
     # ---- clean outlines: conflicts between simplified segments found and repaired (bs_clean_outlines, include/bs_api.h) --
-    def clean_outlines(self, label, top=None, n_labels=None, num=0, den=1, max_rounds=-1, cell_log2=0):
+    def set_outline_sweeps(self, mode):
+        """The sweep mode of every clean count on this context (bs_set_outline_sweeps): 0 off (the default), 1 report,
+        2 repair -- segments whose chord passes over a whole ring without touching it are marked and repaired too."""
+        self._check(self._L.bs_set_outline_sweeps(self._h, int(mode)))
+        self._sweeps_mode = int(mode)
+
+    def outline_sweeps(self):
+        """The figures of the sweep detection of the last clean count on this context (bs_get_outline_sweeps)."""
+        out = _lib.OutlineSweeps()
+        self._check(self._L.bs_get_outline_sweeps(self._h, C.byref(out)))
+        return OutlineSweeps(mode=out.mode, wave_cap=out.wave_cap, ms_sweep=out.ms_sweep,
+                             **{k: getattr(out, k) for k in _lib.SWEEP_FIGURES})
+
+    @contextmanager
+    def _sweeps(self, mode):
+        """the sweep mode for one call (None: the context's), the previous one restored behind it"""
+        if mode is None:
+            yield
+            return
+        prev = getattr(self, "_sweeps_mode", 0)
+        self.set_outline_sweeps(mode)
+        try:
+            yield
+        finally:
+            self.set_outline_sweeps(prev)
+
+    def clean_outlines(self, label, top=None, n_labels=None, num=0, den=1, max_rounds=-1, cell_log2=0, sweeps=None):
         """The simplified outlines with every conflict between kept segments (cross, touch, overlap) repaired by keeping
         further nodes.  max_rounds < 0: until clean; 0: check only (s_flag bit 3 and n_marked_first report the conflicts);
-        > 0: a cap.  cell_log2: the broad-phase cell edge, 0 = the default.  Returns (CleanOutlines, the SimpleOutlines
-        without vertices, the plain Outlines without vertices)."""
+        > 0: a cap.  cell_log2: the broad-phase cell edge, 0 = the default.  sweeps: the sweep mode of this call
+        (set_outline_sweeps), None = the context's.  Returns (CleanOutlines, the SimpleOutlines without vertices, the plain
+        Outlines without vertices)."""
         label = np.ascontiguousarray(label, dtype=np.int32)
         if label.ndim != 2 or label.size == 0:
             raise ValueError("clean_outlines: label must be [height][width]")
@@ -808,19 +838,22 @@ class Context:
         h, w = label.shape
         nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
         out, simple, plain = _lib.CleanOutlines(), _lib.SimpleOutlines(), _lib.Outlines()
-        self._check(self._L.bs_clean_outlines(self._h, label.ctypes.data, None if top is None else top.ctypes.data, w, h, nl,
-                                              int(num), int(den), int(max_rounds), int(cell_log2), C.byref(out),
-                                              C.byref(simple), C.byref(plain)))
+        with self._sweeps(sweeps):
+            self._check(self._L.bs_clean_outlines(self._h, label.ctypes.data, None if top is None else top.ctypes.data, w, h,
+                                                  nl, int(num), int(den), int(max_rounds), int(cell_log2), C.byref(out),
+                                                  C.byref(simple), C.byref(plain)))
         return (_take_clean_outlines(self._L, out, True), _take_simple_outlines(self._L, simple, False),
                 _take_outlines(self._L, plain, False))
 
-    def clean_outlines_dev(self, d_label, d_top, width, height, n_labels, num=0, den=1, max_rounds=-1, cell_log2=0):
+    def clean_outlines_dev(self, d_label, d_top, width, height, n_labels, num=0, den=1, max_rounds=-1, cell_log2=0,
+                           sweeps=None):
         """Device-resident count (bs_clean_outlines_count_dev): d_label and d_top (0: no Z) are device pointers (ints).
-        Returns (CleanOutlines with the vertex arrays None, SimpleOutlines, Outlines)."""
+        sweeps as clean_outlines.  Returns (CleanOutlines with the vertex arrays None, SimpleOutlines, Outlines)."""
         out, simple, plain = _lib.CleanOutlines(), _lib.SimpleOutlines(), _lib.Outlines()
-        self._check(self._L.bs_clean_outlines_count_dev(self._h, d_label or None, d_top or None, width, height, int(n_labels),
-                                                        int(num), int(den), int(max_rounds), int(cell_log2), C.byref(out),
-                                                        C.byref(simple), C.byref(plain)))
+        with self._sweeps(sweeps):
+            self._check(self._L.bs_clean_outlines_count_dev(self._h, d_label or None, d_top or None, width, height,
+                                                            int(n_labels), int(num), int(den), int(max_rounds),
+                                                            int(cell_log2), C.byref(out), C.byref(simple), C.byref(plain)))
         return (_take_clean_outlines(self._L, out, False), _take_simple_outlines(self._L, simple, False),
                 _take_outlines(self._L, plain, False))
 
@@ -865,16 +898,18 @@ class Context:
         [n_triangles][3] int32."""
         self._check(self._L.bs_outline_triangles_emit_dev(self._h, d_tri or None))
 
-    def roof_mesh(self, roof_facets, solids, tolerance_mm=0, bin=None):
+    def roof_mesh(self, roof_facets, solids, tolerance_mm=0, bin=None, sweeps=None):
         """outline_triangles() of the facet image of roof_facets() / roof_structure() with the tops of solids(), at a
         tolerance in millimetres (bin: the pixel edge, by default the Solids'), beside roof_polygons(clean=True): returns
-        (OutlineTriangles, CleanOutlines, the plain Outlines)."""
+        (OutlineTriangles, CleanOutlines, the plain Outlines).  sweeps: the sweep mode of the call (set_outline_sweeps)."""
         if roof_facets.facet is None:
             raise ValueError("roof_mesh: the facet image is on the device: use outline_triangles_dev")
         if solids.top is None:
             raise ValueError("roof_mesh: the Solids carry no top image (solids(top=True))")
         num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
-        t, c, _, plain = self.outline_triangles(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)
+        with self._sweeps(sweeps):
+            t, c, _, plain = self.outline_triangles(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num,
+                                                    den=den)
         return t, c, plain
 
     # ---- polygon solids: a closed mesh per building over the clean vertices and the triangles (bs_poly_solids) ------------
@@ -929,19 +964,20 @@ class Context:
         self._check(self._L.bs_poly_solids_emit_dev(self._h, d_vertex or None, d_face_offset or None, d_face_index or None,
                                                     d_face_building or None, d_face_kind or None))
 
-    def building_model(self, roof_facets, solids, tolerance_mm=0, bin=None):
+    def building_model(self, roof_facets, solids, tolerance_mm=0, bin=None, sweeps=None):
         """poly_solids() of the facet image and facet_building of roof_facets() / roof_structure() with the tops, bin and
         base_z of solids(), at a tolerance in millimetres, beside roof_mesh(): returns (PolySolids, OutlineTriangles,
-        CleanOutlines, the plain Outlines)."""
+        CleanOutlines, the plain Outlines).  sweeps: the sweep mode of the call (set_outline_sweeps)."""
         if roof_facets.facet is None:
             raise ValueError("building_model: the facet image is on the device: use poly_solids_dev")
         if solids.top is None:
             raise ValueError("building_model: the Solids carry no top image (solids(top=True))")
         b = solids.bin if bin is None else bin
         num, den = simplify_tolerance(tolerance_mm, b)
-        p, t, c, _, plain = self.poly_solids(roof_facets.facet, solids.top, roof_facets.facet_building,
-                                             n_labels=roof_facets.n_facets, n_buildings=solids.n_buildings, num=num, den=den,
-                                             bin=b, base_z=solids.base_z)
+        with self._sweeps(sweeps):
+            p, t, c, _, plain = self.poly_solids(roof_facets.facet, solids.top, roof_facets.facet_building,
+                                                 n_labels=roof_facets.n_facets, n_buildings=solids.n_buildings, num=num,
+                                                 den=den, bin=b, base_z=solids.base_z)
         return p, t, c, plain
 
     # ---- model raster: the outline triangles back on the lattice, and the model's error (bs_model_raster) -----------------
@@ -980,16 +1016,18 @@ class Context:
                                                 d_model or None, d_cover or None, d_mz2 or None, C.byref(out)))
         return _take_model_raster(self._L, out)
 
-    def model_fidelity(self, roof_facets, solids, tolerance_mm=0, bin=None):
+    def model_fidelity(self, roof_facets, solids, tolerance_mm=0, bin=None, sweeps=None):
         """What the polygon model of building_model() at this tolerance costs, per building: model_raster() of the facet
         image of roof_facets() / roof_structure() with the tops of solids(), its per-label figures added up by
-        facet_building.  Returns (ModelFidelity, ModelRaster)."""
+        facet_building.  sweeps: the sweep mode of the call (set_outline_sweeps).  Returns (ModelFidelity,
+        ModelRaster)."""
         if roof_facets.facet is None:
             raise ValueError("model_fidelity: the facet image is on the device: use model_raster_dev")
         if solids.top is None:
             raise ValueError("model_fidelity: the Solids carry no top image (solids(top=True))")
         num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
-        r = self.model_raster(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)[0]
+        with self._sweeps(sweeps):
+            r = self.model_raster(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)[0]
         return model_fidelity_of(r, roof_facets.facet_building, solids.n_buildings), r
 
 
@@ -1663,6 +1701,27 @@ class CleanOutlines(SimpleOutlines):
     repair_rounds: int = 0
     n_entries: int = 0
     max_cell_entries: int = 0
+
+
+@dataclass
+class OutlineSweeps:
+    """bs_outline_sweeps: the figures of the sweep detection of a clean count as include/bs_api.h names them."""
+    mode: int = 0
+    wave_cap: int = 0
+    n_lens_segments_first: int = 0
+    n_sweeping_first: int = 0
+    n_sweeping_only_first: int = 0
+    n_swept_pairs_first: int = 0
+    max_abs_winding: int = 0
+    sweep_rounds: int = 0
+    n_sweeping_left: int = 0
+    n_items_first: int = 0
+    n_items_swapped_first: int = 0
+    n_candidates_first: int = 0
+    n_exact_first: int = 0
+    n_exact_wave_first: int = 0
+    n_rejected_first: int = 0
+    ms_sweep: float = 0.0
 
 
 _CLEAN_TOTALS = ("max_rounds", "cell_log2", "n_svertices_before", "n_marked_first", "n_marked_left", "n_forced", "repair_rounds",

@@ -247,6 +247,8 @@ void bs_destroy(bs_ctx* c)
     b.release();
   for (auto& b : c->uc)
     b.release();
+  for (auto& b : c->sw)
+    b.release();
   for (auto& b : c->tr)
     b.release();
   for (auto& b : c->ps)
@@ -391,6 +393,28 @@ int bs_selftest_forge_next(bs_ctx* ctx, int mode)
   if (!ctx || mode < 0 || mode > 2)
     return BS_ERR_INVALID;
   ctx->forge_mode = mode;
+  return BS_OK;
+}
+
+int bs_set_outline_sweeps(bs_ctx* ctx, int32_t mode)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (mode < 0 || mode > 2)
+    return bs::fail(ctx, BS_ERR_INVALID, "outline sweeps: the mode is 0 (off), 1 (report) or 2 (repair)");
+  ctx->sweeps_mode = mode;
+  return BS_OK;
+}
+
+int bs_get_outline_sweeps(bs_ctx* ctx, struct bs_outline_sweeps* out)
+{
+  if (!ctx || !out)
+    return BS_ERR_INVALID;
+  *out = ctx->sweeps;
+  if (out->wave_cap == 0) {  // (no clean count yet)
+    out->mode = ctx->sweeps_mode;
+    out->wave_cap = BS_SWEEP_WAVE_CAP;
+  }
   return BS_OK;
 }
 

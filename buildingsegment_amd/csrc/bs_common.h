@@ -283,6 +283,10 @@ struct bs_ctx {
   bool uc_valid = false, uc_has_z = false;
   int64_t uc_nsv = 0;
   double uc_ms_emit = 0;
+  // sweeps (bs_sweep.hip): the mode of bs_set_outline_sweeps, the figures of the last successful clean count, scratch
+  int sweeps_mode = 0;
+  bs_outline_sweeps sweeps{};
+  bs::DevBuf sw[8];
   // what the last successful bs_clean_outlines_count_dev leaves for the outline triangles (bs_triangulate.hip), all inside
   // uc: the clean vertices, the ring of every vertex, the first vertex of every ring
   const int2* uc_xy = nullptr;

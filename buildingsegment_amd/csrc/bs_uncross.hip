@@ -7,6 +7,8 @@
 //             binary searches; the pair tests -- a thread per entry against the entries behind it in a run of at most
 //             HEAVY, a workgroup per tile of 256 entries with the tile's segments in LDS against the entries behind it in
 //             longer runs; the marked segments counted
+//   sweeps    with bs_set_outline_sweeps on, bs_sweep.hip marks the segments whose lens winds around a kept vertex, between
+//             the pair tests and the count: its item count travels in the first read, its counts in the second
 //   repair    the nodes of marked segments become active with their segment (L, R) from the scan and the list; one forced
 //             round of the simplified stage's three kernels keeps every marked segment's choice
 //   rings     the place of every kept vertex from the scan and the rotation, the flags, area2 over runs
@@ -29,6 +31,7 @@
 #include "bs_outline.h"
 #pragma clang diagnostic pop
 #include "bs_segscan.h"
+#include "bs_sweep.h"
 
 namespace bs {
 namespace {
@@ -43,7 +46,6 @@ constexpr int SWEEP_CAP = 1024;    // workgroups of the grid-stride passes
 constexpr int HEAVY = 64;          // a run of more entries is tested tile by tile
 constexpr int TILE = 256;
 constexpr int32_t KEPT = -1, DROPPED = -2;  // seg.x of a node that is not active (bs_simplify.hip)
-enum { W_ERR, W_MARKED, W_MAXCELL, W_CHANGED, W_COUNT };
 constexpr unsigned F_REPAIRED = 4, F_MARKED = 8;
 
 inline int sweep(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(nblk(n, 256), SWEEP_CAP)); }
@@ -440,7 +442,8 @@ struct FinalArrays {
 // minus the kept nodes in front of h0's place there, modulo the ring's kept count
 __global__ __launch_bounds__(256) void uncross_final_kernel(const int2* __restrict__ seg, const int32_t* __restrict__ kscan,
                                                             const uint8_t* __restrict__ kept0, const uint8_t* __restrict__ mark,
-                                                            const int2* __restrict__ xy, const int32_t* __restrict__ z,
+                                                            const uint8_t* __restrict__ smark, const int2* __restrict__ xy,
+                                                            const int32_t* __restrict__ z,
                                                             const int32_t* __restrict__ right, const int32_t* __restrict__ ring,
                                                             const uint8_t* __restrict__ flag, const int32_t* __restrict__ noff,
                                                             const int32_t* __restrict__ rot_of, int32_t N, int32_t nr, bool has_z,
@@ -472,7 +475,9 @@ __global__ __launch_bounds__(256) void uncross_final_kernel(const int2* __restri
     O.xy[d] = xy[q];
     O.right[d] = right[q];
     O.ring[d] = r;
-    O.flag[d] = (uint8_t)((flag[q] & 3u) | (kept0[q] ? 0u : F_REPAIRED) | (mark[k] ? F_MARKED : 0u));
+    const unsigned sm = smark ? smark[k] : 0u;  // (sweeps on: a mark that only a sweep set is no conflict)
+    O.flag[d] = (uint8_t)((flag[q] & 3u) | (kept0[q] ? 0u : F_REPAIRED) | (mark[k] && !(sm & SM_ONLY) ? F_MARKED : 0u) |
+                          (sm & SM_SWEEPING ? F_SWEEPING : 0u));
     if (has_z)
       O.z[d] = z[q];
   }
@@ -602,6 +607,11 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   struct bs_clean_outlines res;
   memset(&res, 0, sizeof res);
   CGuard guard{&res, &sm, &pl};
+  const int mode = ctx->sweeps_mode;
+  struct bs_outline_sweeps sw;
+  memset(&sw, 0, sizeof sw);
+  sw.mode = mode;
+  sw.wave_cap = BS_SWEEP_WAVE_CAP;
   const int k = cell_log2 == 0 ? BS_CLEAN_DEFAULT_CELL_LOG2 : cell_log2;
   const int32_t nr = (int32_t)sm.n_rings;
   const bool has_z = d_top != nullptr;
@@ -651,6 +661,7 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
     ctx->uc_z = ctx->uc[UC_FZ].as<int32_t>();  // (for bs_polysolid.hip)
     ctx->uc_right = ctx->uc[UC_FRIGHT].as<int32_t>();
     ctx->uc_valid = true;
+    ctx->sweeps = sw;
     return BS_OK;
   };
   const bs_ctx::SimplifyState S = ctx->sp_state;
@@ -663,7 +674,7 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->uc;
   Events ev;
-  for (int i = 0; i < 6; i++)
+  for (int i = 0; i < (mode ? 10 : 6); i++)
     BS_HIP(ctx, hipEventCreate(&ev.e[i]));
   BS_HIP(ctx, B[UC_MISC].reserve(256));
   BS_HIP(ctx, B[UC_RLABEL].reserve(4 * (size_t)nr));
@@ -709,6 +720,7 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   uncross_kept0_kernel<<<g, 256, 0, st>>>(segK, N, kept0);
   int64_t rounds = 0;
   double ms_detect = 0, ms_repair = 0;
+  const SweepRun SR{st, segK, kscan, klist, S.xy, S.ring, S.noff, N, nr, width, height, d_words, mode};
   bool repair_pending = false;
   int h_words[W_COUNT] = {};
   for (;;) {
@@ -721,7 +733,13 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
                                                d_err);
     tb = B[UC_TMP].cap;
     BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[UC_TMP].p, tb, cc, eoff, N + 1, st));
-    long long E64 = 0;
+    long long E64 = 0, I64 = 0;
+    if (mode) {  // the sweep pass's items: counted here, so that their count travels in the first read
+      BS_HIP(ctx, hipEventRecord(ev.e[6], st));
+      if (int rcs = sweep_begin(ctx, SR, &I64))
+        return rcs;
+      BS_HIP(ctx, hipEventRecord(ev.e[7], st));
+    }
     int32_t nseg = 0;
     int h_err = 0;
     BS_HIP(ctx, hipMemcpyAsync(&E64, eoff + N, 8, hipMemcpyDeviceToHost, st));
@@ -737,6 +755,10 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
       return internal(ctx, 0x20000);
     if (E64 > INT32_MAX)
       return fail(ctx, BS_ERR_INVALID, "clean outlines: more than 2^31 - 1 (cell, segment) entries: take a larger cell_log2");
+    if (I64 < 0)
+      return internal(ctx, 0x200000);
+    if (I64 > INT32_MAX)
+      return fail(ctx, BS_ERR_INVALID, "clean outlines: more than 2^31 - 1 items of the sweep pass");
     const int32_t E = (int32_t)E64;
     for (int b : {UC_KEY0, UC_KEY1, UC_VAL0, UC_VAL1})
       BS_HIP(ctx, B[b].reserve(4 * (size_t)E));
@@ -755,6 +777,12 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
     uncross_runs_kernel<<<sweep(E), 256, 0, st>>>(key1, val1, E, nseg, run, d_words + W_MAXCELL, d_err);
     uncross_pairs_light_kernel<<<sweep(E), 256, 0, st>>>(run, val1, segxy, seglab, E, nseg, mark, d_err);
     uncross_pairs_heavy_kernel<<<sweep(E), 256, 0, st>>>(run, val1, segxy, seglab, E, nseg, mark, d_err);
+    if (mode) {
+      BS_HIP(ctx, hipEventRecord(ev.e[8], st));
+      if (int rcs = sweep_detect(ctx, SR, nseg, I64, mark))
+        return rcs;
+      BS_HIP(ctx, hipEventRecord(ev.e[9], st));
+    }
     BS_HIP(ctx, hipMemsetAsync(d_words + W_MARKED, 0, 4, st));
     uncross_count_kernel<<<sweep(nseg), 256, 0, st>>>(mark, nseg, d_words + W_MARKED);
     BS_HIP(ctx, hipMemcpyAsync(h_words, d_words, 4 * W_COUNT, hipMemcpyDeviceToHost, st));
@@ -764,14 +792,36 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
     ms_detect += ev.ms(0, 1);
     if (h_words[W_ERR])
       return internal(ctx, h_words[W_ERR]);
+    // (mode 2: the count is over conflicting and sweeping segments; n_marked_* are the conflicting ones)
+    const int n_conflicting = h_words[W_MARKED] - (mode == 2 ? h_words[W_S_ONLY] : 0);
+    if (mode) {
+      sw.ms_sweep += ev.ms(6, 7) + ev.ms(8, 9);
+      if (rounds == 0) {
+        sw.n_lens_segments_first = h_words[W_S_LENS];
+        sw.n_sweeping_first = h_words[W_S_SWEEPING];
+        sw.n_sweeping_only_first = h_words[W_S_ONLY];
+        sw.n_swept_pairs_first = h_words[W_S_PAIRS];
+        sw.n_items_first = I64;
+        sw.n_items_swapped_first = h_words[W_S_ITEMS_T];
+        sw.n_candidates_first =
+            (long long)(((unsigned long long)(uint32_t)h_words[W_S_CAND_HI] << 32) | (uint32_t)h_words[W_S_CAND_LO]);
+        sw.n_exact_first = h_words[W_S_EXACT];
+        sw.n_exact_wave_first = h_words[W_S_WAVE];
+        sw.n_rejected_first = h_words[W_S_REJECT];
+      }
+      sw.max_abs_winding = h_words[W_S_MAXW];
+      sw.n_sweeping_left = h_words[W_S_SWEEPING];
+    }
     if (rounds == 0) {
-      res.n_marked_first = h_words[W_MARKED];
+      res.n_marked_first = n_conflicting;
       res.n_entries = E;
     }
-    res.n_marked_left = h_words[W_MARKED];
+    res.n_marked_left = n_conflicting;
     res.n_svertices = nseg;
     if (h_words[W_MARKED] == 0 || rounds == max_rounds)
       break;
+    if (mode == 2 && h_words[W_S_SWEEPING] > 0)
+      sw.sweep_rounds++;
     if (rounds >= N)
       return internal(ctx, 0x40000);  // (every round keeps a node: more rounds than nodes cannot be)
     // ---- repair ----
@@ -786,8 +836,8 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   // ---- rings: the last detection ran over the final kept set: its scan and its marks hold ----
   BS_HIP(ctx, hipEventRecord(ev.e[2], st));
   uncross_offsets_kernel<<<sweep((int64_t)nr + 1), 256, 0, st>>>(kscan, S.noff, nr, N, soff, area2, d_err);
-  uncross_final_kernel<<<g, 256, 0, st>>>(segK, kscan, kept0, mark, S.xy, S.z, S.right, S.ring, S.flag, S.noff, S.rot, N, nr, has_z, O,
-                                          d_err);
+  uncross_final_kernel<<<g, 256, 0, st>>>(segK, kscan, kept0, mark, mode ? sweep_marks(ctx) : nullptr, S.xy, S.z, S.right, S.ring,
+                                          S.flag, S.noff, S.rot, N, nr, has_z, O, d_err);
   uncross_area_kernel<<<g, 256, 0, st>>>(O.xy, O.ring, soff, kscan, N, nr, area2, d_err);
   BS_HIP(ctx, hipEventRecord(ev.e[3], st));
   std::vector<int32_t> h_soff((size_t)nr + 1);

@@ -1252,7 +1252,60 @@ int bs_simple_outlines_write_obj(const struct bs_simple_outlines* o, int32_t bin
  * the loop).  n_svertices_before: the vertex count of the plain simplification; n_marked_first: its marked segments, twins
  * counted each; n_marked_left: 0 unless stopped by max_rounds; n_forced: vertices added; repair_rounds.  Of the broad
  * phase (they depend on cell_log2, nothing else does): n_entries, the (cell, segment) entries of the first detection, and
- * max_cell_entries, the most entries of one cell in any detection. */
+ * max_cell_entries, the most entries of one cell in any detection.
+ *
+ * Sweeps (bs_set_outline_sweeps; off by default).  A chord can pass over a whole foreign ring -- an island, a hole -- without
+ * meeting any of its segments.  No two segments conflict then, but which ring lies inside which has changed.
+ * Lens.  A segment with kept ends a -> b whose ring has the nodes n_1 .. n_m strictly between them, m >= 1, has the lens
+ * a, n_1, .., n_m, b, closed by the chord b -> a: a closed lattice polygon.  A segment without interior nodes has no lens.
+ * Swept vertex.  A kept vertex position w, of any ring, is swept by a segment iff w does not lie on the lens's boundary
+ * (the chord, its ends, the path's runs and nodes; a w on the chord is a touch, which the conflict test owns) and the
+ * winding number of the lens around w is not zero.  The winding is the signed count of the lens's edges that a ray from w
+ * crosses, with a half-open rule at the edges' ends and the sign of every crossing from an orientation test in int64.
+ * Non-zero winding is the test, not odd parity.
+ * Sweeping.  A segment is sweeping iff it sweeps at least one vertex.  A twin has the same lens reversed: it is sweeping in
+ * the same detection and picks the same node.
+ * Round.  In mode 2 a detection marks the conflicting and the sweeping segments over the same kept set; the repair round is
+ * the one above, unchanged, and the loop ends when a detection marks nothing.  In mode 1 sweeps are detected and reported
+ * and never marked: the vertices equal mode 0's.
+ * Termination.  A sweeping segment has interior nodes, so the argument above holds: the kept set grows, repair_rounds <
+ * n_nodes, and with every node kept no lens exists.
+ * Not promised.  After the repair every chord is free of conflicts and its lens winds around no kept vertex.  Chords that
+ * are homotopic to their paths in the plane punctured at the kept vertices would leave the rings isotopic to the original
+ * ones, so that every hole lies in its outer ring and every label triangulates; zero winding is slightly weaker than that
+ * homotopy, and nothing is promised.  The tests assert it on their cases.
+ * Figures.  n_marked_first, n_marked_left and s_flag bit 3 keep their meaning: conflicts only.  s_flag gains bit 4: the
+ * segment that starts here was sweeping in the last detection (0 in mode 0; after a repair to the end only mode 1 leaves
+ * it).  repair_rounds, n_forced and bit 2 count every round and every vertex, whichever mark caused them. */
+struct bs_outline_sweeps {
+  int32_t mode;     /* of the count */
+  int32_t wave_cap; /* BS_SWEEP_WAVE_CAP */
+  int64_t n_lens_segments_first; /* segments with a lens at the first detection */
+  int64_t n_sweeping_first;      /* sweeping segments at the first detection, twins counted each */
+  int64_t n_sweeping_only_first; /* those of them that did not also conflict */
+  int64_t n_swept_pairs_first;   /* (vertex position, segment) pairs with non-zero winding at the first detection */
+  int64_t max_abs_winding;       /* over all detections */
+  int64_t sweep_rounds;          /* repair rounds whose detection had a sweeping segment */
+  int64_t n_sweeping_left;       /* sweeping segments of the last detection: 0 unless mode 1 or max_rounds stopped the loop */
+  /* of the layout, at the first detection (they depend on the layout of the device pass, nothing else does) */
+  int64_t n_items_first;         /* (run, lattice line) items */
+  int64_t n_items_swapped_first; /* those of segments with |dx| < |dy|, whose rays run along X */
+  int64_t n_candidates_first;    /* corners of all items' intervals */
+  int64_t n_exact_first;         /* exact tests: candidates that are a kept vertex and no end of the segment */
+  int64_t n_exact_wave_first;    /* those run by a wave: paths of more than wave_cap runs */
+  int64_t n_rejected_first;      /* exact tests that found the boundary or winding 0 */
+  double ms_sweep; /* device time of all sweep detections (HIP events); also inside the clean count's ms_detect */
+};
+#define BS_SWEEP_WAVE_CAP 64
+
+/* The sweep mode of the context, as bs_set_audit a property of the context: every clean count on it follows, also the ones
+ * that bs_outline_triangles*, bs_poly_solids* and bs_model_raster run.  0: off, the default -- every count behaves and
+ * launches as without this paragraph; 1: report; 2: repair.  BS_ERR_INVALID for any other mode. */
+int bs_set_outline_sweeps(bs_ctx* ctx, int32_t mode);
+/* The figures of the last successful clean count on the context; all zero but mode and wave_cap after a count in mode 0 or
+ * before any count. */
+int bs_get_outline_sweeps(bs_ctx* ctx, struct bs_outline_sweeps* out);
+
 struct bs_clean_outlines {
   int32_t width, height;
   int32_t n_labels;
@@ -1275,7 +1328,7 @@ struct bs_clean_outlines {
   uint8_t* s_flag;
   /* device time (HIP events on the context's stream) */
   double ms_simplify; /* the simplified count: the sum of its phases, the plain count included */
-  double ms_detect;   /* all detections: segments, cells, scan, fill, sort, pair tests, the host's reads included */
+  double ms_detect;   /* all detections: segments, cells, scan, fill, sort, pair tests, sweeps, the host's reads included */
   double ms_repair;   /* all repair rounds */
   double ms_rings;    /* places, flags, area2 */
   double ms_emit;     /* the emit (host-memory entry point only) */
@@ -1290,8 +1343,9 @@ struct bs_clean_outlines {
  * valid, 30 puts everything into one cell; no result but n_entries and max_cell_entries depends on it.
  * Errors as bs_simple_outlines_count_dev; also BS_ERR_INVALID for cell_log2 outside 0..30, or where a detection would list more
  * than 2^31 - 1 (cell, segment) entries (take a larger cell_log2).  On any error the outputs are
- * left untouched.  Synchronises: the simplified count's times, then twice per detection (the entry count; the marked
- * count and the error word) -- one detection more than repair rounds -- and once for the result. */
+ * left untouched.  Synchronises: the simplified count's times, then twice per detection (the entry count, with the sweep
+ * pass's item count; the marked count, the sweep counts and the error word) -- one detection more than repair rounds -- and
+ * once for the result.  With sweeps on, also BS_ERR_INVALID where a detection would list more than 2^31 - 1 items. */
 int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t width, int32_t height,
                                 int32_t n_labels, int64_t num, int64_t den, int32_t max_rounds, int32_t cell_log2,
                                 struct bs_clean_outlines* out, struct bs_simple_outlines* simple, struct bs_outlines* plain);
@@ -1330,7 +1384,8 @@ int bs_clean_outlines_write_obj(const struct bs_clean_outlines* o, int32_t bin, 
  * cones, so at most one of them is valid.  The list becomes ... V, M, (the hole from M round), M', V', ...: two occurrences
  * more.  A hole without a valid occurrence gives the label the status BS_TRI_NO_BRIDGE and no triangles: such a hole lies
  * outside its outer ring, which the clean outlines do not notice when a chord sweeps over a whole ring without touching it
- * ("Outline triangles").
+ * -- unless the context repairs sweeps (bs_set_outline_sweeps, mode 2; "clean outlines", paragraph "Sweeps").  This count
+ * runs the clean count itself and follows the context's mode ("Outline triangles", "Sweeps").
  * Ears, scanned as earcut scans, per list in the order of the outer rings.  stop = cursor = the outer ring's first
  * occurrence.  While more than 3 occurrences remain: b = cursor, a its predecessor, c its successor; b is an ear iff
  * orient(a, b, c) > 0 and no other occurrence q of the current list whose position differs from those of a, b and c has
@@ -1526,7 +1581,8 @@ void bs_poly_solids_free(struct bs_poly_solids* s);
  *
  * The inverse of the chain facets -> outlines -> simplified -> clean -> triangles.  Per pixel: the label the model puts there,
  * how many triangles cover it, and the model's height at the pixel centre.  Per label: exact fidelity figures against the label
- * image and top.  Everything is an exact integer.  It reports overlaps and swept holes; it repairs nothing.
+ * image and top.  Everything is an exact integer.  It reports overlaps and swept holes and repairs nothing itself: the
+ * repair is the sweep mode of the clean outlines (bs_set_outline_sweeps), which the host-memory entry point follows.
  *
  * Input.  The state of a successful bs_outline_triangles_count_dev on the context, counted with a top image
  * (bs_poly_solids_count_dev runs that count, so its state serves as well): the clean vertices sxy, sz; tri, tri_offset,
