@@ -35,7 +35,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_roofs", "bs_roofs_free", "bs_roofs_write_obj", "bs_plane_fit_dev", "bs_plane_fit", "bs_plane_fits_free",
            "bs_plane_fit_apply", "bs_solids_count_dev", "bs_solids_emit_dev", "bs_solids", "bs_solids_free",
            "bs_solids_write_obj", "bs_roof_facets_dev", "bs_roof_facets", "bs_roof_facets_free", "bs_roof_edge_kinds",
-           "bs_roof_edges_write_obj", "bs_facet_outlines_count_dev", "bs_facet_outlines_emit_dev", "bs_facet_outlines",
+           "bs_roof_edges_write_obj", "bs_roof_generalise_dev", "bs_roof_generalise", "bs_roof_generalise_free",
+           "bs_facet_outlines_count_dev", "bs_facet_outlines_emit_dev", "bs_facet_outlines",
            "bs_outlines_free", "bs_outlines_write_obj", "bs_simple_outlines_count_dev", "bs_simple_outlines_emit_dev",
            "bs_simple_outlines", "bs_simple_outlines_free", "bs_simple_outlines_write_obj", "bs_clean_outlines_count_dev",
            "bs_clean_outlines_emit_dev", "bs_clean_outlines", "bs_clean_outlines_free", "bs_clean_outlines_write_obj",
@@ -171,6 +172,30 @@ class RoofFacets(C.Structure):
                   ("n_step", C.c_int64), ("step_abs_sum", C.c_int64), ("step_abs_max", C.c_int64), ("rise_sum", C.c_int64),
                   ("bend_sum", C.c_int64), ("z_min", C.c_int32), ("z_max", C.c_int32), ("bbox", C.c_int32))] +
                 [("ms_label", C.c_double), ("ms_number", C.c_double), ("ms_figures", C.c_double), ("ms_edges", C.c_double)])
+
+
+GEN_FIG_CAP, GEN_PLANE_CAP = 1024, 1024  # BS_GEN_FIG_CAP, BS_GEN_PLANE_CAP of include/bs_api.h
+GEN_SCALARS = ("n_facets_in", "n_facets_out", "n_edges_in", "n_edges_out", "n_flat_in", "n_flat_out", "n_small_in",
+               "n_small_out", "pixels_changed", "pixels_roofed")
+GEN_EVAL = ("eval_facets", "eval_movers", "eval_movers_small", "eval_movers_flat", "eval_longest_chain")
+GEN_PLANE = ("plane_pixels_in", "plane_pixels_out")
+GEN_BUILDING = ("building_facets_in", "building_facets_out", "building_pixels_changed", "building_sum_abs_dtop",
+                "building_max_abs_dtop")
+GEN_MS = ("ms_tops", "ms_facets", "ms_decide", "ms_apply", "ms_figures")
+
+
+class RoofGeneraliseParams(C.Structure):
+    """bs_roof_generalise_params (include/bs_api.h)"""
+    _fields_ = [("min_pixels", C.c_int64), ("merge_flat", C.c_int32), ("step_tol", C.c_int32), ("bend_tol", C.c_int32),
+                ("max_rounds", C.c_int32)]
+
+
+class RoofGeneralise(C.Structure):
+    """bs_roof_generalise (include/bs_api.h): totals, per-evaluation, per-plane and per-building figures, host memory owned
+    by the library."""
+    _fields_ = ([(k, C.c_int32) for k in ("width", "height", "n_buildings", "n_planes", "rounds", "converged")] +
+                [(k, C.c_int64) for k in GEN_SCALARS] +
+                [(k, C.POINTER(C.c_int64)) for k in GEN_EVAL + GEN_PLANE + GEN_BUILDING] + [(k, C.c_double) for k in GEN_MS])
 
 
 class Outlines(C.Structure):
@@ -419,6 +444,13 @@ def load():
     L.bs_roof_facets_free.restype = None
     L.bs_roof_edge_kinds.argtypes = [fcp, C.c_int32, C.c_int32, vp]
     L.bs_roof_edges_write_obj.argtypes = [ip, ip, ip, C.c_int32, C.c_int32, C.c_int32, fcp, vp, ip, C.c_char_p]
+    gnp = C.POINTER(RoofGeneralise)
+    gen_args = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, dp, ip, ip, ip, C.c_int32, C.c_int32, ip,
+                C.POINTER(RoofGeneraliseParams), ip, gnp]
+    L.bs_roof_generalise_dev.argtypes = gen_args
+    L.bs_roof_generalise.argtypes = gen_args
+    L.bs_roof_generalise_free.argtypes = [gnp]
+    L.bs_roof_generalise_free.restype = None
     olp = C.POINTER(Outlines)
     L.bs_facet_outlines_count_dev.argtypes = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, olp]
     L.bs_facet_outlines.argtypes = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, olp]

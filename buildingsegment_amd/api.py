@@ -11,6 +11,7 @@ library; nothing is computed in Python and there is no CPU fallback.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 from contextlib import contextmanager
 from dataclasses import dataclass, field
@@ -662,12 +663,59 @@ class Context:
                                                d_face_building or None, d_face_kind or None))
 
     def solid_model(self, xyz, plane_idx, planes, bin=100, bin_height=1000, threshold=10, kernel_size=5, iterations=2,
-                    min_normal_z=0.5, min_votes=1, refit=False, base_z=None, flat=None):
-        """roof_model() followed by solids(): returns (Footprints, Buildings, Roofs, Solids)."""
+                    min_normal_z=0.5, min_votes=1, refit=False, base_z=None, flat=None, generalise=None):
+        """roof_model() followed by solids(): returns (Footprints, Buildings, Roofs, Solids).  generalise: a dict of the
+        parameters of generalise_roofs() (min_pixels, merge_flat, step_tol, bend_tol, max_rounds); the Roofs returned are
+        then the generalised ones and the Solids theirs."""
         fp, b, r = self.roof_model(xyz, plane_idx, planes, bin=bin, bin_height=bin_height, threshold=threshold,
                                    kernel_size=kernel_size, iterations=iterations, min_normal_z=min_normal_z,
                                    min_votes=min_votes, refit=refit)
+        if generalise is not None:
+            r = self.generalise_roofs(b.map, r, b, base_z=base_z, flat=flat, **generalise).roofs
         return fp, b, r, self.solids(b.map, r, b, base_z=base_z, flat=flat)
+
+    # ---- roof generalisation: small and coplanar facets merged (bs_roof_generalise, include/bs_api.h) ------------------
+    def generalise_roofs(self, bmap, roofs, buildings=None, base_z=None, flat=None, min_pixels=0, merge_flat=False,
+                         step_tol=200, bend_tol=0, max_rounds=64):
+        """Merge every roof facet with fewer than min_pixels pixels, and (merge_flat) every facet across a FLAT edge, into
+        its highest-ranking neighbour with the longest common border, round by round until nothing moves (or max_rounds
+        rounds were applied).  The arguments before min_pixels are those of solids().  Returns RoofGeneralise: the
+        figures, .roof (the new roof image) and .roofs (a Roofs every later stage accepts)."""
+        bmap = np.ascontiguousarray(bmap, dtype=np.int32)
+        if roofs.roof is None:
+            raise ValueError("generalise_roofs: the roof image is on the device: use generalise_roofs_dev")
+        roof = np.ascontiguousarray(roofs.roof, dtype=np.int32)
+        if bmap.ndim != 2 or roof.shape != bmap.shape:
+            raise ValueError("generalise_roofs: bmap and roofs.roof must be [height][width] of the same size")
+        base_z, flat = _solid_defaults(buildings, base_z, flat)
+        h, w = bmap.shape
+        tabs = _solid_tables(roofs.normal, roofs.center, roofs.z_min, roofs.z_max)
+        par = _lib.RoofGeneraliseParams(int(min_pixels), int(merge_flat), int(step_tol), int(bend_tol), int(max_rounds))
+        new = np.empty((h, w), dtype=np.int32)
+        out = _lib.RoofGeneralise()
+        self._check(self._L.bs_roof_generalise(self._h, bmap.ctypes.data, roof.ctypes.data, w, h, len(flat), len(tabs[0]),
+                                               *[t.ctypes.data for t in tabs], int(roofs.bin), base_z,
+                                               (flat if len(flat) else np.zeros(1, np.int32)).ctypes.data, C.byref(par),
+                                               new.ctypes.data, C.byref(out)))
+        g = _take_roof_generalise(self._L, out, new)
+        g.roofs = copy.copy(roofs)  # the tables, z_min / z_max and bin stay
+        g.roofs.roof, g.roofs.pixels, g.roofs.support, g.roofs.height = new, g.plane_pixels_out[1:].copy(), None, None
+        return g
+
+    def generalise_roofs_dev(self, d_map, d_roof, width, height, normal, center, z_min, z_max, bin, base_z, flat, d_roof_out,
+                             min_pixels=0, merge_flat=False, step_tol=200, bend_tol=0, max_rounds=64):
+        """Device-resident form (bs_roof_generalise_dev): d_map, d_roof and d_roof_out ([height][width] int32, written; it
+        may be d_roof) are device pointers (ints), the tables host arrays; len(flat) is n_buildings.  Returns
+        RoofGeneralise with roof and roofs None."""
+        tabs = _solid_tables(normal, center, z_min, z_max)
+        flat = np.ascontiguousarray(flat, dtype=np.int32).reshape(-1)
+        par = _lib.RoofGeneraliseParams(int(min_pixels), int(merge_flat), int(step_tol), int(bend_tol), int(max_rounds))
+        out = _lib.RoofGeneralise()
+        self._check(self._L.bs_roof_generalise_dev(self._h, d_map or None, d_roof or None, width, height, len(flat),
+                                                   len(tabs[0]), *[t.ctypes.data for t in tabs], int(bin), int(base_z),
+                                                   (flat if len(flat) else np.zeros(1, np.int32)).ctypes.data,
+                                                   C.byref(par), d_roof_out or None, C.byref(out)))
+        return _take_roof_generalise(self._L, out, None)
 
     # ---- roof facets and the edges between them (bs_roof_facets, include/bs_api.h) -------------------------------------
     def roof_facets(self, bmap, roof, top, n_buildings=None, n_planes=None):
@@ -1417,6 +1465,59 @@ def write_solids_obj(solids, path, origin=None):
                                          str(path).encode())
     if rc != 0:
         raise BsError(rc, f"cannot write {path} (or the mesh arrays do not fit each other)")
+
+
+@dataclass
+class RoofGeneralise:
+    """bs_roof_generalise: rounds (applied evaluations), converged, the in / out totals, the per-evaluation arrays
+    [rounds + 1] (eval_*), the per-plane pixel counts [n_planes + 1] (entry 0 = unroofed) and the per-building figures as
+    include/bs_api.h names them; roof is the new roof image (None after generalise_roofs_dev) and roofs the Roofs over it."""
+    width: int
+    image_height: int
+    n_buildings: int
+    n_planes: int
+    rounds: int
+    converged: int
+    n_facets_in: int
+    n_facets_out: int
+    n_edges_in: int
+    n_edges_out: int
+    n_flat_in: int
+    n_flat_out: int
+    n_small_in: int
+    n_small_out: int
+    pixels_changed: int
+    pixels_roofed: int
+    eval_facets: np.ndarray
+    eval_movers: np.ndarray
+    eval_movers_small: np.ndarray
+    eval_movers_flat: np.ndarray
+    eval_longest_chain: np.ndarray
+    plane_pixels_in: np.ndarray
+    plane_pixels_out: np.ndarray
+    building_facets_in: np.ndarray
+    building_facets_out: np.ndarray
+    building_pixels_changed: np.ndarray
+    building_sum_abs_dtop: np.ndarray
+    building_max_abs_dtop: np.ndarray
+    info: dict = field(default_factory=dict)
+    roof: np.ndarray | None = field(default=None, repr=False)
+    roofs: "Roofs | None" = field(default=None, repr=False)
+
+
+def _take_roof_generalise(L, out, roof) -> RoofGeneralise:
+    """Copy a bs_roof_generalise into numpy arrays and release it."""
+    try:
+        arrs = {}
+        for group, n in ((_lib.GEN_EVAL, out.rounds + 1), (_lib.GEN_PLANE, out.n_planes + 1),
+                         (_lib.GEN_BUILDING, out.n_buildings)):
+            for name in group:
+                arrs[name] = np.ctypeslib.as_array(getattr(out, name), (n,)).copy() if n else np.zeros(0, np.int64)
+        info = {k: getattr(out, k) for k in _lib.GEN_MS}
+        return RoofGeneralise(out.width, out.height, out.n_buildings, out.n_planes, out.rounds, out.converged,
+                              *[getattr(out, k) for k in _lib.GEN_SCALARS], info=info, roof=roof, **arrs)
+    finally:
+        L.bs_roof_generalise_free(C.byref(out))
 
 
 @dataclass

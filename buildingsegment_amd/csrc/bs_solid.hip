@@ -23,6 +23,7 @@
 
 #include "bs_common.h"
 #include "bs_roofheight.h"
+#include "bs_tops.h"
 
 namespace bs {
 namespace {
@@ -122,50 +123,7 @@ __device__ inline unsigned mids_mask(const Corner& K, int32_t c, int32_t za, int
   return K.d & below_mask(K, hi) & ~below_mask(K, lo + 1);
 }
 
-// ---- 1. tops ---------------------------------------------------------------------------------------------------------
-struct Tables {  // per plane, device: entry p - 1 is plane p
-  const double* normal;
-  const int32_t* center;
-  const int32_t* z_min;
-  const int32_t* z_max;
-};
-
-__global__ __launch_bounds__(256) void tops_kernel(const int32_t* __restrict__ map, const int32_t* __restrict__ roof, int w,
-                                                   int h, int32_t nb, int32_t npl, Tables t,
-                                                   const int32_t* __restrict__ flat, int bin, int32_t base,
-                                                   int4* __restrict__ top, int32_t* __restrict__ cmap, int* __restrict__ bad)
-{
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= (int64_t)w * h)
-    return;
-  int32_t c = map[i];
-  const int32_t r = roof[i];
-  if (c >= nb || r > npl || (r > 0 && c < 0)) {
-    atomicOr(bad, 1);
-    c = -1;
-  }
-  int4 v = make_int4(INT32_MIN, INT32_MIN, INT32_MIN, INT32_MIN);
-  if (c >= 0) {
-    if (r > 0) {
-      const int y = (int)(i / w), x = (int)(i - (int64_t)y * w);
-      const int32_t s = r - 1;
-      const double* n = t.normal + 3 * s;
-      const int32_t* ce = t.center + 3 * s;
-      const int32_t lo = t.z_min[s], hi = t.z_max[s];
-      const int64_t X0 = (int64_t)x * bin, Y0 = (int64_t)y * bin;
-      v.x = max(base, (int32_t)roof_height(n, ce, lo, hi, X0, Y0));
-      v.y = max(base, (int32_t)roof_height(n, ce, lo, hi, X0 + bin, Y0));
-      v.z = max(base, (int32_t)roof_height(n, ce, lo, hi, X0, Y0 + bin));
-      v.w = max(base, (int32_t)roof_height(n, ce, lo, hi, X0 + bin, Y0 + bin));
-    } else {
-      v.x = v.y = v.z = v.w = max(base, flat[c]);
-    }
-  } else {
-    c = -1;
-  }
-  top[i] = v;
-  cmap[i] = c;
-}
+// ---- 1. tops: tops_kernel of bs_tops.h ------------------------------------------------------------------------------
 
 // ---- figures ---------------------------------------------------------------------------------------------------------
 struct Fig {  // per building, device

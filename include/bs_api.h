@@ -1013,6 +1013,103 @@ int bs_roof_edges_write_obj(const int32_t* facet, const int32_t* map, const int3
                             int32_t bin, const struct bs_roof_facets* f, const uint8_t* kind, const int32_t* origin,
                             const char* path);
 
+/* ---- roof generalisation: small facets and facets across a FLAT edge merged into their neighbours ----
+ *
+ * A step between bs_roofs and bs_solids_count_dev: its output is a new roof image, and every later stage runs on it
+ * unchanged.  Inputs are those of bs_solids_count_dev: map, roof, width, height, n_buildings, n_planes, the host tables
+ * normal / center / z_min / z_max, bin, base_z and flat; and the parameters below.  The plane of a building pixel is
+ * P = roof > 0 ? roof : 0.
+ *
+ * The state is an image R, R0 = roof.  An EVALUATION of R is:
+ * 1. T = the tops of (map, R): step 1 of the solids, with the same H, the same clamps and the same flat.
+ * 2. The facets and edges of (map, R, T) exactly as "roof facets" defines them: ids by ascending start pixel, pixels,
+ *    plane, building, and per edge length, step_abs_sum and bend_sum.
+ * 3. kind(e) by the rule of bs_roof_edge_kinds(step_tol, bend_tol).
+ * 4. g OUTRANKS f iff pixels[g] > pixels[f], or they are equal and g < f.
+ * 5. A neighbour g of f (an edge {f, g} exists) is a CANDIDATE of f iff plane[g] > 0, g outranks f, and
+ *    pixels[f] < min_pixels or (merge_flat and kind == FLAT).  Its reason is FLAT when merge_flat and the edge is FLAT,
+ *    else SMALL.
+ * 6. target[f] is the candidate with the largest length; among equals the one that outranks the others.  A facet without
+ *    a candidate STAYS; every other facet MOVES.
+ * 7. end[f] = f if f stays, else end[target[f]].  Ranks rise strictly along a chain, so chains are finite and acyclic.
+ *    The chain of f has as many links as there are moves from f to end[f]; longest_chain is the largest (0 without a mover).
+ * 8. movers is the number of facets that move; movers_small / movers_flat split it by the reason of the target.
+ * APPLYING an evaluation gives R': a pixel of a moving facet f gets plane[end[f]] (always > 0); every other pixel keeps its
+ * value bit for bit, -1 and 0 included.
+ *
+ * The call runs evaluations r = 1, 2, ..., max_rounds + 1.  An evaluation with movers == 0 ends it (converged = 1);
+ * evaluation max_rounds + 1 is never applied (converged = 0 if it has movers); every other evaluation is applied.  rounds is
+ * the number of applied evaluations, so there are rounds + 1 evaluations and the last one is always of the final image.
+ * max_rounds = 0 only reports.  Every moving chain joins one connected region of one plane, so the facet count falls by at
+ * least movers in each applied round and the loop ends without the cap.
+ *
+ * Consequences.  Pixels of different buildings never merge (no edge between them).  Diagonal contact is no edge.  An
+ * unroofed facet (plane 0) is never a target, but it can move and become roofed.  min_pixels <= 1 with merge_flat == 0
+ * returns the input with rounds == 0.  A converged output run again with the same parameters returns itself with
+ * rounds == 0.  Everything is an exact integer except the division inside H, which the roof stage pins. */
+struct bs_roof_generalise_params {
+  int64_t min_pixels; /* facets with fewer pixels look for a neighbour; 0 or 1: none */
+  int32_t merge_flat; /* != 0: a facet also moves across a FLAT edge */
+  int32_t step_tol;   /* of bs_roof_edge_kinds */
+  int32_t bend_tol;   /* of bs_roof_edge_kinds */
+  int32_t max_rounds; /* applied evaluations at most */
+};
+
+#define BS_GEN_FIG_CAP 1024   /* buildings 0 .. cap - 1: per-building figures reduced in LDS, global atomics from the cap on */
+#define BS_GEN_PLANE_CAP 1024 /* planes 0 .. cap - 1 (0 = unroofed): pixel counts in LDS, global atomics from the cap on */
+
+/* (no typedef: the host-memory entry point below has the struct's name, so the type is always `struct bs_roof_generalise`) */
+struct bs_roof_generalise {
+  int32_t width, height, n_buildings, n_planes;
+  int32_t rounds, converged;
+  /* "in": the first evaluation, "out": the last.  n_flat: FLAT edges; n_small: facets below min_pixels */
+  int64_t n_facets_in, n_facets_out, n_edges_in, n_edges_out, n_flat_in, n_flat_out, n_small_in, n_small_out;
+  int64_t pixels_changed; /* pixels whose output value differs from the input */
+  int64_t pixels_roofed;  /* of those: P was 0 and is now > 0 */
+  /* per evaluation [rounds + 1]; host memory owned by the library */
+  int64_t* eval_facets;
+  int64_t* eval_movers;
+  int64_t* eval_movers_small;
+  int64_t* eval_movers_flat;
+  int64_t* eval_longest_chain;
+  /* per plane [n_planes + 1], entry 0 = unroofed: building pixels with that P */
+  int64_t* plane_pixels_in;
+  int64_t* plane_pixels_out;
+  /* per building [n_buildings].  dtop = |T_last - T_first| over the four corners of every pixel of the building, T_first
+   * and T_last the tops of the first and the last evaluation: what min_pixels and the tolerances are chosen by */
+  int64_t* building_facets_in;
+  int64_t* building_facets_out;
+  int64_t* building_pixels_changed;
+  int64_t* building_sum_abs_dtop;
+  int64_t* building_max_abs_dtop;
+  /* device time (HIP events on the context's stream), summed over the evaluations */
+  double ms_tops;    /* step 1 */
+  double ms_facets;  /* step 2, the read-backs of its sizes included */
+  double ms_decide;  /* steps 3 to 8 */
+  double ms_apply;   /* the applied rounds */
+  double ms_figures; /* the per-plane and per-building figures, once */
+};
+
+/* d_map, d_roof and d_roof_out ([height][width] int32, written; it may be d_roof) are device pointers, the tables and flat
+ * host arrays as for bs_solids_count_dev; out's arrays are host memory owned by the library (bs_roof_generalise_free, which
+ * accepts a zeroed struct).  The stage works in scratch of its own: it does not disturb what bs_solids_count_dev,
+ * bs_roof_facets_dev or any *_count_dev left on the context for its *_emit_dev, and it keeps no state itself.
+ * BS_ERR_INVALID: null pointer, width or height < 1, width * height >= 2^30 or (width + 1) * (height + 1) >= 2^31,
+ * n_buildings or n_planes < 0, bin < 1, or a negative parameter.  BS_ERR_RANGE: a map value >= n_buildings, a roof value >
+ * n_planes, or roof > 0 where map < 0.  On any error d_roof_out and out are left untouched and the context stays usable.
+ * Synchronises. */
+int bs_roof_generalise_dev(bs_ctx* ctx, const int32_t* d_map, const int32_t* d_roof, int32_t width, int32_t height,
+                           int32_t n_buildings, int32_t n_planes, const double* normal, const int32_t* center,
+                           const int32_t* z_min, const int32_t* z_max, int32_t bin, int32_t base_z, const int32_t* flat,
+                           const struct bs_roof_generalise_params* params, int32_t* d_roof_out,
+                           struct bs_roof_generalise* out);
+/* Host-memory twin: map, roof and roof_out (may be roof) are host pointers. */
+int bs_roof_generalise(bs_ctx* ctx, const int32_t* map, const int32_t* roof, int32_t width, int32_t height,
+                       int32_t n_buildings, int32_t n_planes, const double* normal, const int32_t* center,
+                       const int32_t* z_min, const int32_t* z_max, int32_t bin, int32_t base_z, const int32_t* flat,
+                       const struct bs_roof_generalise_params* params, int32_t* roof_out, struct bs_roof_generalise* out);
+void bs_roof_generalise_free(struct bs_roof_generalise* g);
+
 /* ---- facet outlines: every label of a label image as polygon rings with holes ----
  *
  * Input: label[height][width] of int32, negative = outside, else 0 .. n_labels - 1; in the pipeline the facet image of
