@@ -44,7 +44,7 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_outline_triangles_count_dev", "bs_outline_triangles_emit_dev", "bs_outline_triangles",
            "bs_outline_triangles_free", "bs_outline_triangles_write_obj", "bs_poly_solids_count_dev",
            "bs_poly_solids_emit_dev", "bs_poly_solids", "bs_poly_solids_free", "bs_model_raster_dev", "bs_model_raster",
-           "bs_model_raster_free"]
+           "bs_model_raster_free", "bs_point_residuals_dev", "bs_point_residuals", "bs_point_residuals_free"]
 
 
 class Params(C.Structure):
@@ -308,6 +308,24 @@ class ModelRaster(C.Structure):
                 [(k, C.c_double) for k in MRASTER_MS])
 
 
+PRESID_FIG_CAP = 256  # BS_PRESID_FIG_CAP of include/bs_api.h
+PRESID_CHUNK = 256    # BS_PRESID_CHUNK
+PRESID_GRID = 2048    # BS_PRESID_GRID
+PRESID_HEAD = ("width", "height", "n_labels", "bin", "clip2", "fig_cap", "chunk", "grid")
+PRESID_FIGURES = ("points", "multi", "above", "below", "in_points", "sum_r2", "sum_abs_r2", "max_abs_r2", "sq_lo", "sq_hi",
+                  "plane_points", "plane_in")
+PRESID_TOTALS = ("n_points", "n_triangles", "total_points", "total_above", "total_below", "total_in_points", "total_sum_r2",
+                 "total_sum_abs_r2", "max_abs_r2_all", "total_sq_lo", "total_sq_hi", "total_plane_points", "total_plane_in",
+                 "n_uncovered", "n_multi", "n_rows", "n_items", "max_list", "n_empty_pixel", "n_height_wide")
+PRESID_MS = ("ms_rows", "ms_spans", "ms_lists", "ms_points")
+
+
+class PointResiduals(C.Structure):
+    """bs_point_residuals (include/bs_api.h): totals and per-label figures, host memory owned by the library."""
+    _fields_ = ([(k, C.c_int32) for k in PRESID_HEAD] + [(k, C.c_int64) for k in PRESID_TOTALS] +
+                [(k, C.POINTER(C.c_int64)) for k in PRESID_FIGURES] + [(k, C.c_double) for k in PRESID_MS])
+
+
 class BsError(RuntimeError):
     def __init__(self, status, detail=""):
         self.status = status
@@ -498,5 +516,11 @@ def load():
                                   otp, cop, sop, olp]
     L.bs_model_raster_free.argtypes = [mrp]
     L.bs_model_raster_free.restype = None
+    prp = C.POINTER(PointResiduals)
+    L.bs_point_residuals_dev.argtypes = [vp, ip, C.c_int64, C.c_int32, ip, ip, C.c_int32, ip, ip, ip, prp]
+    L.bs_point_residuals.argtypes = [vp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, ip, C.c_int64,
+                                     C.c_int32, ip, ip, C.c_int32, ip, ip, ip, prp, otp, cop, sop, olp]
+    L.bs_point_residuals_free.argtypes = [prp]
+    L.bs_point_residuals_free.restype = None
     _LIB = L
     return L

@@ -1078,6 +1078,79 @@ class Context:
             r = self.model_raster(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)[0]
         return model_fidelity_of(r, roof_facets.facet_building, solids.n_buildings), r
 
+    # ---- point residuals: every point of the cloud against the polygon model (bs_point_residuals) -------------------------
+    def point_residuals(self, label, top, xyz, n_labels=None, num=0, den=1, cell_log2=0, bin=1, plane_idx=None,
+                        label_plane=None, clip2=None, outputs=True):
+        """Every point of the cloud against the outline triangles of the images (include/bs_api.h, "point residuals").
+        label is [height][width], top [height][width][4] as Solids.top, xyz [n][3] int32 millimetres shifted to the origin
+        of the images.  plane_idx [n] and label_plane [n_labels] come together or not at all.  clip2: the inlier bound in
+        doubled millimetres, None for no clipping.  outputs=False leaves the three per-point arrays out (None) and computes
+        the figures alone.  Returns (PointResiduals, OutlineTriangles, the CleanOutlines with their vertices, the
+        SimpleOutlines without vertices, the plain Outlines without vertices)."""
+        label = np.ascontiguousarray(label, dtype=np.int32)
+        if label.ndim != 2 or label.size == 0:
+            raise ValueError("point_residuals: label must be [height][width]")
+        if top is None:
+            raise ValueError("point_residuals: the stage needs a top image")
+        top = np.ascontiguousarray(top, dtype=np.int32)
+        if top.shape != label.shape + (4,):
+            raise ValueError("point_residuals: top must be [height][width][4]")
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError("point_residuals: xyz must be [n][3]")
+        h, w = label.shape
+        n = len(xyz)
+        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        pi, lp = _plane_pair("point_residuals", plane_idx, label_plane, n, nl)
+        arr = [np.empty(n, np.int32) for _ in range(3)] if outputs else [None] * 3
+        out, tri, clean = _lib.PointResiduals(), _lib.OutlineTriangles(), _lib.CleanOutlines()
+        simple, plain = _lib.SimpleOutlines(), _lib.Outlines()
+        self._check(self._L.bs_point_residuals(self._h, label.ctypes.data, top.ctypes.data, w, h, nl, int(num), int(den),
+                                               int(cell_log2), xyz.ctypes.data, n, int(bin),
+                                               pi.ctypes.data if pi is not None else None,
+                                               lp.ctypes.data if lp is not None else None, _clip2(clip2),
+                                               *[a.ctypes.data if a is not None else None for a in arr], C.byref(out),
+                                               C.byref(tri), C.byref(clean), C.byref(simple), C.byref(plain)))
+        return (_take_point_residuals(self._L, out, *arr), _take_outline_triangles(self._L, tri, True),
+                _take_clean_outlines(self._L, clean, True), _take_simple_outlines(self._L, simple, False),
+                _take_outlines(self._L, plain, False))
+
+    def point_residuals_dev(self, d_xyz, n, bin=1, d_plane_idx=0, label_plane=None, clip2=None, d_label_out=0, d_r2=0,
+                            d_cover=0):
+        """Device-resident stage (bs_point_residuals_dev) over the triangles that the last outline_triangles_dev or
+        poly_solids_dev left on this context, which it does not change: d_xyz [n][3] and d_plane_idx [n] are device pointers
+        (ints), label_plane a host table of that count's n_labels; d_label_out, d_r2, d_cover device pointers to int32 [n]
+        or 0.  Returns the PointResiduals with its per-point arrays None."""
+        lp = None if label_plane is None else np.ascontiguousarray(label_plane, dtype=np.int32).reshape(-1)
+        out = _lib.PointResiduals()
+        self._check(self._L.bs_point_residuals_dev(self._h, d_xyz or None, int(n), int(bin), d_plane_idx or None,
+                                                   lp.ctypes.data if lp is not None else None, _clip2(clip2),
+                                                   d_label_out or None, d_r2 or None, d_cover or None, C.byref(out)))
+        if lp is not None and len(lp) != out.n_labels:
+            self._L.bs_point_residuals_free(C.byref(out))
+            raise ValueError("point_residuals_dev: label_plane must have one entry per label of the count")
+        return _take_point_residuals(self._L, out)
+
+    def point_fidelity(self, xyz, roof_facets, solids, tolerance_mm=0, plane_idx=None, clip_mm=None, bin=None, sweeps=None):
+        """How far the polygon model of building_model() at this tolerance lies from the points it was built from, per
+        building, beside model_fidelity(): point_residuals() of the cloud against the facet image of roof_facets() /
+        roof_structure() with the tops of solids(), its per-label figures added up by facet_building.  plane_idx: the
+        planes of the points, compared with facet_plane.  clip_mm: the inlier bound in millimetres, None for no clipping.
+        sweeps: the sweep mode of the call (set_outline_sweeps).  Returns (PointFidelity, PointResiduals)."""
+        if roof_facets.facet is None:
+            raise ValueError("point_fidelity: the facet image is on the device: use point_residuals_dev")
+        if solids.top is None:
+            raise ValueError("point_fidelity: the Solids carry no top image (solids(top=True))")
+        b = solids.bin if bin is None else bin
+        num, den = simplify_tolerance(tolerance_mm, b)
+        if clip_mm is not None and (int(clip_mm) != clip_mm or clip_mm < 0):
+            raise ValueError("point_fidelity: clip_mm must be a whole number >= 0")
+        with self._sweeps(sweeps):
+            r = self.point_residuals(roof_facets.facet, solids.top, xyz, n_labels=roof_facets.n_facets, num=num, den=den, bin=b,
+                                     plane_idx=plane_idx, label_plane=None if plane_idx is None else roof_facets.facet_plane,
+                                     clip2=None if clip_mm is None else 2 * int(clip_mm), outputs=False)[0]
+        return point_fidelity_of(r, roof_facets.facet_building, solids.n_buildings), r
+
 
 @dataclass
 class PlaneVotes:
@@ -2125,6 +2198,143 @@ def model_fidelity_of(raster, label_building, n_buildings=None) -> ModelFidelity
     rmse = np.array([(sq[c] / 4 / int(n[c])) ** 0.5 for c in range(nb)], np.float64)
     return ModelFidelity(nb, pixels, pixels - kept, add(raster.model_pixels) - kept, add(raster.multi), errp,
                          add(raster.sum_abs_e2) / 2.0 / n, mx / 2.0, rmse)
+
+
+NO_CLIP2 = (1 << 31) - 1  # clip2 of a call without clipping: no |r2| reaches it
+
+
+def _clip2(clip2):
+    if clip2 is None:
+        return NO_CLIP2
+    c = int(clip2)
+    if c != clip2 or c > NO_CLIP2:
+        raise ValueError("clip2 must be a whole number below 2^31 or None")
+    return c
+
+
+def _plane_pair(who, plane_idx, label_plane, n, nl):
+    if (plane_idx is None) != (label_plane is None):
+        raise ValueError(f"{who}: plane_idx and label_plane come together or not at all")
+    if plane_idx is None:
+        return None, None
+    pi = np.ascontiguousarray(plane_idx, dtype=np.int32).reshape(-1)
+    lp = np.ascontiguousarray(label_plane, dtype=np.int32).reshape(-1)
+    if len(pi) != n or len(lp) != nl:
+        raise ValueError(f"{who}: plane_idx must have one entry per point and label_plane one per label")
+    return pi, (lp if nl else np.zeros(1, np.int32))
+
+
+@dataclass
+class PointResiduals:
+    """bs_point_residuals: the totals, the per-label figures (points, multi, above, below, and over the inliers in_points,
+    sum_r2, sum_abs_r2, max_abs_r2, sq_lo, sq_hi; plane_points, plane_in; the sum of r2 squared of label l is
+    sq_hi[l] * 2^32 + sq_lo[l]) and the three per-point arrays: label (the label of the triangle over the point, -1: none),
+    r2 (twice the point's height above the model, INT32_MIN where none), cover (the triangles that cover it).  The arrays
+    are None after point_residuals_dev."""
+    width: int
+    height: int
+    n_labels: int
+    bin: int
+    clip2: int
+    fig_cap: int
+    chunk: int
+    grid: int
+    n_points: int
+    n_triangles: int
+    total_points: int
+    total_above: int
+    total_below: int
+    total_in_points: int
+    total_sum_r2: int
+    total_sum_abs_r2: int
+    max_abs_r2_all: int
+    total_sq_lo: int
+    total_sq_hi: int
+    total_plane_points: int
+    total_plane_in: int
+    n_uncovered: int
+    n_multi: int
+    n_rows: int
+    n_items: int
+    max_list: int
+    n_empty_pixel: int
+    n_height_wide: int
+    points: np.ndarray
+    multi: np.ndarray
+    above: np.ndarray
+    below: np.ndarray
+    in_points: np.ndarray
+    sum_r2: np.ndarray
+    sum_abs_r2: np.ndarray
+    max_abs_r2: np.ndarray
+    sq_lo: np.ndarray
+    sq_hi: np.ndarray
+    plane_points: np.ndarray
+    plane_in: np.ndarray
+    info: dict = field(default_factory=dict)
+    label: np.ndarray | None = field(default=None, repr=False)
+    r2: np.ndarray | None = field(default=None, repr=False)
+    cover: np.ndarray | None = field(default=None, repr=False)
+
+
+def _take_point_residuals(L, out, label=None, r2=None, cover=None) -> PointResiduals:
+    """Copy a bs_point_residuals into numpy arrays and release it."""
+    n = out.n_labels
+    try:
+        arrs = {k: (np.ctypeslib.as_array(getattr(out, k), (n,)).copy() if n else np.zeros(0, np.int64))
+                for k in _lib.PRESID_FIGURES}
+        info = {k: getattr(out, k) for k in _lib.PRESID_MS}
+        return PointResiduals(*[getattr(out, k) for k in _lib.PRESID_HEAD + _lib.PRESID_TOTALS], info=info, label=label, r2=r2,
+                              cover=cover, **arrs)
+    finally:
+        L.bs_point_residuals_free(C.byref(out))
+
+
+@dataclass
+class PointFidelity:
+    """Per building, from a PointResiduals and the building of every label.  points: the points over one of its labels;
+    inlier_share, above_share, below_share: the parts of them within the clip, above and below it; over the inliers the
+    bias (the signed mean residual), the mean absolute residual, the maximum and the RMSE in millimetres; plane_share: the
+    part of the points whose plane is the plane of their label, plane_in_share: the part of those that are inliers (both
+    0 without a plane table).  A building without a point (or an inlier) has 0 in the shares (the means)."""
+    n_buildings: int
+    points: np.ndarray
+    in_points: np.ndarray
+    inlier_share: np.ndarray
+    above_share: np.ndarray
+    below_share: np.ndarray
+    bias_mm: np.ndarray
+    mean_abs_mm: np.ndarray
+    max_abs_mm: np.ndarray
+    rmse_mm: np.ndarray
+    plane_share: np.ndarray
+    plane_in_share: np.ndarray
+
+
+def point_fidelity_of(res, label_building, n_buildings=None) -> PointFidelity:
+    """The per-label figures of a PointResiduals added up by building (host only; Python integers for the sum of squares)."""
+    lb = np.ascontiguousarray(label_building, dtype=np.int64).reshape(-1)
+    if len(lb) != res.n_labels:
+        raise ValueError("point_fidelity_of: label_building must have one entry per label")
+    nb = (int(lb.max()) + 1 if len(lb) else 0) if n_buildings is None else int(n_buildings)
+    if len(lb) and (lb.min() < 0 or lb.max() >= nb):
+        raise ValueError("point_fidelity_of: a label_building value outside 0 .. n_buildings - 1")
+
+    def add(v):
+        s = np.zeros(nb, np.int64)
+        np.add.at(s, lb, v)
+        return s
+
+    points, inl, ppts = add(res.points), add(res.in_points), add(res.plane_points)
+    mx = np.zeros(nb, np.int64)
+    np.maximum.at(mx, lb, res.max_abs_r2)
+    sq = [0] * nb
+    for l, c in enumerate(lb.tolist()):
+        sq[c] += (int(res.sq_hi[l]) << 32) + int(res.sq_lo[l])
+    n, ni, npl = np.maximum(points, 1), np.maximum(inl, 1), np.maximum(ppts, 1)
+    rmse = np.array([(sq[c] / 4 / int(ni[c])) ** 0.5 for c in range(nb)], np.float64)
+    return PointFidelity(nb, points, inl, inl / n, add(res.above) / n, add(res.below) / n, add(res.sum_r2) / 2.0 / ni,
+                         add(res.sum_abs_r2) / 2.0 / ni, mx / 2.0, rmse, ppts / n, add(res.plane_in) / npl)
 
 
 def simplify_tolerance(tolerance_mm, bin):

@@ -255,6 +255,8 @@ void bs_destroy(bs_ctx* c)
     b.release();
   for (auto& b : c->mr)
     b.release();
+  for (auto& b : c->pr)
+    b.release();
   for (auto& b : c->gn)
     b.release();
   for (auto& b : c->bt)

@@ -312,6 +312,7 @@ struct bs_ctx {
   int64_t ps_nv = 0, ps_nf = 0, ps_ni = 0, ps_ntri = 0;
   double ps_ms_emit[2] = {0, 0};  // vertex pass, face passes of the last emit
   bs::DevBuf mr[20];  // scratch of the model raster (bs_modelraster.hip); it keeps no state between calls
+  bs::DevBuf pr[16];  // scratch of the point residuals (bs_pointresid.hip); it keeps no state between calls
   bs::DevBuf gn[32];  // scratch of the roof generalisation (bs_generalise.hip); it keeps no state between calls
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)

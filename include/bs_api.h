@@ -1763,6 +1763,98 @@ int bs_model_raster(bs_ctx* ctx, const int32_t* label, const int32_t* top, int32
                     struct bs_simple_outlines* simple, struct bs_outlines* plain);
 void bs_model_raster_free(struct bs_model_raster* r);
 
+/* ---- point residuals: every point of the cloud against the polygon model ----
+ *
+ * The first check of the chain against its input: how far the model of the outline triangles lies from the points it was built
+ * from.  Per point: the label of the triangle over it, how many triangles cover it, and twice its height above the model.  Per
+ * label: the residual figures by which tolerance_mm, min_pixels and merge_flat are chosen.  Everything is an exact integer.
+ *
+ * Input.  The state of a successful bs_outline_triangles_count_dev or bs_poly_solids_count_dev with a top image, on the
+ * context: the clean vertices sxy, sz; tri, tri_offset, label_status; its width, height and n_labels.  bin >= 1.  A cloud
+ * d_xyz [n][3] int32 in millimetres, shifted to its origin as for bs_assign_buildings_dev; every point's base pixel
+ * (x / bin, y / bin) lies inside the image.  Optionally d_plane_idx [n] together with a host table label_plane [n_labels] (in
+ * the pipeline: facet_plane of the roof facets): both or neither.  clip2 >= 0 (int32): the inlier bound in doubled millimetres.
+ *
+ * Coverage, in doubled millimetres.  Point i stands for the centre of its millimetre cell: P = (2 x + 1, 2 y + 1).  Vertex v
+ * stands at Q = (2 bin sxy[v].x, 2 bin sxy[v].y).  The weights w_a, w_b, w_c, the ownership rule for a weight of 0 (v.y > u.y),
+ * cover, win (the lowest covering slot) and M (its label by tri_offset) are word for word those of "model raster", with P and
+ * Q in place of its centre and corners.  P is odd and Q even, so P never lies on a vertex or on an axis-parallel edge; it can
+ * lie on a slanted edge, and there the rule decides.  At bin == 1 the definition is the model raster's own.
+ *
+ * Residual.  For win = t: D, N and mz2 = floor((4 N + D) / (2 D)) as in "model raster"; r2[i] = 2 z_i - mz2, and INT32_MIN
+ * where win < 0.  With width * bin and height * bin <= 2^24, |sz| < 2^24 and |z| < 2^24, D stays below 2^52, but 4 N + D does
+ * not fit 64 bits.  The value is the mathematical one: the library forms it relative to the lowest of the three sz, in 64 bits
+ * where the bit lengths of D and of the largest height difference prove per point that this fits, and in 128 bits elsewhere
+ * (n_height_wide counts those points).
+ *
+ * Figures per label l, all int64, over the points with M = l: points; multi (cover > 1); above (r2 > clip2) and below
+ * (r2 < -clip2); over the inliers (neither): in_points, sum_r2 (signed: the bias), sum_abs_r2, max_abs_r2, sq_lo and sq_hi
+ * (the sum of r2^2 split as in "model raster"); with the plane table plane_points = #{plane_idx[i] == label_plane[l]} and
+ * plane_in, those of them that are inliers (both 0 without the table).  Totals: the sums of these (max_abs_r2_all: the
+ * maximum; n_multi: the sum of multi); n_uncovered = #{win < 0}.  And of the implementation ("Point residuals"):
+ * n_rows and n_items, the row items and the entries of the per-pixel lists; max_list, the longest list; n_empty_pixel, the
+ * points whose pixel has an empty list; n_height_wide.
+ *
+ * Promised.  n = sum points + n_uncovered.  points = in_points + above + below for every label.  At tolerance 0 with every
+ * label BS_TRI_OK or BS_TRI_EMPTY: M_i = L(base pixel of i) for every point.  At bin == 1 with the points (x, y, .) of all
+ * pixels in raster order: M, cover and mz2 (2 z - r2) equal the three images of bs_model_raster_dev on the same state.
+ *
+ * Errors.  BS_ERR_INVALID: no valid triangle state, or a state counted without top; a null cloud or out, n < 1, bin < 1,
+ * clip2 < 0; only one of d_plane_idx / label_plane.  BS_ERR_RANGE: 2^29 points or more; a point with a negative x or y, or
+ * whose pixel lies outside the image; |z| >= 2^24; an extent width * bin or height * bin above 2^24; |sz| >= 2^24 on a vertex
+ * of a triangle; 2^31 or more list entries.  On any error the outputs are untouched and the context stays usable: the cloud
+ * and the state are checked in passes of their own before the pass that writes. */
+#define BS_PRESID_FIG_CAP 256 /* labels below this number have their figures reduced in LDS (16 KiB), the rest by global atomics */
+#define BS_PRESID_CHUNK 256   /* the list entries of one workgroup while the lists are built */
+#define BS_PRESID_GRID 2048   /* workgroups of 256 of the pass over the points: beyond 524 288 points a thread takes several */
+
+struct bs_point_residuals {
+  int32_t width, height, n_labels, bin, clip2;
+  int32_t fig_cap, chunk, grid; /* BS_PRESID_FIG_CAP, BS_PRESID_CHUNK, BS_PRESID_GRID of the library */
+  int64_t n_points, n_triangles; /* n; all slots of the triangle state */
+  int64_t total_points, total_above, total_below, total_in_points, total_sum_r2, total_sum_abs_r2, max_abs_r2_all, total_sq_lo,
+      total_sq_hi, total_plane_points, total_plane_in;
+  int64_t n_uncovered, n_multi;
+  int64_t n_rows, n_items, max_list, n_empty_pixel, n_height_wide;
+  /* per label; host memory owned by the library */
+  int64_t* points;       /* [n_labels] */
+  int64_t* multi;        /* [n_labels] */
+  int64_t* above;        /* [n_labels] */
+  int64_t* below;        /* [n_labels] */
+  int64_t* in_points;    /* [n_labels] */
+  int64_t* sum_r2;       /* [n_labels] */
+  int64_t* sum_abs_r2;   /* [n_labels] */
+  int64_t* max_abs_r2;   /* [n_labels] */
+  int64_t* sq_lo;        /* [n_labels] */
+  int64_t* sq_hi;        /* [n_labels] */
+  int64_t* plane_points; /* [n_labels] */
+  int64_t* plane_in;     /* [n_labels] */
+  /* device time (HIP events on the context's stream) */
+  double ms_rows;   /* clearing, the check of the cloud, the rows of every slot, their sum, the host's read of n_rows */
+  double ms_spans;  /* the span of every row item, their sum, the host's read of n_items */
+  double ms_lists;  /* the count per pixel, its sum, the fill through the cursors */
+  double ms_points; /* the pass over the points: the outputs and the figures; the host's read of the result */
+};
+
+/* Measures the cloud against the triangles of the last successful bs_outline_triangles_count_dev (or bs_poly_solids_count_dev)
+ * on this context where they lie and changes none of that state: bs_outline_triangles_emit_dev and bs_poly_solids_emit_dev
+ * stay valid.  d_label_out, d_r2, d_cover: device arrays int32 [n] for M, r2 and cover; each may be NULL.  d_plane_idx is a
+ * device pointer, label_plane a host pointer.  The figures are always computed; out's per-label arrays are host memory owned
+ * by the library (bs_point_residuals_free, which accepts a zeroed struct).  Synchronises: once for n_rows, once for n_items,
+ * once for the checks, once for the result. */
+int bs_point_residuals_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const int32_t* d_plane_idx,
+                           const int32_t* label_plane, int32_t clip2, int32_t* d_label_out, int32_t* d_r2, int32_t* d_cover,
+                           struct bs_point_residuals* out);
+/* Host-memory twin: label, top, the cloud, plane_idx and the three outputs (each may be NULL) are host pointers.  Runs
+ * bs_outline_triangles on the images, then the stage; hands the results of the stages before to *tri, *clean, *simple and
+ * *plain unless they are NULL, as bs_outline_triangles returns them.  Errors of both. */
+int bs_point_residuals(bs_ctx* ctx, const int32_t* label, const int32_t* top, int32_t width, int32_t height, int32_t n_labels,
+                       int64_t num, int64_t den, int32_t cell_log2, const int32_t* xyz, int64_t n, int32_t bin,
+                       const int32_t* plane_idx, const int32_t* label_plane, int32_t clip2, int32_t* label_out, int32_t* r2,
+                       int32_t* cover, struct bs_point_residuals* out, struct bs_outline_triangles* tri,
+                       struct bs_clean_outlines* clean, struct bs_simple_outlines* simple, struct bs_outlines* plain);
+void bs_point_residuals_free(struct bs_point_residuals* r);
+
 #ifdef __cplusplus
 }
 #endif
