@@ -44,7 +44,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_outline_triangles_count_dev", "bs_outline_triangles_emit_dev", "bs_outline_triangles",
            "bs_outline_triangles_free", "bs_outline_triangles_write_obj", "bs_poly_solids_count_dev",
            "bs_poly_solids_emit_dev", "bs_poly_solids", "bs_poly_solids_free", "bs_model_raster_dev", "bs_model_raster",
-           "bs_model_raster_free", "bs_point_residuals_dev", "bs_point_residuals", "bs_point_residuals_free"]
+           "bs_model_raster_free", "bs_point_residuals_dev", "bs_point_residuals", "bs_point_residuals_free",
+           "bs_terrain_dev", "bs_terrain", "bs_terrain_free", "bs_set_building_bases", "bs_get_building_bases"]
 
 
 class Params(C.Structure):
@@ -326,6 +327,24 @@ class PointResiduals(C.Structure):
                 [(k, C.POINTER(C.c_int64)) for k in PRESID_FIGURES] + [(k, C.c_double) for k in PRESID_MS])
 
 
+TERRAIN_MAX_RING = 255  # BS_TERRAIN_MAX_RING of include/bs_api.h
+TERRAIN_FIG_CAP = 1024  # BS_TERRAIN_FIG_CAP
+TERRAIN_GRID = 2048     # BS_TERRAIN_GRID
+TERRAIN_HEAD = ("width", "height", "n_buildings", "bin", "ring", "q_num", "q_den", "min_ground", "fallback_z", "fig_cap", "grid",
+                "rounds_used", "n_fallback", "reserved")
+TERRAIN_TOTALS = ("n_points", "n_ring_pixels", "n_ground_pixels", "n_ring_points")
+TERRAIN_WIDE = ("ring_pixels", "ground_pixels", "ring_points", "ground_sum")
+TERRAIN_NARROW = ("ground_min", "ground_max", "ground", "status")
+TERRAIN_MS = ("ms_ring", "ms_points", "ms_pixels", "ms_pick")
+
+
+class Terrain(C.Structure):
+    """bs_terrain (include/bs_api.h): totals and per-building figures, host memory owned by the library."""
+    _fields_ = ([(k, C.c_int32) for k in TERRAIN_HEAD] + [(k, C.c_int64) for k in TERRAIN_TOTALS] +
+                [(k, C.POINTER(C.c_int64)) for k in TERRAIN_WIDE] + [(k, C.POINTER(C.c_int32)) for k in TERRAIN_NARROW] +
+                [(k, C.c_double) for k in TERRAIN_MS])
+
+
 class BsError(RuntimeError):
     def __init__(self, status, detail=""):
         self.status = status
@@ -522,5 +541,13 @@ def load():
                                      C.c_int32, ip, ip, C.c_int32, ip, ip, ip, prp, otp, cop, sop, olp]
     L.bs_point_residuals_free.argtypes = [prp]
     L.bs_point_residuals_free.restype = None
+    tnp = C.POINTER(Terrain)
+    for fn in (L.bs_terrain_dev, L.bs_terrain):
+        fn.argtypes = [vp, ip, C.c_int64, C.c_int32, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                       C.c_int32, ip, vp, ip, tnp]
+    L.bs_terrain_free.argtypes = [tnp]
+    L.bs_terrain_free.restype = None
+    L.bs_set_building_bases.argtypes = [vp, ip, C.c_int32]
+    L.bs_get_building_bases.argtypes = [vp, ip, C.c_int32, C.POINTER(C.c_int32)]
     _LIB = L
     return L

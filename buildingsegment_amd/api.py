@@ -642,7 +642,9 @@ class Context:
                                       *[t.ctypes.data for t in tabs], int(roofs.bin), base_z,
                                       (flat if len(flat) else np.zeros(1, np.int32)).ctypes.data,
                                       timg.ctypes.data if top else None, C.byref(out)))
-        return _take_solids(self._L, out, timg, True)
+        s = _take_solids(self._L, out, timg, True)
+        s.base = self.building_bases()
+        return s
 
     def solids_dev(self, d_map, d_roof, width, height, normal, center, z_min, z_max, bin, base_z, flat, d_top=0):
         """Device-resident count (bs_solids_count_dev): d_map, d_roof and the optional d_top ([height][width][4] int32)
@@ -655,7 +657,9 @@ class Context:
                                                 len(tabs[0]), *[t.ctypes.data for t in tabs], int(bin), int(base_z),
                                                 (flat if len(flat) else np.zeros(1, np.int32)).ctypes.data,
                                                 d_top or None, C.byref(out)))
-        return _take_solids(self._L, out, None, False)
+        s = _take_solids(self._L, out, None, False)
+        s.base = self.building_bases()
+        return s
 
     def solids_emit_dev(self, d_vertex, d_face_offset, d_face_index, d_face_building, d_face_kind):
         """The mesh of the last solids_dev on this context into device buffers (ints) of exactly its sizes."""
@@ -663,16 +667,30 @@ class Context:
                                                d_face_building or None, d_face_kind or None))
 
     def solid_model(self, xyz, plane_idx, planes, bin=100, bin_height=1000, threshold=10, kernel_size=5, iterations=2,
-                    min_normal_z=0.5, min_votes=1, refit=False, base_z=None, flat=None, generalise=None):
+                    min_normal_z=0.5, min_votes=1, refit=False, base_z=None, flat=None, generalise=None, terrain=None):
         """roof_model() followed by solids(): returns (Footprints, Buildings, Roofs, Solids).  generalise: a dict of the
         parameters of generalise_roofs() (min_pixels, merge_flat, step_tol, bend_tol, max_rounds); the Roofs returned are
-        then the generalised ones and the Solids theirs."""
+        then the generalised ones and the Solids theirs.  terrain: a dict of the parameters of terrain() (ring, q,
+        min_ground; {} for its defaults): the stage runs after the buildings with fallback_z = int(ground_th), its `ground`
+        is the base of every building for the generalisation and the solids (flat defaults to it where a building has no
+        point above ground), the context's own table is restored afterwards, and the Terrain is returned as a fifth
+        value."""
         fp, b, r = self.roof_model(xyz, plane_idx, planes, bin=bin, bin_height=bin_height, threshold=threshold,
                                    kernel_size=kernel_size, iterations=iterations, min_normal_z=min_normal_z,
                                    min_votes=min_votes, refit=refit)
-        if generalise is not None:
-            r = self.generalise_roofs(b.map, r, b, base_z=base_z, flat=flat, **generalise).roofs
-        return fp, b, r, self.solids(b.map, r, b, base_z=base_z, flat=flat)
+        if terrain is None:
+            if generalise is not None:
+                r = self.generalise_roofs(b.map, r, b, base_z=base_z, flat=flat, **generalise).roofs
+            return fp, b, r, self.solids(b.map, r, b, base_z=base_z, flat=flat)
+        t = self.terrain(xyz, b.map, b, bin=bin, fallback_z=int(b.ground_th), **terrain)
+        if flat is None:
+            scalar, flat = _solid_defaults(b, base_z, None)
+            flat = np.where(np.asarray(b.n_above) > 0, flat, t.ground).astype(np.int32)
+        with self._bases(t.ground if b.n_buildings else None):
+            if generalise is not None:
+                r = self.generalise_roofs(b.map, r, b, base_z=base_z, flat=flat, **generalise).roofs
+            s = self.solids(b.map, r, b, base_z=base_z, flat=flat)
+        return fp, b, r, s, t
 
     # ---- roof generalisation: small and coplanar facets merged (bs_roof_generalise, include/bs_api.h) ------------------
     def generalise_roofs(self, bmap, roofs, buildings=None, base_z=None, flat=None, min_pixels=0, merge_flat=False,
@@ -955,7 +973,7 @@ class Context:
         if solids.top is None:
             raise ValueError("roof_mesh: the Solids carry no top image (solids(top=True))")
         num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
-        with self._sweeps(sweeps):
+        with self._sweeps(sweeps), self._bases(getattr(solids, "base", None)):
             t, c, _, plain = self.outline_triangles(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num,
                                                     den=den)
         return t, c, plain
@@ -1022,7 +1040,7 @@ class Context:
             raise ValueError("building_model: the Solids carry no top image (solids(top=True))")
         b = solids.bin if bin is None else bin
         num, den = simplify_tolerance(tolerance_mm, b)
-        with self._sweeps(sweeps):
+        with self._sweeps(sweeps), self._bases(getattr(solids, "base", None)):
             p, t, c, _, plain = self.poly_solids(roof_facets.facet, solids.top, roof_facets.facet_building,
                                                  n_labels=roof_facets.n_facets, n_buildings=solids.n_buildings, num=num,
                                                  den=den, bin=b, base_z=solids.base_z)
@@ -1074,7 +1092,7 @@ class Context:
         if solids.top is None:
             raise ValueError("model_fidelity: the Solids carry no top image (solids(top=True))")
         num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
-        with self._sweeps(sweeps):
+        with self._sweeps(sweeps), self._bases(getattr(solids, "base", None)):
             r = self.model_raster(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)[0]
         return model_fidelity_of(r, roof_facets.facet_building, solids.n_buildings), r
 
@@ -1145,11 +1163,137 @@ class Context:
         num, den = simplify_tolerance(tolerance_mm, b)
         if clip_mm is not None and (int(clip_mm) != clip_mm or clip_mm < 0):
             raise ValueError("point_fidelity: clip_mm must be a whole number >= 0")
-        with self._sweeps(sweeps):
+        with self._sweeps(sweeps), self._bases(getattr(solids, "base", None)):
             r = self.point_residuals(roof_facets.facet, solids.top, xyz, n_labels=roof_facets.n_facets, num=num, den=den, bin=b,
                                      plane_idx=plane_idx, label_plane=None if plane_idx is None else roof_facets.facet_plane,
                                      clip2=None if clip_mm is None else 2 * int(clip_mm), outputs=False)[0]
         return point_fidelity_of(r, roof_facets.facet_building, solids.n_buildings), r
+
+    # ---- per-building bases: solids that stand on the terrain (bs_set_building_bases, include/bs_api.h) --------------------
+    def set_building_bases(self, base):
+        """The base of every building for solids(), generalise_roofs() and poly_solids() on this context, in place of
+        their scalar base_z (bs_set_building_bases): base [n_buildings] int32, in the pipeline Terrain.ground.  None
+        switches it off, the default.  A call over another number of buildings is refused while it is set."""
+        if base is None:
+            self._check(self._L.bs_set_building_bases(self._h, None, 0))
+            return
+        b = np.ascontiguousarray(base, dtype=np.int32).reshape(-1)
+        if not np.array_equal(b, np.asarray(base).reshape(-1)):
+            raise ValueError("set_building_bases: the bases must be whole numbers that fit 32 bits")
+        self._check(self._L.bs_set_building_bases(self._h, b.ctypes.data if len(b) else None, len(b)))
+
+    def building_bases(self):
+        """The table of set_building_bases() as the context holds it (bs_get_building_bases), or None while it is off."""
+        n = C.c_int32(0)
+        self._check(self._L.bs_get_building_bases(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        b = np.empty(n.value, np.int32)
+        self._check(self._L.bs_get_building_bases(self._h, b.ctypes.data, n.value, C.byref(n)))
+        return b
+
+    @contextmanager
+    def _bases(self, base):
+        """the building bases for one call (None: off), the previous table restored behind it"""
+        prev = self.building_bases()
+        self.set_building_bases(base)
+        try:
+            yield
+        finally:
+            self.set_building_bases(prev)
+
+    # ---- terrain: the ground height of every building from the points around it (bs_terrain, include/bs_api.h) ----------
+    def terrain(self, xyz, bmap, buildings_or_n, bin=100, ring=10, q=(1, 2), min_ground=8, fallback_z=0, images=True):
+        """The ground every building stands on, read from the lowest points of the pixels just outside its footprint
+        (include/bs_api.h, "terrain").  xyz [n][3] int32 millimetres shifted to its origin, bmap the building map,
+        buildings_or_n the Buildings of building_map() or their number.  ring: how many pixels the ring reaches out;
+        q = (num, den): the quantile of the ring pixels' lowest points that becomes `ground`; min_ground: the fewest ring
+        pixels with a point that a quantile is taken of; fallback_z: the ground of a building with fewer.  images=False leaves
+        the three images out (None).  Returns Terrain."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError("terrain: xyz must be [n][3]")
+        bmap = np.ascontiguousarray(bmap, dtype=np.int32)
+        if bmap.ndim != 2 or bmap.size == 0:
+            raise ValueError("terrain: bmap must be [height][width]")
+        h, w = bmap.shape
+        nb = int(getattr(buildings_or_n, "n_buildings", buildings_or_n))
+        owner, dist, low = ((np.empty((h, w), np.int32), np.empty((h, w), np.uint8), np.empty((h, w), np.int32)) if images
+                            else (None, None, None))
+        out = _lib.Terrain()
+        self._check(self._L.bs_terrain(self._h, xyz.ctypes.data, len(xyz), int(bin), bmap.ctypes.data, w, h, nb, int(ring),
+                                       *_quantile(q), int(min_ground), int(fallback_z),
+                                       *[a.ctypes.data if a is not None else None for a in (owner, dist, low)], C.byref(out)))
+        return _take_terrain(self._L, out, owner, dist, low)
+
+    def terrain_dev(self, d_xyz, n, d_map, width, height, n_buildings, bin=100, ring=10, q=(1, 2), min_ground=8, fallback_z=0,
+                    d_owner=0, d_dist=0, d_low=0):
+        """Device-resident stage (bs_terrain_dev): d_xyz [n][3] int32 and d_map [height][width] int32 are device pointers
+        (ints); d_owner (int32), d_dist (uint8) and d_low (int32), [height][width] each, are device pointers or 0.  Returns
+        the Terrain with its images None."""
+        out = _lib.Terrain()
+        self._check(self._L.bs_terrain_dev(self._h, d_xyz or None, int(n), int(bin), d_map or None, int(width), int(height),
+                                           int(n_buildings), int(ring), *_quantile(q), int(min_ground), int(fallback_z),
+                                           d_owner or None, d_dist or None, d_low or None, C.byref(out)))
+        return _take_terrain(self._L, out)
+
+
+@dataclass
+class Terrain:
+    """bs_terrain: the parameters, the totals, the per-building figures (ring_pixels, ground_pixels, ring_points,
+    ground_sum, ground_min, ground_max, ground, status: 0 the quantile, 1 fallback_z) and the three images: owner (the
+    building whose ring reached the pixel, the building itself on its own pixels, -1: never reached), dist (the round that
+    reached it) and low (the lowest point of a ring pixel, INT32_MAX: none, or no ring pixel).  `ground` is the table
+    Context.set_building_bases() takes.  The images are None after terrain_dev or images=False."""
+    width: int
+    height: int
+    n_buildings: int
+    bin: int
+    ring: int
+    q_num: int
+    q_den: int
+    min_ground: int
+    fallback_z: int
+    fig_cap: int
+    grid: int
+    rounds_used: int
+    n_fallback: int
+    n_points: int
+    n_ring_pixels: int
+    n_ground_pixels: int
+    n_ring_points: int
+    ring_pixels: np.ndarray
+    ground_pixels: np.ndarray
+    ring_points: np.ndarray
+    ground_sum: np.ndarray
+    ground_min: np.ndarray
+    ground_max: np.ndarray
+    ground: np.ndarray
+    status: np.ndarray
+    info: dict = field(default_factory=dict)
+    owner: np.ndarray | None = field(default=None, repr=False)
+    dist: np.ndarray | None = field(default=None, repr=False)
+    low: np.ndarray | None = field(default=None, repr=False)
+
+
+def _quantile(q):
+    num, den = q
+    if int(num) != num or int(den) != den or not (0 <= num <= den and 1 <= den < 2 ** 31):
+        raise ValueError("q must be (num, den), whole numbers with 0 <= num <= den and 1 <= den < 2^31")
+    return int(num), int(den)
+
+
+def _take_terrain(L, out, owner=None, dist=None, low=None) -> Terrain:
+    """Copy a bs_terrain into numpy arrays and release it."""
+    n = out.n_buildings
+    try:
+        arrs = {k: (np.ctypeslib.as_array(getattr(out, k), (n,)).copy() if n else np.zeros(0, dt))
+                for names, dt in ((_lib.TERRAIN_WIDE, np.int64), (_lib.TERRAIN_NARROW, np.int32)) for k in names}
+        head = {k: getattr(out, k) for k in _lib.TERRAIN_HEAD + _lib.TERRAIN_TOTALS if k != "reserved"}
+        info = {k: getattr(out, k) for k in _lib.TERRAIN_MS}
+        return Terrain(**head, **arrs, info=info, owner=owner, dist=dist, low=low)
+    finally:
+        L.bs_terrain_free(C.byref(out))
 
 
 @dataclass
@@ -1432,7 +1576,8 @@ class Solids:
     """bs_solids: the totals, the per-building figures, and the mesh (None after solids_dev: it is written by
     solids_emit_dev).  vertex is [n_vertices][4] int32 {X, Y, Z, building} in millimetres, face f has the vertices
     face_index[face_offset[f] : face_offset[f + 1]]; face_kind 0 top, 1 floor, 2 wall.  The volume of building c in
-    mm^3 is volume6[c] * bin^2 / 6."""
+    mm^3 is volume6[c] * bin^2 / 6.  base: the per-building table the Solids were built under (set_building_bases), None
+    for the scalar base_z."""
     n_buildings: int
     width: int
     image_height: int
@@ -1460,6 +1605,7 @@ class Solids:
     face_index: np.ndarray | None = field(default=None, repr=False)
     face_building: np.ndarray | None = field(default=None, repr=False)
     face_kind: np.ndarray | None = field(default=None, repr=False)
+    base: np.ndarray | None = field(default=None, repr=False)
 
 
 _SOLID_ARRAYS = (("pixels", np.int64), ("vertices", np.int64), ("faces", np.int64), ("wall_faces", np.int64),

@@ -22,6 +22,19 @@ int fail(bs_ctx* ctx, int status, const char* what, hipError_t e)
   return status;
 }
 
+int building_bases(bs_ctx* ctx, int32_t n_buildings, const char* who, const int32_t** d_table)
+{
+  *d_table = nullptr;
+  if (ctx->bases.empty())
+    return BS_OK;
+  if ((size_t)n_buildings != ctx->bases.size()) {
+    const std::string msg = std::string(who) + ": n_buildings differs from the table of bs_set_building_bases";
+    return fail(ctx, BS_ERR_INVALID, msg.c_str());
+  }
+  *d_table = ctx->bases_dev.as<int32_t>();
+  return BS_OK;
+}
+
 int check_params(bs_ctx* ctx, const bs_params* p, int64_t n)
 {
   if (!p)
@@ -259,6 +272,9 @@ void bs_destroy(bs_ctx* c)
     b.release();
   for (auto& b : c->gn)
     b.release();
+  for (auto& b : c->tn)
+    b.release();
+  c->bases_dev.release();
   for (auto& b : c->bt)
     b.release();
   c->tile_desc.release();
@@ -419,6 +435,39 @@ int bs_get_outline_sweeps(bs_ctx* ctx, struct bs_outline_sweeps* out)
     out->mode = ctx->sweeps_mode;
     out->wave_cap = BS_SWEEP_WAVE_CAP;
   }
+  return BS_OK;
+}
+
+int bs_set_building_bases(bs_ctx* ctx, const int32_t* base, int32_t n_buildings)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (n_buildings < 0 || (n_buildings > 0 && !base))
+    return bs::fail(ctx, BS_ERR_INVALID, "building bases: a null table with n_buildings > 0, or n_buildings < 0");
+  // a count under another table (or none) must not be emitted under this one
+  ctx->sd_valid = false;
+  ctx->ps_valid = false;
+  ctx->bases.clear();  // (off, also where the copy below fails)
+  if (!base || n_buildings == 0)
+    return BS_OK;
+  BS_HIP(ctx, hipSetDevice(ctx->device));
+  BS_HIP(ctx, ctx->bases_dev.reserve(4 * (size_t)n_buildings));
+  BS_HIP(ctx, hipMemcpyAsync(ctx->bases_dev.p, base, 4 * (size_t)n_buildings, hipMemcpyHostToDevice, ctx->stream));
+  BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->bases.assign(base, base + n_buildings);
+  return BS_OK;
+}
+
+int bs_get_building_bases(bs_ctx* ctx, int32_t* base, int32_t capacity, int32_t* n_buildings)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (!n_buildings || capacity < 0 || (capacity > 0 && !base))
+    return bs::fail(ctx, BS_ERR_INVALID, "building bases: a null pointer or a negative capacity");
+  *n_buildings = (int32_t)ctx->bases.size();
+  const size_t m = std::min<size_t>((size_t)capacity, ctx->bases.size());
+  if (m)
+    memcpy(base, ctx->bases.data(), 4 * m);
   return BS_OK;
 }
 

@@ -248,6 +248,7 @@ struct bs_ctx {
   bs::DevBuf sd[14];
   bool sd_valid = false;
   int32_t sd_w = 0, sd_h = 0, sd_bin = 0, sd_base = 0;
+  bool sd_bases = false;  // the count ran under bs_set_building_bases: the emit reads bases_dev
   int64_t sd_nv = 0, sd_nf = 0, sd_ni = 0;
   double sd_ms_emit[2] = {0, 0};  // vertex pass, face pass of the last emit
   bs::DevBuf fc[16];  // scratch of the roof facets and their edges (bs_facet.hip)
@@ -309,11 +310,16 @@ struct bs_ctx {
   bs::DevBuf ps[36];
   bool ps_valid = false;
   int32_t ps_bin = 0, ps_base = 0, ps_nl = 0, ps_nr = 0, ps_nsv = 0;
+  bool ps_bases = false;  // the count ran under bs_set_building_bases: the emit reads bases_dev
   int64_t ps_nv = 0, ps_nf = 0, ps_ni = 0, ps_ntri = 0;
   double ps_ms_emit[2] = {0, 0};  // vertex pass, face passes of the last emit
   bs::DevBuf mr[20];  // scratch of the model raster (bs_modelraster.hip); it keeps no state between calls
   bs::DevBuf pr[16];  // scratch of the point residuals (bs_pointresid.hip); it keeps no state between calls
   bs::DevBuf gn[32];  // scratch of the roof generalisation (bs_generalise.hip); it keeps no state between calls
+  // per-building bases (bs_set_building_bases): the host table, its copy on the device; empty = off
+  std::vector<int32_t> bases;
+  bs::DevBuf bases_dev;
+  bs::DevBuf tn[16];  // scratch of the terrain stage (bs_terrain.hip); it keeps no state between calls
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew
@@ -365,7 +371,9 @@ int launch_knn_normals(bs_ctx* ctx, const GridDev& g, int64_t q_begin, int64_t q
                        int64_t* n_uncertified, int32_t* d_npos = nullptr);
 int launch_knn_normals_tiled(bs_ctx* ctx, const TiledGridDev& g, const bs_params& p, int32_t* d_neigh,
                              double* d_normals, int32_t* d_npos);
-// capi.hip
+// capi.hip: the device table of bs_set_building_bases for a call over n_buildings, nullptr while the switch is off;
+// BS_ERR_INVALID (worded for `who`) where the table's length differs
+int building_bases(bs_ctx* ctx, int32_t n_buildings, const char* who, const int32_t** d_table);
 int region_grow_dev_impl(bs_ctx* ctx, const int32_t* d_xyz, const double* d_normals, const int32_t* d_neigh,
                          int64_t n, const bs_params* p, int32_t* d_plane_idx, bool trusted_neigh);
 int check_params(bs_ctx* ctx, const bs_params* p, int64_t n);

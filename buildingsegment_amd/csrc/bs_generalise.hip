@@ -320,7 +320,8 @@ struct Job {  // one call
   bs_ctx* ctx;
   const int32_t* map;  // the caller's
   int w, h;
-  int32_t nb, npl, bin, base;
+  int32_t nb, npl, bin;
+  Bases base;
   Tables tab;
   const int32_t* tab_flat;
   Rule rule;
@@ -554,6 +555,9 @@ extern "C" int bs_roof_generalise_dev(bs_ctx* ctx, const int32_t* d_map, const i
   if (!d_map || !d_roof || !d_roof_out || !out ||
       bad_call(width, height, n_buildings, n_planes, normal, center, z_min, z_max, bin, flat, params))
     return fail(ctx, BS_ERR_INVALID, GEN_INVALID);
+  const int32_t* d_bases = nullptr;
+  if (const int rc = building_bases(ctx, n_buildings, "roof generalisation", &d_bases))
+    return rc;
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int w = width, h = height;
@@ -569,7 +573,7 @@ extern "C" int bs_roof_generalise_dev(bs_ctx* ctx, const int32_t* d_map, const i
   J.nb = nb;
   J.npl = npl;
   J.bin = bin;
-  J.base = base_z;
+  J.base = Bases{d_bases, base_z};
   J.rule = Rule{(long long)params->min_pixels, params->merge_flat != 0, params->step_tol, params->bend_tol};
   for (auto& e : J.ev.e)
     BS_HIP(ctx, hipEventCreate(&e));

@@ -63,7 +63,15 @@ struct In {  // what the stages before left on the device, and the per-label wor
   int32_t nsv, nr, nl, w1;  // (w1 = width + 1: a corner's index is Y * w1 + X)
   int32_t base, bin;
   long long ntri;
+  // per-building bases (bs_set_building_bases): the table, nullptr while the switch is off; for the range check of the count
+  // the buildings of the labels as the caller gave them (those of an open building too) and their number
+  const int32_t* bases;
+  const int32_t* lb;
+  int32_t nb;
 };
+
+// base_z of building c, a checked building number
+__device__ inline int32_t base_of(const In& A, int32_t c) { return A.bases ? A.bases[c] : A.base; }
 
 struct Fig {  // per building, device
   unsigned long long *walls, *crossing, *area2, *volume6;
@@ -107,9 +115,20 @@ __global__ __launch_bounds__(256) void ps_keys_kernel(In A, unsigned long long* 
     int32_t r, l, c = -1;
     unsigned long long key = NONE, col = NONE;
     const int32_t z = A.z[i];
-    if ((long long)z - A.base >= Z_LIMIT || (long long)z - A.base <= -Z_LIMIT)
+    const bool known = vertex_of(A, i, r, l, c, words + W_ERR);
+    // the base the vertex is measured against: under the switch that of its label's building, open or not (the host has
+    // checked the table of the labels; a vertex without a ring or a label is an internal error and measured against nothing)
+    long long base = A.base;
+    bool measured = true;
+    if (A.bases) {
+      const int32_t b = known ? A.lb[l] : -1;
+      measured = (uint32_t)b < (uint32_t)A.nb;
+      if (measured)
+        base = A.bases[b];
+    }
+    if (measured && ((long long)z - base >= Z_LIMIT || (long long)z - base <= -Z_LIMIT))
       atomicOr(words + W_RANGE, 1);
-    if (vertex_of(A, i, r, l, c, words + W_ERR) && c >= 0) {
+    if (known && c >= 0) {
       const int2 p = A.xy[i], q = A.xy[next_of(A, i, r)];
       const uint32_t ci = (uint32_t)p.y * (uint32_t)A.w1 + (uint32_t)p.x, cj = (uint32_t)q.y * (uint32_t)A.w1 + (uint32_t)q.x;
       col = ((unsigned long long)(uint32_t)c << 32) | ci;
@@ -124,7 +143,7 @@ __global__ __launch_bounds__(256) void ps_keys_kernel(In A, unsigned long long* 
     twin[i] = -1;
     const uint32_t e = 2u * (uint32_t)i;
     zk[e] = (uint32_t)z ^ 0x80000000u;
-    zk[e + 1] = (uint32_t)A.base ^ 0x80000000u;
+    zk[e + 1] = (uint32_t)(known && c >= 0 ? base_of(A, c) : A.base) ^ 0x80000000u;
     ev[e] = e;
     ev[e + 1] = e + 1;
     ck[e] = ck[e + 1] = col;
@@ -237,7 +256,7 @@ __device__ inline bool wall_of(const In& A, const int32_t* __restrict__ twin, co
                                int32_t l, Wall& w, int* err)
 {
   const int32_t e = next_of(A, i, r), t = twin[i];
-  int32_t bs = A.base, be = A.base;
+  int32_t bs = base_of(A, A.lc[l]), be = bs;
   w.va_s = vnum[2 * (int64_t)i];
   w.va_e = vnum[2 * (int64_t)e];
   w.emit = true;
@@ -410,7 +429,7 @@ __global__ __launch_bounds__(256) void ps_tri_kernel(In A, int32_t nb, Fig f, in
         const int2 pa = A.xy[a], pb = A.xy[b], pd = A.xy[d];
         const long long o = (long long)(pb.x - pa.x) * (pd.y - pa.y) - (long long)(pb.y - pa.y) * (pd.x - pa.x);
         area = (unsigned long long)o;
-        vol = (unsigned long long)(o * ((long long)A.z[a] + A.z[b] + A.z[d] - 3ll * A.base));
+        vol = (unsigned long long)(o * ((long long)A.z[a] + A.z[b] + A.z[d] - 3ll * base_of(A, c)));
       } else {
         c = -1;
       }
@@ -482,7 +501,7 @@ __global__ __launch_bounds__(256) void ps_emit_vertex_kernel(In A, const int32_t
       continue;
     }
     const int2 p = A.xy[i];
-    o.vertex[v] = make_int4(p.x * A.bin, p.y * A.bin, (e & 1) ? A.base : A.z[i], c);
+    o.vertex[v] = make_int4(p.x * A.bin, p.y * A.bin, (e & 1) ? base_of(A, c) : A.z[i], c);
   }
 }
 
@@ -645,6 +664,10 @@ int poly_solids(bs_ctx* ctx, const struct bs_outline_triangles& t, const struct 
   res.n_roof_faces = tb;
   ctx->ps_bin = bin;
   ctx->ps_base = base_z;
+  const int32_t* d_bases = nullptr;
+  if (const int rc = building_bases(ctx, nb, "polygon solids", &d_bases))
+    return rc;
+  ctx->ps_bases = d_bases != nullptr;
   ctx->ps_nl = nl;
   ctx->ps_nr = nr;
   ctx->ps_nsv = nsv;
@@ -703,7 +726,7 @@ int poly_solids(bs_ctx* ctx, const struct bs_outline_triangles& t, const struct 
   int* d_err = d_words + W_ERR;
   const In A{ctx->uc_xy, ctx->uc_z, ctx->uc_right, ctx->uc_ring, ctx->uc_soff, B[PS_RLABEL].as<int32_t>(), B[PS_LC].as<int32_t>(),
              B[PS_LV0].as<int32_t>(), B[PS_TB2].as<long long>(), B[PS_TOFF].as<long long>(), ctx->tr_tri, nsv, nr, nl, width + 1,
-             base_z, bin, ntri};
+             base_z, bin, ntri, d_bases, d_label_building, nb};
   unsigned long long *tk0 = B[PS_TK0].as<unsigned long long>(), *tk1 = B[PS_TK1].as<unsigned long long>();
   int32_t *tv0 = B[PS_TV0].as<int32_t>(), *tv1 = B[PS_TV1].as<int32_t>(), *twin = B[PS_TWIN].as<int32_t>();
   uint32_t *zk0 = B[PS_ZK0].as<uint32_t>(), *zk1 = B[PS_ZK1].as<uint32_t>();
@@ -805,7 +828,8 @@ int check_args(bs_ctx* ctx, const void* label, const void* top, const void* lb, 
 {
   if (!label || !top || !out || (n_labels > 0 && !lb) || nb < 0 || bin < 1)
     return fail(ctx, BS_ERR_INVALID, PS_INVALID);
-  return BS_OK;
+  const int32_t* d_bases;  // (a table of another length: refused before the stages in front run)
+  return building_bases(ctx, nb, "polygon solids", &d_bases);
 }
 
 void hand_over(struct bs_outline_triangles* tri, struct bs_clean_outlines* clean, struct bs_simple_outlines* simple,
@@ -914,7 +938,9 @@ extern "C" int bs_poly_solids_emit_dev(bs_ctx* ctx, int32_t* d_vertex, int32_t* 
   DevBuf* B = ctx->ps;
   const In A{ctx->uc_xy, ctx->uc_z, ctx->uc_right, ctx->uc_ring, ctx->uc_soff, B[PS_RLABEL].as<int32_t>(), B[PS_LC].as<int32_t>(),
              B[PS_LV0].as<int32_t>(), B[PS_TB2].as<long long>(), B[PS_TOFF].as<long long>(), ctx->tr_tri, ctx->ps_nsv, ctx->ps_nr,
-             ctx->ps_nl, 0, ctx->ps_base, ctx->ps_bin, ctx->ps_ntri};
+             ctx->ps_nl, 0, ctx->ps_base, ctx->ps_bin, ctx->ps_ntri,
+             // (bs_set_building_bases ends the validity of a count, so the table is still the count's)
+             ctx->ps_bases ? ctx->bases_dev.as<int32_t>() : nullptr, nullptr, 0};
   const Mesh o{reinterpret_cast<int4*>(d_vertex), d_face_offset, d_face_index, d_face_building, d_face_kind, nv, nf, ni};
   int* d_err = B[PS_MISC].as<int>() + W_ERR;
   const int32_t *vnum = B[PS_VNUM].as<int32_t>(), *wscan = B[PS_WSCAN].as<int32_t>();

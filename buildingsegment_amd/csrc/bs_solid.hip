@@ -59,7 +59,7 @@ struct Corner {
 };
 
 __device__ inline Corner corner_of(const int32_t* __restrict__ map, const int32_t* __restrict__ top, int w, int h, int X, int Y,
-                                   int32_t base)
+                                   Bases base)
 {
   Corner K;
   uint64_t* const k[8] = {&K.k0, &K.k1, &K.k2, &K.k3, &K.k4, &K.k5, &K.k6, &K.k7};
@@ -71,7 +71,7 @@ __device__ inline Corner corner_of(const int32_t* __restrict__ map, const int32_
       const int64_t p = (int64_t)py * w + px;
       const int32_t c = map[p];
       if (c >= 0) {
-        a = key_of(c, base);
+        a = key_of(c, base.of(c));
         b = key_of(c, top[4 * p + (3 - q)]);
       }
     }
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void fig_init_kernel(Fig f, int32_t nb)
 
 // ---- 2. vertices -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void corner_count_kernel(const int32_t* __restrict__ map, const int32_t* __restrict__ top,
-                                                           int w, int h, int32_t base, int32_t nb,
+                                                           int w, int h, Bases base, int32_t nb,
                                                            uint8_t* __restrict__ ccnt, Fig f)
 {
   __shared__ unsigned s_nv[FIG_CAP];
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void corner_count_kernel(const int32_t* __rest
 }
 
 __global__ __launch_bounds__(256) void vertex_emit_kernel(const int32_t* __restrict__ map, const int32_t* __restrict__ top,
-                                                          int w, int h, int bin, int32_t base,
+                                                          int w, int h, int bin, Bases base,
                                                           const int32_t* __restrict__ voff, int4* __restrict__ vertex)
 {
   const int64_t nc = (int64_t)(w + 1) * (h + 1);
@@ -196,10 +196,10 @@ __global__ __launch_bounds__(256) void vertex_emit_kernel(const int32_t* __restr
 // The neighbour's tops at the two ends of wall edge d of pixel (x, y) of building c; false: the neighbour emits the wall
 // (same building, smaller row-major index).  same: the neighbour is a pixel of c.
 __device__ inline bool wall_other(const int32_t* __restrict__ map, const int4* __restrict__ top, int w, int h, int x, int y,
-                                  int32_t c, int d, int32_t base, int32_t* bs, int32_t* be)
+                                  int32_t c, int d, Bases base, int32_t* bs, int32_t* be)
 {
   const int nx = x + (d == 1) - (d == 3), ny = y + (d == 2) - (d == 0);
-  *bs = *be = base;
+  *bs = *be = base.of(c);
   if (nx < 0 || nx >= w || ny < 0 || ny >= h)
     return true;
   const int64_t q = (int64_t)ny * w + nx;
@@ -227,7 +227,7 @@ __device__ inline bool wall_other(const int32_t* __restrict__ map, const int4* _
 
 // faces | indices << 3 | crossing walls << 9 of every pixel
 __global__ __launch_bounds__(256) void face_count_kernel(const int32_t* __restrict__ map, const int4* __restrict__ top, int w,
-                                                         int h, int32_t base, uint16_t* __restrict__ pcnt)
+                                                         int h, Bases base, uint16_t* __restrict__ pcnt)
 {
   const int64_t npix = (int64_t)w * h;
   const int32_t* top1 = reinterpret_cast<const int32_t*>(top);
@@ -274,13 +274,13 @@ struct CornerIds {
 };
 
 __device__ inline CornerIds corner_ids(const int32_t* __restrict__ map, const int32_t* __restrict__ top, int w, int h, int X,
-                                       int Y, int32_t base, int32_t v0, int32_t c, int32_t tz, int32_t zs, int32_t ze)
+                                       int Y, Bases base, int32_t v0, int32_t c, int32_t tz, int32_t zs, int32_t ze)
 {
   const Corner K = corner_of(map, top, w, h, X, Y, base);
   CornerIds r;
   r.v0 = v0;
   r.d = K.d;
-  r.base = v0 + rank_of(K, key_of(c, base));
+  r.base = v0 + rank_of(K, key_of(c, base.of(c)));
   r.top = v0 + rank_of(K, key_of(c, tz));
   r.os = v0 + rank_of(K, key_of(c, zs));
   r.oe = v0 + rank_of(K, key_of(c, ze));
@@ -322,7 +322,7 @@ __device__ inline void emit_wall(const CornerIds& s, const CornerIds& e, int32_t
 }
 
 __global__ __launch_bounds__(256) void face_emit_kernel(const int32_t* __restrict__ map, const int4* __restrict__ top, int w,
-                                                        int h, int32_t base, const int32_t* __restrict__ voff,
+                                                        int h, Bases base, const int32_t* __restrict__ voff,
                                                         const int32_t* __restrict__ foff, const int32_t* __restrict__ ioff,
                                                         int32_t n_faces, int32_t n_indices, FaceOut o)
 {
@@ -384,7 +384,7 @@ __device__ inline void fig_global(const Fig& f, int32_t c, unsigned pix, unsigne
 }
 
 __global__ __launch_bounds__(256) void figures_kernel(const int32_t* __restrict__ map, const int4* __restrict__ top,
-                                                      const uint16_t* __restrict__ pcnt, int64_t npix, int32_t base,
+                                                      const uint16_t* __restrict__ pcnt, int64_t npix, Bases base,
                                                       int32_t nb, Fig f)
 {
   __shared__ unsigned s_pix[FIG_CAP], s_faces[FIG_CAP], s_walls[FIG_CAP], s_cross[FIG_CAP];
@@ -417,7 +417,7 @@ __global__ __launch_bounds__(256) void figures_kernel(const int32_t* __restrict_
       cross = p >> 9;
       mn = min(min(T.x, T.y), min(T.z, T.w));
       mx = max(max(T.x, T.y), max(T.z, T.w));
-      vol = (unsigned long long)(2ll * T.x + 2ll * T.w + (long long)T.y + (long long)T.z - 6ll * base);
+      vol = (unsigned long long)(2ll * T.x + 2ll * T.w + (long long)T.y + (long long)T.z - 6ll * base.of(c));
     }
     unsigned isum = ind;
     for (int o = 32; o > 0; o >>= 1)
@@ -561,6 +561,10 @@ extern "C" int bs_solids_count_dev(bs_ctx* ctx, const int32_t* d_map, const int3
   if (!d_map || !d_roof || !out || bad_image(width, height) || n_buildings < 0 || n_planes < 0 || bin < 1 ||
       (n_buildings > 0 && !flat) || (n_planes > 0 && (!normal || !center || !z_min || !z_max)))
     return fail(ctx, BS_ERR_INVALID, SOLIDS_INVALID);
+  const int32_t* d_bases = nullptr;
+  if (const int rc = building_bases(ctx, n_buildings, "solids", &d_bases))
+    return rc;
+  const Bases bases{d_bases, base_z};
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const int w = width, h = height;
@@ -624,7 +628,7 @@ extern "C" int bs_solids_count_dev(bs_ctx* ctx, const int32_t* d_map, const int3
   // ---- tops (into the context: nothing of the caller's is written before the checks have passed) ----
   BS_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, st));
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
-  tops_kernel<<<nblk(npix, 256), 256, 0, st>>>(d_map, d_roof, w, h, nb, npl, tab, tab_flat, bin, base_z, top, cmap, d_bad);
+  tops_kernel<<<nblk(npix, 256), 256, 0, st>>>(d_map, d_roof, w, h, nb, npl, tab, tab_flat, bin, bases, top, cmap, d_bad);
   BS_HIP(ctx, hipEventRecord(ev.e[1], st));
   int h_bad = 0;
   BS_HIP(ctx, hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st));
@@ -636,11 +640,11 @@ extern "C" int bs_solids_count_dev(bs_ctx* ctx, const int32_t* d_map, const int3
 
   // ---- vertices, faces, figures ----
   fig_init_kernel<<<nblk(std::max<int32_t>(nb, 4), 256), 256, 0, st>>>(f, nb);
-  corner_count_kernel<<<grid_of(nc), 256, 0, st>>>(cmap, top1, w, h, base_z, nb, ccnt, f);
+  corner_count_kernel<<<grid_of(nc), 256, 0, st>>>(cmap, top1, w, h, bases, nb, ccnt, f);
   BS_HIP(ctx, hipEventRecord(ev.e[2], st));
-  face_count_kernel<<<grid_of(npix), 256, 0, st>>>(cmap, top, w, h, base_z, pcnt);
+  face_count_kernel<<<grid_of(npix), 256, 0, st>>>(cmap, top, w, h, bases, pcnt);
   BS_HIP(ctx, hipEventRecord(ev.e[3], st));
-  figures_kernel<<<grid_of(npix), 256, 0, st>>>(cmap, top, pcnt, npix, base_z, nb, f);
+  figures_kernel<<<grid_of(npix), 256, 0, st>>>(cmap, top, pcnt, npix, bases, nb, f);
   BS_HIP(ctx, hipEventRecord(ev.e[4], st));
 
   if (!alloc_solids(out, nb)) {
@@ -725,6 +729,7 @@ extern "C" int bs_solids_count_dev(bs_ctx* ctx, const int32_t* d_map, const int3
   ctx->sd_h = h;
   ctx->sd_bin = bin;
   ctx->sd_base = base_z;
+  ctx->sd_bases = d_bases != nullptr;
   ctx->sd_nv = nv;
   ctx->sd_nf = nf;
   ctx->sd_ni = ni;
@@ -747,16 +752,18 @@ extern "C" int bs_solids_emit_dev(bs_ctx* ctx, int32_t* d_vertex, int32_t* d_fac
   const int w = ctx->sd_w, h = ctx->sd_h;
   const int64_t npix = (int64_t)w * h, nc = (int64_t)(w + 1) * (h + 1);
   DevBuf* B = ctx->sd;
+  // (bs_set_building_bases ends the validity of a count, so the table is still the count's)
+  const Bases bases{ctx->sd_bases ? ctx->bases_dev.as<int32_t>() : nullptr, ctx->sd_base};
   Events ev;
   for (int k = 0; k < 3; k++)
     BS_HIP(ctx, hipEventCreate(&ev.e[k]));
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
   if (nv > 0)
     vertex_emit_kernel<<<grid_of(nc), 256, 0, st>>>(B[SD_MAP].as<int32_t>(), B[SD_TOP].as<int32_t>(), w, h, ctx->sd_bin,
-                                                    ctx->sd_base, B[SD_VOFF].as<int32_t>(), reinterpret_cast<int4*>(d_vertex));
+                                                    bases, B[SD_VOFF].as<int32_t>(), reinterpret_cast<int4*>(d_vertex));
   BS_HIP(ctx, hipEventRecord(ev.e[1], st));
   const FaceOut o{d_face_offset, d_face_index, d_face_building, d_face_kind};
-  face_emit_kernel<<<grid_of(npix), 256, 0, st>>>(B[SD_MAP].as<int32_t>(), B[SD_TOP].as<int4>(), w, h, ctx->sd_base,
+  face_emit_kernel<<<grid_of(npix), 256, 0, st>>>(B[SD_MAP].as<int32_t>(), B[SD_TOP].as<int4>(), w, h, bases,
                                                   B[SD_VOFF].as<int32_t>(), B[SD_FOFF].as<int32_t>(),
                                                   B[SD_IOFF].as<int32_t>(), (int32_t)nf, (int32_t)ni, o);
   BS_HIP(ctx, hipEventRecord(ev.e[2], st));

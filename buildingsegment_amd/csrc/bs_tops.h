@@ -16,9 +16,17 @@ struct Tables {  // per plane, device: entry p - 1 is plane p
   const int32_t* z_max;
 };
 
+// base_z of building c (include/bs_api.h, "per-building bases"): the table of bs_set_building_bases while it is set, the
+// call's scalar otherwise.  c is a checked building number.
+struct Bases {
+  const int32_t* table;
+  int32_t scalar;
+  __device__ int32_t of(int32_t c) const { return table ? table[c] : scalar; }
+};
+
 __global__ __launch_bounds__(256) void tops_kernel(const int32_t* __restrict__ map, const int32_t* __restrict__ roof, int w,
                                                    int h, int32_t nb, int32_t npl, Tables t,
-                                                   const int32_t* __restrict__ flat, int bin, int32_t base,
+                                                   const int32_t* __restrict__ flat, int bin, Bases bases,
                                                    int4* __restrict__ top, int32_t* __restrict__ cmap, int* __restrict__ bad)
 {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -32,6 +40,7 @@ __global__ __launch_bounds__(256) void tops_kernel(const int32_t* __restrict__ m
   }
   int4 v = make_int4(INT32_MIN, INT32_MIN, INT32_MIN, INT32_MIN);
   if (c >= 0) {
+    const int32_t base = bases.of(c);
     if (r > 0) {
       const int y = (int)(i / w), x = (int)(i - (int64_t)y * w);
       const int32_t s = r - 1;

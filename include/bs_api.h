@@ -1855,6 +1855,104 @@ int bs_point_residuals(bs_ctx* ctx, const int32_t* label, const int32_t* top, in
                        struct bs_clean_outlines* clean, struct bs_simple_outlines* simple, struct bs_outlines* plain);
 void bs_point_residuals_free(struct bs_point_residuals* r);
 
+/* ---- terrain: the ground height of every building from the points around it ----
+ *
+ * ground_th is the lower edge of the height bin that holds the median z of the whole tile: it separates the points above
+ * ground for the raster and was never a floor height.  The ground next to a building is in the points that fall just outside
+ * its footprint; this stage reads it there.  Everything is an exact integer and independent of the order of summation.
+ *
+ * Input.  The cloud d_xyz [n][3] int32 in millimetres shifted to its origin, 1 <= n < 2^29, every |coordinate| < 2^23; bin >= 1;
+ * map [height][width] as bs_building_map writes it (any negative value is outside, -1) with n_buildings >= 0;
+ * ring in 1 .. BS_TERRAIN_MAX_RING; a quantile q_num / q_den with 0 <= q_num <= q_den, 1 <= q_den < 2^31; min_ground >= 1;
+ * fallback_z.
+ *
+ * 1. Ring, in exactly `ring` synchronous rounds over the image alone.  owner_0 = map, and dist = 0 where map >= 0.  In round
+ * r every pixel with owner_{r-1} == -1 looks at its 4-neighbours inside the image that have owner_{r-1} >= 0; if there is one,
+ * the pixel takes the smallest owner among them and dist = r.  A label moves one pixel per round, and only through outside
+ * pixels: a pocket behind another building is reached around the corner or not at all.  rounds_used = the rounds that labelled
+ * something.  owner [height][width] int32 is -1 where never reached; dist [height][width] uint8 is 0 on buildings and on
+ * unreached pixels, which owner tells apart.  A RING pixel has map == -1 and owner >= 0.
+ *
+ * 2. Low.  For every ring pixel, low = the minimum z over ALL points whose base pixel (x / bin, y / bin) it is -- no ground
+ * threshold, no label test: the lowest return of a pixel beside a wall is the ground or close to it, whatever lies above.
+ * low = INT32_MAX where no point lies, and on every pixel that is no ring pixel.
+ *
+ * 3. Per building c.  G_c = the multiset of low over c's ring pixels with low != INT32_MAX.  ring_pixels; ground_pixels =
+ * |G_c|; ring_points (the points on its ring pixels); ground_min, ground_max (INT32_MAX / INT32_MIN for an empty G_c);
+ * ground_sum.  If ground_pixels >= min_ground: ground = the element of rank floor((ground_pixels - 1) * q_num / q_den) of
+ * G_c in ascending order (64-bit arithmetic) and status = 0.  Otherwise ground = fallback_z and status = 1.  A quantile, not
+ * the minimum: one return from a pit or a multipath echo metres below the terrain must not set the floor.
+ * Totals: n_ring_pixels, n_ground_pixels, n_ring_points, n_fallback (the sums), rounds_used.
+ *
+ * Promised.  ground_min <= ground <= ground_max where status == 0.  The rounds compute the L1 Voronoi diagram of the buildings
+ * cut at `ring`: a ring pixel's dist is its L1 distance to the nearest building pixel, and its owner the lowest index among
+ * the buildings at that distance ("Terrain", has the argument).  n_buildings == 0 is valid: nothing is reached and
+ * no per-building array is touched.
+ *
+ * Errors.  BS_ERR_INVALID: a null cloud, map or out, n < 1, bin < 1, width or height < 1, width * height >= 2^31,
+ * n_buildings < 0, ring outside 1 .. 255, q outside the ranges above, min_ground < 1.  BS_ERR_RANGE: 2^29 points or more; a
+ * point with a negative x / y or whose pixel lies outside the image; a coordinate at or beyond 2^23; a map value
+ * >= n_buildings.  On any of these the outputs and the struct are untouched and the context stays usable: everything is
+ * computed in scratch of the context and copied once the ranges are known.  (BS_ERR_INTERNAL -- a sorted key that is not its
+ * building's -- leaves the struct untouched and the images, which do not depend on the pick, written.) */
+#define BS_TERRAIN_MAX_RING 255
+#define BS_TERRAIN_FIG_CAP 1024 /* buildings below this number have their figures reduced in LDS, the rest by global atomics */
+#define BS_TERRAIN_GRID 2048    /* workgroups of 256 of the pass over the points: beyond 524 288 points a thread takes several */
+
+struct bs_terrain {
+  int32_t width, height, n_buildings, bin, ring, q_num, q_den, min_ground, fallback_z;
+  int32_t fig_cap, grid; /* BS_TERRAIN_FIG_CAP, BS_TERRAIN_GRID of the library */
+  int32_t rounds_used, n_fallback, reserved;
+  int64_t n_points, n_ring_pixels, n_ground_pixels, n_ring_points;
+  /* per building; host memory owned by the library */
+  int64_t* ring_pixels;   /* [n_buildings] */
+  int64_t* ground_pixels; /* [n_buildings] */
+  int64_t* ring_points;   /* [n_buildings] */
+  int64_t* ground_sum;    /* [n_buildings] */
+  int32_t* ground_min;    /* [n_buildings] */
+  int32_t* ground_max;    /* [n_buildings] */
+  int32_t* ground;        /* [n_buildings] */
+  int32_t* status;        /* [n_buildings] 0: the quantile; 1: fallback_z */
+  /* device time (HIP events on the context's stream) */
+  double ms_ring;   /* clearing, the check of the map, the first frontier, the rounds */
+  double ms_points; /* the pass over the points: the check of the cloud, ring_points, low */
+  double ms_pixels; /* the pass over the pixels: the keys and the figures; the host's read of the range flags */
+  double ms_pick;   /* the sort of the keys, the sum of ground_pixels, the pick, the copies into the caller's images, the
+                       host's read of the result */
+};
+
+/* d_xyz and d_map are device pointers.  d_owner [height][width] int32, d_dist [height][width] uint8 and d_low
+ * [height][width] int32 are device images; each may be NULL.  The figures are always computed; out's per-building arrays are
+ * host memory owned by the library (bs_terrain_free, which accepts a zeroed struct).  All `ring` rounds are launched without a
+ * host round trip.  Synchronises: once for the range flags, once for the result. */
+int bs_terrain_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const int32_t* d_map, int32_t width,
+                   int32_t height, int32_t n_buildings, int32_t ring, int32_t q_num, int32_t q_den, int32_t min_ground,
+                   int32_t fallback_z, int32_t* d_owner, uint8_t* d_dist, int32_t* d_low, struct bs_terrain* out);
+/* Host-memory twin: xyz, map and the three images (each may be NULL) are host pointers. */
+int bs_terrain(bs_ctx* ctx, const int32_t* xyz, int64_t n, int32_t bin, const int32_t* map, int32_t width, int32_t height,
+               int32_t n_buildings, int32_t ring, int32_t q_num, int32_t q_den, int32_t min_ground, int32_t fallback_z,
+               int32_t* owner, uint8_t* dist, int32_t* low, struct bs_terrain* out);
+void bs_terrain_free(struct bs_terrain* t);
+
+/* ---- per-building bases: solids that stand on the terrain ----
+ *
+ * A switch of the context, as bs_set_outline_sweeps.  base [n_buildings] is a host table (in the pipeline: ground of
+ * struct bs_terrain); the context keeps a copy.  NULL or n_buildings == 0 switches it off, which is the default.
+ * While it is set, bs_solids_count_dev and its emit, bs_roof_generalise_dev, bs_poly_solids_count_dev and its emit, and their
+ * host-memory twins use base[c] wherever their definition says base_z for a pixel, vertex, wall, floor or figure of building
+ * c: the max(base_z, .) of the tops, the vertex sets of the corners and columns, the floor, the outer walls, volume6, and the
+ * 2^24 range check of the polygon solids (a clean vertex is measured against the base of its label's building, open or not).
+ * The definitions are per building already, so every building's mesh stays closed and oriented, and building c of a run under
+ * the switch is building c of a scalar run with base_z = base[c].  The scalar base_z of a call is still validated and
+ * reported in its struct.  A call of these stages whose n_buildings differs from the table's is BS_ERR_INVALID.  Switched
+ * off, every byte these stages write is what they write without this paragraph.
+ * Setting or clearing the table ends the validity of the last bs_solids_count_dev and bs_poly_solids_count_dev on the context:
+ * an emit follows the table of its count.  BS_ERR_INVALID: n_buildings < 0, or a null table with n_buildings > 0. */
+int bs_set_building_bases(bs_ctx* ctx, const int32_t* base, int32_t n_buildings);
+/* *n_buildings = the length of the table (0: off); its first min(capacity, length) entries into base, which may be NULL
+ * with capacity == 0.  BS_ERR_INVALID: a null n_buildings, a negative capacity, or a null base with capacity > 0. */
+int bs_get_building_bases(bs_ctx* ctx, int32_t* base, int32_t capacity, int32_t* n_buildings);
+
 #ifdef __cplusplus
 }
 #endif
