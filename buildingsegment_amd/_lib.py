@@ -45,7 +45,9 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_outline_triangles_free", "bs_outline_triangles_write_obj", "bs_poly_solids_count_dev",
            "bs_poly_solids_emit_dev", "bs_poly_solids", "bs_poly_solids_free", "bs_model_raster_dev", "bs_model_raster",
            "bs_model_raster_free", "bs_point_residuals_dev", "bs_point_residuals", "bs_point_residuals_free",
-           "bs_terrain_dev", "bs_terrain", "bs_terrain_free", "bs_set_building_bases", "bs_get_building_bases"]
+           "bs_terrain_dev", "bs_terrain", "bs_terrain_free", "bs_set_building_bases", "bs_get_building_bases",
+           "bs_ground_dev", "bs_ground", "bs_ground_free", "bs_set_ground_model", "bs_set_ground_model_dev",
+           "bs_get_ground_model"]
 
 
 class Params(C.Structure):
@@ -345,6 +347,33 @@ class Terrain(C.Structure):
                 [(k, C.c_double) for k in TERRAIN_MS])
 
 
+GROUND_MAX_STEPS = 16    # BS_GROUND_MAX_STEPS of include/bs_api.h
+GROUND_MAX_RADIUS = 255  # BS_GROUND_MAX_RADIUS
+GROUND_GRID = 2048       # BS_GROUND_GRID
+GROUND_ROW_LDS = 2048    # BS_GROUND_ROW_LDS
+GROUND_EMPTY = 2 ** 31 - 1
+GROUND_HEAD = ("width", "height", "cell", "n_steps")
+GROUND_TABLES = ("radius", "threshold")
+GROUND_NARROW = ("grid", "row_lds", "dtm_min", "dtm_max", "hag_min", "hag_max")
+GROUND_WIDE = ("n_ground_pixels", "n_object_pixels", "n_empty_pixels", "n_filled_pixels", "n_ground_points", "n_low_points",
+               "n_object_points", "sum_hag_ground")
+GROUND_MS = ("ms_low", "ms_open", "ms_points")
+
+
+class GroundParams(C.Structure):
+    """bs_ground_params (include/bs_api.h)"""
+    _fields_ = ([("cell", C.c_int32), ("n_steps", C.c_int32), ("radius", C.c_int32 * GROUND_MAX_STEPS)] +
+                [(k, C.c_int32) for k in ("s_num", "s_den", "dh0", "dh_max", "tol", "min_height")])
+
+
+class Ground(C.Structure):
+    """bs_ground (include/bs_api.h): the lattice, the steps and the figures; it owns no memory."""
+    _fields_ = ([(k, C.c_int32) for k in GROUND_HEAD] + [(k, C.c_int32 * GROUND_MAX_STEPS) for k in GROUND_TABLES] +
+                [(k, C.c_int32) for k in GROUND_NARROW] + [("n_points", C.c_int64), ("step_pixels", C.c_int64 * GROUND_MAX_STEPS)] +
+                [(k, C.c_int64) for k in GROUND_WIDE] + [(k, C.c_double) for k in GROUND_MS] +
+                [("ms_step", C.c_double * GROUND_MAX_STEPS)])
+
+
 class BsError(RuntimeError):
     def __init__(self, status, detail=""):
         self.status = status
@@ -549,5 +578,13 @@ def load():
     L.bs_terrain_free.restype = None
     L.bs_set_building_bases.argtypes = [vp, ip, C.c_int32]
     L.bs_get_building_bases.argtypes = [vp, ip, C.c_int32, C.POINTER(C.c_int32)]
+    gdp, i32p = C.POINTER(Ground), C.POINTER(C.c_int32)
+    for fn in (L.bs_ground_dev, L.bs_ground):
+        fn.argtypes = [vp, ip, C.c_int64, ip, C.POINTER(GroundParams), ip, ip, vp, ip, vp, gdp]
+    L.bs_ground_free.argtypes = [gdp]
+    L.bs_ground_free.restype = None
+    for fn in (L.bs_set_ground_model, L.bs_set_ground_model_dev):
+        fn.argtypes = [vp, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.bs_get_ground_model.argtypes = [vp, ip, C.c_int64, i32p, i32p, i32p, i32p]
     _LIB = L
     return L

@@ -520,11 +520,20 @@ class Context:
         return PlaneVotes(pb, vin, vtot, vout)
 
     def buildings(self, xyz, plane_idx=None, n_planes=0, bin=100, bin_height=1000, threshold=10, kernel_size=5,
-                  iterations=2):
+                  iterations=2, ground=None):
         """The whole 2-D branch for a cloud shifted to its origin: raster -> footprints (with the closed mask) ->
         building map -> point assignment -> plane votes (when plane_idx, the labels of segment(), is given).
-        Returns (Footprints, Buildings); the Buildings carry map, building_idx, ground_th and votes."""
+        Returns (Footprints, Buildings); the Buildings carry map, building_idx, ground_th and votes.  ground: a dict of
+        the parameters of ground() ({} for its defaults): the stage runs first, the raster and the assignment of this call
+        measure "above ground" against its dtm (set_ground_model; the context's own model is restored afterwards), and
+        the Ground is returned as a third value."""
         xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        if ground is not None:
+            g = self.ground(xyz, points=False, **ground)
+            with self._ground_model(g):
+                fp, b = self.buildings(xyz, plane_idx, n_planes, bin=bin, bin_height=bin_height, threshold=threshold,
+                                       kernel_size=kernel_size, iterations=iterations)
+            return fp, b, g
         img, th = self.grid_picture(xyz, bin=bin, bin_height=bin_height)
         fp, mask = self.footprints(img, threshold=threshold, kernel_size=kernel_size, iterations=iterations,
                                    return_mask=True)
@@ -600,11 +609,19 @@ class Context:
         return _take_fits(self._L, out, None)
 
     def roof_model(self, xyz, plane_idx, planes, bin=100, bin_height=1000, threshold=10, kernel_size=5, iterations=2,
-                   min_normal_z=0.5, min_votes=1, refit=False):
+                   min_normal_z=0.5, min_votes=1, refit=False, ground=None):
         """buildings() -> roof_homes -> roofs for a cloud shifted to its origin, its labels and the planes of segment().
         Returns (Footprints, Buildings, Roofs); the Roofs carry home, normal, center and bin for write_roofs_obj.
         refit=True: plane_fit() after buildings(), and homes and roofs from the refitted normal / center tables (which
-        the Roofs then carry, with the PlaneFits as `fit`)."""
+        the Roofs then carry, with the PlaneFits as `fit`).  ground: as for buildings(); the roofs of this call count their
+        points against the same dtm, and the Ground is returned as a fourth value."""
+        if ground is not None:
+            g = self.ground(xyz, points=False, **ground)
+            with self._ground_model(g):
+                out = self.roof_model(xyz, plane_idx, planes, bin=bin, bin_height=bin_height, threshold=threshold,
+                                      kernel_size=kernel_size, iterations=iterations, min_normal_z=min_normal_z,
+                                      min_votes=min_votes, refit=refit)
+            return out + (g,)
         n_planes = len(planes)
         if [p.id for p in planes] != list(range(1, n_planes + 1)):
             raise ValueError("roof_model: planes must be the planes 1 .. n of segment(), in order")
@@ -667,14 +684,23 @@ class Context:
                                                d_face_building or None, d_face_kind or None))
 
     def solid_model(self, xyz, plane_idx, planes, bin=100, bin_height=1000, threshold=10, kernel_size=5, iterations=2,
-                    min_normal_z=0.5, min_votes=1, refit=False, base_z=None, flat=None, generalise=None, terrain=None):
+                    min_normal_z=0.5, min_votes=1, refit=False, base_z=None, flat=None, generalise=None, terrain=None,
+                    ground=None):
         """roof_model() followed by solids(): returns (Footprints, Buildings, Roofs, Solids).  generalise: a dict of the
         parameters of generalise_roofs() (min_pixels, merge_flat, step_tol, bend_tol, max_rounds); the Roofs returned are
         then the generalised ones and the Solids theirs.  terrain: a dict of the parameters of terrain() (ring, q,
         min_ground; {} for its defaults): the stage runs after the buildings with fallback_z = int(ground_th), its `ground`
         is the base of every building for the generalisation and the solids (flat defaults to it where a building has no
         point above ground), the context's own table is restored afterwards, and the Terrain is returned as a fifth
-        value."""
+        value.  ground: as for roof_model(); the Ground is returned as an additional last value."""
+        if ground is not None:
+            g = self.ground(xyz, points=False, **ground)
+            with self._ground_model(g):
+                out = self.solid_model(xyz, plane_idx, planes, bin=bin, bin_height=bin_height, threshold=threshold,
+                                       kernel_size=kernel_size, iterations=iterations, min_normal_z=min_normal_z,
+                                       min_votes=min_votes, refit=refit, base_z=base_z, flat=flat, generalise=generalise,
+                                       terrain=terrain)
+            return out + (g,)
         fp, b, r = self.roof_model(xyz, plane_idx, planes, bin=bin, bin_height=bin_height, threshold=threshold,
                                    kernel_size=kernel_size, iterations=iterations, min_normal_z=min_normal_z,
                                    min_votes=min_votes, refit=refit)
@@ -1236,6 +1262,167 @@ class Context:
                                            int(n_buildings), int(ring), *_quantile(q), int(min_ground), int(fallback_z),
                                            d_owner or None, d_dist or None, d_low or None, C.byref(out)))
         return _take_terrain(self._L, out)
+
+    # ---- ground: a terrain raster of the tile by a progressive morphological filter (bs_ground, include/bs_api.h) ---------
+    def ground(self, xyz, extent=None, params=None, images=True, points=True, **kw):
+        """The ground surface of a cloud shifted to its origin, per pixel of a lattice of params["cell"] millimetres
+        (include/bs_api.h, "ground").  params: a dict of ground_params(), or its keywords directly.  images=False leaves
+        low, dtm and step out (None), points=False hag and cls.  Returns Ground."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError("ground: xyz must be [n][3]")
+        p = ground_params(**kw) if params is None else dict(params, **kw)
+        ext = np.ascontiguousarray(xyz.max(0) if extent is None else extent, dtype=np.int32)
+        w, h = grid_dims(ext, p["cell"])
+        low, dtm, step = ((np.empty((h, w), np.int32), np.empty((h, w), np.int32), np.empty((h, w), np.uint8)) if images
+                          else (None, None, None))
+        hag, cls = (np.empty(len(xyz), np.int32), np.empty(len(xyz), np.uint8)) if points else (None, None)
+        out = _lib.Ground()
+        self._check(self._L.bs_ground(self._h, xyz.ctypes.data, len(xyz), ext.ctypes.data, C.byref(_ground_struct(p)),
+                                      *[a.ctypes.data if a is not None else None for a in (low, dtm, step, hag, cls)],
+                                      C.byref(out)))
+        return _take_ground(self._L, out, p, low, dtm, step, hag, cls)
+
+    def ground_dev(self, d_xyz, n, extent, params=None, d_low=0, d_dtm=0, d_step=0, d_hag=0, d_class=0, **kw):
+        """Device-resident stage (bs_ground_dev): d_xyz [n][3] int32 is a device pointer (int); d_low, d_dtm (int32
+        [height][width]), d_step (uint8 [height][width]), d_hag (int32 [n]) and d_class (uint8 [n]) are device pointers or
+        0.  Returns the Ground with its arrays None."""
+        p = ground_params(**kw) if params is None else dict(params, **kw)
+        ext = np.ascontiguousarray(extent, dtype=np.int32)
+        out = _lib.Ground()
+        self._check(self._L.bs_ground_dev(self._h, d_xyz or None, int(n), ext.ctypes.data, C.byref(_ground_struct(p)),
+                                          d_low or None, d_dtm or None, d_step or None, d_hag or None, d_class or None,
+                                          C.byref(out)))
+        return _take_ground(self._L, out, p)
+
+    def set_ground_model(self, dtm, cell=None, min_height=None, device=False):
+        """The ground surface that grid_picture(), assign_buildings() and roofs() on this context measure "above ground"
+        against, in place of their scalar ground_th (bs_set_ground_model): dtm [height][width] int32 over a lattice of
+        `cell` millimetres, INT32_MAX where it holds nothing; a point counts iff z >= dtm[pixel] + min_height.  dtm may be a
+        Ground (its dtm, cell and min_height are the defaults).  None switches it off, the default.  device=True: dtm is
+        (device pointer, width, height)."""
+        if dtm is None:
+            self._check(self._L.bs_set_ground_model(self._h, None, 0, 0, 0, 0))
+            return
+        if isinstance(dtm, Ground):
+            cell = dtm.cell if cell is None else cell
+            min_height = dtm.min_height if min_height is None else min_height
+            dtm = dtm.dtm
+        if cell is None or min_height is None:
+            raise ValueError("set_ground_model: cell and min_height are needed")
+        if device:
+            ptr, w, h = dtm
+            self._check(self._L.bs_set_ground_model_dev(self._h, ptr or None, int(w), int(h), int(cell), int(min_height)))
+            return
+        if dtm is None:
+            raise ValueError("set_ground_model: this Ground holds no dtm (images=False, or ground_dev)")
+        t = np.ascontiguousarray(dtm, dtype=np.int32)
+        if t.ndim != 2 or t.size == 0 or not np.array_equal(t, np.asarray(dtm)):
+            raise ValueError("set_ground_model: dtm must be [height][width] whole numbers that fit 32 bits")
+        self._check(self._L.bs_set_ground_model(self._h, t.ctypes.data, t.shape[1], t.shape[0], int(cell), int(min_height)))
+
+    def ground_model(self):
+        """(dtm [height][width] int32, cell, min_height) as the context holds it (bs_get_ground_model), or None while the
+        switch is off."""
+        w, h, cell, mh = (C.c_int32(0) for _ in range(4))
+        self._check(self._L.bs_get_ground_model(self._h, None, 0, C.byref(w), C.byref(h), C.byref(cell), C.byref(mh)))
+        if w.value == 0:
+            return None
+        t = np.empty((h.value, w.value), np.int32)
+        self._check(self._L.bs_get_ground_model(self._h, t.ctypes.data, t.size, C.byref(w), C.byref(h), C.byref(cell),
+                                                C.byref(mh)))
+        return t, cell.value, mh.value
+
+    @contextmanager
+    def _ground_model(self, ground):
+        """the ground model for one call (None: off), the previous one restored behind it"""
+        prev = self.ground_model()
+        self.set_ground_model(ground)
+        try:
+            yield
+        finally:
+            if prev is None:
+                self.set_ground_model(None)
+            else:
+                self.set_ground_model(prev[0], prev[1], prev[2])
+
+
+def ground_params(cell=500, max_radius_mm=12800, slope=(3, 10), dh0=200, dh_max=2500, tol=200, min_height=2000, radius=None):
+    """The parameters of Context.ground() as a dict: cell (mm), radius (pixels per step; by default doubled 1, 2, 4, ...
+    while r * cell <= max_radius_mm), s_num / s_den (the slope), dh0, dh_max, tol, min_height (mm)."""
+    if radius is None:
+        radius, r = [], 1
+        while r * cell <= max_radius_mm and r <= _lib.GROUND_MAX_RADIUS and len(radius) < _lib.GROUND_MAX_STEPS:
+            radius.append(r)
+            r *= 2
+    return dict(cell=int(cell), radius=[int(r) for r in radius], s_num=int(slope[0]), s_den=int(slope[1]), dh0=int(dh0),
+                dh_max=int(dh_max), tol=int(tol), min_height=int(min_height))
+
+
+def _ground_struct(p):
+    q = _lib.GroundParams()
+    rad = list(p["radius"])
+    if len(rad) > _lib.GROUND_MAX_STEPS:
+        raise ValueError("ground: more than 16 steps")
+    q.cell, q.n_steps = int(p["cell"]), len(rad)
+    for k, r in enumerate(rad):
+        q.radius[k] = int(r)
+    for k in ("s_num", "s_den", "dh0", "dh_max", "tol", "min_height"):
+        setattr(q, k, int(p[k]))
+    return q
+
+
+@dataclass
+class Ground:
+    """bs_ground: the lattice (width, height, cell), the steps (radius, threshold, step_pixels: lists of n_steps), the
+    figures, and the arrays: low (the lowest point of every pixel, INT32_MAX: none), dtm (the ground surface, INT32_MAX:
+    nothing within reach), step (0: ground, k: removed in step k, 255: no point), hag (every point's height above dtm)
+    and cls (0 ground, 1 low, 2 object).  tol and min_height are the parameters of the call; a Ground is what
+    Context.set_ground_model() takes.  The arrays are None after ground_dev or where they were switched off."""
+    width: int
+    height: int
+    cell: int
+    n_steps: int
+    radius: list
+    threshold: list
+    step_pixels: list
+    grid: int
+    row_lds: int
+    n_points: int
+    n_ground_pixels: int
+    n_object_pixels: int
+    n_empty_pixels: int
+    n_filled_pixels: int
+    n_ground_points: int
+    n_low_points: int
+    n_object_points: int
+    sum_hag_ground: int
+    dtm_min: int
+    dtm_max: int
+    hag_min: int
+    hag_max: int
+    tol: int
+    min_height: int
+    info: dict = field(default_factory=dict)
+    low: np.ndarray | None = field(default=None, repr=False)
+    dtm: np.ndarray | None = field(default=None, repr=False)
+    step: np.ndarray | None = field(default=None, repr=False)
+    hag: np.ndarray | None = field(default=None, repr=False)
+    cls: np.ndarray | None = field(default=None, repr=False)
+
+
+def _take_ground(L, out, p, low=None, dtm=None, step=None, hag=None, cls=None) -> Ground:
+    """Copy a bs_ground into Python values and release it."""
+    try:
+        k = out.n_steps
+        head = {n: getattr(out, n) for n in _lib.GROUND_HEAD + _lib.GROUND_NARROW + _lib.GROUND_WIDE + ("n_points",)}
+        lists = {n: list(getattr(out, n))[:k] for n in _lib.GROUND_TABLES + ("step_pixels",)}
+        info = {n: getattr(out, n) for n in _lib.GROUND_MS}
+        info["ms_step"] = list(out.ms_step)[:k]
+        return Ground(**head, **lists, tol=int(p["tol"]), min_height=int(p["min_height"]), info=info, low=low, dtm=dtm,
+                      step=step, hag=hag, cls=cls)
+    finally:
+        L.bs_ground_free(C.byref(out))
 
 
 @dataclass

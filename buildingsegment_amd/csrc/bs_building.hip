@@ -318,6 +318,7 @@ __device__ inline void fig_global(const PtFig& f, int32_t b, unsigned cnt, unsig
 }
 
 __global__ __launch_bounds__(256) void assign_kernel(const int32_t* __restrict__ xyz, int64_t n, int bin, double ground_th,
+                                                     GroundRule rule,
                                                      const int32_t* __restrict__ map, int w, int h, int32_t nb,
                                                      int32_t* __restrict__ bidx, PtFig f, int* __restrict__ bad)
 {
@@ -333,9 +334,10 @@ __global__ __launch_bounds__(256) void assign_kernel(const int32_t* __restrict__
   __syncthreads();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x, n64 = (n + 63) & ~(int64_t)63;  // whole waves stay together
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n64; i += stride) {
-    int32_t b = -1, z = 0;
+    int32_t b = -1, x = 0, y = 0, z = 0;
     if (i < n) {
-      const int32_t x = xyz[3 * i], y = xyz[3 * i + 1];
+      x = xyz[3 * i];
+      y = xyz[3 * i + 1];
       z = xyz[3 * i + 2];
       const int32_t px = x / bin, py = y / bin;  // base pixel of the splat, TMC3.cpp:134-135
       if (x < 0 || y < 0 || px >= w || py >= h)
@@ -346,7 +348,7 @@ __global__ __launch_bounds__(256) void assign_kernel(const int32_t* __restrict__
         b = -1;  // (a map of another struct: stay in bounds)
       bidx[i] = b;
     }
-    const bool above = b >= 0 && !((double)z < ground_th);  // TMC3.cpp:139
+    const bool above = b >= 0 && !rule.below(x, y, z, ground_th);  // TMC3.cpp:139
     const int32_t b0 = __shfl(b, 0);
     if (__all(b == b0)) {  // the whole wave in one building (clouds in spatial order): reduce in registers
       if (b0 < 0)
@@ -683,7 +685,7 @@ extern "C" int bs_assign_buildings_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_
   BS_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, st));
   if (nb > 0)
     ptfig_init_kernel<<<nblk(nb, 256), 256, 0, st>>>(f, nb);
-  assign_kernel<<<(int)std::min<int64_t>(nblk(n, 256), 2048), 256, 0, st>>>(d_xyz, n, bin, ground_th, d_map, width, height,
+  assign_kernel<<<(int)std::min<int64_t>(nblk(n, 256), 2048), 256, 0, st>>>(d_xyz, n, bin, ground_th, ground_rule(ctx), d_map, width, height,
                                                                           nb, d_building_idx, f, d_bad);
   BS_HIP(ctx, hipEventRecord(ev.e[1], st));
   int h_bad = 0;

@@ -35,6 +35,13 @@ int building_bases(bs_ctx* ctx, int32_t n_buildings, const char* who, const int3
   return BS_OK;
 }
 
+GroundRule ground_rule(const bs_ctx* ctx)
+{
+  if (!ctx->gm_on)
+    return GroundRule{nullptr, 0, 0, 1, 0};
+  return GroundRule{ctx->gm_dev.as<int32_t>(), ctx->gm_w, ctx->gm_h, ctx->gm_cell, ctx->gm_min};
+}
+
 int check_params(bs_ctx* ctx, const bs_params* p, int64_t n)
 {
   if (!p)
@@ -275,6 +282,9 @@ void bs_destroy(bs_ctx* c)
   for (auto& b : c->tn)
     b.release();
   c->bases_dev.release();
+  for (auto& b : c->gd)
+    b.release();
+  c->gm_dev.release();
   for (auto& b : c->bt)
     b.release();
   c->tile_desc.release();
@@ -468,6 +478,61 @@ int bs_get_building_bases(bs_ctx* ctx, int32_t* base, int32_t capacity, int32_t*
   const size_t m = std::min<size_t>((size_t)capacity, ctx->bases.size());
   if (m)
     memcpy(base, ctx->bases.data(), 4 * m);
+  return BS_OK;
+}
+
+static int set_ground_model(bs_ctx* ctx, const int32_t* dtm, bool on_device, int32_t width, int32_t height, int32_t cell,
+                            int32_t min_height)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (!dtm) {
+    ctx->gm_on = false;
+    return BS_OK;
+  }
+  if (width < 1 || height < 1 || cell < 1 || min_height < 0 || (long long)width * height >= (1ll << 31) - 1)
+    return bs::fail(ctx, BS_ERR_INVALID, "ground model: width, height or cell < 1, width * height >= 2^31 - 1, or min_height < 0");
+  ctx->gm_on = false;  // (off, also where the copy below fails)
+  const size_t bytes = 4 * (size_t)width * (size_t)height;
+  BS_HIP(ctx, hipSetDevice(ctx->device));
+  BS_HIP(ctx, ctx->gm_dev.reserve(bytes));
+  BS_HIP(ctx, hipMemcpyAsync(ctx->gm_dev.p, dtm, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+  BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->gm_w = width;
+  ctx->gm_h = height;
+  ctx->gm_cell = cell;
+  ctx->gm_min = min_height;
+  ctx->gm_on = true;
+  return BS_OK;
+}
+
+int bs_set_ground_model(bs_ctx* ctx, const int32_t* dtm, int32_t width, int32_t height, int32_t cell, int32_t min_height)
+{
+  return set_ground_model(ctx, dtm, false, width, height, cell, min_height);
+}
+
+int bs_set_ground_model_dev(bs_ctx* ctx, const int32_t* d_dtm, int32_t width, int32_t height, int32_t cell, int32_t min_height)
+{
+  return set_ground_model(ctx, d_dtm, true, width, height, cell, min_height);
+}
+
+int bs_get_ground_model(bs_ctx* ctx, int32_t* dtm, int64_t capacity, int32_t* width, int32_t* height, int32_t* cell,
+                        int32_t* min_height)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (!width || !height || !cell || !min_height || capacity < 0 || (capacity > 0 && !dtm))
+    return bs::fail(ctx, BS_ERR_INVALID, "ground model: a null pointer or a negative capacity");
+  *width = ctx->gm_on ? ctx->gm_w : 0;
+  *height = ctx->gm_on ? ctx->gm_h : 0;
+  *cell = ctx->gm_on ? ctx->gm_cell : 0;
+  *min_height = ctx->gm_on ? ctx->gm_min : 0;
+  const int64_t m = ctx->gm_on ? std::min<int64_t>(capacity, (int64_t)ctx->gm_w * ctx->gm_h) : 0;
+  if (m > 0) {
+    BS_HIP(ctx, hipSetDevice(ctx->device));
+    BS_HIP(ctx, hipMemcpyAsync(dtm, ctx->gm_dev.p, 4 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
   return BS_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/bs_api.h"
+#include "bs_groundrule.h"
 
 namespace bs {
 
@@ -320,6 +321,11 @@ struct bs_ctx {
   std::vector<int32_t> bases;
   bs::DevBuf bases_dev;
   bs::DevBuf tn[16];  // scratch of the terrain stage (bs_terrain.hip); it keeps no state between calls
+  bs::DevBuf gd[16];  // scratch of the ground stage (bs_ground.hip); it keeps no state between calls
+  // ground model (bs_set_ground_model): the device copy of the table and its lattice; gm_on == false = off
+  bs::DevBuf gm_dev;
+  bool gm_on = false;
+  int32_t gm_w = 0, gm_h = 0, gm_cell = 0, gm_min = 0;
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew
@@ -374,6 +380,8 @@ int launch_knn_normals_tiled(bs_ctx* ctx, const TiledGridDev& g, const bs_params
 // capi.hip: the device table of bs_set_building_bases for a call over n_buildings, nullptr while the switch is off;
 // BS_ERR_INVALID (worded for `who`) where the table's length differs
 int building_bases(bs_ctx* ctx, int32_t n_buildings, const char* who, const int32_t** d_table);
+// capi.hip: the rule of bs_set_ground_model for a kernel (table == nullptr while the switch is off)
+GroundRule ground_rule(const bs_ctx* ctx);
 int region_grow_dev_impl(bs_ctx* ctx, const int32_t* d_xyz, const double* d_normals, const int32_t* d_neigh,
                          int64_t n, const bs_params* p, int32_t* d_plane_idx, bool trusted_neigh);
 int check_params(bs_ctx* ctx, const bs_params* p, int64_t n);

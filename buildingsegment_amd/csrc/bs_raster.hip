@@ -141,7 +141,7 @@ __global__ void ground_th_tiled_kernel(const int* __restrict__ hist, const Raste
 
 __global__ void emit_pairs_tiled_kernel(const int32_t* __restrict__ xyz, int64_t n, const int32_t* __restrict__ off,
                                         int32_t n_tiles, const RasterTile* __restrict__ tiles, int bin, uint32_t npix,
-                                        const double* __restrict__ th, uint32_t* __restrict__ keys,
+                                        const double* __restrict__ th, GroundRule rule, uint32_t* __restrict__ keys,
                                         uint32_t* __restrict__ vals, int* __restrict__ cnt)
 {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -153,7 +153,7 @@ __global__ void emit_pairs_tiled_kernel(const int32_t* __restrict__ xyz, int64_t
   // a point outside its tile's extent fails the call (zhist_tiled_kernel); it must not splat into a neighbour
   // tile or past the end of cnt
   const bool inside = px >= 0 && py >= 0 && pz >= 0 && px <= T.ext[0] && py <= T.ext[1] && pz <= T.ext[2];
-  const bool keep = inside && !((double)pz < th[t]);  // TMC3.cpp:134
+  const bool keep = inside && !rule.below(px, py, pz, th[t]);  // TMC3.cpp:134
   const int x = px / bin, y = py / bin;
 #pragma unroll
   for (int c = 0; c < 4; c++) {  // c = 2*xi + yi: the reference's loop order (TMC3.cpp:131-132)
@@ -301,7 +301,7 @@ int grid_picture_tiles_dev(bs_ctx* ctx, const int32_t* d_xyz, const int64_t* til
   uint32_t* vals_in = ctx->rs_vals_in.as<uint32_t>();
   uint32_t* keys_out = ctx->rs_keys_out.as<uint32_t>();
   uint32_t* vals_out = ctx->rs_vals_out.as<uint32_t>();
-  emit_pairs_tiled_kernel<<<nblk(n, 256), 256, 0, st>>>(d_xyz, n, doff, n_tiles, dt, bin, npix, d_th, keys_in,
+  emit_pairs_tiled_kernel<<<nblk(n, 256), 256, 0, st>>>(d_xyz, n, doff, n_tiles, dt, bin, npix, d_th, ground_rule(ctx), keys_in,
                                                         vals_in, cnt);
   int end_bit = 1;
   while (end_bit < 32 && (1ull << end_bit) <= (unsigned long long)npix)
@@ -387,6 +387,8 @@ extern "C" int bs_grid_picture_batch_dev(bs_ctx* ctx, const int32_t* d_xyz, cons
     return rc;
   if (!d_xyz || !d_image)
     return fail(ctx, BS_ERR_INVALID, "raster batch: null device pointer");
+  if (ctx->gm_on && n_tiles > 1)
+    return fail(ctx, BS_ERR_INVALID, "raster batch: more than one tile while a ground model is set (bs_set_ground_model)");
   int32_t bad_tile = -1;
   rc = grid_picture_tiles_dev(ctx, d_xyz, tile_offset, n_tiles, extent, bin, bin_height, d_image, ground_th,
                               &bad_tile);
@@ -411,6 +413,8 @@ extern "C" int bs_grid_picture_batch(bs_ctx* ctx, const int32_t* xyz, const int6
     return rc;
   if (!xyz || !image)
     return fail(ctx, BS_ERR_INVALID, "raster batch: null host pointer");
+  if (ctx->gm_on && n_tiles > 1)
+    return fail(ctx, BS_ERR_INVALID, "raster batch: more than one tile while a ground model is set (bs_set_ground_model)");
   std::vector<RasterTile> tl;
   rc = raster_tiles(ctx, tile_offset, n_tiles, extent, bin, bin_height, tl, &npix, &nb);
   if (rc != BS_OK)

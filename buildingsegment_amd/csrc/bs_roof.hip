@@ -45,7 +45,7 @@ struct Tables {  // per plane, device: entry p - 1 is plane p
 };
 
 // the plane (0-based) a point counts for and its pixel; -1: it does not count; -2: its pixel lies outside the image
-__device__ inline int32_t counting(const int32_t* __restrict__ xyz, int64_t i, int bin, double ground_th,
+__device__ inline int32_t counting(const int32_t* __restrict__ xyz, int64_t i, int bin, double ground_th, GroundRule rule,
                                    const int32_t* __restrict__ map, int w, int h, const int32_t* __restrict__ plane,
                                    int32_t npl, const int32_t* __restrict__ home, int64_t* pix, int32_t* zout)
 {
@@ -56,7 +56,7 @@ __device__ inline int32_t counting(const int32_t* __restrict__ xyz, int64_t i, i
   *pix = (int64_t)py * w + px;
   *zout = z;
   const int32_t p = plane[i];
-  if (p < 1 || p > npl || (double)z < ground_th)
+  if (p < 1 || p > npl || rule.below(x, y, z, ground_th))
     return -1;
   const int32_t b = map[*pix];
   return (b >= 0 && home[p - 1] == b) ? p - 1 : -1;
@@ -64,7 +64,7 @@ __device__ inline int32_t counting(const int32_t* __restrict__ xyz, int64_t i, i
 
 // The keys of the counting points, compacted (most points of a cloud are ground or wall; the order does not matter:
 // the keys are sorted next): a workgroup takes KEY_ITEMS * 256 consecutive points and one slot range for all of them.
-__global__ __launch_bounds__(256) void keys_kernel(const int32_t* __restrict__ xyz, int64_t n, int bin, double ground_th,
+__global__ __launch_bounds__(256) void keys_kernel(const int32_t* __restrict__ xyz, int64_t n, int bin, double ground_th, GroundRule rule,
                                                    const int32_t* __restrict__ map, int w, int h,
                                                    const int32_t* __restrict__ plane, int32_t npl,
                                                    const int32_t* __restrict__ home, uint64_t* __restrict__ keys,
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void keys_kernel(const int32_t* __restrict__ x
     int32_t s = -1, z;
     int64_t pix = 0;
     if (i < n) {
-      s = counting(xyz, i, bin, ground_th, map, w, h, plane, npl, home, &pix, &z);
+      s = counting(xyz, i, bin, ground_th, rule, map, w, h, plane, npl, home, &pix, &z);
       if (s == -2)
         atomicOr(bad, 1);
     }
@@ -277,7 +277,7 @@ __device__ inline void ptfig_global(const Fig& f, int32_t s, unsigned cnt, int32
 }
 
 // A supporting point is a counting point whose plane is the final roof of its pixel.
-__global__ __launch_bounds__(256) void ptfig_kernel(const int32_t* __restrict__ xyz, int64_t n, int bin, double ground_th,
+__global__ __launch_bounds__(256) void ptfig_kernel(const int32_t* __restrict__ xyz, int64_t n, int bin, double ground_th, GroundRule rule,
                                                     const int32_t* __restrict__ map, int w, int h,
                                                     const int32_t* __restrict__ plane, int32_t npl,
                                                     const int32_t* __restrict__ home, const int32_t* __restrict__ roof,
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void ptfig_kernel(const int32_t* __restrict__ 
     int32_t s = -1, z = 0;
     if (i < n) {
       int64_t pix = 0;
-      s = counting(xyz, i, bin, ground_th, map, w, h, plane, npl, home, &pix, &z);
+      s = counting(xyz, i, bin, ground_th, rule, map, w, h, plane, npl, home, &pix, &z);
       if (s >= 0 && roof[pix] != s + 1)
         s = -1;
       if (s < 0)
@@ -590,7 +590,7 @@ extern "C" int bs_roofs_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
   BS_HIP(ctx, hipMemsetAsync(d_bad, 0, 4 * (4 + FILL_GROUP + 1), st));
   BS_HIP(ctx, hipMemsetAsync(best, 0, 8 * (size_t)npix, st));
-  keys_kernel<<<nblk(n, 256 * KEY_ITEMS), 256, 0, st>>>(d_xyz, n, bin, ground_th, d_map, w, h, d_plane_idx, npl, tab_home,
+  keys_kernel<<<nblk(n, 256 * KEY_ITEMS), 256, 0, st>>>(d_xyz, n, bin, ground_th, ground_rule(ctx), d_map, w, h, d_plane_idx, npl, tab_home,
                                                         keys, d_nkeys, d_bad);
   int h_flags[4] = {0, 0, 0, 0};  // (before anything is written to the caller's arrays)
   BS_HIP(ctx, hipMemcpyAsync(h_flags, d_bad, 16, hipMemcpyDeviceToHost, st));
@@ -631,7 +631,7 @@ extern "C" int bs_roofs_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_
 
   // ---- figures ----
   fig_init_kernel<<<nblk(std::max<int32_t>(npl, 3), 256), 256, 0, st>>>(f, npl);
-  ptfig_kernel<<<(int)std::min<int64_t>(nblk(n, 256), 2048), 256, 0, st>>>(d_xyz, n, bin, ground_th, d_map, w, h,
+  ptfig_kernel<<<(int)std::min<int64_t>(nblk(n, 256), 2048), 256, 0, st>>>(d_xyz, n, bin, ground_th, ground_rule(ctx), d_map, w, h,
                                                                           d_plane_idx, npl, tab_home, d_roof, f);
   pixfig_kernel<<<(int)std::min<int64_t>(nblk(npix, 256), 4096), 256, 0, st>>>(d_roof, best, w, h, min_votes, npl, f);
   BS_HIP(ctx, hipEventRecord(ev.e[3], st));

@@ -1953,6 +1953,101 @@ int bs_set_building_bases(bs_ctx* ctx, const int32_t* base, int32_t n_buildings)
  * with capacity == 0.  BS_ERR_INVALID: a null n_buildings, a negative capacity, or a null base with capacity > 0. */
 int bs_get_building_bases(bs_ctx* ctx, int32_t* base, int32_t capacity, int32_t* n_buildings);
 
+/* ---- ground: a terrain raster of the tile by a progressive morphological filter ----
+ *
+ * ground_th is one scalar for the whole tile; on a slope it lies below the uphill ground and above the downhill roofs.  This
+ * stage computes a ground surface per pixel (a digital terrain model, DTM) from the cloud alone; bs_set_ground_model below lets
+ * the raster, the point assignment and the roofs read their threshold from it.  Everything is an exact integer.
+ *
+ * Input.  The cloud xyz [n][3] int32 in millimetres shifted to its origin, 1 <= n < 2^29, every |coordinate| < 2^23;
+ * extent[3] as for bs_grid_picture; struct bs_ground_params: cell > 0 (mm); n_steps K in 1 .. BS_GROUND_MAX_STEPS; radius[k]
+ * (k < K) in pixels, strictly increasing, each in 1 .. BS_GROUND_MAX_RADIUS; a slope s_num / s_den with s_num >= 0 and
+ * s_den > 0; dh0, dh_max, tol, min_height >= 0 (mm).  The lattice is bs_grid_dims(extent, cell) = (width, height); the pixel
+ * of a point is (x / cell, y / cell), no splat.  EMPTY = INT32_MAX.
+ *
+ * 1. low [height][width] int32: the lowest z of all points of the pixel, EMPTY without a point.
+ * 2. S_0 = low; step [height][width] uint8 = 255 where low is EMPTY and 0 elsewhere; r_0 = 0.
+ * 3. For k = 1 .. K, with r = radius[k - 1]:  E = erode(S_{k-1}, r): per pixel the minimum over the (2r+1)^2 square around
+ *    it clipped to the image, IGNORING EMPTY (EMPTY if all are);  O_k = dilate(E, r): the maximum over the same square,
+ *    ignoring EMPTY;  threshold[k - 1] = t_k = min(dh_max, dh0 + floor(s_num * (r_k - r_{k-1}) * cell / s_den)), exact;
+ *    every pixel with step == 0, S_{k-1} != EMPTY and S_{k-1} - O_k > t_k (strictly) gets step = k -- the first step that
+ *    flags a pixel stays -- and step_pixels[k - 1] counts them;  S_k = O_k.
+ * 4. dtm [height][width] int32 = low where step == 0, else S_K.  It stays EMPTY where no point lies within reach.
+ * 5. Per point: hag [n] int32 = z - dtm[pixel];  class [n] uint8 = 0 (ground) iff step[pixel] == 0 and hag <= tol,
+ *    else 2 (object) iff hag >= min_height, else 1.
+ *
+ * Figures, all exact.  n_ground_pixels (step == 0), n_object_pixels (step in 1 .. K), n_empty_pixels (low EMPTY),
+ * n_filled_pixels (low EMPTY, dtm not); n_ground_points, n_low_points, n_object_points (classes 0, 1, 2); dtm_min, dtm_max
+ * over the pixels with a dtm (INT32_MAX / INT32_MIN when there is none); hag_min, hag_max over all points; sum_hag_ground
+ * over the points of class 0.
+ *
+ * Promised.  dtm <= low wherever low != EMPTY (an opening never rises above its input, and a pixel that no step flagged
+ * keeps low), so hag >= 0; a pixel EMPTY in low has step 255 and counts neither as ground nor as object.
+ *
+ * Errors.  BS_ERR_INVALID: a null cloud, extent, params or out, n < 1, cell < 1, a bad extent, K or a radius outside the
+ * ranges above, radii not strictly increasing, s_num < 0, s_den < 1, a negative dh0, dh_max, tol or min_height.
+ * BS_ERR_RANGE: 2^29 points or more; width * height >= 2^31 - 1; a point with a negative x / y or whose pixel lies outside
+ * the lattice; a coordinate at or beyond 2^23.  On any of these the outputs and the struct are untouched and the context
+ * stays usable: everything before the host's first wait works in scratch of the context. */
+#define BS_GROUND_MAX_STEPS 16
+#define BS_GROUND_MAX_RADIUS 255
+#define BS_GROUND_GRID 2048  /* workgroups of 256 of the two passes over the points: beyond 524 288 points a thread takes several */
+#define BS_GROUND_ROW_LDS 2048 /* entries of a row segment in LDS in the x passes: 2048 - 2 r outputs and r of apron each side */
+
+struct bs_ground_params {
+  int32_t cell, n_steps;
+  int32_t radius[BS_GROUND_MAX_STEPS];
+  int32_t s_num, s_den, dh0, dh_max, tol, min_height;
+};
+
+struct bs_ground {
+  int32_t width, height, cell, n_steps;
+  int32_t radius[BS_GROUND_MAX_STEPS], threshold[BS_GROUND_MAX_STEPS];
+  int32_t grid, row_lds; /* BS_GROUND_GRID, BS_GROUND_ROW_LDS of the library */
+  int32_t dtm_min, dtm_max, hag_min, hag_max;
+  int64_t n_points;
+  int64_t step_pixels[BS_GROUND_MAX_STEPS];
+  int64_t n_ground_pixels, n_object_pixels, n_empty_pixels, n_filled_pixels;
+  int64_t n_ground_points, n_low_points, n_object_points, sum_hag_ground;
+  /* device time (HIP events on the context's stream) */
+  double ms_low;    /* clearing, the check of the cloud, low */
+  double ms_open;   /* the K steps and the pass over the pixels (dtm and its figures); the host's read of the range flags */
+  double ms_points; /* the pass over the points, the copies into the caller's images, the host's read of the figures */
+  double ms_step[BS_GROUND_MAX_STEPS]; /* each step of ms_open */
+};
+
+/* d_xyz is a device pointer.  d_low, d_dtm ([height][width] int32), d_step ([height][width] uint8), d_hag ([n] int32) and
+ * d_class ([n] uint8) are device buffers; each may be NULL.  The figures are always computed.  All K steps are launched
+ * without a host round trip.  Synchronises: once for the range flags, once for the result. */
+int bs_ground_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, const int32_t* extent, const struct bs_ground_params* params,
+                  int32_t* d_low, int32_t* d_dtm, uint8_t* d_step, int32_t* d_hag, uint8_t* d_class, struct bs_ground* out);
+/* Host-memory twin: xyz and the five outputs (each may be NULL) are host pointers. */
+int bs_ground(bs_ctx* ctx, const int32_t* xyz, int64_t n, const int32_t* extent, const struct bs_ground_params* params,
+              int32_t* low, int32_t* dtm, uint8_t* step, int32_t* hag, uint8_t* cls, struct bs_ground* out);
+/* Zeroes the struct (it owns no memory); accepts a zeroed struct and NULL. */
+void bs_ground_free(struct bs_ground* g);
+
+/* ---- ground model: the 2-D branch relative to a terrain raster ----
+ *
+ * A switch of the context, as bs_set_building_bases.  dtm [height][width] int32 is a host table over a lattice of `cell`
+ * millimetres (in the pipeline: dtm of bs_ground), INT32_MAX where it holds nothing; the context keeps a device copy.  A NULL
+ * table switches it off, which is the default.  While it is set, bs_grid_picture*, bs_assign_buildings* and bs_roofs* decide
+ * "below ground" per point: wherever their definition says z < ground_th they test
+ *     z < dtm[y / cell][x / cell] + min_height          (64-bit)
+ * and a point with a negative x or y, whose model pixel lies outside the table, or whose model pixel is INT32_MAX falls back
+ * to z < ground_th.  ground_th is still computed, taken and returned as before.  bs_grid_picture_batch* with more than one
+ * tile refuse with BS_ERR_INVALID while it is set (one table cannot serve two tiles); the solo forms and a batch of one work.
+ * Switched off, every byte these stages write is what they write without this paragraph.
+ * BS_ERR_INVALID: width, height or cell < 1, width * height >= 2^31 - 1, min_height < 0. */
+int bs_set_ground_model(bs_ctx* ctx, const int32_t* dtm, int32_t width, int32_t height, int32_t cell, int32_t min_height);
+/* The same from a device table (copied on the context's stream; the call waits for the copy). */
+int bs_set_ground_model_dev(bs_ctx* ctx, const int32_t* d_dtm, int32_t width, int32_t height, int32_t cell,
+                            int32_t min_height);
+/* The four numbers of the model (all 0 while it is off) and its first min(capacity, width * height) entries into dtm, which
+ * may be NULL with capacity == 0.  BS_ERR_INVALID: a null number, a negative capacity, or a null dtm with capacity > 0. */
+int bs_get_ground_model(bs_ctx* ctx, int32_t* dtm, int64_t capacity, int32_t* width, int32_t* height, int32_t* cell,
+                        int32_t* min_height);
+
 #ifdef __cplusplus
 }
 #endif
