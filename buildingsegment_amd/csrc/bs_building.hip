@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "bs_common.h"
+#include "bs_host.h"
 #include "bs_uf.h"
 
 namespace bs {
@@ -35,8 +36,6 @@ constexpr int64_t VOTE_DENSE_CELLS = 1ll << 22;  // dense vote histogram in HBM 
 // scratch of bs_ctx::bd
 enum { BD_LAB1, BD_LAB2, BD_SCAN, BD_TMP, BD_PIX, BD_MISC, BD_FIG, BD_VOTE, BD_KEYS, BD_KEYS2, BD_RUNS, BD_IN_A, BD_IN_B,
        BD_IN_C };
-
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 
 // ---- classes of the two labelling passes: 1 = the 8-connected class, 0 = the 4-connected one ---------------------
 struct MaskClass {  // pass 1 on the unpadded mask: foreground / background (the frame is background)
@@ -482,21 +481,6 @@ __global__ __launch_bounds__(256) void vote_runs_kernel(const uint64_t* __restri
     vote(v, (int64_t)key[r], (unsigned long long)len[r], nb);
 }
 
-struct Events {
-  hipEvent_t e[5] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  float ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.f;
-  }
-};
-
 template <class Cls>
 void launch_label(Cls cls, int wp, int hp, int32_t* parent, hipStream_t st)
 {
@@ -568,7 +552,7 @@ extern "C" int bs_building_map_dev(bs_ctx* ctx, const uint8_t* d_mask, int32_t w
   const int w = width, h = height, wp = w + 2, hp = h + 2;
   const int64_t np = (int64_t)wp * hp, npix = (int64_t)w * h;
   DevBuf* B = ctx->bd;
-  Events ev;
+  Events<5> ev;
   for (auto& e : ev.e)
     BS_HIP(ctx, hipEventCreate(&e));
   BS_HIP(ctx, B[BD_LAB1].reserve(4 * np));
@@ -669,7 +653,7 @@ extern "C" int bs_assign_buildings_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_
   const int32_t nb = inout->n_buildings;
   const size_t m = (size_t)std::max(nb, 1);
   DevBuf* B = ctx->bd;
-  Events ev;
+  Events<2> ev;
   for (int k = 0; k < 2; k++)
     BS_HIP(ctx, hipEventCreate(&ev.e[k]));
   BS_HIP(ctx, B[BD_FIG].reserve(32 * m));

@@ -25,6 +25,7 @@
 #include <cstring>
 
 #include "bs_common.h"
+#include "bs_host.h"
 #include "bs_uf.h"
 
 namespace bs {
@@ -526,8 +527,6 @@ __global__ __launch_bounds__(256) void mask_out_tiled_kernel(const uint8_t* __re
   out[i] = m[T.pbase + (int64_t)(y + 1) * T.wp + x + 1] ? 255 : 0;
 }
 
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
-
 // getStructuringElement(MORPH_ELLIPSE, Size(s, s)): row i has the run c - dx .. c + dx,
 // dx = cvRound(c * sqrt((r*r - dy*dy) / (r*r))), dy = i - r, r = c = s / 2
 Ellipse make_ellipse(int s)
@@ -543,21 +542,6 @@ Ellipse make_ellipse(int s)
   }
   return e;
 }
-
-struct Events {
-  hipEvent_t e[6] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  float ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.f;
-  }
-};
 
 }  // namespace
 }  // namespace bs
@@ -635,7 +619,7 @@ int footprints_tiles_dev(bs_ctx* ctx, const double* d_image, const int32_t* widt
   BS_HIP(ctx, hipMemcpyAsync(dd, desc.data(), desc.size(), hipMemcpyHostToDevice, st));
 
   DevBuf* B = ctx->fp;
-  Events ev;
+  Events<6> ev;
   for (auto& e : ev.e)
     BS_HIP(ctx, hipEventCreate(&e));
   BS_HIP(ctx, B[0].reserve(np));

@@ -37,28 +37,6 @@ static_assert(TW == LABEL_TW && TH == LABEL_TH, "the labelling tile of bs_facet_
 enum { FC_PARENT, FC_SCAN, FC_FLAGS, FC_TMP, FC_MISC, FC_FFIG, FC_KEYS, FC_KEYS2, FC_VALS, FC_VALS2, FC_EID, FC_EFIG, FC_IN_MAP,
        FC_IN_ROOF, FC_IN_TOP, FC_FACET };
 
-struct Events {
-  hipEvent_t e[11] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  double ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.0;
-  }
-};
-
-template <class T>
-bool alloc(T** p, size_t n)
-{
-  *p = (T*)calloc(std::max<size_t>(n, 1), sizeof(T));
-  return *p != nullptr;
-}
-
 // (every array is allocated even after a failure: bs_roof_facets_free takes them all)
 bool alloc_facets(struct bs_roof_facets* s, size_t nf)
 {
@@ -78,15 +56,7 @@ bool alloc_edges(struct bs_roof_facets* s, size_t ne)
   return std::all_of(std::begin(ok), std::end(ok), [](bool b) { return b; });
 }
 
-struct Guard {  // frees a half-built result unless it is handed over
-  struct bs_roof_facets* s;
-  bool keep = false;
-  ~Guard()
-  {
-    if (!keep)
-      bs_roof_facets_free(s);
-  }
-};
+using Guard = FreeUnlessKept<struct bs_roof_facets, bs_roof_facets_free>;
 
 // (a pixel edge is numbered 2 * pixel + direction in 32 bits)
 bool bad_image(int32_t w, int32_t h) { return w < 1 || h < 1 || (int64_t)w * h >= (1ll << 30); }
@@ -145,7 +115,7 @@ extern "C" int bs_roof_facets_dev(bs_ctx* ctx, const int32_t* d_map, const int32
   DevBuf* B = ctx->fc;
   const int4* top = reinterpret_cast<const int4*>(d_top);
   const Cls cls{d_map, d_roof};
-  Events ev;
+  Events<11> ev;
   for (auto& e : ev.e)
     BS_HIP(ctx, hipEventCreate(&e));
 

@@ -10,6 +10,7 @@
 #include <climits>
 
 #include "bs_common.h"
+#include "bs_host.h"
 #include "bs_segscan.h"
 #include "bs_uf.h"
 
@@ -19,7 +20,6 @@ namespace {
 constexpr int LABEL_TW = 64, LABEL_TH = 16;  // labelling tile: a row is one wave, 8 KB (classes) + 4 KB (parents) of LDS
 constexpr int GRID_CAP = 4096;   // workgroups of the grid-stride passes
 
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 inline int grid_of(int64_t n) { return (int)std::min<int64_t>(nblk(n, 256), GRID_CAP); }
 
 constexpr unsigned long long NONE = ~0ull;  // the class of a pixel outside every building
@@ -456,14 +456,6 @@ __global__ __launch_bounds__(256) void edge_reduce_kernel(const unsigned long lo
       atomicMax(E.bbox + 4 * (int64_t)e + 3, Y1);
     }
   }
-}
-
-int bits_of(int64_t n)  // bits that hold 0 .. n - 1 (at least 1)
-{
-  int b = 1;
-  while (b < 32 && (1ll << b) < n)
-    b++;
-  return b;
 }
 
 }  // namespace

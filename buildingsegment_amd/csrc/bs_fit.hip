@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "bs_common.h"
+#include "bs_host.h"
 #include "bs_normal.h"
 
 namespace bs {
@@ -28,8 +29,6 @@ constexpr int FIT_GRID = 256;      // workgroups of a point pass at most (then t
 constexpr int32_t FIT_LIM = 1 << 23;
 // scratch of bs_ctx::ft
 enum { FT_TAB, FT_MISC, FT_IN_XYZ, FT_IN_PLANE, FT_OUT };
-
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 
 struct Fit {  // per plane, device: entry p - 1 is plane p
   unsigned long long* cnt;   // [m]
@@ -392,21 +391,6 @@ __global__ __launch_bounds__(FIT_THREADS) void residuals_kernel(const int32_t* _
     residuals_global(f, k, s_max[k], s_abs[k], s_sq[k]);
 }
 
-struct Events {
-  hipEvent_t e[6] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  float ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.f;
-  }
-};
-
 bool alloc_fits(struct bs_plane_fits* r, int32_t npl)
 {
   const size_t m = (size_t)std::max(npl, 1);
@@ -477,7 +461,7 @@ extern "C" int bs_plane_fit_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, co
   const int32_t npl = n_planes;
   const size_t m = (size_t)std::max(npl, 1);
   DevBuf* B = ctx->ft;
-  Events ev;
+  Events<6> ev;
   for (auto& e : ev.e)
     BS_HIP(ctx, hipEventCreate(&e));
   BS_HIP(ctx, B[FT_TAB].reserve(FIT_BYTES * m));

@@ -296,21 +296,6 @@ __global__ __launch_bounds__(256) void gen_figures_kernel(const int32_t* __restr
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-struct Events {
-  hipEvent_t e[8] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  double ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.0;
-  }
-};
-
 struct Eval {  // what one evaluation reports
   int64_t facets = 0, edges = 0, flat = 0, small = 0, movers = 0, movers_small = 0, movers_flat = 0, chain = 0;
   std::vector<ull> bfac;  // facets per building
@@ -325,7 +310,7 @@ struct Job {  // one call
   Tables tab;
   const int32_t* tab_flat;
   Rule rule;
-  Events ev;
+  Events<8> ev;
   double ms_tops = 0, ms_facets = 0, ms_decide = 0;
 };
 
@@ -347,7 +332,7 @@ int evaluate(Job& J, int4* top, Eval* out)
   int32_t* facet = B[GN_FACET].as<int32_t>();
   ull* counters = B[GN_MISC].as<ull>();
   int* d_bad = reinterpret_cast<int*>(counters + CN_BAD);
-  Events& ev = J.ev;
+  Events<8>& ev = J.ev;
   hipcub::CountingInputIterator<int32_t> idx(0);
   hipcub::TransformInputIterator<int32_t, RootFlag, hipcub::CountingInputIterator<int32_t>> roots(idx, RootFlag{parent});
 

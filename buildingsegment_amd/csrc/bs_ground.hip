@@ -26,6 +26,7 @@
 #include <cstring>
 
 #include "bs_common.h"
+#include "bs_host.h"
 
 namespace bs {
 namespace {
@@ -48,23 +49,6 @@ enum { R_XY = 1, R_COORD = 2 };  // the bits of the range word
 // the 64-bit words of GD_MISC
 enum { M_RANGE, M_STEP, M_GROUND_PIX = M_STEP + MAX_STEPS, M_OBJECT_PIX, M_EMPTY_PIX, M_FILLED_PIX, M_GROUND_PTS, M_LOW_PTS,
        M_OBJECT_PTS, M_SUM_HAG, M_DTM_MIN, M_DTM_MAX, M_HAG_MIN, M_HAG_MAX, M_WORDS };
-
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
-
-struct Events {
-  hipEvent_t e[4 + MAX_STEPS] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  double ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.0;
-  }
-};
 
 // minimum, or maximum with EMPTY below everything
 template <bool MAX>
@@ -476,7 +460,7 @@ int ground(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t width, int32_t 
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->gd;
-  Events ev;
+  Events<4 + MAX_STEPS> ev;
   for (int i = 0; i < 4 + K; i++)
     BS_HIP(ctx, hipEventCreate(&ev.e[i]));
   BS_HIP(ctx, B[GD_MISC].reserve(8 * M_WORDS));

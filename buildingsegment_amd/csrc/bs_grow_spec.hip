@@ -58,6 +58,7 @@
 
 #include "bs_centerdiv.h"
 #include "bs_common.h"
+#include "bs_host.h"
 
 namespace bs {
 
@@ -2636,8 +2637,6 @@ __global__ void fill_i32_kernel(int32_t* p, int64_t n, int32_t v)
   if (i < n)
     p[i] = v;
 }
-
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 
 struct ToI64 {
   __host__ __device__ int64_t operator()(int32_t v) const { return (int64_t)v; }

@@ -14,6 +14,8 @@
 // No work item's time grows with a triangle's box or area.  Every index read from memory is checked before it is used as an
 // address; a violation sets err and the call returns BS_ERR_INTERNAL.  The three images are built in scratch and copied to
 // the caller's only after the last check, so that an error leaves them untouched.
+// The walk from slots to rows to spans to items is bs_trispan.h's, shared with bs_pointresid.hip; what a span is (crossing,
+// below) is this file's.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -23,11 +25,10 @@
 #include <cstring>
 #include <vector>
 
+#include "bs_chain.h"
 #include "bs_common.h"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (the ranking kernels of bs_outline.h are not launched here)
-#include "bs_outline.h"
-#pragma clang diagnostic pop
+#include "bs_host.h"
+#include "bs_trispan.h"
 
 namespace bs {
 namespace {
@@ -37,51 +38,15 @@ enum { MR_MISC, MR_TMP, MR_ROWCNT, MR_ROWSCAN, MR_ROWS, MR_SPANSCAN, MR_WIN, MR_
        MR_OUT, MR_COUNT };
 static_assert(MR_COUNT <= (int)(sizeof(bs_ctx::mr) / sizeof(DevBuf)), "bs_ctx::mr is too short");
 
-constexpr int SWEEP_CAP = 1024;              // workgroups of a grid-stride pass
 constexpr int FIG_CAP = BS_MRASTER_FIG_CAP;  // labels 0 .. FIG_CAP - 1: figures reduced in LDS (24 KiB in mr_figures_kernel)
 constexpr int CHUNK = BS_MRASTER_CHUNK;      // pixel items of one workgroup
 constexpr int CHUNK_GRID = 1 << 20;          // workgroups of the pixel pass; beyond, a workgroup takes several chunks
 constexpr int FIG_GRID = BS_MRASTER_FIG_GRID;  // workgroups of the figures pass (its LDS tables let six of them share a CU)
-constexpr int32_t Z_LIMIT = 1 << 24;
 constexpr unsigned NO_SLOT = ~0u;
 enum { W_ERR, W_RANGE, W_WORDS = 4 };                                                  // the int words of MR_MISC
 enum { C_UNCOVERED, C_SPILL, C_MOVED, C_MULTI, C_COVER, C_EMPTY, C_MAXSPAN, C_COUNT };  // its 64-bit counters, behind the words
 enum { E_TRI = 1, E_ROW = 2, E_ITEM = 4, E_WIN = 8 };                                   // the bits of W_ERR
 enum { F_PIXELS, F_MODEL, F_KEPT, F_MULTI, F_ERRP, F_SABS, F_MABS, F_SQLO, F_SQHI, F_COUNT };  // the arrays of MR_FIG
-
-inline int sweep(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(nblk(n, 256), SWEEP_CAP)); }
-
-struct In {  // what the triangle count left on the device
-  const int2* xy;
-  const int32_t* z;
-  const int32_t* tri;
-  const long long* toff;  // tri_offset [nl + 1]
-  int32_t nsv, nl, w, h;
-  long long ntri;
-};
-
-// the three clean vertices of slot t, checked; false for a slot of -1 (a failed label's), and with err for any other index
-// outside the vertices
-__device__ inline bool tri_of(const In& A, long long t, int32_t& a, int32_t& b, int32_t& c, int* err)
-{
-  a = A.tri[3 * t];
-  b = A.tri[3 * t + 1];
-  c = A.tri[3 * t + 2];
-  if (a == -1 && b == -1 && c == -1)
-    return false;
-  if ((uint32_t)a >= (uint32_t)A.nsv || (uint32_t)b >= (uint32_t)A.nsv || (uint32_t)c >= (uint32_t)A.nsv) {
-    atomicOr(err, E_TRI);
-    return false;
-  }
-  return true;
-}
-
-// the pixel rows y0 .. y1 - 1 whose centre line crosses the box of the triangle, inside the image
-__device__ inline void rows_of(const In& A, int2 a, int2 b, int2 c, int32_t& y0, int32_t& y1)
-{
-  y0 = max(min(a.y, min(b.y, c.y)), 0);
-  y1 = min(max(a.y, max(b.y, c.y)), A.h);
-}
 
 __device__ inline bool owns(long long w, bool up) { return w > 0 || (w == 0 && up); }
 
@@ -98,47 +63,20 @@ __device__ inline bool weights_of(int2 a, int2 b, int2 c, int32_t x, int32_t y, 
 }
 
 // ---- 1. rows --------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mr_rows_kernel(In A, int32_t* __restrict__ rowcnt, int* __restrict__ words)
+// (the rows of a slot: those whose centre line crosses the box of the triangle)
+__global__ __launch_bounds__(256) void mr_rows_kernel(TriCountDev A, int32_t* __restrict__ rowcnt, int* __restrict__ words)
 {
   for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < A.ntri; t += (long long)gridDim.x * blockDim.x) {
     int32_t a, b, c, cnt = 0;
-    if (tri_of(A, t, a, b, c, words + W_ERR)) {
-      const int32_t za = A.z[a], zb = A.z[b], zc = A.z[c];
-      if (za >= Z_LIMIT || za <= -Z_LIMIT || zb >= Z_LIMIT || zb <= -Z_LIMIT || zc >= Z_LIMIT || zc <= -Z_LIMIT)
+    if (tri_of(A, t, a, b, c, words + W_ERR, E_TRI)) {
+      if (!sz_in_range(A.z[a], A.z[b], A.z[c]))
         atomicOr(words + W_RANGE, 1);
       int32_t y0, y1;
-      rows_of(A, A.xy[a], A.xy[b], A.xy[c], y0, y1);
+      rows_of(A.h, A.xy[a], A.xy[b], A.xy[c], y0, y1);
       cnt = max(y1 - y0, 0);
     }
     rowcnt[t] = cnt;
   }
-}
-
-struct RowCount {  // 0 for the entry behind the last
-  const int32_t* cnt;
-  long long n;
-  __host__ __device__ long long operator()(long long i) const { return i < n ? cnt[i] : 0; }
-};
-struct SpanCount {
-  const int4* rows;
-  long long n;
-  __host__ __device__ long long operator()(long long i) const { return i < n ? rows[i].w : 0; }
-};
-using Idx = hipcub::CountingInputIterator<long long>;
-using RowCountIt = hipcub::TransformInputIterator<long long, RowCount, Idx>;
-using SpanCountIt = hipcub::TransformInputIterator<long long, SpanCount, Idx>;
-
-// the last k in 0 .. n - 1 with scan[k] <= i, searched between lo and hi (scan is an exclusive sum: scan[0] = 0)
-__device__ inline long long last_le(const long long* __restrict__ scan, long long lo, long long hi, long long i)
-{
-  while (lo < hi) {
-    const long long mid = (lo + hi + 1) >> 1;
-    if (scan[mid] <= i)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
 }
 
 // ---- 2. spans -------------------------------------------------------------------------------------------------------------
@@ -163,38 +101,24 @@ __device__ inline void crossing(long long ux, long long uy, long long vx, long l
   last = max(last, q);
 }
 
-__global__ __launch_bounds__(256) void mr_spans_kernel(In A, const long long* __restrict__ rowscan, long long n_rows,
+__global__ __launch_bounds__(256) void mr_spans_kernel(TriCountDev A, const long long* __restrict__ rowscan, long long n_rows,
                                                        int4* __restrict__ rows, int* __restrict__ words,
                                                        unsigned long long* __restrict__ counters)
 {
   unsigned empties = 0;
   int32_t longest = 0;
   for (long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x; r < n_rows; r += (long long)gridDim.x * blockDim.x) {
-    const long long t = last_le(rowscan, 0, A.ntri - 1, r);
-    int32_t a, b, c, x0 = 0, len = 0, y = 0;
-    if (tri_of(A, t, a, b, c, words + W_ERR)) {
-      const int2 pa = A.xy[a], pb = A.xy[b], pc = A.xy[c];
-      int32_t y0, y1;
-      rows_of(A, pa, pb, pc, y0, y1);
-      y = y0 + (int32_t)(r - rowscan[t]);
-      if (y < y0 || y >= y1) {
-        atomicOr(words + W_ERR, E_ROW);
-      } else {
-        const long long yc = 2ll * y + 1;
-        long long xlo = LLONG_MAX, xhi = LLONG_MIN;
-        crossing(2ll * pb.x, 2ll * pb.y, 2ll * pc.x, 2ll * pc.y, yc, xlo, xhi);
-        crossing(2ll * pc.x, 2ll * pc.y, 2ll * pa.x, 2ll * pa.y, yc, xlo, xhi);
-        crossing(2ll * pa.x, 2ll * pa.y, 2ll * pb.x, 2ll * pb.y, yc, xlo, xhi);
-        if (xlo != LLONG_MAX) {  // the pixels xlo .. xhi have their centres between the two crossings
-          const long long f = max(xlo, 0ll), l = min(xhi, (long long)A.w - 1);
-          if (f <= l) {
-            x0 = (int32_t)f;
-            len = (int32_t)(l - f + 1);
-          }
-        }
-      }
-    } else {
-      atomicOr(words + W_ERR, E_ROW);  // (a slot of -1 has no row)
+    long long t;
+    int2 pa, pb, pc;
+    int32_t x0 = 0, len = 0, y = 0;
+    if (row_of(A, rowscan, r, t, pa, pb, pc, y, words + W_ERR, E_TRI, E_ROW)) {
+      const long long yc = 2ll * y + 1;
+      long long xlo = LLONG_MAX, xhi = LLONG_MIN;
+      crossing(2ll * pb.x, 2ll * pb.y, 2ll * pc.x, 2ll * pc.y, yc, xlo, xhi);
+      crossing(2ll * pc.x, 2ll * pc.y, 2ll * pa.x, 2ll * pa.y, yc, xlo, xhi);
+      crossing(2ll * pa.x, 2ll * pa.y, 2ll * pb.x, 2ll * pb.y, yc, xlo, xhi);
+      if (xlo != LLONG_MAX)  // the pixels xlo .. xhi have their centres between the two crossings
+        clip_span(A.w, xlo, xhi, x0, len);
     }
     rows[r] = make_int4((int32_t)t, y, x0, len);
     empties += len == 0;
@@ -213,9 +137,10 @@ __global__ __launch_bounds__(256) void mr_spans_kernel(In A, const long long* __
 }
 
 // ---- 3. pixel items -------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(CHUNK) void mr_pixels_kernel(In A, const long long* __restrict__ spanscan, const int4* __restrict__ rows,
-                                                          long long n_rows, long long n_items, unsigned* __restrict__ win,
-                                                          unsigned* __restrict__ cover, int* __restrict__ err)
+__global__ __launch_bounds__(CHUNK) void mr_pixels_kernel(TriCountDev A, const long long* __restrict__ spanscan,
+                                                          const int4* __restrict__ rows, long long n_rows, long long n_items,
+                                                          unsigned* __restrict__ win, unsigned* __restrict__ cover,
+                                                          int* __restrict__ err)
 {
   __shared__ long long s_row[2];  // the rows of the first and of the last item of the chunk
   const long long n_chunks = (n_items + CHUNK - 1) / CHUNK;
@@ -226,19 +151,13 @@ __global__ __launch_bounds__(CHUNK) void mr_pixels_kernel(In A, const long long*
     __syncthreads();
     const long long i = base + threadIdx.x;
     if (i <= last) {
-      const long long r = last_le(spanscan, s_row[0], s_row[1], i);
-      const int4 rec = rows[r];
-      const long long off = i - spanscan[r];
-      const int32_t y = rec.y;
-      const long long x = rec.z + off;
-      int32_t a, b, c;
-      if (off < 0 || off >= rec.w || (uint32_t)rec.x >= (uint64_t)A.ntri || (uint32_t)y >= (uint32_t)A.h || x < 0 || x >= A.w) {
-        atomicOr(err, E_ITEM);
-      } else if (tri_of(A, rec.x, a, b, c, err)) {
+      int32_t slot, y, a, b, c;
+      long long x;
+      if (item_of(A, spanscan, rows, s_row, i, slot, x, y, err, E_ITEM) && tri_of(A, slot, a, b, c, err, E_TRI)) {
         long long wa, wb, wc;
         if (weights_of(A.xy[a], A.xy[b], A.xy[c], (int32_t)x, y, wa, wb, wc)) {
           const long long p = (long long)y * A.w + x;
-          atomicMin(win + p, (unsigned)rec.x);
+          atomicMin(win + p, (unsigned)slot);
           atomicAdd(cover + p, 1u);
         }
       }
@@ -251,9 +170,6 @@ __global__ __launch_bounds__(CHUNK) void mr_pixels_kernel(In A, const long long*
 struct Fig {  // per label, device
   unsigned long long* f[F_COUNT];
 };
-
-// the label of triangle slot q: the last l with toff[l] <= q
-__device__ inline int32_t label_of_slot(const In& A, long long q) { return (int32_t)last_le(A.toff, 0, A.nl - 1, q); }
 
 struct Tables {  // the figures of the labels below FIG_CAP, in LDS
   unsigned cnt[5][FIG_CAP];  // F_PIXELS .. F_ERRP
@@ -296,10 +212,10 @@ __device__ inline void add_error(Tables& T, const Fig& f, int32_t l, unsigned lo
 }
 
 // win holds the winning slot of every pixel (NO_SLOT: none) and leaves as M
-__global__ __launch_bounds__(256) void mr_figures_kernel(In A, const int32_t* __restrict__ label, const int32_t* __restrict__ top,
-                                                         long long npix, int32_t* win, const unsigned* __restrict__ cover,
-                                                         int32_t* __restrict__ mz2, Fig f, int* __restrict__ words,
-                                                         unsigned long long* __restrict__ counters)
+__global__ __launch_bounds__(256) void mr_figures_kernel(TriCountDev A, const int32_t* __restrict__ label,
+                                                         const int32_t* __restrict__ top, long long npix, int32_t* win,
+                                                         const unsigned* __restrict__ cover, int32_t* __restrict__ mz2, Fig f,
+                                                         int* __restrict__ words, unsigned long long* __restrict__ counters)
 {
   __shared__ Tables T;
   for (int k = threadIdx.x; k < FIG_CAP; k += blockDim.x) {
@@ -324,7 +240,7 @@ __global__ __launch_bounds__(256) void mr_figures_kernel(In A, const int32_t* __
       const unsigned t = (unsigned)win[p];
       int32_t h2 = INT32_MIN, a, b, c;
       if (t != NO_SLOT) {
-        if (t >= (unsigned long long)A.ntri || !tri_of(A, t, a, b, c, words + W_ERR)) {
+        if (t >= (unsigned long long)A.ntri || !tri_of(A, t, a, b, c, words + W_ERR, E_TRI)) {
           atomicOr(words + W_ERR, E_WIN);
         } else {
           const int32_t y = (int32_t)((uint32_t)p / (uint32_t)A.w), x = (int32_t)((uint32_t)p - (uint32_t)y * (uint32_t)A.w);  // (p < 2^29)
@@ -339,7 +255,7 @@ __global__ __launch_bounds__(256) void mr_figures_kernel(In A, const int32_t* __
             if (num - q * den < 0)
               q--;
             h2 = (int32_t)q;
-            M = label_of_slot(A, t);
+            M = label_of_slot(A.toff, A.nl, t);
           }
         }
       }
@@ -448,19 +364,20 @@ int internal(bs_ctx* ctx, int err)
 int raster(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t width, int32_t height, int32_t* d_model,
            int32_t* d_cover, int32_t* d_mz2, struct bs_model_raster& res)
 {
-  if (!ctx->tr_valid || !ctx->uc_valid)
-    return fail(ctx, BS_ERR_INVALID, "model raster: no successful triangle count on this context");
-  if (!ctx->uc_has_z)
-    return fail(ctx, BS_ERR_INVALID, "model raster: the triangle count had no top image");
+  TriCountDev A;
+  int rc = tri_count_dev(ctx, "model raster", A);
+  if (rc != BS_OK)
+    return rc;
   if (!d_label || !d_top)
     return fail(ctx, BS_ERR_INVALID, "model raster: null pointer");
-  if (width != ctx->tr_w || height != ctx->tr_h)
+  if (width != A.w || height != A.h)
     return fail(ctx, BS_ERR_INVALID, "model raster: the image size differs from the triangle count's");
-  const int32_t nl = ctx->tr_nl, nsv = (int32_t)ctx->uc_nsv;
-  const long long ntri = ctx->tr_tri && ctx->tr_toff ? ctx->tr_ntri : 0, npix = (long long)width * height;
-  if (ntri >= INT32_MAX)
-    return fail(ctx, BS_ERR_INVALID, "model raster: 2^31 triangle slots or more");
-  if (ntri > 0 && (!ctx->uc_xy || !ctx->uc_z || nl < 1))
+  const int32_t nl = A.nl;
+  const long long ntri = A.ntri, npix = (long long)width * height;
+  rc = check_slots(ctx, "model raster", A, BS_ERR_INVALID);
+  if (rc != BS_OK)
+    return rc;
+  if (ntri > 0 && (!A.xy || !A.z || nl < 1))
     return internal(ctx, 0x10000);
   res.width = width;
   res.height = height;
@@ -477,7 +394,7 @@ int raster(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t wi
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->mr;
-  Events ev;
+  Events<5> ev;
   for (int i = 0; i < 5; i++)
     BS_HIP(ctx, hipEventCreate(&ev.e[i]));
   const size_t fig_bytes = 8 * (size_t)F_COUNT * std::max<size_t>(nls, 1), misc_bytes = 4 * W_WORDS + 8 * C_COUNT;
@@ -497,7 +414,6 @@ int raster(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t wi
   Fig f;
   for (int j = 0; j < F_COUNT; j++)
     f.f[j] = B[MR_FIG].as<unsigned long long>() + (size_t)j * std::max<size_t>(nls, 1);
-  const In A{ctx->uc_xy, ctx->uc_z, ctx->tr_tri, ctx->tr_toff, nsv, nl, width, height, ntri};
   long long n_rows = 0, n_items = 0;
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
   BS_HIP(ctx, hipMemsetAsync(d_words, 0, misc_bytes, st));
@@ -506,13 +422,8 @@ int raster(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t wi
   BS_HIP(ctx, hipMemsetAsync(cover, 0, 4 * (size_t)npix, st));
   if (ntri > 0) {
     // 1. rows
-    size_t t1 = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t1, RowCountIt(Idx(0), RowCount{nullptr, 0}), (long long*)nullptr, (int)(ntri + 1), st));
-    BS_HIP(ctx, B[MR_TMP].reserve(std::max<size_t>(t1, 256)));
     mr_rows_kernel<<<sweep(ntri), 256, 0, st>>>(A, rowcnt, d_words);
-    size_t tbytes = B[MR_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[MR_TMP].p, tbytes, RowCountIt(Idx(0), RowCount{rowcnt, ntri}), rowscan, (int)(ntri + 1), st));
-    BS_HIP(ctx, hipMemcpyAsync(&n_rows, rowscan + ntri, 8, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, scan_counts(B[MR_TMP], RowCount{rowcnt, ntri}, ntri, rowscan, &n_rows, st));
     BS_HIP(ctx, hipStreamSynchronize(st));  // n_rows
   }
   BS_HIP(ctx, hipEventRecord(ev.e[1], st));
@@ -520,17 +431,12 @@ int raster(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t wi
     return fail(ctx, BS_ERR_INVALID, "model raster: 2^31 row items or more");
   if (n_rows > 0) {
     // 2. spans
-    size_t t2 = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, SpanCountIt(Idx(0), SpanCount{nullptr, 0}), (long long*)nullptr, (int)(n_rows + 1), st));
-    BS_HIP(ctx, B[MR_TMP].reserve(std::max<size_t>(t2, 256)));
     BS_HIP(ctx, B[MR_ROWS].reserve(16 * (size_t)n_rows));
     BS_HIP(ctx, B[MR_SPANSCAN].reserve(8 * ((size_t)n_rows + 1)));
     int4* rows = B[MR_ROWS].as<int4>();
     long long* spanscan = B[MR_SPANSCAN].as<long long>();
     mr_spans_kernel<<<sweep(n_rows), 256, 0, st>>>(A, rowscan, n_rows, rows, d_words, d_counters);
-    size_t tbytes = B[MR_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[MR_TMP].p, tbytes, SpanCountIt(Idx(0), SpanCount{rows, n_rows}), spanscan, (int)(n_rows + 1), st));
-    BS_HIP(ctx, hipMemcpyAsync(&n_items, spanscan + n_rows, 8, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, scan_counts(B[MR_TMP], SpanCount{rows, n_rows}, n_rows, spanscan, &n_items, st));
     BS_HIP(ctx, hipStreamSynchronize(st));  // n_items
     BS_HIP(ctx, hipEventRecord(ev.e[2], st));
     // 3. pixel items
@@ -597,28 +503,7 @@ int raster(bs_ctx* ctx, const int32_t* d_label, const int32_t* d_top, int32_t wi
   return BS_OK;
 }
 
-struct RGuard {  // frees half-built results unless they are handed over
-  struct bs_model_raster* r;
-  struct bs_outline_triangles* t;
-  struct bs_clean_outlines* c;
-  struct bs_simple_outlines* s;
-  struct bs_outlines* plain;
-  bool keep = false;
-  ~RGuard()
-  {
-    if (!keep) {
-      bs_model_raster_free(r);
-      if (t)
-        bs_outline_triangles_free(t);
-      if (c)
-        bs_clean_outlines_free(c);
-      if (s)
-        bs_simple_outlines_free(s);
-      if (plain)
-        bs_outlines_free(plain);
-    }
-  }
-};
+using ResultGuard = FreeUnlessKept<struct bs_model_raster, bs_model_raster_free>;
 
 }  // namespace
 }  // namespace bs
@@ -650,7 +535,7 @@ extern "C" int bs_model_raster_dev(bs_ctx* ctx, const int32_t* d_label, const in
     return fail(ctx, BS_ERR_INVALID, "model raster: null pointer");
   struct bs_model_raster res;
   memset(&res, 0, sizeof res);
-  RGuard guard{&res, nullptr, nullptr, nullptr, nullptr};
+  ResultGuard guard{&res};
   const int rc = raster(ctx, d_label, d_top, width, height, d_model, d_cover, d_mz2, res);
   if (rc != BS_OK)
     return rc;
@@ -668,16 +553,14 @@ extern "C" int bs_model_raster(bs_ctx* ctx, const int32_t* label, const int32_t*
     return BS_ERR_INVALID;
   if (!label || !top || !out)
     return fail(ctx, BS_ERR_INVALID, "model raster: null pointer");
-  struct bs_outline_triangles t;
-  struct bs_clean_outlines cl;
-  struct bs_simple_outlines sm;
-  struct bs_outlines pl;
-  int rc = bs_outline_triangles(ctx, label, top, width, height, n_labels, num, den, cell_log2, &t, &cl, &sm, &pl);
+  Chain ch;
+  int rc = bs_outline_triangles(ctx, label, top, width, height, n_labels, num, den, cell_log2, &ch.tri, &ch.clean, &ch.simple, &ch.plain);
   if (rc != BS_OK)
     return rc;
+  ch.has_tri = ch.has_clean = ch.has_simple = ch.has_plain = true;
   struct bs_model_raster res;
   memset(&res, 0, sizeof res);
-  RGuard guard{&res, &t, &cl, &sm, &pl};
+  ResultGuard guard{&res};
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->mr;
   const size_t npix = (size_t)width * (size_t)height;
@@ -698,22 +581,7 @@ extern "C" int bs_model_raster(bs_ctx* ctx, const int32_t* label, const int32_t*
       BS_HIP(ctx, hipMemcpyAsync(host[k], d_out + (size_t)k * npix, 4 * npix, hipMemcpyDeviceToHost, st));
   BS_HIP(ctx, hipStreamSynchronize(st));
   guard.keep = true;
-  if (tri)
-    *tri = t;
-  else
-    bs_outline_triangles_free(&t);
-  if (clean)
-    *clean = cl;
-  else
-    bs_clean_outlines_free(&cl);
-  if (simple)
-    *simple = sm;
-  else
-    bs_simple_outlines_free(&sm);
-  if (plain)
-    *plain = pl;
-  else
-    bs_outlines_free(&pl);
+  ch.hand_over(tri, clean, simple, plain);
   *out = res;
   return BS_OK;
 }

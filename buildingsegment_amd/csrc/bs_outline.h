@@ -1,12 +1,13 @@
 // bs_outline.h -- what the facet outlines (bs_outline.hip) and the simplified outlines built on them (bs_simplify.hip)
-// share: the names of the scratch buffers of bs_ctx::ol, the cut and the Wyllie round of the ranking, the layout of the
-// per-ring arrays on the device, and small host helpers.  Everything is internal to a translation unit.
+// share: the names of the scratch buffers of bs_ctx::ol, the cut and the Wyllie round of the ranking, and the layout of the
+// per-ring arrays on the device.  (The host helpers of every stage are bs_host.h's.)  Everything is internal to a
+// translation unit.
 #pragma once
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "bs_common.h"
+#include "bs_host.h"
 
 namespace bs {
 namespace {
@@ -19,7 +20,6 @@ enum { OL_FLAGS, OL_BASE, OL_TMP, OL_MISC, OL_HNUM, OL_SUCC, OL_VERT, OL_MN0, OL
        OL_OUT_Z, OL_COUNT };
 static_assert(OL_COUNT <= (int)(sizeof(bs_ctx::ol) / sizeof(DevBuf)), "bs_ctx::ol is too short");
 
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 inline int grid_of(int64_t n) { return (int)std::min<int64_t>(nblk(n, 256), GRID_CAP); }
 
 // ---- rank ----------------------------------------------------------------------------------------------------------------
@@ -83,39 +83,6 @@ inline RingOut ring_out_at(void* p, size_t n)
   r.of_slot = r.vertices + n;
   r.offset = r.of_slot + n;
   return r;
-}
-
-struct Events {
-  hipEvent_t e[10] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  double ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.0;
-  }
-};
-
-template <class T>
-bool alloc(T** p, size_t n)
-{
-  *p = (T*)calloc(std::max<size_t>(n, 1), sizeof(T));
-  return *p != nullptr;
-}
-
-// (a half-edge is numbered 4 * pixel + side in 31 bits)
-inline bool bad_image(int32_t w, int32_t h) { return w < 1 || h < 1 || (int64_t)w * h >= (1ll << 29); }
-
-inline int bits_of(int64_t n)  // bits that hold 0 .. n - 1 (at least 1)
-{
-  int b = 1;
-  while (b < 32 && (1ll << b) < n)
-    b++;
-  return b;
 }
 
 inline int rounds_of(int64_t n)  // the smallest R with 2^R >= n

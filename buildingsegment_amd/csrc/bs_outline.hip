@@ -22,7 +22,9 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "bs_chain.h"  // (bad_image)
 #include "bs_common.h"
+#include "bs_host.h"
 #include "bs_outline.h"
 #include "bs_segscan.h"
 
@@ -352,15 +354,7 @@ __global__ __launch_bounds__(256) void outline_emit_kernel(const int32_t* __rest
     z[d] = zv[i];
 }
 
-struct Guard {  // frees a half-built result unless it is handed over
-  struct bs_outlines* s;
-  bool keep = false;
-  ~Guard()
-  {
-    if (!keep)
-      bs_outlines_free(s);
-  }
-};
+using Guard = FreeUnlessKept<struct bs_outlines, bs_outlines_free>;
 
 const char* const OUTLINES_INVALID = "facet outlines: null pointer, width or height < 1, width * height >= 2^29, n_labels < 0, "
                                      "or d_top not 16-byte aligned";
@@ -407,7 +401,7 @@ extern "C" int bs_facet_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   const int w = width, h = height;
   const int64_t npix = (int64_t)w * h;
   DevBuf* B = ctx->ol;
-  Events ev;
+  Events<10> ev;
   for (auto& e : ev.e)
     BS_HIP(ctx, hipEventCreate(&e));
   hipcub::CountingInputIterator<int32_t> idx(0);
@@ -618,7 +612,7 @@ extern "C" int bs_facet_outlines_emit_dev(bs_ctx* ctx, int32_t* d_xy, int32_t* d
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->ol;
-  Events ev;
+  Events<2> ev;
   BS_HIP(ctx, hipEventCreate(&ev.e[0]));
   BS_HIP(ctx, hipEventCreate(&ev.e[1]));
   const int32_t n = (int32_t)ctx->ol_nhalf;

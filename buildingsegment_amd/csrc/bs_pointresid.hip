@@ -14,6 +14,8 @@
 //             wave at a time in registers, then through LDS tables below FIG_CAP and by global atomics above
 // No work item's time grows with a triangle's box or area.  Every index read from memory is checked before it is used as an
 // address; a violation sets err and the call returns BS_ERR_INTERNAL.
+// The walk from slots to rows to spans to entries is bs_trispan.h's, shared with bs_modelraster.hip; what a span is
+// (band_vertex and band_crossing, below) is this file's.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -23,7 +25,10 @@
 #include <cstring>
 #include <vector>
 
+#include "bs_chain.h"
 #include "bs_common.h"
+#include "bs_host.h"
+#include "bs_trispan.h"
 
 namespace bs {
 namespace {
@@ -33,12 +38,10 @@ enum { PR_MISC, PR_TMP, PR_ROWCNT, PR_ROWSCAN, PR_ROWS, PR_SPANSCAN, PR_REC, PR_
        PR_IN_PLANE, PR_OUT, PR_COUNT };
 static_assert(PR_COUNT <= (int)(sizeof(bs_ctx::pr) / sizeof(DevBuf)), "bs_ctx::pr is too short");
 
-constexpr int SWEEP_CAP = 1024;             // workgroups of a grid-stride pass over slots, row items or the cloud's check
 constexpr int FIG_CAP = BS_PRESID_FIG_CAP;  // labels 0 .. FIG_CAP - 1: figures reduced in LDS (16 KiB in pr_points_kernel)
 constexpr int CHUNK = BS_PRESID_CHUNK;      // list entries of one workgroup
 constexpr int CHUNK_GRID = 1 << 20;         // workgroups of the list passes; beyond, a workgroup takes several chunks
 constexpr int GRID = BS_PRESID_GRID;        // workgroups of the pass over the points: eight of them share a CU
-constexpr int32_t Z_LIMIT = 1 << 24;
 constexpr long long EXTENT_LIMIT = 1ll << 24;
 constexpr unsigned NO_SLOT = ~0u;
 enum { W_ERR, W_RANGE, W_WORDS = 4 };                                          // the int words of PR_MISC
@@ -49,92 +52,24 @@ enum { R_SZ = 1, R_XY = 2, R_Z = 4 };                                          /
 enum { F_POINTS, F_MULTI, F_ABOVE, F_BELOW, F_IN, F_PPOINTS, F_PIN, F_SR, F_SABS, F_MABS, F_SQLO, F_SQHI, F_COUNT };
 constexpr int N_CNT = F_PIN + 1;
 
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
-inline int sweep(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(nblk(n, 256), SWEEP_CAP)); }
-
-struct Events {
-  hipEvent_t e[5] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  double ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.0;
-  }
-};
-
-template <class T>
-bool alloc(T** p, size_t n)
-{
-  *p = (T*)calloc(std::max<size_t>(n, 1), sizeof(T));
-  return *p != nullptr;
-}
-
-struct In {  // what the triangle count left on the device
-  const int2* xy;
-  const int32_t* z;
-  const int32_t* tri;
-  const long long* toff;  // tri_offset [nl + 1]
-  int32_t nsv, nl, w, h;
-  long long ntri;
-};
-
-// the three clean vertices of slot t, checked; false for a slot of -1 (a failed label's), and with err for any other index
-// outside the vertices
-__device__ inline bool tri_of(const In& A, long long t, int32_t& a, int32_t& b, int32_t& c, int* err)
-{
-  a = A.tri[3 * t];
-  b = A.tri[3 * t + 1];
-  c = A.tri[3 * t + 2];
-  if (a == -1 && b == -1 && c == -1)
-    return false;
-  if ((uint32_t)a >= (uint32_t)A.nsv || (uint32_t)b >= (uint32_t)A.nsv || (uint32_t)c >= (uint32_t)A.nsv) {
-    atomicOr(err, E_TRI);
-    return false;
-  }
-  return true;
-}
-
-// the pixel rows y0 .. y1 - 1 that the triangle touches, inside the image
-__device__ inline void rows_of(int32_t h, int2 a, int2 b, int2 c, int32_t& y0, int32_t& y1)
-{
-  y0 = max(min(a.y, min(b.y, c.y)), 0);
-  y1 = min(max(a.y, max(b.y, c.y)), h);
-}
-
-// the last k in 0 .. n - 1 with scan[k] <= i, searched between lo and hi (scan is an exclusive sum: scan[0] = 0)
-__device__ inline long long last_le(const long long* __restrict__ scan, long long lo, long long hi, long long i)
-{
-  while (lo < hi) {
-    const long long mid = (lo + hi + 1) >> 1;
-    if (scan[mid] <= i)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
-}
-
 // ---- 1. rows, records, and the check of the cloud ---------------------------------------------------------------------------
+// (the rows of a slot: those that the triangle touches)
 // record t: {a.x, a.y, b.x, b.y}, {c.x, c.y, sz[a], sz[b]}, {sz[c], label, valid, 0}
-__global__ __launch_bounds__(256) void pr_rows_kernel(In A, int32_t* __restrict__ rowcnt, int4* __restrict__ rec, int* __restrict__ words)
+__global__ __launch_bounds__(256) void pr_rows_kernel(TriCountDev A, int32_t* __restrict__ rowcnt, int4* __restrict__ rec,
+                                                      int* __restrict__ words)
 {
   for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < A.ntri; t += (long long)gridDim.x * blockDim.x) {
     int32_t a, b, c, cnt = 0;
     int4 r0 = make_int4(0, 0, 0, 0), r1 = r0, r2 = r0;
-    if (tri_of(A, t, a, b, c, words + W_ERR)) {
+    if (tri_of(A, t, a, b, c, words + W_ERR, E_TRI)) {
       const int32_t za = A.z[a], zb = A.z[b], zc = A.z[c];
-      if (za >= Z_LIMIT || za <= -Z_LIMIT || zb >= Z_LIMIT || zb <= -Z_LIMIT || zc >= Z_LIMIT || zc <= -Z_LIMIT)
+      if (!sz_in_range(za, zb, zc))
         atomicOr(words + W_RANGE, R_SZ);
       const int2 pa = A.xy[a], pb = A.xy[b], pc = A.xy[c];
       int32_t y0, y1;
       rows_of(A.h, pa, pb, pc, y0, y1);
       cnt = max(y1 - y0, 0);
-      const int32_t l = (int32_t)last_le(A.toff, 0, A.nl - 1, t);
+      const int32_t l = label_of_slot(A.toff, A.nl, t);
       r0 = make_int4(pa.x, pa.y, pb.x, pb.y);
       r1 = make_int4(pc.x, pc.y, za, zb);
       r2 = make_int4(zc, l, 1, 0);
@@ -163,25 +98,12 @@ __global__ __launch_bounds__(256) void pr_check_kernel(const int32_t* __restrict
     atomicOr(words + W_RANGE, bad);
 }
 
-struct RowCount {  // 0 for the entry behind the last
-  const int32_t* cnt;
-  long long n;
-  __host__ __device__ long long operator()(long long i) const { return i < n ? cnt[i] : 0; }
-};
-struct SpanCount {
-  const int4* rows;
-  long long n;
-  __host__ __device__ long long operator()(long long i) const { return i < n ? rows[i].w : 0; }
-};
-struct PixCount {
+struct PixCount {  // 0 for the entry behind the last
   const unsigned* cnt;
   long long n;
   __host__ __device__ unsigned operator()(long long i) const { return i < n ? cnt[i] : 0u; }
 };
-using Idx = hipcub::CountingInputIterator<long long>;
-using RowCountIt = hipcub::TransformInputIterator<long long, RowCount, Idx>;
-using SpanCountIt = hipcub::TransformInputIterator<long long, SpanCount, Idx>;
-using PixCountIt = hipcub::TransformInputIterator<unsigned, PixCount, Idx>;
+using PixCountIt = hipcub::TransformInputIterator<unsigned, PixCount, Idx64>;
 
 // ---- 2. spans -------------------------------------------------------------------------------------------------------------
 // the crossing of the edge u -> v with the lattice line Y = k where that lies strictly between its ends, at
@@ -211,39 +133,26 @@ __device__ inline void band_vertex(int2 u, int32_t y, long long& lo, long long& 
   }
 }
 
-__global__ __launch_bounds__(256) void pr_spans_kernel(In A, const long long* __restrict__ rowscan, long long n_rows,
+__global__ __launch_bounds__(256) void pr_spans_kernel(TriCountDev A, const long long* __restrict__ rowscan, long long n_rows,
                                                        int4* __restrict__ rows, int* __restrict__ words)
 {
   for (long long r = blockIdx.x * (long long)blockDim.x + threadIdx.x; r < n_rows; r += (long long)gridDim.x * blockDim.x) {
-    const long long t = last_le(rowscan, 0, A.ntri - 1, r);
-    int32_t a, b, c, x0 = 0, len = 0, y = 0;
-    if (tri_of(A, t, a, b, c, words + W_ERR)) {
-      const int2 pa = A.xy[a], pb = A.xy[b], pc = A.xy[c];
-      int32_t y0, y1;
-      rows_of(A.h, pa, pb, pc, y0, y1);
-      y = y0 + (int32_t)(r - rowscan[t]);
-      if (y < y0 || y >= y1) {
-        atomicOr(words + W_ERR, E_ROW);
-      } else {  // the band y <= Y <= y + 1: its vertices and the crossings of its two lines
-        long long lo = LLONG_MAX, hi = LLONG_MIN;
-        band_vertex(pa, y, lo, hi);
-        band_vertex(pb, y, lo, hi);
-        band_vertex(pc, y, lo, hi);
-        for (int32_t k = y; k <= y + 1; k++) {
-          band_crossing(pb, pc, k, lo, hi);
-          band_crossing(pc, pa, k, lo, hi);
-          band_crossing(pa, pb, k, lo, hi);
-        }
-        if (lo != LLONG_MAX) {  // the columns floor(xmin) .. ceil(xmax) - 1
-          const long long f = max(lo, 0ll), l = min(hi - 1, (long long)A.w - 1);
-          if (f <= l) {
-            x0 = (int32_t)f;
-            len = (int32_t)(l - f + 1);
-          }
-        }
+    long long t;
+    int2 pa, pb, pc;
+    int32_t x0 = 0, len = 0, y = 0;
+    if (row_of(A, rowscan, r, t, pa, pb, pc, y, words + W_ERR, E_TRI, E_ROW)) {
+      // the band y <= Y <= y + 1: its vertices and the crossings of its two lines
+      long long lo = LLONG_MAX, hi = LLONG_MIN;
+      band_vertex(pa, y, lo, hi);
+      band_vertex(pb, y, lo, hi);
+      band_vertex(pc, y, lo, hi);
+      for (int32_t k = y; k <= y + 1; k++) {
+        band_crossing(pb, pc, k, lo, hi);
+        band_crossing(pc, pa, k, lo, hi);
+        band_crossing(pa, pb, k, lo, hi);
       }
-    } else {
-      atomicOr(words + W_ERR, E_ROW);  // (a slot of -1 has no row)
+      if (lo != LLONG_MAX)  // the columns floor(xmin) .. ceil(xmax) - 1
+        clip_span(A.w, lo, hi - 1, x0, len);
     }
     rows[r] = make_int4((int32_t)t, y, x0, len);
   }
@@ -253,10 +162,11 @@ __global__ __launch_bounds__(256) void pr_spans_kernel(In A, const long long* __
 // FILL false: cnt[p] += 1 for the pixel of every entry.  FILL true: cnt is the cursor (zeroed again), off the exclusive sum:
 // the slot goes to list[off[p] + cursor++]
 template <bool FILL>
-__global__ __launch_bounds__(CHUNK) void pr_lists_kernel(In A, const long long* __restrict__ spanscan, const int4* __restrict__ rows,
-                                                         long long n_rows, long long n_items, unsigned* __restrict__ cnt,
-                                                         const unsigned* __restrict__ off, unsigned* __restrict__ list,
-                                                         int* __restrict__ err, unsigned long long* __restrict__ counters)
+__global__ __launch_bounds__(CHUNK) void pr_lists_kernel(TriCountDev A, const long long* __restrict__ spanscan,
+                                                         const int4* __restrict__ rows, long long n_rows, long long n_items,
+                                                         unsigned* __restrict__ cnt, const unsigned* __restrict__ off,
+                                                         unsigned* __restrict__ list, int* __restrict__ err,
+                                                         unsigned long long* __restrict__ counters)
 {
   __shared__ long long s_row[2];  // the rows of the first and of the last entry of the chunk
   const long long n_chunks = (n_items + CHUNK - 1) / CHUNK;
@@ -268,14 +178,9 @@ __global__ __launch_bounds__(CHUNK) void pr_lists_kernel(In A, const long long* 
     __syncthreads();
     const long long i = base + threadIdx.x;
     if (i <= last) {
-      const long long r = last_le(spanscan, s_row[0], s_row[1], i);
-      const int4 rec = rows[r];
-      const long long o = i - spanscan[r];
-      const int32_t y = rec.y;
-      const long long x = rec.z + o;
-      if (o < 0 || o >= rec.w || (uint32_t)rec.x >= (uint64_t)A.ntri || (uint32_t)y >= (uint32_t)A.h || x < 0 || x >= A.w) {
-        atomicOr(err, E_ITEM);
-      } else {
+      int32_t slot, y;
+      long long x;
+      if (item_of(A, spanscan, rows, s_row, i, slot, x, y, err, E_ITEM)) {
         const long long p = (long long)y * A.w + x;
         if (!FILL) {
           atomicAdd(cnt + p, 1u);
@@ -285,7 +190,7 @@ __global__ __launch_bounds__(CHUNK) void pr_lists_kernel(In A, const long long* 
           if (at >= off[p + 1] || at >= (unsigned long long)n_items)
             atomicOr(err, E_LIST);
           else
-            list[at] = (unsigned)rec.x;
+            list[at] = (unsigned)slot;
           longest = max(longest, k + 1);
         }
       }
@@ -571,23 +476,24 @@ int range_error(bs_ctx* ctx, int bits)
 int residuals(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const int32_t* d_plane_idx, const int32_t* label_plane,
               int32_t clip2, int32_t* d_label_out, int32_t* d_r2, int32_t* d_cover, struct bs_point_residuals& res)
 {
-  if (!ctx->tr_valid || !ctx->uc_valid)
-    return fail(ctx, BS_ERR_INVALID, "point residuals: no successful triangle count on this context");
-  if (!ctx->uc_has_z)
-    return fail(ctx, BS_ERR_INVALID, "point residuals: the triangle count had no top image");
+  TriCountDev A;
+  int rc = tri_count_dev(ctx, "point residuals", A);
+  if (rc != BS_OK)
+    return rc;
   if (!d_xyz || n < 1 || bin < 1 || clip2 < 0)
     return fail(ctx, BS_ERR_INVALID, "point residuals: a null cloud, n < 1, bin < 1 or clip2 < 0");
   if ((d_plane_idx == nullptr) != (label_plane == nullptr))
     return fail(ctx, BS_ERR_INVALID, "point residuals: plane_idx and label_plane come together or not at all");
   if (n >= (1ll << 29))
     return fail(ctx, BS_ERR_RANGE, "point residuals: 2^29 points or more");
-  const int32_t width = ctx->tr_w, height = ctx->tr_h, nl = ctx->tr_nl, nsv = (int32_t)ctx->uc_nsv;
+  const int32_t width = A.w, height = A.h, nl = A.nl;
   if ((long long)width * bin > EXTENT_LIMIT || (long long)height * bin > EXTENT_LIMIT)
     return fail(ctx, BS_ERR_RANGE, "point residuals: an extent (width or height times bin) above 2^24");
-  const long long ntri = ctx->tr_tri && ctx->tr_toff ? ctx->tr_ntri : 0, npix = (long long)width * height;
-  if (ntri >= INT32_MAX)
-    return fail(ctx, BS_ERR_RANGE, "point residuals: 2^31 triangle slots or more");
-  if (width < 1 || height < 1 || npix >= INT32_MAX || (ntri > 0 && (!ctx->uc_xy || !ctx->uc_z || nl < 1)))
+  const long long ntri = A.ntri, npix = (long long)width * height;
+  rc = check_slots(ctx, "point residuals", A, BS_ERR_RANGE);
+  if (rc != BS_OK)
+    return rc;
+  if (width < 1 || height < 1 || npix >= INT32_MAX || (ntri > 0 && (!A.xy || !A.z || nl < 1)))
     return internal(ctx, 0x10000);
   res.width = width;
   res.height = height;
@@ -608,7 +514,7 @@ int residuals(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const i
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->pr;
-  Events ev;
+  Events<5> ev;
   for (int i = 0; i < 5; i++)
     BS_HIP(ctx, hipEventCreate(&ev.e[i]));
   const size_t fig_bytes = 8 * (size_t)F_COUNT * nl1, misc_bytes = 4 * W_WORDS + 8 * C_COUNT;
@@ -629,7 +535,6 @@ int residuals(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const i
   int4* rec = B[PR_REC].as<int4>();
   int32_t* d_label_plane = B[PR_PLANE].as<int32_t>();
   const Fig f{B[PR_FIG].as<unsigned long long>(), (long long)nl1};
-  const In A{ctx->uc_xy, ctx->uc_z, ctx->tr_tri, ctx->tr_toff, nsv, nl, width, height, ntri};
   long long n_rows = 0, n_items = 0;
   int h_words[W_WORDS] = {};
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
@@ -641,13 +546,8 @@ int residuals(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const i
   pr_check_kernel<<<sweep(n), 256, 0, st>>>(d_xyz, n, bin, width, height, d_words);
   if (ntri > 0) {
     // 1. rows
-    size_t t1 = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t1, RowCountIt(Idx(0), RowCount{nullptr, 0}), (long long*)nullptr, (int)(ntri + 1), st));
-    BS_HIP(ctx, B[PR_TMP].reserve(std::max<size_t>(t1, 256)));
     pr_rows_kernel<<<sweep(ntri), 256, 0, st>>>(A, rowcnt, rec, d_words);
-    size_t tbytes = B[PR_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[PR_TMP].p, tbytes, RowCountIt(Idx(0), RowCount{rowcnt, ntri}), rowscan, (int)(ntri + 1), st));
-    BS_HIP(ctx, hipMemcpyAsync(&n_rows, rowscan + ntri, 8, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, scan_counts(B[PR_TMP], RowCount{rowcnt, ntri}, ntri, rowscan, &n_rows, st));
   }
   BS_HIP(ctx, hipMemcpyAsync(h_words, d_words, 4 * W_WORDS, hipMemcpyDeviceToHost, st));
   BS_HIP(ctx, hipStreamSynchronize(st));  // n_rows, and the ranges of the cloud and of sz
@@ -663,16 +563,10 @@ int residuals(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const i
   const long long* spanscan = nullptr;
   if (n_rows > 0) {
     // 2. spans
-    size_t t2 = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, SpanCountIt(Idx(0), SpanCount{nullptr, 0}), (long long*)nullptr, (int)(n_rows + 1), st));
-    BS_HIP(ctx, B[PR_TMP].reserve(std::max<size_t>(t2, 256)));
     BS_HIP(ctx, B[PR_ROWS].reserve(16 * (size_t)n_rows));
     BS_HIP(ctx, B[PR_SPANSCAN].reserve(8 * ((size_t)n_rows + 1)));
     pr_spans_kernel<<<sweep(n_rows), 256, 0, st>>>(A, rowscan, n_rows, B[PR_ROWS].as<int4>(), d_words);
-    size_t tbytes = B[PR_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[PR_TMP].p, tbytes, SpanCountIt(Idx(0), SpanCount{B[PR_ROWS].as<int4>(), n_rows}),
-                                                 B[PR_SPANSCAN].as<long long>(), (int)(n_rows + 1), st));
-    BS_HIP(ctx, hipMemcpyAsync(&n_items, B[PR_SPANSCAN].as<long long>() + n_rows, 8, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, scan_counts(B[PR_TMP], SpanCount{B[PR_ROWS].as<int4>(), n_rows}, n_rows, B[PR_SPANSCAN].as<long long>(), &n_items, st));
     BS_HIP(ctx, hipStreamSynchronize(st));  // n_items
     rows = B[PR_ROWS].as<int4>();
     spanscan = B[PR_SPANSCAN].as<long long>();
@@ -689,10 +583,10 @@ int residuals(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const i
     pr_lists_kernel<false><<<chunk_grid, CHUNK, 0, st>>>(A, spanscan, rows, n_rows, n_items, cnt, off, list, d_words + W_ERR, d_counters);
   {
     size_t t3 = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t3, PixCountIt(Idx(0), PixCount{nullptr, 0}), (unsigned*)nullptr, (int)(npix + 1), st));
+    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t3, PixCountIt(Idx64(0), PixCount{nullptr, 0}), (unsigned*)nullptr, (int)(npix + 1), st));
     BS_HIP(ctx, B[PR_TMP].reserve(std::max<size_t>(t3, 256)));
     size_t tbytes = B[PR_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[PR_TMP].p, tbytes, PixCountIt(Idx(0), PixCount{cnt, npix}), off, (int)(npix + 1), st));
+    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[PR_TMP].p, tbytes, PixCountIt(Idx64(0), PixCount{cnt, npix}), off, (int)(npix + 1), st));
   }
   if (n_items > 0) {
     BS_HIP(ctx, hipMemsetAsync(cnt, 0, 4 * (size_t)npix, st));
@@ -748,28 +642,7 @@ int residuals(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const i
   return BS_OK;
 }
 
-struct RGuard {  // frees half-built results unless they are handed over
-  struct bs_point_residuals* r;
-  struct bs_outline_triangles* t;
-  struct bs_clean_outlines* c;
-  struct bs_simple_outlines* s;
-  struct bs_outlines* plain;
-  bool keep = false;
-  ~RGuard()
-  {
-    if (!keep) {
-      bs_point_residuals_free(r);
-      if (t)
-        bs_outline_triangles_free(t);
-      if (c)
-        bs_clean_outlines_free(c);
-      if (s)
-        bs_simple_outlines_free(s);
-      if (plain)
-        bs_outlines_free(plain);
-    }
-  }
-};
+using ResultGuard = FreeUnlessKept<struct bs_point_residuals, bs_point_residuals_free>;
 
 }  // namespace
 }  // namespace bs
@@ -805,7 +678,7 @@ extern "C" int bs_point_residuals_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t
     return fail(ctx, BS_ERR_INVALID, "point residuals: null pointer");
   struct bs_point_residuals res;
   memset(&res, 0, sizeof res);
-  RGuard guard{&res, nullptr, nullptr, nullptr, nullptr};
+  ResultGuard guard{&res};
   const int rc = residuals(ctx, d_xyz, n, bin, d_plane_idx, label_plane, clip2, d_label_out, d_r2, d_cover, res);
   if (rc != BS_OK)
     return rc;
@@ -829,16 +702,14 @@ extern "C" int bs_point_residuals(bs_ctx* ctx, const int32_t* label, const int32
     return fail(ctx, BS_ERR_INVALID, "point residuals: a null cloud, n < 1, bin < 1 or clip2 < 0");
   if (n >= (1ll << 29))
     return fail(ctx, BS_ERR_RANGE, "point residuals: 2^29 points or more");
-  struct bs_outline_triangles t;
-  struct bs_clean_outlines cl;
-  struct bs_simple_outlines sm;
-  struct bs_outlines pl;
-  int rc = bs_outline_triangles(ctx, label, top, width, height, n_labels, num, den, cell_log2, &t, &cl, &sm, &pl);
+  Chain ch;
+  int rc = bs_outline_triangles(ctx, label, top, width, height, n_labels, num, den, cell_log2, &ch.tri, &ch.clean, &ch.simple, &ch.plain);
   if (rc != BS_OK)
     return rc;
+  ch.has_tri = ch.has_clean = ch.has_simple = ch.has_plain = true;
   struct bs_point_residuals res;
   memset(&res, 0, sizeof res);
-  RGuard guard{&res, &t, &cl, &sm, &pl};
+  ResultGuard guard{&res};
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->pr;
   const size_t np = (size_t)n;
@@ -861,22 +732,7 @@ extern "C" int bs_point_residuals(bs_ctx* ctx, const int32_t* label, const int32
       BS_HIP(ctx, hipMemcpyAsync(host[k], d_out + (size_t)k * np, 4 * np, hipMemcpyDeviceToHost, st));
   BS_HIP(ctx, hipStreamSynchronize(st));
   guard.keep = true;
-  if (tri)
-    *tri = t;
-  else
-    bs_outline_triangles_free(&t);
-  if (clean)
-    *clean = cl;
-  else
-    bs_clean_outlines_free(&cl);
-  if (simple)
-    *simple = sm;
-  else
-    bs_simple_outlines_free(&sm);
-  if (plain)
-    *plain = pl;
-  else
-    bs_outlines_free(&pl);
+  ch.hand_over(tri, clean, simple, plain);
   *out = res;
   return BS_OK;
 }

@@ -15,6 +15,9 @@
 // The per-building figures are reduced as bs_solid.hip reduces its own: a wave inside one building in registers, buildings
 // below FIG_CAP through LDS tables, the rest by global atomics.  Every index read from memory is checked before it is used
 // as an address; a violation sets err and the call returns BS_ERR_INTERNAL.
+// The label of a triangle slot (last_le, label_of_slot) is bs_trispan.h's, shared with the model raster and the point
+// residuals; tri_of is this file's own, since a slot of a contributing label is never -1.  The entry points own the results
+// of the stages before through bs_chain.h's Chain and hand them over at their end; an early return frees them.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -24,11 +27,10 @@
 #include <cstring>
 #include <vector>
 
+#include "bs_chain.h"
 #include "bs_common.h"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (the ranking kernels of bs_outline.h are not launched here)
-#include "bs_outline.h"
-#pragma clang diagnostic pop
+#include "bs_host.h"
+#include "bs_trispan.h"  // (last_le, label_of_slot, Z_LIMIT)
 
 namespace bs {
 namespace {
@@ -39,14 +41,10 @@ enum { PS_MISC, PS_TMP, PS_LC, PS_LV0, PS_TB2, PS_TOFF, PS_RLABEL, PS_TK0, PS_TK
        PS_COUNT };
 static_assert(PS_COUNT <= (int)(sizeof(bs_ctx::ps) / sizeof(DevBuf)), "bs_ctx::ps is too short");
 
-constexpr int SWEEP_CAP = 1024;  // workgroups of a grid-stride pass
 constexpr int FIG_CAP = BS_POLY_FIG_CAP;  // buildings 0 .. FIG_CAP - 1: figures reduced in LDS (20 KiB in ps_wall_kernel)
 constexpr unsigned long long NONE = ~0ull;
-constexpr int32_t Z_LIMIT = 1 << 24;
 enum { W_ERR, W_RANGE, W_COUNT };                                               // the words of PS_MISC
 enum { E_RING = 1, E_LABEL = 2, E_TWIN = 4, E_VNUM = 8, E_TRI = 16, E_EMIT = 32 };  // the bits of W_ERR
-
-inline int sweep(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(nblk(n, 256), SWEEP_CAP)); }
 
 struct In {  // what the stages before left on the device, and the per-label words of the host
   const int2* xy;
@@ -380,21 +378,7 @@ __global__ __launch_bounds__(256) void ps_wall_kernel(In A, const int32_t* __res
       fig_walls(f, k, s_walls[k], s_cross[k], s_mw[k], s_mn[k], s_mx[k]);
 }
 
-// the label of triangle slot q: the last l with toff[l] <= q
-__device__ inline int32_t label_of_slot(const In& A, long long q)
-{
-  int32_t lo = 0, hi = A.nl - 1;
-  while (lo < hi) {
-    const int32_t mid = (int32_t)(((long long)lo + hi + 1) >> 1);
-    if (A.toff[mid] <= q)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
-}
-
-// the three clean vertices of slot q of a contributing label, checked
+// the three clean vertices of slot q of a contributing label (so never a slot of -1, unlike bs_trispan.h's), checked
 __device__ inline bool tri_of(const In& A, long long q, int32_t& a, int32_t& b, int32_t& d, int* err)
 {
   a = A.tri[3 * q];
@@ -418,7 +402,7 @@ __global__ __launch_bounds__(256) void ps_tri_kernel(In A, int32_t nb, Fig f, in
     int32_t c = -1;
     unsigned long long area = 0, vol = 0;
     if (q < A.ntri) {
-      const int32_t l = label_of_slot(A, q);
+      const int32_t l = label_of_slot(A.toff, A.nl, q);
       int32_t a, b, d;
       c = A.lc[l];
       if (c >= nb) {
@@ -511,7 +495,7 @@ __global__ __launch_bounds__(256) void ps_emit_tri_kernel(In A, const int32_t* _
   if (blockIdx.x == 0 && threadIdx.x == 0)
     o.offset[o.nf] = (int32_t)o.ni;
   for (long long q = blockIdx.x * (long long)blockDim.x + threadIdx.x; q < A.ntri; q += (long long)gridDim.x * blockDim.x) {
-    const int32_t l = label_of_slot(A, q), c = A.lc[l];
+    const int32_t l = label_of_slot(A.toff, A.nl, q), c = A.lc[l];
     int32_t a, b, d;
     if (c < 0 || !tri_of(A, q, a, b, d, err))
       continue;
@@ -572,24 +556,7 @@ __global__ __launch_bounds__(256) void ps_emit_wall_kernel(In A, const int32_t* 
   }
 }
 
-struct PGuard {  // frees half-built results unless they are handed over
-  struct bs_poly_solids* p;
-  struct bs_outline_triangles* t;
-  struct bs_clean_outlines* c;
-  struct bs_simple_outlines* s;
-  struct bs_outlines* plain;
-  bool keep = false;
-  ~PGuard()
-  {
-    if (!keep) {
-      bs_poly_solids_free(p);
-      bs_outline_triangles_free(t);
-      bs_clean_outlines_free(c);
-      bs_simple_outlines_free(s);
-      bs_outlines_free(plain);
-    }
-  }
-};
+using ResultGuard = FreeUnlessKept<struct bs_poly_solids, bs_poly_solids_free>;
 
 int internal(bs_ctx* ctx, int err)
 {
@@ -678,7 +645,7 @@ int poly_solids(bs_ctx* ctx, const struct bs_outline_triangles& t, const struct 
   if (!ctx->uc_xy || !ctx->uc_z || !ctx->uc_right || !ctx->uc_ring || !ctx->uc_soff || (ntri > 0 && !ctx->tr_tri))
     return internal(ctx, 0x10000);
   // ---- device ----
-  Events ev;
+  Events<4> ev;
   for (int i = 0; i < 4; i++)
     BS_HIP(ctx, hipEventCreate(&ev.e[i]));
   size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
@@ -832,28 +799,6 @@ int check_args(bs_ctx* ctx, const void* label, const void* top, const void* lb, 
   return building_bases(ctx, nb, "polygon solids", &d_bases);
 }
 
-void hand_over(struct bs_outline_triangles* tri, struct bs_clean_outlines* clean, struct bs_simple_outlines* simple,
-               struct bs_outlines* plain, struct bs_outline_triangles& t, struct bs_clean_outlines& c, struct bs_simple_outlines& s,
-               struct bs_outlines& p)
-{
-  if (tri)
-    *tri = t;
-  else
-    bs_outline_triangles_free(&t);
-  if (clean)
-    *clean = c;
-  else
-    bs_clean_outlines_free(&c);
-  if (simple)
-    *simple = s;
-  else
-    bs_simple_outlines_free(&s);
-  if (plain)
-    *plain = p;
-  else
-    bs_outlines_free(&p);
-}
-
 }  // namespace
 }  // namespace bs
 
@@ -895,21 +840,20 @@ extern "C" int bs_poly_solids_count_dev(bs_ctx* ctx, const int32_t* d_label, con
   int rc = check_args(ctx, d_label, d_top, d_label_building, n_labels, n_buildings, bin, out);
   if (rc != BS_OK)
     return rc;
-  struct bs_outline_triangles t;
-  struct bs_clean_outlines cl;
-  struct bs_simple_outlines sm;
-  struct bs_outlines pl;
-  rc = bs_outline_triangles_count_dev(ctx, d_label, d_top, width, height, n_labels, num, den, cell_log2, &t, &cl, &sm, &pl);
+  Chain ch;
+  rc = bs_outline_triangles_count_dev(ctx, d_label, d_top, width, height, n_labels, num, den, cell_log2, &ch.tri, &ch.clean, &ch.simple,
+                                      &ch.plain);
   if (rc != BS_OK)
     return rc;
+  ch.has_tri = ch.has_clean = ch.has_simple = ch.has_plain = true;
   struct bs_poly_solids res;
   memset(&res, 0, sizeof res);
-  PGuard guard{&res, &t, &cl, &sm, &pl};
-  rc = poly_solids(ctx, t, cl, width, d_label_building, n_buildings, bin, base_z, res);
+  ResultGuard guard{&res};
+  rc = poly_solids(ctx, ch.tri, ch.clean, width, d_label_building, n_buildings, bin, base_z, res);
   if (rc != BS_OK)
     return rc;
   guard.keep = true;
-  hand_over(tri, clean, simple, plain, t, cl, sm, pl);
+  ch.hand_over(tri, clean, simple, plain);
   *out = res;
   ctx->ps_valid = true;
   return BS_OK;
@@ -945,7 +889,7 @@ extern "C" int bs_poly_solids_emit_dev(bs_ctx* ctx, int32_t* d_vertex, int32_t* 
   int* d_err = B[PS_MISC].as<int>() + W_ERR;
   const int32_t *vnum = B[PS_VNUM].as<int32_t>(), *wscan = B[PS_WSCAN].as<int32_t>();
   const long long* iscan = B[PS_ISCAN].as<long long>();
-  Events ev;
+  Events<3> ev;
   for (int k = 0; k < 3; k++)
     BS_HIP(ctx, hipEventCreate(&ev.e[k]));
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
@@ -977,22 +921,20 @@ extern "C" int bs_poly_solids(bs_ctx* ctx, const int32_t* label, const int32_t* 
   int rc = check_args(ctx, label, top, label_building, n_labels, n_buildings, bin, out);
   if (rc != BS_OK)
     return rc;
-  struct bs_outline_triangles t;
-  struct bs_clean_outlines cl;
-  struct bs_simple_outlines sm;
-  struct bs_outlines pl;
-  rc = bs_outline_triangles(ctx, label, top, width, height, n_labels, num, den, cell_log2, &t, &cl, &sm, &pl);
+  Chain ch;
+  rc = bs_outline_triangles(ctx, label, top, width, height, n_labels, num, den, cell_log2, &ch.tri, &ch.clean, &ch.simple, &ch.plain);
   if (rc != BS_OK)
     return rc;
+  ch.has_tri = ch.has_clean = ch.has_simple = ch.has_plain = true;
   struct bs_poly_solids res;
   memset(&res, 0, sizeof res);
-  PGuard guard{&res, &t, &cl, &sm, &pl};
+  ResultGuard guard{&res};
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->ps;
   BS_HIP(ctx, B[PS_IN_LB].reserve(4 * (size_t)std::max(n_labels, 1)));
   if (n_labels > 0)
     BS_HIP(ctx, hipMemcpyAsync(B[PS_IN_LB].p, label_building, 4 * (size_t)n_labels, hipMemcpyHostToDevice, st));
-  rc = poly_solids(ctx, t, cl, width, B[PS_IN_LB].as<int32_t>(), n_buildings, bin, base_z, res);
+  rc = poly_solids(ctx, ch.tri, ch.clean, width, B[PS_IN_LB].as<int32_t>(), n_buildings, bin, base_z, res);
   if (rc != BS_OK)
     return rc;
   const size_t nv = (size_t)res.n_vertices, nf = (size_t)res.n_faces, ni = (size_t)res.n_indices;
@@ -1024,7 +966,7 @@ extern "C" int bs_poly_solids(bs_ctx* ctx, const int32_t* label, const int32_t* 
   res.ms_emit_vertices = ctx->ps_ms_emit[0];
   res.ms_emit_faces = ctx->ps_ms_emit[1];
   guard.keep = true;
-  hand_over(tri, clean, simple, plain, t, cl, sm, pl);
+  ch.hand_over(tri, clean, simple, plain);
   *out = res;
   ctx->ps_valid = true;
   return BS_OK;

@@ -27,6 +27,7 @@
 
 #include "../../include/bs_detmath.h"
 #include "bs_common.h"
+#include "bs_host.h"
 
 namespace bs {
 namespace {
@@ -165,8 +166,6 @@ __global__ void emit_pairs_tiled_kernel(const int32_t* __restrict__ xyz, int64_t
       atomicAdd(&cnt[pix], 1);
   }
 }
-
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 
 }  // namespace
 }  // namespace bs

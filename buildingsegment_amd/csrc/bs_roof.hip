@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "bs_common.h"
+#include "bs_host.h"
 #include "bs_roofheight.h"
 
 namespace bs {
@@ -35,8 +36,6 @@ constexpr int FILL_GRID = 512; // workgroups of a fill kernel (grid-stride over 
 // scratch of bs_ctx::rf
 enum { RF_KEYS, RF_KEYS2, RF_RUNS, RF_TMP, RF_BEST, RF_NEXT, RF_LIST_A, RF_LIST_B, RF_MISC, RF_TAB, RF_FIG, RF_IN_XYZ,
        RF_IN_MAP, RF_IN_PLANE, RF_OUT };
-
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 
 struct Tables {  // per plane, device: entry p - 1 is plane p
   const int32_t* home;
@@ -444,21 +443,6 @@ __global__ __launch_bounds__(256) void height_kernel(const int32_t* __restrict__
   height[i] = v;
 }
 
-struct Events {
-  hipEvent_t e[5] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  float ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.f;
-  }
-};
-
 bool alloc_roofs(struct bs_roofs* r, int32_t npl)
 {
   const size_t m = (size_t)std::max(npl, 1);
@@ -529,7 +513,7 @@ extern "C" int bs_roofs_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_
   const int64_t npix = (int64_t)w * h;
   const size_t m = (size_t)std::max(npl, 1);
   DevBuf* B = ctx->rf;
-  Events ev;
+  Events<5> ev;
   for (auto& e : ev.e)
     BS_HIP(ctx, hipEventCreate(&e));
 

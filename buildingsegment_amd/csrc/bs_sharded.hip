@@ -40,7 +40,8 @@ namespace bs {
 
 namespace {
 
-inline int nblk(int64_t n, int b) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + b - 1) / b, 0x7fffffff)); }
+// (unlike bs_host.h's nblk: at least 1 and at most INT_MAX)
+inline int nblk_clamped(int64_t n, int b) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + b - 1) / b, 0x7fffffff)); }
 
 __host__ __device__ inline uint64_t spread21s(uint64_t v)
 {
@@ -440,9 +441,9 @@ int local_all_reduce(void* h, void* d_buf, int64_t count, int dtype, int op, voi
   if (c->rank == 0) {  // rank 0 folds every peer's buffer into its own ...
     for (int r = 1; r < S->world && !rc; r++) {
       if (dtype == BS_I64)
-        reduce_i64_kernel<<<nblk(count, 256), 256, 0, st>>>((int64_t*)d_buf, (const int64_t*)S->ptr[r], count, op);
+        reduce_i64_kernel<<<nblk_clamped(count, 256), 256, 0, st>>>((int64_t*)d_buf, (const int64_t*)S->ptr[r], count, op);
       else
-        reduce_i32_kernel<<<nblk(count, 256), 256, 0, st>>>((int32_t*)d_buf, (const int32_t*)S->ptr[r], count, op);
+        reduce_i32_kernel<<<nblk_clamped(count, 256), 256, 0, st>>>((int32_t*)d_buf, (const int32_t*)S->ptr[r], count, op);
     }
     rc = hipStreamSynchronize(st) != hipSuccess;
   }
@@ -730,7 +731,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
   int4* rows = P.buf<int4>(ROWS, (size_t)m);
   SH_CHECK(rows);
   if (m > 0)
-    pack_rows_kernel<<<nblk(m, 256), 256, 0, st>>>(d_xyz, d_gidx, m, rows);
+    pack_rows_kernel<<<nblk_clamped(m, 256), 256, 0, st>>>(d_xyz, d_gidx, m, rows);
   int32_t bb[6];
   int rc = bbox_dev(ctx, d_xyz, m, bb);
   if (rc != BS_OK)
@@ -765,16 +766,16 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
     int4* srt = P.buf<int4>(SEND, (size_t)m);
     SH_CHECK(ka && kb && va && vb && srt);
     if (m > 0) {
-      morton_key_kernel<<<nblk(m, 256), 256, 0, st>>>(rows, m, origin, shift, ka, va);
+      morton_key_kernel<<<nblk_clamped(m, 256), 256, 0, st>>>(rows, m, origin, shift, ka, va);
       rc = sort_pairs_u64(ctx, ka, kb, va, vb, m, 63);
       if (rc != BS_OK)
         return rc;
-      gather_int4_kernel<<<nblk(m, 256), 256, 0, st>>>(rows, vb, m, srt);
+      gather_int4_kernel<<<nblk_clamped(m, 256), 256, 0, st>>>(rows, vb, m, srt);
     }
     const int S = 1024;
     uint64_t* d_s = (uint64_t*)P.buf<int64_t>(SMALL, 64 + (size_t)(world + 2) * S + 64) + 64;
     SH_CHECK(d_s);
-    sample_kernel<<<nblk(S, 256), 256, 0, st>>>(kb, m, S, d_s);
+    sample_kernel<<<nblk_clamped(S, 256), 256, 0, st>>>(kb, m, S, d_s);
     rc = P.all_gather(d_s, d_s + S, (int64_t)sizeof(uint64_t) * S);
     if (rc != BS_OK)
       return rc;
@@ -824,7 +825,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
       int64_t nocc = 0;
       int32_t* d_cnt = (int32_t*)P.buf<int64_t>(SMALL, 64);
       if (n_own > 0) {
-        voxel_key_kernel<<<nblk(n_own, 256), 256, 0, st>>>(own, n_own, origin, v, vk);
+        voxel_key_kernel<<<nblk_clamped(n_own, 256), 256, 0, st>>>(own, n_own, origin, v, vk);
         rc = sort_keys<uint64_t>(ctx, vk, vs, n_own);
         if (rc != BS_OK)
           return rc;
@@ -862,7 +863,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
       for (int r = 0; r < world; r++) {
         if (r == rank || n_own == 0 || cnts[r] == 0)
           continue;
-        halo_mark_kernel<<<nblk(n_own, 256), 256, 0, st>>>(vk, n_own, occ_all + (size_t)r * cap, cnts[r], flags);
+        halo_mark_kernel<<<nblk_clamped(n_own, 256), 256, 0, st>>>(vk, n_own, occ_all + (size_t)r * cap, cnts[r], flags);
         size_t tb = 0;
         BS_HIP(ctx, hipcub::DeviceSelect::Flagged(nullptr, tb, own, flags, send + soff, d_cnt, (int)n_own, st));
         BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
@@ -885,9 +886,9 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
     int32_t* lg = P.buf<int32_t>(LOC_GIDX, (size_t)nl);
     SH_CHECK(lxyz && lg);
     if (n_own > 0)
-      unpack_rows_kernel<<<nblk(n_own, 256), 256, 0, st>>>(own, n_own, lxyz, lg);
+      unpack_rows_kernel<<<nblk_clamped(n_own, 256), 256, 0, st>>>(own, n_own, lxyz, lg);
     if (n_halo > 0)
-      unpack_rows_kernel<<<nblk(n_halo, 256), 256, 0, st>>>(halo_rows, n_halo, lxyz + 3 * n_own, lg + n_own);
+      unpack_rows_kernel<<<nblk_clamped(n_halo, 256), 256, 0, st>>>(halo_rows, n_halo, lxyz + 3 * n_own, lg + n_own);
     gidx_own = lg;  // the first n_own entries
     lap(inf.ms_halo);
     int64_t unc = 0;
@@ -925,7 +926,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
   if (P.live()) {
     int32_t* parent = P.buf<int32_t>(PARENT, (size_t)n_total);
     SH_CHECK(parent);
-    iota_kernel<<<nblk(n_total, 256), 256, 0, st>>>(parent, n_total);
+    iota_kernel<<<nblk_clamped(n_total, 256), 256, 0, st>>>(parent, n_total);
     for (int it = 1;; it++) {
       int64_t hooks = 0;
       const int lrc = bs_cc_hook_dev(ctx, neigh, gidx_own, n_own, k, parent, n_total, &hooks);
@@ -952,7 +953,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
     int32_t* root = P.buf<int32_t>(ROOT, (size_t)n_own + 16);
     SH_CHECK(root);
     if (n_own > 0)
-      lookup_kernel<<<nblk(n_own, 256), 256, 0, st>>>(parent, gidx_own, n_own, root);
+      lookup_kernel<<<nblk_clamped(n_own, 256), 256, 0, st>>>(parent, gidx_own, n_own, root);
     lap(inf.ms_components);
 
     // ---- 5. deal + redistribution ----
@@ -1020,7 +1021,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
     int32_t* dvs = dv + n_own + 8;
     std::vector<int64_t> send(world, 0);
     if (n_own > 0) {
-      dest_key_kernel<<<nblk(n_own, 256), 256, 0, st>>>(root, n_own, d_uniq, d_dest, nu, dk, dv);
+      dest_key_kernel<<<nblk_clamped(n_own, 256), 256, 0, st>>>(root, n_own, d_uniq, d_dest, nu, dk, dv);
       int bits = 1;
       while ((1 << bits) < world)
         bits++;
@@ -1040,20 +1041,20 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
     SH_CHECK(sbuf);
     void* got = nullptr;
     if (n_own > 0)
-      gather_int4_kernel<<<nblk(n_own, 256), 256, 0, st>>>(own, dvs, n_own, (int4*)sbuf);
+      gather_int4_kernel<<<nblk_clamped(n_own, 256), 256, 0, st>>>(own, dvs, n_own, (int4*)sbuf);
     rc = P.all_to_all_rows(sbuf, send, sizeof(int4), G_OWN, &got, &n_loc);
     if (rc != BS_OK)
       return rc;
     g_own = (int4*)got;
     if (n_own > 0)
-      gather_rows_kernel<<<nblk(n_own * (int64_t)k, 256), 256, 0, st>>>(neigh, dvs, n_own, k, (int32_t*)sbuf);
+      gather_rows_kernel<<<nblk_clamped(n_own * (int64_t)k, 256), 256, 0, st>>>(neigh, dvs, n_own, k, (int32_t*)sbuf);
     int64_t n2 = 0;
     rc = P.all_to_all_rows(sbuf, send, (int64_t)sizeof(int32_t) * k, G_NG, &got, &n2);
     if (rc != BS_OK)
       return rc;
     g_ng = (int32_t*)got;
     if (n_own > 0)
-      gather_rows_kernel<<<nblk(n_own * 6, 256), 256, 0, st>>>((const int32_t*)normals, dvs, n_own, 6, (int32_t*)sbuf);
+      gather_rows_kernel<<<nblk_clamped(n_own * 6, 256), 256, 0, st>>>((const int32_t*)normals, dvs, n_own, 6, (int32_t*)sbuf);
     rc = P.all_to_all_rows(sbuf, send, (int64_t)sizeof(double) * 3, G_NR, &got, &n2);
     if (rc != BS_OK)
       return rc;
@@ -1084,16 +1085,16 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
   int32_t* owner_l = nullptr;
   int32_t np_local = 0;
   if (n_loc > 0) {
-    row_gidx_kernel<<<nblk(n_loc, 256), 256, 0, st>>>(g_own, n_loc, gl, io);
+    row_gidx_kernel<<<nblk_clamped(n_loc, 256), 256, 0, st>>>(g_own, n_loc, gl, io);
     lrc = sort_pairs_i32(ctx, gl, sg, io, perm, n_loc);
     if (lrc == BS_OK) {
-      dup_check_kernel<<<nblk(n_loc, 256), 256, 0, st>>>(sg, n_loc, d_bad);
+      dup_check_kernel<<<nblk_clamped(n_loc, 256), 256, 0, st>>>(sg, n_loc, d_bad);
       int4* srt = (int4*)P.buf<char>(SEND, (size_t)n_loc * sizeof(int4) + 64);
       SH_CHECK(srt);
-      gather_int4_kernel<<<nblk(n_loc, 256), 256, 0, st>>>(g_own, perm, n_loc, srt);
-      unpack_rows_kernel<<<nblk(n_loc, 256), 256, 0, st>>>(srt, n_loc, l_xyz, nullptr);
-      gather_rows_kernel<<<nblk(n_loc * 6, 256), 256, 0, st>>>((const int32_t*)g_nr, perm, n_loc, 6, (int32_t*)l_nr);
-      gather_rows_kernel<<<nblk(n_loc * (int64_t)k, 256), 256, 0, st>>>(g_ng, perm, n_loc, k, l_tmp);
+      gather_int4_kernel<<<nblk_clamped(n_loc, 256), 256, 0, st>>>(g_own, perm, n_loc, srt);
+      unpack_rows_kernel<<<nblk_clamped(n_loc, 256), 256, 0, st>>>(srt, n_loc, l_xyz, nullptr);
+      gather_rows_kernel<<<nblk_clamped(n_loc * 6, 256), 256, 0, st>>>((const int32_t*)g_nr, perm, n_loc, 6, (int32_t*)l_nr);
+      gather_rows_kernel<<<nblk_clamped(n_loc * (int64_t)k, 256), 256, 0, st>>>(g_ng, perm, n_loc, k, l_tmp);
       int32_t bad = 0;
       if (hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         lrc = fail(ctx, BS_ERR_HIP, "bs_segment_sharded: copy failed");
@@ -1155,7 +1156,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
     rc = bs_plane_seeds_dev(ctx, sl, np_local, &dummy);
     if (rc != BS_OK)
       return rc;
-    lookup_kernel<<<nblk(np_local, 256), 256, 0, st>>>(sg, sl, np_local, sp);  // local seed -> global index
+    lookup_kernel<<<nblk_clamped(np_local, 256), 256, 0, st>>>(sg, sl, np_local, sp);  // local seed -> global index
   }
   rc = P.all_gather(sp, sp_all, (int64_t)sizeof(int32_t) * capp);
   if (rc != BS_OK)
@@ -1173,16 +1174,16 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
     if (rc != BS_OK)
       return rc;
   }
-  fill_kernel<<<nblk(n_total, 256), 256, 0, st>>>(d_plane_idx, n_total, -1);
+  fill_kernel<<<nblk_clamped(n_total, 256), 256, 0, st>>>(d_plane_idx, n_total, -1);
   if (n_loc > 0) {
     int32_t* owner_g = P.buf<int32_t>(KEYS_B, 2 * (size_t)n_loc + 32);
     SH_CHECK(owner_g);
     int32_t* lab_g = owner_g + n_loc + 8;
-    lookup_kernel<<<nblk(n_loc, 256), 256, 0, st>>>(sg, owner_l, n_loc, owner_g);
+    lookup_kernel<<<nblk_clamped(n_loc, 256), 256, 0, st>>>(sg, owner_l, n_loc, owner_g);
     rc = bs_labels_from_owner_dev(ctx, owner_g, n_loc, seeds_sorted, (int32_t)np_tot, lab_g);
     if (rc != BS_OK)
       return rc;
-    scatter_labels_kernel<<<nblk(n_loc, 256), 256, 0, st>>>(sg, lab_g, n_loc, d_plane_idx);
+    scatter_labels_kernel<<<nblk_clamped(n_loc, 256), 256, 0, st>>>(sg, lab_g, n_loc, d_plane_idx);
   }
   rc = P.all_reduce(d_plane_idx, n_total, BS_I32, BS_MAX);  // every point has exactly one growing rank; the others hold -1
   if (rc != BS_OK)

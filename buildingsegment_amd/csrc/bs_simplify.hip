@@ -18,6 +18,9 @@
 // No thread walks a ring or an arc: the only loops in kernels are grid strides, the four pixels of a block and the steps of
 // a wave scan.  Every index read from memory is checked before it is used as an address; a violation sets err and the call
 // returns BS_ERR_INTERNAL.  No kernel reads an array that a thread of the same launch writes.
+// The entry points own the plain outlines and their own result through bs_chain.h's Chain and hand them over at their end;
+// an early return frees them.  bs_outline.h is what this file shares with bs_outline.hip (the ranking kernels, the scratch
+// of bs_ctx::ol); launch sizes, events and host arrays are bs_host.h's.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -27,6 +30,7 @@
 #include <cstring>
 #include <vector>
 
+#include "bs_chain.h"
 #include "bs_common.h"
 #include "bs_outline.h"
 #include "bs_segscan.h"
@@ -598,19 +602,6 @@ __global__ __launch_bounds__(256) void simplify_emit_kernel(FinalArrays O, int64
   }
 }
 
-struct SGuard {  // frees half-built results unless they are handed over
-  struct bs_simple_outlines* s;
-  struct bs_outlines* plain;
-  bool keep = false;
-  ~SGuard()
-  {
-    if (!keep) {
-      bs_simple_outlines_free(s);
-      bs_outlines_free(plain);
-    }
-  }
-};
-
 const char* const SIMPLE_INVALID = "simplified outlines: null pointer, width or height < 1, width * height >= 2^29, n_labels < 0, "
                                    "d_top not 16-byte aligned, num outside [0, 2^31) or den outside [1, 2^31)";
 
@@ -677,14 +668,13 @@ extern "C" int bs_simple_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label,
   if (!d_label || !out || bad_image(width, height) || n_labels < 0 || (reinterpret_cast<uintptr_t>(d_top) & 15u) ||
       bad_tolerance(num, den))
     return fail(ctx, BS_ERR_INVALID, SIMPLE_INVALID);
-  struct bs_outlines pl;
-  memset(&pl, 0, sizeof pl);
-  struct bs_simple_outlines res;
-  memset(&res, 0, sizeof res);
+  Chain ch;  // (its simplified outlines are this call's own result)
+  struct bs_outlines& pl = ch.plain;
+  struct bs_simple_outlines& res = ch.simple;
   int rc = bs_facet_outlines_count_dev(ctx, d_label, d_top, width, height, n_labels, &pl);
   if (rc != BS_OK)
     return rc;
-  SGuard guard{&res, &pl};
+  ch.has_plain = ch.has_simple = true;
   const int w = width, h = height;
   const bool has_z = d_top != nullptr;
   const int32_t nr = (int32_t)pl.n_rings;
@@ -707,12 +697,7 @@ extern "C" int bs_simple_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label,
     memcpy(res.ring_area2, pl.ring_area2, 8 * (size_t)nr);
   }
   auto hand_over = [&]() {
-    if (plain)
-      *plain = pl;
-    else
-      bs_outlines_free(&pl);
-    *out = res;
-    guard.keep = true;
+    ch.hand_over(nullptr, nullptr, out, plain);
     return BS_OK;
   };
   if (pl.n_half == 0) {  // no labelled pixel: no ring, every offset 0
@@ -729,7 +714,7 @@ extern "C" int bs_simple_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label,
   const int nb = nblk(n, 256);
   DevBuf* B = ctx->sp;
   DevBuf* OB = ctx->ol;
-  Events ev;
+  Events<10> ev;
   for (auto& e : ev.e)
     BS_HIP(ctx, hipEventCreate(&e));
   hipcub::CountingInputIterator<int32_t> idx(0);
@@ -936,7 +921,7 @@ extern "C" int bs_simple_outlines_emit_dev(bs_ctx* ctx, int32_t* d_sxy, int32_t*
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->sp;
-  Events ev;
+  Events<2> ev;
   BS_HIP(ctx, hipEventCreate(&ev.e[0]));
   BS_HIP(ctx, hipEventCreate(&ev.e[1]));
   const FinalArrays O{B[SP_FXY].as<int2>(), B[SP_FZ].as<int32_t>(), B[SP_FRIGHT].as<int32_t>(), B[SP_FRING].as<int32_t>(),
@@ -969,13 +954,13 @@ extern "C" int bs_simple_outlines(bs_ctx* ctx, const int32_t* label, const int32
     BS_HIP(ctx, B[SP_IN_TOP].reserve(16 * npix));
     BS_HIP(ctx, hipMemcpyAsync(B[SP_IN_TOP].p, top, 16 * npix, hipMemcpyHostToDevice, st));
   }
-  struct bs_simple_outlines res;
-  struct bs_outlines pl;
+  Chain ch;  // (its simplified outlines are this call's own result)
+  struct bs_simple_outlines& res = ch.simple;
   int rc = bs_simple_outlines_count_dev(ctx, B[SP_IN_LABEL].as<int32_t>(), top ? B[SP_IN_TOP].as<int32_t>() : nullptr, width, height,
-                                        n_labels, num, den, &res, &pl);
+                                        n_labels, num, den, &res, &ch.plain);
   if (rc != BS_OK)
     return rc;
-  SGuard guard{&res, &pl};
+  ch.has_plain = ch.has_simple = true;
   const size_t nv = (size_t)res.n_svertices;
   if (!alloc(&res.sxy, 2 * nv) || (top && !alloc(&res.sz, nv)) || !alloc(&res.s_right, nv) || !alloc(&res.s_flag, nv))
     return fail(ctx, BS_ERR_NOMEM, "simplified outlines: host allocation");
@@ -996,12 +981,7 @@ extern "C" int bs_simple_outlines(bs_ctx* ctx, const int32_t* label, const int32
     BS_HIP(ctx, hipStreamSynchronize(st));
     res.ms_emit = ctx->sp_ms_emit;
   }
-  if (plain)
-    *plain = pl;
-  else
-    bs_outlines_free(&pl);
-  *out = res;
-  guard.keep = true;
+  ch.hand_over(nullptr, nullptr, out, plain);
   return BS_OK;
 }
 

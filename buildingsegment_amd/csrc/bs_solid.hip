@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "bs_common.h"
+#include "bs_host.h"
 #include "bs_roofheight.h"
 #include "bs_tops.h"
 
@@ -34,7 +35,6 @@ constexpr int GRID_CAP = 4096; // workgroups of the grid-stride passes
 enum { SD_TOP, SD_MAP, SD_CCNT, SD_VOFF, SD_PCNT, SD_FOFF, SD_IOFF, SD_TMP, SD_TAB, SD_FIG, SD_MISC, SD_IN_MAP, SD_IN_ROOF,
        SD_OUT };
 
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
 inline int grid_of(int64_t n) { return (int)std::min<int64_t>(nblk(n, 256), GRID_CAP); }
 
 constexpr uint64_t NO_KEY = ~0ull;
@@ -487,21 +487,6 @@ using CornerIt = hipcub::TransformInputIterator<int32_t, ByteCount, const uint8_
 using FaceIt = hipcub::TransformInputIterator<int32_t, FaceCount, const uint16_t*>;
 using IndexIt = hipcub::TransformInputIterator<int32_t, IndexCount, const uint16_t*>;
 
-struct Events {
-  hipEvent_t e[7] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  float ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.f;
-  }
-};
-
 bool alloc_solids(struct bs_solids* s, int32_t nb)
 {
   const size_t m = (size_t)std::max(nb, 1);
@@ -572,7 +557,7 @@ extern "C" int bs_solids_count_dev(bs_ctx* ctx, const int32_t* d_map, const int3
   const int64_t npix = (int64_t)w * h, nc = (int64_t)(w + 1) * (h + 1);
   const size_t mp = (size_t)std::max(npl, 1), mb = (size_t)std::max(nb, 1);
   DevBuf* B = ctx->sd;
-  Events ev;
+  Events<7> ev;
   for (auto& e : ev.e)
     BS_HIP(ctx, hipEventCreate(&e));
 
@@ -754,7 +739,7 @@ extern "C" int bs_solids_emit_dev(bs_ctx* ctx, int32_t* d_vertex, int32_t* d_fac
   DevBuf* B = ctx->sd;
   // (bs_set_building_bases ends the validity of a count, so the table is still the count's)
   const Bases bases{ctx->sd_bases ? ctx->bases_dev.as<int32_t>() : nullptr, ctx->sd_base};
-  Events ev;
+  Events<3> ev;
   for (int k = 0; k < 3; k++)
     BS_HIP(ctx, hipEventCreate(&ev.e[k]));
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));

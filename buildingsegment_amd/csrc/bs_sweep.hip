@@ -21,16 +21,14 @@
 #include <algorithm>
 #include <climits>
 
+#include "bs_host.h"
 #include "bs_sweep.h"
 
 namespace bs {
 namespace {
 
-constexpr int SWEEP_CAP = 1024;  // workgroups of the grid-stride passes
 constexpr int32_t KEPT = -1;     // seg.x of a kept node (bs_simplify.hip)
 constexpr int E_RUNS = 1024, E_ITEMS = 2048, E_TEST = 4096;  // phase bits of the error word
-
-inline int sweep(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, SWEEP_CAP)); }
 
 struct SweepDev {
   const int2* segK;

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "bs_common.h"
+#include "bs_host.h"
 
 namespace bs {
 namespace {
@@ -44,30 +45,6 @@ enum { E_PICK = 1 };                        // the bits of W_ERR
 // the arrays of TN_FIG: four of 64 bits, then four of 32
 enum { F_RING_PIXELS, F_GROUND_PIXELS, F_RING_POINTS, F_SUM, F_WIDE };
 enum { G_MIN, G_MAX, G_GROUND, G_STATUS, G_NARROW };
-
-inline int nblk(int64_t n, int b) { return (int)((n + b - 1) / b); }
-
-struct Events {
-  hipEvent_t e[5] = {};
-  ~Events()
-  {
-    for (auto& x : e)
-      if (x)
-        (void)hipEventDestroy(x);
-  }
-  double ms(int i, int j)
-  {
-    float t = 0;
-    return hipEventElapsedTime(&t, e[i], e[j]) == hipSuccess ? t : 0.0;
-  }
-};
-
-template <class T>
-bool alloc(T** p, size_t n)
-{
-  *p = (T*)calloc(std::max<size_t>(n, 1), sizeof(T));
-  return *p != nullptr;
-}
 
 struct Fig {  // per building, device: array j starts j * stride entries behind its base
   unsigned long long* wide;
@@ -446,7 +423,7 @@ int terrain(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const int
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->tn;
-  Events ev;
+  Events<5> ev;
   for (int i = 0; i < 5; i++)
     BS_HIP(ctx, hipEventCreate(&ev.e[i]));
   const size_t fig_bytes = (8 * (size_t)F_WIDE + 4 * (size_t)G_NARROW) * nb1;
@@ -560,15 +537,7 @@ int terrain(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const int
   return BS_OK;
 }
 
-struct TGuard {  // frees a half-built result unless it is handed over
-  struct bs_terrain* t;
-  bool keep = false;
-  ~TGuard()
-  {
-    if (!keep)
-      bs_terrain_free(t);
-  }
-};
+using TGuard = FreeUnlessKept<struct bs_terrain, bs_terrain_free>;
 
 }  // namespace
 }  // namespace bs

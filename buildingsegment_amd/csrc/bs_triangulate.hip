@@ -17,6 +17,8 @@
 // segment or a bridge, so the blockers of a bridge are exactly those.
 // The host reads once, for the result.  Every index read from memory is checked before it is used as an address; a
 // violation sets err and the call returns BS_ERR_INTERNAL.
+// The entry points own the results of the stages before and their own through bs_chain.h's Chain and hand them over at their
+// end; an early return frees them.  Launch sizes, events and host arrays are bs_host.h's.
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -24,11 +26,9 @@
 #include <cstring>
 #include <vector>
 
+#include "bs_chain.h"
 #include "bs_common.h"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (the ranking kernels of bs_outline.h are not launched here)
-#include "bs_outline.h"
-#pragma clang diagnostic pop
+#include "bs_host.h"
 
 namespace bs {
 namespace {
@@ -37,11 +37,8 @@ namespace {
 enum { TR_MISC, TR_ARGS, TR_DESC, TR_LIST, TR_OUTER, TR_RKEY, TR_RM, TR_LOUT, TR_BRIDGE, TR_TRI, TR_WS, TR_OUT, TR_TOFF, TR_COUNT };
 static_assert(TR_COUNT <= (int)(sizeof(bs_ctx::tr) / sizeof(DevBuf)), "bs_ctx::tr is too short");
 
-constexpr int SWEEP_CAP = 1024;
 constexpr int32_t F_IN = 1 << 29, F_CUR = 1 << 30, IDX = F_IN - 1;
 constexpr unsigned long long NONE = ~0ull;
-
-inline int sweep(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(nblk(n, 256), SWEEP_CAP)); }
 
 struct LabelDesc {  // per label, from the host
   int32_t r0, r1;   // its rings
@@ -498,26 +495,6 @@ __global__ __launch_bounds__(256) void tri_emit_kernel(const int32_t* __restrict
     dst[i] = src[i];
 }
 
-struct TGuard {  // frees half-built results unless they are handed over
-  struct bs_outline_triangles* t;
-  struct bs_clean_outlines* c;
-  struct bs_simple_outlines* s;
-  struct bs_outlines* plain;
-  bool keep = false;
-  ~TGuard()
-  {
-    if (!keep) {
-      bs_outline_triangles_free(t);
-      if (c)
-        bs_clean_outlines_free(c);
-      if (s)
-        bs_simple_outlines_free(s);
-      if (plain)
-        bs_outlines_free(plain);
-    }
-  }
-};
-
 int internal(bs_ctx* ctx, int err)
 {
   char msg[96];
@@ -594,7 +571,7 @@ int triangulate(bs_ctx* ctx, const struct bs_clean_outlines& c, struct bs_outlin
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->tr;
-  Events ev;
+  Events<5> ev;
   for (int i = 0; i < 5; i++)
     BS_HIP(ctx, hipEventCreate(&ev.e[i]));
   std::vector<int32_t> list;
@@ -704,32 +681,16 @@ extern "C" int bs_outline_triangles_count_dev(bs_ctx* ctx, const int32_t* d_labe
   ctx->tr_valid = false;
   if (!out)
     return fail(ctx, BS_ERR_INVALID, "outline triangles: null pointer");
-  struct bs_clean_outlines cl;
-  struct bs_simple_outlines sm;
-  struct bs_outlines pl;
-  int rc = bs_clean_outlines_count_dev(ctx, d_label, d_top, width, height, n_labels, num, den, -1, cell_log2, &cl, &sm, &pl);
+  Chain ch;  // (its triangles are this call's own result)
+  int rc = bs_clean_outlines_count_dev(ctx, d_label, d_top, width, height, n_labels, num, den, -1, cell_log2, &ch.clean, &ch.simple,
+                                       &ch.plain);
   if (rc != BS_OK)
     return rc;
-  struct bs_outline_triangles res;
-  memset(&res, 0, sizeof res);
-  TGuard guard{&res, &cl, &sm, &pl};
-  rc = triangulate(ctx, cl, res);
+  ch.has_plain = ch.has_simple = ch.has_clean = ch.has_tri = true;
+  rc = triangulate(ctx, ch.clean, ch.tri);
   if (rc != BS_OK)
     return rc;
-  if (clean)
-    *clean = cl;
-  else
-    bs_clean_outlines_free(&cl);
-  if (simple)
-    *simple = sm;
-  else
-    bs_simple_outlines_free(&sm);
-  if (plain)
-    *plain = pl;
-  else
-    bs_outlines_free(&pl);
-  *out = res;
-  guard.keep = true;
+  ch.hand_over(out, clean, simple, plain);
   ctx->tr_valid = true;
   return BS_OK;
 }
@@ -748,7 +709,7 @@ extern "C" int bs_outline_triangles_emit_dev(bs_ctx* ctx, int32_t* d_tri)
     return BS_OK;
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  Events ev;
+  Events<2> ev;
   BS_HIP(ctx, hipEventCreate(&ev.e[0]));
   BS_HIP(ctx, hipEventCreate(&ev.e[1]));
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
@@ -769,16 +730,13 @@ extern "C" int bs_outline_triangles(bs_ctx* ctx, const int32_t* label, const int
   ctx->tr_valid = false;
   if (!out)
     return fail(ctx, BS_ERR_INVALID, "outline triangles: null pointer");
-  struct bs_clean_outlines cl;
-  struct bs_simple_outlines sm;
-  struct bs_outlines pl;
-  int rc = bs_clean_outlines(ctx, label, top, width, height, n_labels, num, den, -1, cell_log2, &cl, &sm, &pl);
+  Chain ch;  // (its triangles are this call's own result)
+  struct bs_outline_triangles& res = ch.tri;
+  int rc = bs_clean_outlines(ctx, label, top, width, height, n_labels, num, den, -1, cell_log2, &ch.clean, &ch.simple, &ch.plain);
   if (rc != BS_OK)
     return rc;
-  struct bs_outline_triangles res;
-  memset(&res, 0, sizeof res);
-  TGuard guard{&res, &cl, &sm, &pl};
-  rc = triangulate(ctx, cl, res);
+  ch.has_plain = ch.has_simple = ch.has_clean = ch.has_tri = true;
+  rc = triangulate(ctx, ch.clean, res);
   if (rc != BS_OK)
     return rc;
   const size_t n = 3 * (size_t)res.n_triangles;
@@ -797,20 +755,7 @@ extern "C" int bs_outline_triangles(bs_ctx* ctx, const int32_t* label, const int
     BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     res.ms_emit = ctx->tr_ms_emit;
   }
-  if (clean)
-    *clean = cl;
-  else
-    bs_clean_outlines_free(&cl);
-  if (simple)
-    *simple = sm;
-  else
-    bs_simple_outlines_free(&sm);
-  if (plain)
-    *plain = pl;
-  else
-    bs_outlines_free(&pl);
-  *out = res;
-  guard.keep = true;
+  ch.hand_over(out, clean, simple, plain);
   ctx->tr_valid = true;
   return BS_OK;
 }

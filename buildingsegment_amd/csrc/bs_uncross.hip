@@ -16,6 +16,8 @@
 // for the result.  Every index read from memory is checked before it is used as an address; a violation sets err and the
 // call returns BS_ERR_INTERNAL.  No kernel reads an array that a thread of the same launch writes.  Marks are plain stores
 // of 1: neither the order of the entries nor a pair met in several cells shows in a result.
+// The entry points own the results of the stages before through bs_chain.h's Chain (the clean outlines among them) and hand
+// them over at their end; an early return frees them.  Launch sizes, events and host arrays are bs_host.h's.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -25,11 +27,9 @@
 #include <cstring>
 #include <vector>
 
+#include "bs_chain.h"
 #include "bs_common.h"
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"  // (the ranking kernels of bs_outline.h are not launched here)
-#include "bs_outline.h"
-#pragma clang diagnostic pop
+#include "bs_host.h"
 #include "bs_segscan.h"
 #include "bs_sweep.h"
 
@@ -42,13 +42,10 @@ enum { UC_MISC, UC_TMP, UC_RLABEL, UC_KSCAN, UC_KLIST, UC_KEPT0, UC_SEGXY, UC_SE
        UC_OUT_XY, UC_OUT_Z, UC_OUT_RIGHT, UC_OUT_FLAG, UC_COUNT };
 static_assert(UC_COUNT <= (int)(sizeof(bs_ctx::uc) / sizeof(DevBuf)), "bs_ctx::uc is too short");
 
-constexpr int SWEEP_CAP = 1024;    // workgroups of the grid-stride passes
 constexpr int HEAVY = 64;          // a run of more entries is tested tile by tile
 constexpr int TILE = 256;
 constexpr int32_t KEPT = -1, DROPPED = -2;  // seg.x of a node that is not active (bs_simplify.hip)
 constexpr unsigned F_REPAIRED = 4, F_MARKED = 8;
-
-inline int sweep(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(nblk(n, 256), SWEEP_CAP)); }
 
 struct KeptFlag {  // 0 for the entry behind the last
   const int2* seg;
@@ -535,23 +532,6 @@ __global__ __launch_bounds__(256) void uncross_emit_kernel(FinalArrays O, int64_
   }
 }
 
-struct CGuard {  // frees half-built results unless they are handed over
-  struct bs_clean_outlines* c;
-  struct bs_simple_outlines* s;
-  struct bs_outlines* plain;
-  bool keep = false;
-  ~CGuard()
-  {
-    if (!keep) {
-      bs_clean_outlines_free(c);
-      if (s)
-        bs_simple_outlines_free(s);
-      if (plain)
-        bs_outlines_free(plain);
-    }
-  }
-};
-
 int internal(bs_ctx* ctx, int err)
 {
   char msg[96];
@@ -599,14 +579,13 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   ctx->ps_valid = false;  // (the polygon solids' emit reads the clean vertices)
   if (!out || cell_log2 < 0 || cell_log2 > 30)
     return fail(ctx, BS_ERR_INVALID, "clean outlines: null pointer or cell_log2 outside 0 .. 30");
-  struct bs_simple_outlines sm;
-  struct bs_outlines pl;
-  int rc = bs_simple_outlines_count_dev(ctx, d_label, d_top, width, height, n_labels, num, den, &sm, &pl);
+  Chain ch;  // (its clean outlines are this call's own result)
+  struct bs_simple_outlines& sm = ch.simple;
+  struct bs_clean_outlines& res = ch.clean;
+  int rc = bs_simple_outlines_count_dev(ctx, d_label, d_top, width, height, n_labels, num, den, &sm, &ch.plain);
   if (rc != BS_OK)
     return rc;
-  struct bs_clean_outlines res;
-  memset(&res, 0, sizeof res);
-  CGuard guard{&res, &sm, &pl};
+  ch.has_plain = ch.has_simple = ch.has_clean = true;
   const int mode = ctx->sweeps_mode;
   struct bs_outline_sweeps sw;
   memset(&sw, 0, sizeof sw);
@@ -643,17 +622,8 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
     memcpy(res.s_ring_arcs, sm.s_ring_arcs, 8 * (size_t)nr);
   }
   auto hand_over = [&]() {
-    if (simple)
-      *simple = sm;
-    else
-      bs_simple_outlines_free(&sm);
-    if (plain)
-      *plain = pl;
-    else
-      bs_outlines_free(&pl);
-    *out = res;
-    guard.keep = true;
     ctx->uc_nsv = res.n_svertices;
+    ch.hand_over(nullptr, out, simple, plain);
     ctx->uc_has_z = has_z;
     ctx->uc_xy = ctx->uc[UC_FXY].as<int2>();  // (for bs_triangulate.hip)
     ctx->uc_ring = ctx->uc[UC_FRING].as<int32_t>();
@@ -673,7 +643,7 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   DevBuf* B = ctx->uc;
-  Events ev;
+  Events<10> ev;
   for (int i = 0; i < (mode ? 10 : 6); i++)
     BS_HIP(ctx, hipEventCreate(&ev.e[i]));
   BS_HIP(ctx, B[UC_MISC].reserve(256));
@@ -881,7 +851,7 @@ extern "C" int bs_clean_outlines_emit_dev(bs_ctx* ctx, int32_t* d_sxy, int32_t* 
     return BS_OK;
   BS_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  Events ev;
+  Events<2> ev;
   BS_HIP(ctx, hipEventCreate(&ev.e[0]));
   BS_HIP(ctx, hipEventCreate(&ev.e[1]));
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
@@ -912,14 +882,13 @@ extern "C" int bs_clean_outlines(bs_ctx* ctx, const int32_t* label, const int32_
     BS_HIP(ctx, B[UC_IN_TOP].reserve(16 * npix));
     BS_HIP(ctx, hipMemcpyAsync(B[UC_IN_TOP].p, top, 16 * npix, hipMemcpyHostToDevice, st));
   }
-  struct bs_clean_outlines res;
-  struct bs_simple_outlines sm;
-  struct bs_outlines pl;
+  Chain ch;  // (its clean outlines are this call's own result)
+  struct bs_clean_outlines& res = ch.clean;
   int rc = bs_clean_outlines_count_dev(ctx, B[UC_IN_LABEL].as<int32_t>(), top ? B[UC_IN_TOP].as<int32_t>() : nullptr, width, height,
-                                       n_labels, num, den, max_rounds, cell_log2, &res, &sm, &pl);
+                                       n_labels, num, den, max_rounds, cell_log2, &res, &ch.simple, &ch.plain);
   if (rc != BS_OK)
     return rc;
-  CGuard guard{&res, &sm, &pl};
+  ch.has_plain = ch.has_simple = ch.has_clean = true;
   const size_t nv = (size_t)res.n_svertices;
   if (!alloc(&res.sxy, 2 * nv) || (top && !alloc(&res.sz, nv)) || !alloc(&res.s_right, nv) || !alloc(&res.s_flag, nv))
     return fail(ctx, BS_ERR_NOMEM, "clean outlines: host allocation");
@@ -940,16 +909,7 @@ extern "C" int bs_clean_outlines(bs_ctx* ctx, const int32_t* label, const int32_
     BS_HIP(ctx, hipStreamSynchronize(st));
     res.ms_emit = ctx->uc_ms_emit;
   }
-  if (simple)
-    *simple = sm;
-  else
-    bs_simple_outlines_free(&sm);
-  if (plain)
-    *plain = pl;
-  else
-    bs_outlines_free(&pl);
-  *out = res;
-  guard.keep = true;
+  ch.hand_over(nullptr, out, simple, plain);
   return BS_OK;
 }
 
