@@ -47,7 +47,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_model_raster_free", "bs_point_residuals_dev", "bs_point_residuals", "bs_point_residuals_free",
            "bs_terrain_dev", "bs_terrain", "bs_terrain_free", "bs_set_building_bases", "bs_get_building_bases",
            "bs_ground_dev", "bs_ground", "bs_ground_free", "bs_set_ground_model", "bs_set_ground_model_dev",
-           "bs_get_ground_model"]
+           "bs_get_ground_model", "bs_plane_quality", "bs_roof_evidence_dev", "bs_roof_evidence", "bs_set_footprint_screen",
+           "bs_set_footprint_screen_dev", "bs_get_footprint_screen"]
 
 
 class Params(C.Structure):
@@ -374,6 +375,20 @@ class Ground(C.Structure):
                 [("ms_step", C.c_double * GROUND_MAX_STEPS)])
 
 
+EVIDENCE_RMAX = 15   # BS_EVIDENCE_RMAX
+EVIDENCE_TILE = 32   # BS_EVIDENCE_TILE
+EVIDENCE_GRID = 256  # BS_EVIDENCE_GRID
+EVIDENCE_NARROW = ("width", "height", "r", "min_points", "num", "den", "grid", "tile", "max_window", "pad_")
+EVIDENCE_WIDE = ("n_points", "n_counted", "n_planar", "n_pixels", "pixels_kept", "pixels_rejected", "pixels_thin")
+EVIDENCE_MS = ("ms_counts", "ms_window")
+
+
+class RoofEvidence(C.Structure):
+    """bs_roof_evidence (include/bs_api.h): the lattice, the parameters and the figures; it owns no memory."""
+    _fields_ = ([(k, C.c_int32) for k in EVIDENCE_NARROW] + [(k, C.c_int64) for k in EVIDENCE_WIDE] +
+                [(k, C.c_double) for k in EVIDENCE_MS])
+
+
 class BsError(RuntimeError):
     def __init__(self, status, detail=""):
         self.status = status
@@ -586,5 +601,12 @@ def load():
     for fn in (L.bs_set_ground_model, L.bs_set_ground_model_dev):
         fn.argtypes = [vp, ip, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.bs_get_ground_model.argtypes = [vp, ip, C.c_int64, i32p, i32p, i32p, i32p]
+    L.bs_plane_quality.argtypes = [fitp, C.c_int64, C.c_int32, vp]
+    for fn in (L.bs_roof_evidence_dev, L.bs_roof_evidence):
+        fn.argtypes = [vp, ip, C.c_int64, ip, C.c_int32, vp, ip, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                       vp, ip, ip, ip, ip, C.POINTER(RoofEvidence)]
+    for fn in (L.bs_set_footprint_screen, L.bs_set_footprint_screen_dev):
+        fn.argtypes = [vp, vp, C.c_int32, C.c_int32]
+    L.bs_get_footprint_screen.argtypes = [vp, vp, C.c_int64, i32p, i32p]
     _LIB = L
     return L

@@ -12,8 +12,9 @@ library; nothing is computed in Python and there is no CPU fallback.
 from __future__ import annotations
 
 import copy
+import warnings
 import ctypes as C
-from contextlib import contextmanager
+from contextlib import contextmanager, nullcontext
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -66,6 +67,7 @@ class Context:
         if rc != 0:
             raise BsError(rc, "bs_create failed (is a gfx950 GPU visible?)")
         self.device = device
+        self._screen_dev = None  # (pointer, width, height) while set_footprint_screen(device=True) holds
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -520,29 +522,38 @@ class Context:
         return PlaneVotes(pb, vin, vtot, vout)
 
     def buildings(self, xyz, plane_idx=None, n_planes=0, bin=100, bin_height=1000, threshold=10, kernel_size=5,
-                  iterations=2, ground=None):
+                  iterations=2, ground=None, evidence=None):
         """The whole 2-D branch for a cloud shifted to its origin: raster -> footprints (with the closed mask) ->
         building map -> point assignment -> plane votes (when plane_idx, the labels of segment(), is given).
         Returns (Footprints, Buildings); the Buildings carry map, building_idx, ground_th and votes.  ground: a dict of
         the parameters of ground() ({} for its defaults): the stage runs first, the raster and the assignment of this call
         measure "above ground" against its dtm (set_ground_model; the context's own model is restored afterwards), and
-        the Ground is returned as a third value."""
+        the Ground is returned as a third value.  evidence: a dict of evidence_params() ({} for its defaults; it needs
+        plane_idx and n_planes): plane_fit -> plane_quality -> roof_evidence run after the raster, under the ground model
+        if one was asked for, the footprints of this call are taken under its keep image (set_footprint_screen; the
+        context's own screen is restored afterwards), and the RoofEvidence is returned as the last value."""
         xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        if evidence is not None and plane_idx is None:
+            raise ValueError("buildings: evidence needs plane_idx, the labels of segment()")
         if ground is not None:
             g = self.ground(xyz, points=False, **ground)
             with self._ground_model(g):
-                fp, b = self.buildings(xyz, plane_idx, n_planes, bin=bin, bin_height=bin_height, threshold=threshold,
-                                       kernel_size=kernel_size, iterations=iterations)
-            return fp, b, g
+                out = self.buildings(xyz, plane_idx, n_planes, bin=bin, bin_height=bin_height, threshold=threshold,
+                                     kernel_size=kernel_size, iterations=iterations, evidence=evidence)
+            return out[:2] + (g,) + out[2:]
         img, th = self.grid_picture(xyz, bin=bin, bin_height=bin_height)
-        fp, mask = self.footprints(img, threshold=threshold, kernel_size=kernel_size, iterations=iterations,
-                                   return_mask=True)
+        ev = None
+        if evidence is not None:
+            ev = self._evidence(xyz, plane_idx, n_planes, bin, th, evidence)
+        with self._footprint_screen(ev.keep) if ev is not None else nullcontext():
+            fp, mask = self.footprints(img, threshold=threshold, kernel_size=kernel_size, iterations=iterations,
+                                       return_mask=True)
         bmap, b = self.building_map(mask)
         b.map, b.ground_th = bmap, th
         b.building_idx = self.assign_buildings(xyz, bmap, b, bin=bin, ground_th=th)
         if plane_idx is not None:
             b.votes = self.plane_buildings(plane_idx, b.building_idx, n_planes, b.n_buildings)
-        return fp, b
+        return (fp, b) if ev is None else (fp, b, ev)
 
     # ---- roofs: the plane over every pixel of a building and its height there (bs_roofs, include/bs_api.h) ----------
     def roofs(self, xyz, bmap, plane_idx, home, normal, center, bin=100, ground_th=0.0, min_votes=1, support=True,
@@ -609,26 +620,27 @@ class Context:
         return _take_fits(self._L, out, None)
 
     def roof_model(self, xyz, plane_idx, planes, bin=100, bin_height=1000, threshold=10, kernel_size=5, iterations=2,
-                   min_normal_z=0.5, min_votes=1, refit=False, ground=None):
+                   min_normal_z=0.5, min_votes=1, refit=False, ground=None, evidence=None):
         """buildings() -> roof_homes -> roofs for a cloud shifted to its origin, its labels and the planes of segment().
         Returns (Footprints, Buildings, Roofs); the Roofs carry home, normal, center and bin for write_roofs_obj.
         refit=True: plane_fit() after buildings(), and homes and roofs from the refitted normal / center tables (which
         the Roofs then carry, with the PlaneFits as `fit`).  ground: as for buildings(); the roofs of this call count their
-        points against the same dtm, and the Ground is returned as a fourth value."""
+        points against the same dtm, and the Ground is returned as a fourth value.  evidence: as for buildings(); the
+        RoofEvidence is returned as the last value."""
         if ground is not None:
             g = self.ground(xyz, points=False, **ground)
             with self._ground_model(g):
                 out = self.roof_model(xyz, plane_idx, planes, bin=bin, bin_height=bin_height, threshold=threshold,
                                       kernel_size=kernel_size, iterations=iterations, min_normal_z=min_normal_z,
-                                      min_votes=min_votes, refit=refit)
-            return out + (g,)
+                                      min_votes=min_votes, refit=refit, evidence=evidence)
+            return out[:3] + (g,) + out[3:]
         n_planes = len(planes)
         if [p.id for p in planes] != list(range(1, n_planes + 1)):
             raise ValueError("roof_model: planes must be the planes 1 .. n of segment(), in order")
         normal = np.array([p.normal for p in planes], dtype=np.float64).reshape(n_planes, 3)
         center = np.array([p.center for p in planes], dtype=np.int32).reshape(n_planes, 3)
-        fp, b = self.buildings(xyz, plane_idx, n_planes, bin=bin, bin_height=bin_height, threshold=threshold,
-                               kernel_size=kernel_size, iterations=iterations)
+        fp, b, *ev = self.buildings(xyz, plane_idx, n_planes, bin=bin, bin_height=bin_height, threshold=threshold,
+                                    kernel_size=kernel_size, iterations=iterations, evidence=evidence)
         fit = None
         if refit:
             fit = self.plane_fit(xyz, plane_idx, n_planes)
@@ -636,7 +648,7 @@ class Context:
         home = roof_homes(normal, b.votes.plane_building, b.votes.votes_in, b.votes.votes_total, min_normal_z)
         r = self.roofs(xyz, b.map, plane_idx, home, normal, center, bin=bin, ground_th=b.ground_th, min_votes=min_votes)
         r.fit = fit
-        return fp, b, r
+        return (fp, b, r) + tuple(ev)
 
     # ---- solids: a closed oriented mesh per building from the roof image (bs_solids, include/bs_api.h) ---------------
     def solids(self, bmap, roofs, buildings=None, base_z=None, flat=None, top=True):
@@ -685,29 +697,31 @@ class Context:
 
     def solid_model(self, xyz, plane_idx, planes, bin=100, bin_height=1000, threshold=10, kernel_size=5, iterations=2,
                     min_normal_z=0.5, min_votes=1, refit=False, base_z=None, flat=None, generalise=None, terrain=None,
-                    ground=None):
+                    ground=None, evidence=None):
         """roof_model() followed by solids(): returns (Footprints, Buildings, Roofs, Solids).  generalise: a dict of the
         parameters of generalise_roofs() (min_pixels, merge_flat, step_tol, bend_tol, max_rounds); the Roofs returned are
         then the generalised ones and the Solids theirs.  terrain: a dict of the parameters of terrain() (ring, q,
         min_ground; {} for its defaults): the stage runs after the buildings with fallback_z = int(ground_th), its `ground`
         is the base of every building for the generalisation and the solids (flat defaults to it where a building has no
         point above ground), the context's own table is restored afterwards, and the Terrain is returned as a fifth
-        value.  ground: as for roof_model(); the Ground is returned as an additional last value."""
+        value.  ground: as for roof_model(); the Ground is returned as an additional value after these.  evidence: as for
+        buildings(); the RoofEvidence is returned as the last value."""
         if ground is not None:
             g = self.ground(xyz, points=False, **ground)
             with self._ground_model(g):
                 out = self.solid_model(xyz, plane_idx, planes, bin=bin, bin_height=bin_height, threshold=threshold,
                                        kernel_size=kernel_size, iterations=iterations, min_normal_z=min_normal_z,
                                        min_votes=min_votes, refit=refit, base_z=base_z, flat=flat, generalise=generalise,
-                                       terrain=terrain)
-            return out + (g,)
-        fp, b, r = self.roof_model(xyz, plane_idx, planes, bin=bin, bin_height=bin_height, threshold=threshold,
-                                   kernel_size=kernel_size, iterations=iterations, min_normal_z=min_normal_z,
-                                   min_votes=min_votes, refit=refit)
+                                       terrain=terrain, evidence=evidence)
+            return (out + (g,)) if evidence is None else (out[:-1] + (g, out[-1]))
+        fp, b, r, *ev = self.roof_model(xyz, plane_idx, planes, bin=bin, bin_height=bin_height, threshold=threshold,
+                                        kernel_size=kernel_size, iterations=iterations, min_normal_z=min_normal_z,
+                                        min_votes=min_votes, refit=refit, evidence=evidence)
+        ev = tuple(ev)
         if terrain is None:
             if generalise is not None:
                 r = self.generalise_roofs(b.map, r, b, base_z=base_z, flat=flat, **generalise).roofs
-            return fp, b, r, self.solids(b.map, r, b, base_z=base_z, flat=flat)
+            return (fp, b, r, self.solids(b.map, r, b, base_z=base_z, flat=flat)) + ev
         t = self.terrain(xyz, b.map, b, bin=bin, fallback_z=int(b.ground_th), **terrain)
         if flat is None:
             scalar, flat = _solid_defaults(b, base_z, None)
@@ -716,7 +730,7 @@ class Context:
             if generalise is not None:
                 r = self.generalise_roofs(b.map, r, b, base_z=base_z, flat=flat, **generalise).roofs
             s = self.solids(b.map, r, b, base_z=base_z, flat=flat)
-        return fp, b, r, s, t
+        return (fp, b, r, s, t) + ev
 
     # ---- roof generalisation: small and coplanar facets merged (bs_roof_generalise, include/bs_api.h) ------------------
     def generalise_roofs(self, bmap, roofs, buildings=None, base_z=None, flat=None, min_pixels=0, merge_flat=False,
@@ -1345,6 +1359,189 @@ class Context:
                 self.set_ground_model(None)
             else:
                 self.set_ground_model(prev[0], prev[1], prev[2])
+
+    # ---- roof evidence and the footprint screen (bs_roof_evidence, bs_set_footprint_screen; include/bs_api.h) ------------------
+    def roof_evidence(self, xyz, plane_idx, n_planes, plane_ok=None, extent=None, bin=100, ground_th=0.0, params=None, images=True,
+                      **kw):
+        """Per pixel of the raster's lattice, whether the points above ground look like a roof (include/bs_api.h, "roof
+        evidence"): the share of them on a plane that counts (plane_ok uint8 [n_planes] of plane_quality(); None: every plane),
+        over a (2r+1)^2 window.  ground_th is the raster's; a ground model of the context takes its place.  params: a dict of
+        evidence_params(), or its keywords directly.  images=False leaves everything but keep out.  Returns RoofEvidence."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+        if xyz.ndim != 2 or xyz.shape[1] != 3:
+            raise ValueError("roof_evidence: xyz must be [n][3]")
+        pi = np.ascontiguousarray(plane_idx, dtype=np.int32)
+        if pi.shape != (len(xyz),):
+            raise ValueError("roof_evidence: plane_idx must be [n]")
+        p = evidence_params(**kw) if params is None else dict(params, **kw)
+        ok = _plane_ok(plane_ok, n_planes)
+        ext = np.ascontiguousarray(xyz.max(0) if extent is None else extent, dtype=np.int32)
+        w, h = grid_dims(ext, bin)
+        keep = np.empty((h, w), np.uint8)
+        imgs = [np.empty((h, w), np.int32) if images else None for _ in range(4)]
+        out = _lib.RoofEvidence()
+        self._check(self._L.bs_roof_evidence(self._h, xyz.ctypes.data, len(xyz), pi.ctypes.data, int(n_planes),
+                                             ok.ctypes.data if ok is not None and len(ok) else None, ext.ctypes.data, int(bin),
+                                             float(ground_th), p["r"], p["min_points"], p["num"], p["den"], keep.ctypes.data,
+                                             *[a.ctypes.data if a is not None else None for a in imgs], C.byref(out)))
+        return _take_evidence(out, n_planes, ok, keep, *imgs)
+
+    def roof_evidence_dev(self, d_xyz, n, d_plane_idx, n_planes, extent, d_keep, plane_ok=None, bin=100, ground_th=0.0,
+                          params=None, d_above=0, d_planar=0, d_win_above=0, d_win_planar=0, **kw):
+        """Device-resident stage (bs_roof_evidence_dev): d_xyz [n][3] and d_plane_idx [n] int32, d_keep (uint8
+        [height][width]) and the optional int32 images are device pointers (ints); plane_ok stays a host table.  Returns the
+        RoofEvidence with its images None."""
+        p = evidence_params(**kw) if params is None else dict(params, **kw)
+        ok = _plane_ok(plane_ok, n_planes)
+        ext = np.ascontiguousarray(extent, dtype=np.int32)
+        out = _lib.RoofEvidence()
+        self._check(self._L.bs_roof_evidence_dev(self._h, d_xyz or None, int(n), d_plane_idx or None, int(n_planes),
+                                                 ok.ctypes.data if ok is not None and len(ok) else None, ext.ctypes.data,
+                                                 int(bin), float(ground_th), p["r"], p["min_points"], p["num"], p["den"],
+                                                 d_keep or None, d_above or None, d_planar or None, d_win_above or None,
+                                                 d_win_planar or None, C.byref(out)))
+        return _take_evidence(out, n_planes, ok)
+
+    def set_footprint_screen(self, keep, device=False):
+        """The image that footprints() on this context ANDs into its thresholded mask before the closing
+        (bs_set_footprint_screen): keep [height][width], non-zero = the pixel may be foreground; a RoofEvidence stands for its
+        keep.  None switches it off, the default.  device=True: keep is (device pointer, width, height); the image is not
+        copied and must outlive the switch."""
+        self._screen_dev = None
+        if keep is None:
+            self._check(self._L.bs_set_footprint_screen(self._h, None, 0, 0))
+            return
+        if device:
+            ptr, w, h = keep
+            self._check(self._L.bs_set_footprint_screen_dev(self._h, ptr or None, int(w), int(h)))
+            self._screen_dev = (ptr, int(w), int(h)) if ptr else None
+            return
+        if isinstance(keep, RoofEvidence):
+            keep = keep.keep
+            if keep is None:
+                raise ValueError("set_footprint_screen: this RoofEvidence holds no keep image (roof_evidence_dev)")
+        k = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        if k.ndim != 2 or k.size == 0:
+            raise ValueError("set_footprint_screen: keep must be [height][width]")
+        self._check(self._L.bs_set_footprint_screen(self._h, k.ctypes.data, k.shape[1], k.shape[0]))
+
+    def footprint_screen(self):
+        """keep uint8 [height][width] as the context reads it now (bs_get_footprint_screen), or None while the switch is off."""
+        w, h = C.c_int32(0), C.c_int32(0)
+        self._check(self._L.bs_get_footprint_screen(self._h, None, 0, C.byref(w), C.byref(h)))
+        if w.value == 0:
+            return None
+        k = np.empty((h.value, w.value), np.uint8)
+        self._check(self._L.bs_get_footprint_screen(self._h, k.ctypes.data, k.size, C.byref(w), C.byref(h)))
+        return k
+
+    @contextmanager
+    def _footprint_screen(self, keep):
+        """the footprint screen for one call, the previous one (a device image as the pointer it was) restored behind it"""
+        prev_dev = getattr(self, "_screen_dev", None)
+        prev = None if prev_dev else self.footprint_screen()
+        self.set_footprint_screen(keep)
+        try:
+            yield
+        finally:
+            if prev_dev:
+                self.set_footprint_screen(prev_dev, device=True)
+            else:
+                self.set_footprint_screen(prev)
+
+    def _evidence(self, xyz, plane_idx, n_planes, bin, ground_th, evidence):
+        """plane_fit -> plane_quality -> roof_evidence for evidence= of buildings()"""
+        p = evidence_params(**evidence)
+        fit = self.plane_fit(xyz, plane_idx, n_planes)
+        ok = plane_quality(fit, p["min_plane_points"], p["max_rms_mm"])
+        ev = self.roof_evidence(xyz, plane_idx, n_planes, ok, bin=bin, ground_th=ground_th, params=p, images=False)
+        ev.fit = fit
+        if ev.n_planes > 0 and ev.planes_ok == 0:
+            warnings.warn(f"evidence: none of the {ev.n_planes} planes passes the quality rule (max_rms_mm={p['max_rms_mm']}, "
+                          f"min_plane_points={p['min_plane_points']}): the screen rejects every pixel and no building will be found; "
+                          "read RoofEvidence.fit (r_sq_sum / n_points) and choose max_rms_mm from it", RuntimeWarning, stacklevel=3)
+        return ev
+
+
+def evidence_params(r=3, min_points=1, share=(1, 2), min_plane_points=0, max_rms_mm=100):
+    """The parameters of Context.roof_evidence() and of evidence= as a dict: r (pixels, the window is (2r+1)^2), min_points
+    (counting points a window needs), num / den (the share of them that must lie on a good plane), and the rule of
+    plane_quality() that says which planes are good: min_plane_points and max_rms_mm."""
+    return dict(r=int(r), min_points=int(min_points), num=int(share[0]), den=int(share[1]),
+                min_plane_points=int(min_plane_points), max_rms_mm=int(max_rms_mm))
+
+
+def plane_quality(fits, min_points=0, max_rms_mm=100) -> np.ndarray:
+    """ok uint8 [n_planes] of a PlaneFits (bs_plane_quality; host only): a plane counts iff it was fitted, has at least
+    min_points points and the rms residual of its fit is at most max_rms_mm -- exactly, in integers: r_sq_sum <= max_rms_mm^2
+    * n_points.  The slabs the grower cuts out of a tree crown fail it."""
+    L = _lib.load()
+    n = int(fits.n_planes)
+    arrs = {k: np.ascontiguousarray(getattr(fits, k), dtype=dt).reshape(-1)
+            for k, dt in (("status", np.int32), ("n_points", np.int64), ("r_sq_sum", np.int64))}
+    if any(len(a) != n for a in arrs.values()):
+        raise ValueError("plane_quality: status, n_points and r_sq_sum must be [n_planes]")
+    f = _lib.PlaneFits()
+    f.n_planes = n
+    f.status = arrs["status"].ctypes.data_as(C.POINTER(C.c_int32))
+    f.n_points = arrs["n_points"].ctypes.data_as(C.POINTER(C.c_int64))
+    f.r_sq_sum = arrs["r_sq_sum"].ctypes.data_as(C.POINTER(C.c_int64))
+    ok = np.zeros(n, np.uint8)
+    rc = L.bs_plane_quality(C.byref(f), int(min_points), int(max_rms_mm), ok.ctypes.data if n else None)
+    if rc != _lib.BS_OK:
+        raise BsError(rc, "plane quality: min_points < 0 or max_rms_mm outside 0 .. 32767")
+    return ok
+
+
+@dataclass
+class RoofEvidence:
+    """bs_roof_evidence: the lattice, the parameters of the call, the figures, and the images [height][width]: keep (uint8, what
+    Context.set_footprint_screen() takes), above, planar, win_above, win_planar (int32).  plane_ok is the table the call
+    counted by (None: every plane), n_planes its length and planes_ok how many of its planes count: with planes_ok == 0 <
+    n_planes nothing is planar and keep is all zero.  The images are None after roof_evidence_dev or where they were switched
+    off."""
+    width: int
+    height: int
+    r: int
+    min_points: int
+    num: int
+    den: int
+    grid: int
+    tile: int
+    max_window: int
+    n_points: int
+    n_counted: int
+    n_planar: int
+    n_pixels: int
+    pixels_kept: int
+    pixels_rejected: int
+    pixels_thin: int
+    n_planes: int = 0
+    planes_ok: int = 0
+    info: dict = field(default_factory=dict)
+    plane_ok: np.ndarray | None = field(default=None, repr=False)
+    keep: np.ndarray | None = field(default=None, repr=False)
+    above: np.ndarray | None = field(default=None, repr=False)
+    planar: np.ndarray | None = field(default=None, repr=False)
+    win_above: np.ndarray | None = field(default=None, repr=False)
+    win_planar: np.ndarray | None = field(default=None, repr=False)
+    fit: PlaneFits | None = field(default=None, repr=False)  # the fit plane_ok was judged by, after evidence=
+
+
+def _take_evidence(out, n_planes, plane_ok=None, keep=None, above=None, planar=None, win_above=None, win_planar=None) -> RoofEvidence:
+    head = {n: getattr(out, n) for n in _lib.EVIDENCE_NARROW[:-1] + _lib.EVIDENCE_WIDE}
+    head.update(n_planes=int(n_planes), planes_ok=int(n_planes) if plane_ok is None else int(np.count_nonzero(plane_ok)))
+    return RoofEvidence(**head, info={n: getattr(out, n) for n in _lib.EVIDENCE_MS}, plane_ok=plane_ok, keep=keep, above=above,
+                        planar=planar, win_above=win_above, win_planar=win_planar)
+
+
+def _plane_ok(plane_ok, n_planes):
+    if plane_ok is None:
+        return None
+    ok = np.ascontiguousarray(np.asarray(plane_ok) != 0, dtype=np.uint8).reshape(-1)
+    if len(ok) != int(n_planes):
+        raise ValueError("roof_evidence: plane_ok must be [n_planes]")
+    return ok
 
 
 def ground_params(cell=500, max_radius_mm=12800, slope=(3, 10), dh0=200, dh_max=2500, tol=200, min_height=2000, radius=None):

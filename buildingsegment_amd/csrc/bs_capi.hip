@@ -285,6 +285,9 @@ void bs_destroy(bs_ctx* c)
   for (auto& b : c->gd)
     b.release();
   c->gm_dev.release();
+  for (auto& b : c->evd)
+    b.release();
+  c->fs_dev.release();
   for (auto& b : c->bt)
     b.release();
   c->tile_desc.release();
@@ -531,6 +534,58 @@ int bs_get_ground_model(bs_ctx* ctx, int32_t* dtm, int64_t capacity, int32_t* wi
   if (m > 0) {
     BS_HIP(ctx, hipSetDevice(ctx->device));
     BS_HIP(ctx, hipMemcpyAsync(dtm, ctx->gm_dev.p, 4 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+    BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return BS_OK;
+}
+
+static int set_footprint_screen(bs_ctx* ctx, const uint8_t* keep, bool on_device, int32_t width, int32_t height)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (!keep) {
+    ctx->fs_ptr = nullptr;
+    return BS_OK;
+  }
+  if (width < 1 || height < 1 || (long long)width * height >= (1ll << 31) - 1)
+    return bs::fail(ctx, BS_ERR_INVALID, "footprint screen: width or height < 1, or width * height >= 2^31 - 1");
+  ctx->fs_ptr = nullptr;  // (off, also where the copy below fails)
+  if (!on_device) {
+    const size_t bytes = (size_t)width * (size_t)height;
+    BS_HIP(ctx, hipSetDevice(ctx->device));
+    BS_HIP(ctx, ctx->fs_dev.reserve(bytes));
+    BS_HIP(ctx, hipMemcpyAsync(ctx->fs_dev.p, keep, bytes, hipMemcpyHostToDevice, ctx->stream));
+    BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    keep = ctx->fs_dev.as<uint8_t>();
+  }
+  ctx->fs_w = width;
+  ctx->fs_h = height;
+  ctx->fs_ptr = keep;
+  return BS_OK;
+}
+
+int bs_set_footprint_screen(bs_ctx* ctx, const uint8_t* keep, int32_t width, int32_t height)
+{
+  return set_footprint_screen(ctx, keep, false, width, height);
+}
+
+int bs_set_footprint_screen_dev(bs_ctx* ctx, const uint8_t* d_keep, int32_t width, int32_t height)
+{
+  return set_footprint_screen(ctx, d_keep, true, width, height);
+}
+
+int bs_get_footprint_screen(bs_ctx* ctx, uint8_t* keep, int64_t capacity, int32_t* width, int32_t* height)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if (!width || !height || capacity < 0 || (capacity > 0 && !keep))
+    return bs::fail(ctx, BS_ERR_INVALID, "footprint screen: a null pointer or a negative capacity");
+  *width = ctx->fs_ptr ? ctx->fs_w : 0;
+  *height = ctx->fs_ptr ? ctx->fs_h : 0;
+  const int64_t m = ctx->fs_ptr ? std::min<int64_t>(capacity, (int64_t)ctx->fs_w * ctx->fs_h) : 0;
+  if (m > 0) {
+    BS_HIP(ctx, hipSetDevice(ctx->device));
+    BS_HIP(ctx, hipMemcpyAsync(keep, ctx->fs_ptr, (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
     BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return BS_OK;

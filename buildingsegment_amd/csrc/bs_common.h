@@ -326,6 +326,12 @@ struct bs_ctx {
   bs::DevBuf gm_dev;
   bool gm_on = false;
   int32_t gm_w = 0, gm_h = 0, gm_cell = 0, gm_min = 0;
+  bs::DevBuf evd[10];  // scratch of the roof evidence (bs_evidence.hip); it keeps no state between calls
+  // footprint screen (bs_set_footprint_screen): the image bs_footprints ANDs into its mask; fs_ptr == nullptr = off.  The host
+  // form keeps a copy in fs_dev, the _dev form the caller's pointer
+  bs::DevBuf fs_dev;
+  const uint8_t* fs_ptr = nullptr;
+  int32_t fs_w = 0, fs_h = 0;
   bs::DevBuf sh[25];  // (24 scratch buffers of bs_sharded.hip + the look-up table of bs_remap_rows_dev)
   std::vector<int32_t> sh_seeds;  // all committed seeds of the last bs_segment_sharded (global indices, ascending)
   int64_t sh_nloc = 0;            // points this rank grew

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void max_tiled_kernel(const double* __restrict
 __global__ __launch_bounds__(256) void mask_tiled_kernel(const double* __restrict__ img, const FpTile* __restrict__ tiles,
                                                          const int32_t* __restrict__ pb, int32_t nt, int64_t np, int thr,
                                                          const unsigned long long* __restrict__ mx,
-                                                         uint8_t* __restrict__ m)
+                                                         const uint8_t* __restrict__ screen, uint8_t* __restrict__ m)
 {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= np)
@@ -126,6 +126,8 @@ __global__ __launch_bounds__(256) void mask_tiled_kernel(const double* __restric
       const double q0 = 255.0 * (1.0 * img[3 * ((int64_t)T.ibase + (int64_t)(y - 1) * T.w + (x - 1)) + 1] / max1);
       const int q = q0 > 0 ? (int)q0 : 0;
       v = q > thr;  // threshold(..., 10, 255, THRESH_BINARY), my_function.cpp:20
+      if (screen)  // bs_set_footprint_screen: one tile, whose image is the screen's
+        v &= screen[(int64_t)(y - 1) * T.w + (x - 1)] != 0;
     }
   }
   m[i] = v;
@@ -576,6 +578,10 @@ int footprints_tiles_dev(bs_ctx* ctx, const double* d_image, const int32_t* widt
                          bs_contours* out, int32_t* contour_offset, bs_footprint_info* info, const char* who)
 {
   const int32_t nt = n_tiles;
+  if (ctx->fs_ptr && nt > 1)
+    return fail(ctx, BS_ERR_INVALID, "footprints batch: more than one tile while a footprint screen is set (bs_set_footprint_screen)");
+  if (ctx->fs_ptr && (width[0] != ctx->fs_w || height[0] != ctx->fs_h))
+    return fail(ctx, BS_ERR_INVALID, "footprints: the raster's width / height differ from the footprint screen's");
   std::vector<FpTile> tl(nt);
   std::vector<int32_t> pb(nt + 1), ib(nt + 1), bb(nt + 1);
   std::vector<PixBlock> blk;
@@ -648,7 +654,7 @@ int footprints_tiles_dev(bs_ctx* ctx, const double* d_image, const int32_t* widt
   BS_HIP(ctx, hipMemsetAsync(B[7].p, 0, misc, st));
   if (!blk.empty())
     max_tiled_kernel<<<(int)blk.size(), 256, 0, st>>>(d_image, d_blk, d_mx);
-  mask_tiled_kernel<<<nblk(np, 256), 256, 0, st>>>(d_image, d_tl, d_pb, nt, np, threshold, d_mx, mA);
+  mask_tiled_kernel<<<nblk(np, 256), 256, 0, st>>>(d_image, d_tl, d_pb, nt, np, threshold, d_mx, ctx->fs_ptr, mA);
   BS_HIP(ctx, hipEventRecord(ev.e[1], st));
 
   uint8_t* m = mA;

@@ -2048,6 +2048,86 @@ int bs_set_ground_model_dev(bs_ctx* ctx, const int32_t* d_dtm, int32_t width, in
 int bs_get_ground_model(bs_ctx* ctx, int32_t* dtm, int64_t capacity, int32_t* width, int32_t* height, int32_t* cell,
                         int32_t* min_height);
 
+/* ---- plane quality: which planes of the segmentation are planes ----
+ *
+ * Host only, no context.  The grower cuts slabs of th_thickness out of anything dense, a tree crown included; the fit tells
+ * them apart.  ok [n_planes] uint8, entry p - 1 is plane p:
+ *     ok = status == 0 && n_points >= min_points && r_sq_sum <= (int64) max_rms * max_rms * n_points
+ * that is, the rms residual of the least-squares plane is at most max_rms millimetres.  Integers only.  Only n_planes, status,
+ * n_points and r_sq_sum of f are read.
+ * BS_ERR_INVALID: f NULL, n_planes < 0, a NULL array or ok with n_planes > 0, min_points < 0, max_rms outside 0 .. 32767. */
+int bs_plane_quality(const struct bs_plane_fits* f, int64_t min_points, int32_t max_rms, uint8_t* ok);
+
+/* ---- roof evidence: the share of the points above ground that lie on a good plane, per pixel ----
+ *
+ * bs_footprints makes a building of every connected blob of pixels that a point above ground touches; a tree is such a blob.
+ * This stage says per pixel whether what stands there looks like a roof, and bs_set_footprint_screen below lets the footprints
+ * take it into account.  The cloud is shifted to its origin; the lattice is bs_grid_dims(extent, bin) = (width, height).
+ * All exact integers:
+ *   - a point COUNTS iff it is not below ground by the rule of the raster: !(z < ground_th), or, while bs_set_ground_model is
+ *     set, the per-point rule of that paragraph;
+ *   - the pixel of a point is (x / bin, y / bin), the base pixel of its splat, as in bs_assign_buildings;
+ *   - above[pix] = the counting points of the pixel; planar[pix] = those of them with 1 <= plane_idx <= n_planes and
+ *     plane_ok[plane_idx - 1] != 0 (plane_ok NULL: every plane counts).  Every other label is unlabelled, as in
+ *     bs_plane_buildings;
+ *   - A[pix], P[pix] = the sums of above and planar over the square [x - r, x + r] x [y - r, y + r] clipped to the image;
+ *   - keep[pix] = A >= min_points && (int64) P * den >= (int64) num * A.
+ * With r >= 1 the window covers the far pixels of a point's bilinear splat.  With r = 0 a pixel that only a neighbour's splat
+ * touches has A = 0 and is rejected: r = 0 under the screen eats the east and south rim of every footprint.
+ * 0 <= r <= BS_EVIDENCE_RMAX, min_points >= 1, den >= 1, 0 <= num <= den.
+ * Outputs: keep uint8 [height][width] (0 / 1); above, planar, win_above (A), win_planar (P) int32 [height][width], each may
+ * be NULL.  plane_ok [n_planes] is a host table in both forms.
+ * BS_ERR_INVALID: a null pointer (keep and out included), n < 1, bin < 1, n_planes < 0, a bad extent or parameter.
+ * BS_ERR_RANGE: n >= 2^29, width * height >= 2^31 - 1, or a point with a negative x or y or whose pixel lies outside the
+ * lattice.  On an error no output and nothing of `out` is written. */
+#define BS_EVIDENCE_RMAX 15
+#define BS_EVIDENCE_TILE 32  /* a workgroup of the window kernel writes TILE x TILE pixels */
+#define BS_EVIDENCE_GRID 256 /* workgroups of the window kernel: beyond 256 tiles a workgroup takes several */
+struct bs_roof_evidence {
+  int32_t width, height;
+  int32_t r, min_points, num, den; /* of the call */
+  int32_t grid, tile;              /* BS_GROUND_GRID (the pass over the points), BS_EVIDENCE_TILE of the library */
+  int32_t max_window;              /* the largest A */
+  int32_t pad_;
+  int64_t n_points;        /* n */
+  int64_t n_counted;       /* points that count: the sum of above */
+  int64_t n_planar;        /* of them on a plane that counts: the sum of planar */
+  int64_t n_pixels;        /* pixels with above > 0 */
+  int64_t pixels_kept;     /* keep == 1 */
+  int64_t pixels_rejected; /* A >= min_points, share too low */
+  int64_t pixels_thin;     /* 0 < A < min_points */
+  /* device time (HIP events on the context's stream) */
+  double ms_counts; /* the pass over the points (with the clearing of its image) */
+  double ms_window; /* window sums, keep, images and figures */
+};
+/* d_xyz [n][3], d_plane_idx [n] int32 and the images are device pointers. */
+int bs_roof_evidence_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, const int32_t* d_plane_idx, int32_t n_planes,
+                         const uint8_t* plane_ok, const int32_t* extent, int32_t bin, double ground_th, int32_t r,
+                         int32_t min_points, int32_t num, int32_t den, uint8_t* d_keep, int32_t* d_above, int32_t* d_planar,
+                         int32_t* d_win_above, int32_t* d_win_planar, struct bs_roof_evidence* out);
+/* The same from and into host memory. */
+int bs_roof_evidence(bs_ctx* ctx, const int32_t* xyz, int64_t n, const int32_t* plane_idx, int32_t n_planes,
+                     const uint8_t* plane_ok, const int32_t* extent, int32_t bin, double ground_th, int32_t r,
+                     int32_t min_points, int32_t num, int32_t den, uint8_t* keep, int32_t* above, int32_t* planar,
+                     int32_t* win_above, int32_t* win_planar, struct bs_roof_evidence* out);
+
+/* ---- footprint screen: footprints of the pixels that pass a test ----
+ *
+ * A switch of the context, as bs_set_ground_model.  keep [height][width] uint8 (in the pipeline: keep of bs_roof_evidence over
+ * the raster's lattice); a NULL image switches it off, which is the default.  While it is set, step 2 of bs_footprints[_dev]
+ * reads "foreground iff q > threshold AND keep[pixel] != 0"; the quantisation, the closing, the labelling, the tracing and
+ * the mask output are unchanged.  A call whose width / height differ from the screen's returns BS_ERR_INVALID, and so does
+ * bs_footprints_batch* with more than one tile (one image cannot serve two tiles); a batch of one works.  Switched off,
+ * every byte the footprints write is what they write without this paragraph.
+ * BS_ERR_INVALID: width or height < 1, width * height >= 2^31 - 1. */
+int bs_set_footprint_screen(bs_ctx* ctx, const uint8_t* keep, int32_t width, int32_t height);
+/* The same from a device image, which is NOT copied: the context keeps d_keep and every later footprints call reads whatever it
+ * holds then.  It must stay allocated until the switch is cleared or set again. */
+int bs_set_footprint_screen_dev(bs_ctx* ctx, const uint8_t* d_keep, int32_t width, int32_t height);
+/* width and height of the screen (0 while it is off) and its first min(capacity, width * height) bytes into keep, which may
+ * be NULL with capacity == 0.  BS_ERR_INVALID: a null number, a negative capacity, or a null keep with capacity > 0. */
+int bs_get_footprint_screen(bs_ctx* ctx, uint8_t* keep, int64_t capacity, int32_t* width, int32_t* height);
+
 #ifdef __cplusplus
 }
 #endif
