@@ -13,7 +13,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "bs_common.h"
+#include "bs_host.h"
 
 namespace bs {
 
@@ -289,23 +289,22 @@ int bs_segment_batch(bs_ctx* ctx, const int32_t* xyz, const int64_t* tile_offset
     return rc;
   if (!xyz || !plane_idx)
     return fail(ctx, BS_ERR_INVALID, "null host pointer");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  BS_HIP(ctx, ctx->d_xyz_h.reserve(sizeof(int32_t) * 3 * n));
-  BS_HIP(ctx, ctx->d_neigh_h.reserve(sizeof(int32_t) * n * p->k));
-  BS_HIP(ctx, ctx->d_normals_h.reserve(sizeof(double) * 3 * n));
-  BS_HIP(ctx, ctx->d_plane_h.reserve(sizeof(int32_t) * n));
-  hipStream_t st = ctx->stream;
-  BS_HIP(ctx, hipMemcpyAsync(ctx->d_xyz_h.p, xyz, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice, st));
-  rc = bs_segment_batch_dev(ctx, ctx->d_xyz_h.as<int32_t>(), tile_offset, n_tiles, p, ctx->d_neigh_h.as<int32_t>(),
-                            ctx->d_normals_h.as<double>(), ctx->d_plane_h.as<int32_t>());
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(ctx->d_xyz_h, xyz, 3 * n);
+  int32_t* d_neigh = S.room<int32_t>(ctx->d_neigh_h, n * p->k);
+  double* d_normals = S.room<double>(ctx->d_normals_h, 3 * n);
+  int32_t* d_plane = S.room<int32_t>(ctx->d_plane_h, n);
+  if (!S.ok())
+    return S.status();
+  rc = bs_segment_batch_dev(ctx, d_xyz, tile_offset, n_tiles, p, d_neigh, d_normals, d_plane);
   if (rc != BS_OK)
     return rc;
-  if (neigh)
-    BS_HIP(ctx, hipMemcpyAsync(neigh, ctx->d_neigh_h.p, sizeof(int32_t) * n * p->k, hipMemcpyDeviceToHost, st));
-  if (normals)
-    BS_HIP(ctx, hipMemcpyAsync(normals, ctx->d_normals_h.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipMemcpyAsync(plane_idx, ctx->d_plane_h.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
+  S.download(neigh, d_neigh, n * p->k);
+  S.download(normals, d_normals, 3 * n);
+  S.download(plane_idx, d_plane, n);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
   if (planes || plane_offset)
     return bs_batch_planes_fetch(ctx, planes, plane_offset);
   return BS_OK;

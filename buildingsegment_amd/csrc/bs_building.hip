@@ -623,17 +623,20 @@ extern "C" int bs_building_map(bs_ctx* ctx, const uint8_t* mask, int32_t width, 
     memset(out, 0, sizeof *out);
   if (!mask || !map || !out || bad_raster(width, height))
     return fail(ctx, BS_ERR_INVALID, "building map: null pointer or bad raster size");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
   const size_t npix = (size_t)width * height;
-  BS_HIP(ctx, ctx->bd[BD_IN_A].reserve(npix));
-  BS_HIP(ctx, ctx->bd[BD_IN_B].reserve(4 * npix));
-  BS_HIP(ctx, hipMemcpyAsync(ctx->bd[BD_IN_A].p, mask, npix, hipMemcpyHostToDevice, ctx->stream));
-  const int rc = bs_building_map_dev(ctx, ctx->bd[BD_IN_A].as<uint8_t>(), width, height, ctx->bd[BD_IN_B].as<int32_t>(), out);
+  Staging S(ctx);
+  const uint8_t* d_mask = S.upload(ctx->bd[BD_IN_A], mask, npix);
+  int32_t* d_map = S.room<int32_t>(ctx->bd[BD_IN_B], npix);
+  if (!S.ok())
+    return S.status();
+  int rc = bs_building_map_dev(ctx, d_mask, width, height, d_map, out);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipMemcpyAsync(map, ctx->bd[BD_IN_B].p, 4 * npix, hipMemcpyDeviceToHost, ctx->stream));
-  BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return BS_OK;
+  FreeUnlessKept<bs_buildings, bs_buildings_free> guard{out};
+  S.download(map, d_map, npix);
+  rc = S.finish();
+  guard.keep = rc == BS_OK;
+  return rc;
 }
 
 extern "C" int bs_assign_buildings_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, double ground_th,
@@ -700,21 +703,18 @@ extern "C" int bs_assign_buildings(bs_ctx* ctx, const int32_t* xyz, int64_t n, i
     return fail(ctx, BS_ERR_INVALID, "assign buildings: null pointer, n < 1, bin < 1 or bad raster size");
   if (n >= (1ll << 29))
     return fail(ctx, BS_ERR_RANGE, "assign buildings: 2^29 points or more");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t npix = (size_t)width * height;
   DevBuf* B = ctx->bd;
-  BS_HIP(ctx, B[BD_IN_A].reserve(12 * (size_t)n));
-  BS_HIP(ctx, B[BD_IN_B].reserve(4 * npix));
-  BS_HIP(ctx, B[BD_IN_C].reserve(4 * (size_t)n));
-  BS_HIP(ctx, hipMemcpyAsync(B[BD_IN_A].p, xyz, 12 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  BS_HIP(ctx, hipMemcpyAsync(B[BD_IN_B].p, map, 4 * npix, hipMemcpyHostToDevice, ctx->stream));
-  const int rc = bs_assign_buildings_dev(ctx, B[BD_IN_A].as<int32_t>(), n, bin, ground_th, B[BD_IN_B].as<int32_t>(), width,
-                                         height, B[BD_IN_C].as<int32_t>(), inout);
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(B[BD_IN_A], xyz, 3 * (size_t)n);
+  const int32_t* d_map = S.upload(B[BD_IN_B], map, (size_t)width * height);
+  int32_t* d_idx = S.room<int32_t>(B[BD_IN_C], (size_t)n);
+  if (!S.ok())
+    return S.status();
+  const int rc = bs_assign_buildings_dev(ctx, d_xyz, n, bin, ground_th, d_map, width, height, d_idx, inout);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipMemcpyAsync(building_idx, B[BD_IN_C].p, 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-  BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return BS_OK;
+  S.download(building_idx, d_idx, (size_t)n);
+  return S.finish();
 }
 
 extern "C" int bs_plane_buildings_dev(bs_ctx* ctx, const int32_t* d_plane_idx, const int32_t* d_building_idx, int64_t n,
@@ -806,14 +806,14 @@ extern "C" int bs_plane_buildings(bs_ctx* ctx, const int32_t* plane_idx, const i
     return fail(ctx, BS_ERR_INVALID, "plane buildings: null pointer, n < 1, n_planes < 0 or n_buildings < 0");
   if (n >= (1ll << 29))
     return fail(ctx, BS_ERR_RANGE, "plane buildings: 2^29 points or more");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  DevBuf* B = ctx->bd;
-  BS_HIP(ctx, B[BD_IN_A].reserve(4 * (size_t)n));
-  BS_HIP(ctx, B[BD_IN_C].reserve(4 * (size_t)n));
-  BS_HIP(ctx, hipMemcpyAsync(B[BD_IN_A].p, plane_idx, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  BS_HIP(ctx, hipMemcpyAsync(B[BD_IN_C].p, building_idx, 4 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-  return bs_plane_buildings_dev(ctx, B[BD_IN_A].as<int32_t>(), B[BD_IN_C].as<int32_t>(), n, n_planes, n_buildings,
-                                plane_building, votes_in, votes_total, votes_outside);
+  Staging S(ctx);
+  const int32_t* d_plane = S.upload(ctx->bd[BD_IN_A], plane_idx, (size_t)n);
+  const int32_t* d_building = S.upload(ctx->bd[BD_IN_C], building_idx, (size_t)n);
+  if (!S.ok())
+    return S.status();
+  // (the results are host arrays that the device form fills and waits for: nothing to download or finish)
+  return bs_plane_buildings_dev(ctx, d_plane, d_building, n, n_planes, n_buildings, plane_building, votes_in, votes_total,
+                                votes_outside);
 }
 
 // The format is written down in include/bs_api.h.

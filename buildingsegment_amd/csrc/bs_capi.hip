@@ -6,7 +6,7 @@
 #include <cstring>
 #include <new>
 
-#include "bs_common.h"
+#include "bs_host.h"
 
 namespace bs {
 
@@ -240,69 +240,7 @@ void bs_destroy(bs_ctx* c)
   (void)hipSetDevice(c->device);
   if (c->stream)
     (void)hipStreamSynchronize(c->stream);
-  bs::DevBuf* bufs[] = {&c->keys_in, &c->keys_out, &c->vals_in, &c->vals_out, &c->cub_tmp, &c->uniq_keys,
-                        &c->uniq_cnt, &c->misc, &c->table, &c->spts, &c->slocal, &c->fb_list, &c->d_xyz_h,
-                        &c->d_neigh_h, &c->d_normals_h, &c->d_plane_h, &c->seg_neigh, &c->seg_normals,
-                        &c->rg_list, &c->rg_stack, &c->rg_planes, &c->rg_stats, &c->rg_aux, &c->rg_pstore, &c->rg_rec, &c->rg_radj, &c->rg_roff, &c->rg_geo, &c->rg_gs, &c->rg_disp, &c->seg_npos,
-                        &c->rs_keys_in, &c->rs_keys_out, &c->rs_vals_in, &c->rs_vals_out, &c->rs_cnt, &c->rs_img, &c->rs_tmp};
-  for (auto* b : bufs)
-    b->release();
-  for (auto& b : c->sh)
-    b.release();
-  for (auto& b : c->fp)
-    b.release();
-  for (auto& b : c->bd)
-    b.release();
-  for (auto& b : c->rf)
-    b.release();
-  for (auto& b : c->ft)
-    b.release();
-  for (auto& b : c->sd)
-    b.release();
-  for (auto& b : c->fc)
-    b.release();
-  for (auto& b : c->ol)
-    b.release();
-  for (auto& b : c->sp)
-    b.release();
-  for (auto& b : c->uc)
-    b.release();
-  for (auto& b : c->sw)
-    b.release();
-  for (auto& b : c->tr)
-    b.release();
-  for (auto& b : c->ps)
-    b.release();
-  for (auto& b : c->mr)
-    b.release();
-  for (auto& b : c->pr)
-    b.release();
-  for (auto& b : c->gn)
-    b.release();
-  for (auto& b : c->tn)
-    b.release();
-  c->bases_dev.release();
-  for (auto& b : c->gd)
-    b.release();
-  c->gm_dev.release();
-  for (auto& b : c->evd)
-    b.release();
-  c->fs_dev.release();
-  for (auto& b : c->bt)
-    b.release();
-  c->tile_desc.release();
-  c->rg_hout.release();
-  for (auto& e : c->ev)
-    if (e)
-      (void)hipEventDestroy(e);
-  for (auto& e : c->sev)
-    if (e)
-      (void)hipEventDestroy(e);
-  if (c->side)
-    (void)hipStreamDestroy(c->side);
-  if (c->own_stream)
-    (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;  // the buffers free themselves, then the events and the streams go (bs_ctx_handles)
 }
 
 const char* bs_last_error(const bs_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -674,19 +612,18 @@ int bs_knn_normals(bs_ctx* ctx, const int32_t* xyz, int64_t n, const bs_params* 
   int rc = check_params(ctx, p, n);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  BS_HIP(ctx, ctx->d_xyz_h.reserve(sizeof(int32_t) * 3 * n));
-  BS_HIP(ctx, ctx->d_neigh_h.reserve(sizeof(int32_t) * n * p->k));
-  BS_HIP(ctx, ctx->d_normals_h.reserve(sizeof(double) * 3 * n));
-  BS_HIP(ctx, hipMemcpyAsync(ctx->d_xyz_h.p, xyz, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
-  rc = bs_knn_normals_dev(ctx, ctx->d_xyz_h.as<int32_t>(), nullptr, n, 0, n, p, ctx->d_neigh_h.as<int32_t>(),
-                          ctx->d_normals_h.as<double>(), 0.0, nullptr);
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(ctx->d_xyz_h, xyz, 3 * n);
+  int32_t* d_neigh = S.room<int32_t>(ctx->d_neigh_h, n * p->k);
+  double* d_normals = S.room<double>(ctx->d_normals_h, 3 * n);
+  if (!S.ok())
+    return S.status();
+  rc = bs_knn_normals_dev(ctx, d_xyz, nullptr, n, 0, n, p, d_neigh, d_normals, 0.0, nullptr);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipMemcpyAsync(neigh, ctx->d_neigh_h.p, sizeof(int32_t) * n * p->k, hipMemcpyDeviceToHost, ctx->stream));
-  BS_HIP(ctx, hipMemcpyAsync(normals, ctx->d_normals_h.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, ctx->stream));
-  BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return BS_OK;
+  S.download(neigh, d_neigh, n * p->k);
+  S.download(normals, d_normals, 3 * n);
+  return S.finish();
 }
 
 int bs_knn_normals_halo(bs_ctx* ctx, const int32_t* xyz, const int32_t* gidx, int64_t n, int64_t n_query,
@@ -705,22 +642,19 @@ int bs_knn_normals_halo(bs_ctx* ctx, const int32_t* xyz, const int32_t* gidx, in
   for (int64_t i = 0; i < n; i++)
     if (gidx[i] < 0)
       return fail(ctx, BS_ERR_INVALID, "negative global index");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  BS_HIP(ctx, ctx->d_xyz_h.reserve(sizeof(int32_t) * 3 * n));
-  BS_HIP(ctx, ctx->d_plane_h.reserve(sizeof(int32_t) * n));  // staging for gidx
-  BS_HIP(ctx, ctx->d_neigh_h.reserve(sizeof(int32_t) * std::max<int64_t>(n_query, 1) * p->k));
-  BS_HIP(ctx, ctx->d_normals_h.reserve(sizeof(double) * 3 * std::max<int64_t>(n_query, 1)));
-  hipStream_t st = ctx->stream;
-  BS_HIP(ctx, hipMemcpyAsync(ctx->d_xyz_h.p, xyz, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(ctx->d_plane_h.p, gidx, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
-  rc = bs_knn_normals_dev(ctx, ctx->d_xyz_h.as<int32_t>(), ctx->d_plane_h.as<int32_t>(), n, 0, n_query, p,
-                          ctx->d_neigh_h.as<int32_t>(), ctx->d_normals_h.as<double>(), cert_radius, n_uncertified);
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(ctx->d_xyz_h, xyz, 3 * n);
+  const int32_t* d_gidx = S.upload(ctx->d_plane_h, gidx, n);  // (the labels' slot: this call has none)
+  int32_t* d_neigh = S.room<int32_t>(ctx->d_neigh_h, std::max<int64_t>(n_query, 1) * p->k);
+  double* d_normals = S.room<double>(ctx->d_normals_h, 3 * std::max<int64_t>(n_query, 1));
+  if (!S.ok())
+    return S.status();
+  rc = bs_knn_normals_dev(ctx, d_xyz, d_gidx, n, 0, n_query, p, d_neigh, d_normals, cert_radius, n_uncertified);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipMemcpyAsync(neigh, ctx->d_neigh_h.p, sizeof(int32_t) * n_query * p->k, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipMemcpyAsync(normals, ctx->d_normals_h.p, sizeof(double) * 3 * n_query, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
-  return BS_OK;
+  S.download(neigh, d_neigh, n_query * p->k);
+  S.download(normals, d_normals, 3 * n_query);
+  return S.finish();
 }
 
 int bs_region_grow(bs_ctx* ctx, const int32_t* xyz, const double* normals, const int32_t* neigh, int64_t n,
@@ -739,23 +673,22 @@ int bs_region_grow(bs_ctx* ctx, const int32_t* xyz, const double* normals, const
   for (int64_t i = 0; i < n * (int64_t)p->k; i++)
     if (neigh[i] < 0 || neigh[i] >= n)
       return fail(ctx, BS_ERR_INVALID, "neighbour index out of range");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  BS_HIP(ctx, ctx->d_xyz_h.reserve(sizeof(int32_t) * 3 * n));
-  BS_HIP(ctx, ctx->d_neigh_h.reserve(sizeof(int32_t) * n * p->k));
-  BS_HIP(ctx, ctx->d_normals_h.reserve(sizeof(double) * 3 * n));
-  BS_HIP(ctx, ctx->d_plane_h.reserve(sizeof(int32_t) * n));
-  hipStream_t st = ctx->stream;
-  BS_HIP(ctx, hipMemcpyAsync(ctx->d_xyz_h.p, xyz, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(ctx->d_neigh_h.p, neigh, sizeof(int32_t) * n * p->k, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(ctx->d_normals_h.p, normals, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(ctx->d_xyz_h, xyz, 3 * n);
+  const int32_t* d_neigh = S.upload(ctx->d_neigh_h, neigh, n * p->k);
+  const double* d_normals = S.upload(ctx->d_normals_h, normals, 3 * n);
+  int32_t* d_plane = S.room<int32_t>(ctx->d_plane_h, n);
+  if (!S.ok())
+    return S.status();
   ctx->npos_neigh = nullptr;  // the staging buffers now hold the caller's data, not what a previous bs_segment searched
   ctx->npos_normals = nullptr;
-  rc = region_grow_dev_impl(ctx, ctx->d_xyz_h.as<int32_t>(), ctx->d_normals_h.as<double>(),
-                            ctx->d_neigh_h.as<int32_t>(), n, p, ctx->d_plane_h.as<int32_t>(), true);
+  rc = region_grow_dev_impl(ctx, d_xyz, d_normals, d_neigh, n, p, d_plane, true);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipMemcpyAsync(plane_idx, ctx->d_plane_h.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
+  S.download(plane_idx, d_plane, n);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
   if (planes)
     return bs_planes_fetch(ctx, planes);
   return BS_OK;
@@ -773,23 +706,22 @@ int bs_segment(bs_ctx* ctx, const int32_t* xyz, int64_t n, const bs_params* p, i
   int rc = check_params(ctx, p, n);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  BS_HIP(ctx, ctx->d_xyz_h.reserve(sizeof(int32_t) * 3 * n));
-  BS_HIP(ctx, ctx->d_neigh_h.reserve(sizeof(int32_t) * n * p->k));
-  BS_HIP(ctx, ctx->d_normals_h.reserve(sizeof(double) * 3 * n));
-  BS_HIP(ctx, ctx->d_plane_h.reserve(sizeof(int32_t) * n));
-  hipStream_t st = ctx->stream;
-  BS_HIP(ctx, hipMemcpyAsync(ctx->d_xyz_h.p, xyz, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice, st));
-  rc = bs_segment_dev(ctx, ctx->d_xyz_h.as<int32_t>(), n, p, ctx->d_neigh_h.as<int32_t>(),
-                      ctx->d_normals_h.as<double>(), ctx->d_plane_h.as<int32_t>());
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(ctx->d_xyz_h, xyz, 3 * n);
+  int32_t* d_neigh = S.room<int32_t>(ctx->d_neigh_h, n * p->k);
+  double* d_normals = S.room<double>(ctx->d_normals_h, 3 * n);
+  int32_t* d_plane = S.room<int32_t>(ctx->d_plane_h, n);
+  if (!S.ok())
+    return S.status();
+  rc = bs_segment_dev(ctx, d_xyz, n, p, d_neigh, d_normals, d_plane);
   if (rc != BS_OK)
     return rc;
-  if (neigh)
-    BS_HIP(ctx, hipMemcpyAsync(neigh, ctx->d_neigh_h.p, sizeof(int32_t) * n * p->k, hipMemcpyDeviceToHost, st));
-  if (normals)
-    BS_HIP(ctx, hipMemcpyAsync(normals, ctx->d_normals_h.p, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipMemcpyAsync(plane_idx, ctx->d_plane_h.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
+  S.download(neigh, d_neigh, n * p->k);
+  S.download(normals, d_normals, 3 * n);
+  S.download(plane_idx, d_plane, n);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
   if (planes)
     return bs_planes_fetch(ctx, planes);
   return BS_OK;

@@ -13,10 +13,14 @@
 
 namespace bs {
 
-// ---- small RAII-free device buffer that only grows -----------------------
+// ---- small device buffer that only grows, freed with its owner ------------
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   hipError_t reserve(size_t bytes)
   {
     if (bytes <= cap)
@@ -50,6 +54,10 @@ struct DevBuf {
 struct HostBuf {
   void* p = nullptr;
   size_t cap = 0;
+  HostBuf() = default;
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  ~HostBuf() { release(); }
   hipError_t reserve(size_t bytes)
   {
     if (bytes <= cap)
@@ -200,13 +208,32 @@ struct GrowStats {
 }  // namespace bs
 
 // ---- context ---------------------------------------------------------------
-struct bs_ctx {
-  int device = 0;
+// the streams and events of a context: a base, so that they go after every buffer of bs_ctx has freed itself
+struct bs_ctx_handles {
   hipStream_t own_stream = nullptr;
+  hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipStream_t side = nullptr;  // second stream of the grower (validate3 beside the owner passes)
+  hipEvent_t sev[2] = {nullptr, nullptr};
+  ~bs_ctx_handles()
+  {
+    for (auto& e : ev)
+      if (e)
+        (void)hipEventDestroy(e);
+    for (auto& e : sev)
+      if (e)
+        (void)hipEventDestroy(e);
+    if (side)
+      (void)hipStreamDestroy(side);
+    if (own_stream)
+      (void)hipStreamDestroy(own_stream);
+  }
+};
+
+struct bs_ctx : bs_ctx_handles {
+  int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
   bs_timings tm{};
-  hipEvent_t ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
   // grid scratch
   bs::DevBuf keys_in, keys_out, vals_in, vals_out, cub_tmp, uniq_keys, uniq_cnt, misc;
@@ -230,8 +257,6 @@ struct bs_ctx {
   int audit = 0;       // bs_set_audit
   bs_grow_limits lim{0, 0, 0, 0, -1, -1, 0, 0};  // bs_selftest_grow_limits (all defaults)
   bs_grow_counters gc{};                         // bs_get_grow_counters
-  hipStream_t side = nullptr;  // second stream of the grower (validate3 beside the owner passes)
-  hipEvent_t sev[2] = {nullptr, nullptr};
   // 2-D raster scratch (bs_raster.hip)
   bs::DevBuf rs_keys_in, rs_keys_out, rs_vals_in, rs_vals_out, rs_cnt, rs_img, rs_tmp;
   // cell-sorted order of the last grid build (vals_out): spatially coherent iteration for gathers

@@ -31,6 +31,10 @@
 namespace bs {
 namespace {
 
+// the staging slots of the host forms in bs_ctx::fp (0 .. 20: the scratch of footprints_tiles_dev, by number there)
+enum { FP_IN_IMAGE = 21, FP_OUT_MASK, FP_COUNT };
+static_assert(FP_COUNT <= (int)(sizeof(bs_ctx::fp) / sizeof(DevBuf)), "bs_ctx::fp is too short");
+
 constexpr int32_t END = -1;
 constexpr int TW = 64, TH = 16, RMAX = 7;  // closing tile (outputs) and the largest ellipse radius (15 x 15)
 enum : uint8_t { K_INVALID = 0, K_NORMAL = 1, K_TAIL = 2, K_DEAD = 3, K_EMIT = 4 };
@@ -563,6 +567,8 @@ extern "C" void bs_contours_free(bs_contours* c)
 
 namespace {
 
+using ContoursGuard = FreeUnlessKept<bs_contours, bs_contours_free>;
+
 // fail() with the caller's name in front: "footprints" for the solo call, "footprints batch" for a batch
 int fail_as(bs_ctx* ctx, int status, const char* who, const char* what)
 {
@@ -843,22 +849,20 @@ extern "C" int bs_footprints(bs_ctx* ctx, const double* image, int32_t width, in
     return BS_ERR_INVALID;
   if (!image || !out || width < 1 || height < 1 || (int64_t)(width + 2ll) * (height + 2ll) >= (1ll << 31))
     return fail(ctx, BS_ERR_INVALID, "footprints: null pointer or bad raster size");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t img_bytes = sizeof(double) * 3 * (size_t)width * height;
-  const size_t mask_bytes = (size_t)width * height;
-  BS_HIP(ctx, ctx->fp[21].reserve(img_bytes));
-  if (mask)
-    BS_HIP(ctx, ctx->fp[22].reserve(mask_bytes));
-  BS_HIP(ctx, hipMemcpyAsync(ctx->fp[21].p, image, img_bytes, hipMemcpyHostToDevice, ctx->stream));
-  const int rc = bs_footprints_dev(ctx, ctx->fp[21].as<double>(), width, height, threshold, kernel_size, iterations,
-                                   mask ? ctx->fp[22].as<uint8_t>() : nullptr, out, info);
+  const size_t npix = (size_t)width * height;
+  Staging S(ctx);
+  const double* d_image = S.upload(ctx->fp[FP_IN_IMAGE], image, 3 * npix);
+  uint8_t* d_mask = S.room<uint8_t>(ctx->fp[FP_OUT_MASK], npix, mask != nullptr);
+  if (!S.ok())
+    return S.status();
+  int rc = bs_footprints_dev(ctx, d_image, width, height, threshold, kernel_size, iterations, d_mask, out, info);
   if (rc != BS_OK)
     return rc;
-  if (mask) {
-    BS_HIP(ctx, hipMemcpyAsync(mask, ctx->fp[22].p, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return BS_OK;
+  ContoursGuard guard{out};
+  S.download(mask, d_mask, npix);
+  rc = mask ? S.finish() : BS_OK;  // (without a mask nothing is in flight: the device form has waited for its own copies)
+  guard.keep = rc == BS_OK;
+  return rc;
 }
 
 // my_function.cpp:64-131; the GBK captions of the three header lines and the faces line are written in ASCII.
@@ -947,20 +951,18 @@ extern "C" int bs_footprints_batch(bs_ctx* ctx, const double* image, const int32
   }
   if (npix >= (1ll << 31) - 1)
     return fail(ctx, BS_ERR_RANGE, "footprints batch: 2^31 - 1 pixels or more in all");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t img_bytes = sizeof(double) * 3 * (size_t)npix;
-  BS_HIP(ctx, ctx->fp[21].reserve(img_bytes));
-  if (mask)
-    BS_HIP(ctx, ctx->fp[22].reserve((size_t)npix));
-  BS_HIP(ctx, hipMemcpyAsync(ctx->fp[21].p, image, img_bytes, hipMemcpyHostToDevice, ctx->stream));
-  const int rc = bs_footprints_batch_dev(ctx, ctx->fp[21].as<double>(), width, height, n_tiles, threshold, kernel_size,
-                                         iterations, mask ? ctx->fp[22].as<uint8_t>() : nullptr, out, contour_offset,
-                                         info);
+  Staging S(ctx);
+  const double* d_image = S.upload(ctx->fp[FP_IN_IMAGE], image, 3 * (size_t)npix);
+  uint8_t* d_mask = S.room<uint8_t>(ctx->fp[FP_OUT_MASK], (size_t)npix, mask != nullptr);
+  if (!S.ok())
+    return S.status();
+  int rc = bs_footprints_batch_dev(ctx, d_image, width, height, n_tiles, threshold, kernel_size, iterations, d_mask, out,
+                                   contour_offset, info);
   if (rc != BS_OK)
     return rc;
-  if (mask) {
-    BS_HIP(ctx, hipMemcpyAsync(mask, ctx->fp[22].p, (size_t)npix, hipMemcpyDeviceToHost, ctx->stream));
-    BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return BS_OK;
+  ContoursGuard guard{out};
+  S.download(mask, d_mask, (size_t)npix);
+  rc = mask ? S.finish() : BS_OK;  // (without a mask nothing is in flight: the device form has waited for its own copies)
+  guard.keep = rc == BS_OK;
+  return rc;
 }

@@ -342,32 +342,29 @@ extern "C" int bs_roof_evidence(bs_ctx* ctx, const int32_t* xyz, int64_t n, cons
     return rc;
   struct bs_roof_evidence res;
   memset(&res, 0, sizeof res);
-  hipStream_t st = ctx->stream;
   DevBuf* B = ctx->evd;
   const size_t np = (size_t)a.width * (size_t)a.height, nn = (size_t)n;
-  int32_t* host[4] = {above, planar, win_above, win_planar};
-  const int buf[4] = {EV_ABOVE, EV_PLANAR, EV_WIN_ABOVE, EV_WIN_PLANAR};
-  int32_t* dev[4] = {nullptr, nullptr, nullptr, nullptr};
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  BS_HIP(ctx, B[EV_IN_XYZ].reserve(12 * nn));
-  BS_HIP(ctx, B[EV_IN_PLANE].reserve(4 * nn));
-  BS_HIP(ctx, B[EV_KEEP].reserve(np));
-  for (int k = 0; k < 4; k++)
-    if (host[k]) {
-      BS_HIP(ctx, B[buf[k]].reserve(4 * np));
-      dev[k] = B[buf[k]].as<int32_t>();
-    }
-  BS_HIP(ctx, hipMemcpyAsync(B[EV_IN_XYZ].p, xyz, 12 * nn, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(B[EV_IN_PLANE].p, plane_idx, 4 * nn, hipMemcpyHostToDevice, st));
-  rc = evidence(ctx, B[EV_IN_XYZ].as<int32_t>(), n, B[EV_IN_PLANE].as<int32_t>(), plane_ok, a, B[EV_KEEP].as<uint8_t>(), dev[0],
-                dev[1], dev[2], dev[3], res);
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(B[EV_IN_XYZ], xyz, 3 * nn);
+  const int32_t* d_plane = S.upload(B[EV_IN_PLANE], plane_idx, nn);
+  uint8_t* d_keep = S.room<uint8_t>(B[EV_KEEP], np);
+  int32_t* d_above = S.room<int32_t>(B[EV_ABOVE], np, above != nullptr);
+  int32_t* d_planar = S.room<int32_t>(B[EV_PLANAR], np, planar != nullptr);
+  int32_t* d_win_above = S.room<int32_t>(B[EV_WIN_ABOVE], np, win_above != nullptr);
+  int32_t* d_win_planar = S.room<int32_t>(B[EV_WIN_PLANAR], np, win_planar != nullptr);
+  if (!S.ok())
+    return S.status();
+  rc = evidence(ctx, d_xyz, n, d_plane, plane_ok, a, d_keep, d_above, d_planar, d_win_above, d_win_planar, res);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipMemcpyAsync(keep, B[EV_KEEP].p, np, hipMemcpyDeviceToHost, st));
-  for (int k = 0; k < 4; k++)
-    if (host[k])
-      BS_HIP(ctx, hipMemcpyAsync(host[k], dev[k], 4 * np, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
+  S.download(keep, d_keep, np);
+  S.download(above, d_above, np);
+  S.download(planar, d_planar, np);
+  S.download(win_above, d_win_above, np);
+  S.download(win_planar, d_win_planar, np);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
   *out = res;
   return BS_OK;
 }

@@ -286,28 +286,26 @@ extern "C" int bs_roof_facets(bs_ctx* ctx, const int32_t* map, const int32_t* ro
     return BS_ERR_INVALID;
   if (!map || !roof || !top || !facet || !out || bad_image(width, height) || n_buildings < 0 || n_planes < 0)
     return fail(ctx, BS_ERR_INVALID, FACETS_INVALID);
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   const size_t npix = (size_t)width * height;
   DevBuf* B = ctx->fc;
-  BS_HIP(ctx, B[FC_IN_MAP].reserve(4 * npix));
-  BS_HIP(ctx, B[FC_IN_ROOF].reserve(4 * npix));
-  BS_HIP(ctx, B[FC_IN_TOP].reserve(16 * npix));
-  BS_HIP(ctx, B[FC_FACET].reserve(4 * npix));
-  BS_HIP(ctx, hipMemcpyAsync(B[FC_IN_MAP].p, map, 4 * npix, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(B[FC_IN_ROOF].p, roof, 4 * npix, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(B[FC_IN_TOP].p, top, 16 * npix, hipMemcpyHostToDevice, st));
-  const int rc = bs_roof_facets_dev(ctx, B[FC_IN_MAP].as<int32_t>(), B[FC_IN_ROOF].as<int32_t>(), B[FC_IN_TOP].as<int32_t>(),
-                                    width, height, n_buildings, n_planes, B[FC_FACET].as<int32_t>(), out);
+  Staging S(ctx);
+  const int32_t* d_map = S.upload(B[FC_IN_MAP], map, npix);
+  const int32_t* d_roof = S.upload(B[FC_IN_ROOF], roof, npix);
+  const int32_t* d_top = S.upload(B[FC_IN_TOP], top, 4 * npix);
+  int32_t* d_facet = S.room<int32_t>(B[FC_FACET], npix);
+  if (!S.ok())
+    return S.status();
+  struct bs_roof_facets res;
+  int rc = bs_roof_facets_dev(ctx, d_map, d_roof, d_top, width, height, n_buildings, n_planes, d_facet, &res);
   if (rc != BS_OK)
     return rc;
-  hipError_t e = hipMemcpyAsync(facet, B[FC_FACET].p, 4 * npix, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    bs_roof_facets_free(out);
-    return fail(ctx, BS_ERR_HIP, "roof facets: copy to the host", e);
-  }
+  Guard guard{&res};
+  S.download(facet, d_facet, npix);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
+  guard.keep = true;
+  *out = res;
   return BS_OK;
 }
 

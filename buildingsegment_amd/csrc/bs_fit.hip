@@ -563,22 +563,23 @@ extern "C" int bs_plane_fit(bs_ctx* ctx, const int32_t* xyz, int64_t n, const in
     return fail(ctx, BS_ERR_INVALID, FIT_INVALID);
   if (n >= (1ll << 29))
     return fail(ctx, BS_ERR_RANGE, "plane fit: 2^29 points or more");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   DevBuf* B = ctx->ft;
-  BS_HIP(ctx, B[FT_IN_XYZ].reserve(12 * (size_t)n));
-  BS_HIP(ctx, B[FT_IN_PLANE].reserve(4 * (size_t)n));
-  if (residual)
-    BS_HIP(ctx, B[FT_OUT].reserve(4 * (size_t)n));
-  BS_HIP(ctx, hipMemcpyAsync(B[FT_IN_XYZ].p, xyz, 12 * (size_t)n, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(B[FT_IN_PLANE].p, plane_idx, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-  int32_t* d_res = residual ? B[FT_OUT].as<int32_t>() : nullptr;
-  const int rc = bs_plane_fit_dev(ctx, B[FT_IN_XYZ].as<int32_t>(), n, B[FT_IN_PLANE].as<int32_t>(), n_planes, d_res, out);
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(B[FT_IN_XYZ], xyz, 3 * (size_t)n);
+  const int32_t* d_plane = S.upload(B[FT_IN_PLANE], plane_idx, (size_t)n);
+  int32_t* d_res = S.room<int32_t>(B[FT_OUT], (size_t)n, residual != nullptr);
+  if (!S.ok())
+    return S.status();
+  struct bs_plane_fits r;  // (out is written at the end alone: an error leaves it untouched)
+  int rc = bs_plane_fit_dev(ctx, d_xyz, n, d_plane, n_planes, d_res, &r);
   if (rc != BS_OK)
     return rc;
-  if (residual) {
-    BS_HIP(ctx, hipMemcpyAsync(residual, d_res, 4 * (size_t)n, hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipStreamSynchronize(st));
-  }
+  FreeUnlessKept<struct bs_plane_fits, bs_plane_fits_free> guard{&r};
+  S.download(residual, d_res, (size_t)n);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
+  guard.keep = true;
+  *out = r;
   return BS_OK;
 }

@@ -738,28 +738,25 @@ extern "C" int bs_roof_generalise(bs_ctx* ctx, const int32_t* map, const int32_t
   if (!map || !roof || !roof_out || !out ||
       bad_call(width, height, n_buildings, n_planes, normal, center, z_min, z_max, bin, flat, params))
     return fail(ctx, BS_ERR_INVALID, GEN_INVALID);
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   const size_t npix = (size_t)width * height;
   DevBuf* B = ctx->gn;
-  BS_HIP(ctx, B[GN_OUT].reserve(4 * npix));
-  BS_HIP(ctx, B[GN_IN_ROOF].reserve(4 * npix));
-  BS_HIP(ctx, B[GN_IN_MAP].reserve(4 * npix));
-  BS_HIP(ctx, hipMemcpyAsync(B[GN_IN_MAP].p, map, 4 * npix, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(B[GN_IN_ROOF].p, roof, 4 * npix, hipMemcpyHostToDevice, st));
+  Staging S(ctx);
+  int32_t* d_out = S.room<int32_t>(B[GN_OUT], npix);
+  const int32_t* d_roof = S.upload(B[GN_IN_ROOF], roof, npix);
+  const int32_t* d_map = S.upload(B[GN_IN_MAP], map, npix);
+  if (!S.ok())
+    return S.status();
   struct bs_roof_generalise res;
-  const int rc = bs_roof_generalise_dev(ctx, B[GN_IN_MAP].as<int32_t>(), B[GN_IN_ROOF].as<int32_t>(), width, height, n_buildings,
-                                        n_planes, normal, center, z_min, z_max, bin, base_z, flat, params,
-                                        B[GN_OUT].as<int32_t>(), &res);
+  int rc = bs_roof_generalise_dev(ctx, d_map, d_roof, width, height, n_buildings, n_planes, normal, center, z_min, z_max, bin,
+                                  base_z, flat, params, d_out, &res);
   if (rc != BS_OK)
     return rc;
-  hipError_t e = hipMemcpyAsync(roof_out, B[GN_OUT].p, 4 * npix, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  if (e != hipSuccess) {
-    bs_roof_generalise_free(&res);
-    return fail(ctx, BS_ERR_HIP, "roof generalise: copy to the host", e);
-  }
+  FreeUnlessKept<struct bs_roof_generalise, bs_roof_generalise_free> guard{&res};
+  S.download(roof_out, d_out, npix);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
+  guard.keep = true;
   *out = res;
   return BS_OK;
 }

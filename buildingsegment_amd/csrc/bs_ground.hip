@@ -592,31 +592,25 @@ extern "C" int bs_ground(bs_ctx* ctx, const int32_t* xyz, int64_t n, const int32
     return rc;
   struct bs_ground res;
   memset(&res, 0, sizeof res);
-  hipStream_t st = ctx->stream;
   DevBuf* B = ctx->gd;
   const size_t np = (size_t)width * (size_t)height, nn = (size_t)n;
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  BS_HIP(ctx, B[GD_IN_XYZ].reserve(12 * nn));
-  if (hag)
-    BS_HIP(ctx, B[GD_HAG].reserve(4 * nn));
-  if (cls)
-    BS_HIP(ctx, B[GD_CLASS].reserve(nn));
-  BS_HIP(ctx, hipMemcpyAsync(B[GD_IN_XYZ].p, xyz, 12 * nn, hipMemcpyHostToDevice, st));
-  rc = ground(ctx, B[GD_IN_XYZ].as<int32_t>(), n, width, height, *params, threshold, nullptr, nullptr, nullptr,
-              hag ? B[GD_HAG].as<int32_t>() : nullptr, cls ? B[GD_CLASS].as<uint8_t>() : nullptr, res);
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(B[GD_IN_XYZ], xyz, 3 * nn);
+  int32_t* d_hag = S.room<int32_t>(B[GD_HAG], nn, hag != nullptr);
+  uint8_t* d_class = S.room<uint8_t>(B[GD_CLASS], nn, cls != nullptr);
+  if (!S.ok())
+    return S.status();
+  rc = ground(ctx, d_xyz, n, width, height, *params, threshold, nullptr, nullptr, nullptr, d_hag, d_class, res);
   if (rc != BS_OK)
     return rc;
-  if (low)
-    BS_HIP(ctx, hipMemcpyAsync(low, B[GD_LOW].p, 4 * np, hipMemcpyDeviceToHost, st));
-  if (dtm)
-    BS_HIP(ctx, hipMemcpyAsync(dtm, B[GD_DTM].p, 4 * np, hipMemcpyDeviceToHost, st));
-  if (step)
-    BS_HIP(ctx, hipMemcpyAsync(step, B[GD_STEP].p, np, hipMemcpyDeviceToHost, st));
-  if (hag)
-    BS_HIP(ctx, hipMemcpyAsync(hag, B[GD_HAG].p, 4 * nn, hipMemcpyDeviceToHost, st));
-  if (cls)
-    BS_HIP(ctx, hipMemcpyAsync(cls, B[GD_CLASS].p, nn, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
+  S.download(low, B[GD_LOW].as<int32_t>(), np);
+  S.download(dtm, B[GD_DTM].as<int32_t>(), np);
+  S.download(step, B[GD_STEP].as<uint8_t>(), np);
+  S.download(hag, d_hag, nn);
+  S.download(cls, d_class, nn);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
   *out = res;
   return BS_OK;
 }

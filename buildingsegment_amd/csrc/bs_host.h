@@ -1,5 +1,6 @@
 // bs_host.h -- the small host helpers that every stage file used to define for itself: launch sizes, the events of a call's
-// timings, the zeroed host arrays of a result.  Everything is internal to a translation unit.
+// timings, the zeroed host arrays of a result, the staging of a host entry point through the context's buffers (Staging) and
+// the device mesh of the two solid stages (DevMesh).  Everything is internal to a translation unit.
 #pragma once
 
 #include <algorithm>
@@ -55,6 +56,93 @@ struct FreeUnlessKept {
   {
     if (!keep)
       FREE(r);
+  }
+};
+
+// The staging of a host entry point through the context's DevBuf slots: select the device, upload the inputs, make room for
+// the outputs, call the _dev form, download what the caller asked for, finish.  The first HIP error sticks and every later
+// step does nothing, so a host form checks ok() once before the device call and returns finish() at its end; either reports
+// BS_ERR_HIP through fail() with the step's name and the HIP error string.
+struct Staging {
+  bs_ctx* ctx;
+  hipError_t e;
+  const char* what = "host staging: hipSetDevice";
+
+  explicit Staging(bs_ctx* c) : ctx(c), e(hipSetDevice(c->device)) {}
+  bool ok() const { return e == hipSuccess; }
+  int status() const { return ok() ? BS_OK : fail(ctx, BS_ERR_HIP, what, e); }
+  hipError_t step(hipError_t r, const char* name)
+  {
+    if (r != hipSuccess)
+      what = name;
+    return r;
+  }
+
+  // n elements of T in slot b; nullptr, and nothing reserved, where the output is not wanted
+  template <class T>
+  T* room(DevBuf& b, size_t n, bool wanted = true)
+  {
+    if (!wanted || !ok() || (e = step(b.reserve(sizeof(T) * n), "host staging: room")) != hipSuccess)
+      return nullptr;
+    return b.as<T>();
+  }
+  // room for n elements and their copy from the host; an optional input that is NULL stays NULL on the device
+  template <class T>
+  T* upload(DevBuf& b, const T* host, size_t n)
+  {
+    T* d = room<T>(b, n, host != nullptr);
+    if (d)
+      e = step(hipMemcpyAsync(d, host, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream), "host staging: upload");
+    return d;
+  }
+  // n elements back to the host where the caller gave a place for them
+  template <class T>
+  void download(T* host, const T* dev, size_t n)
+  {
+    if (host && n && ok())
+      e = step(hipMemcpyAsync(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost, ctx->stream), "host staging: download");
+  }
+  int finish()
+  {
+    if (ok())
+      e = step(hipStreamSynchronize(ctx->stream), "host staging: finish");
+    return status();
+  }
+};
+
+// The device mesh of the two solid stages in one slot: vertex (4 int32 each) | face_offset [nf + 1] | face_index [ni] |
+// face_building [nf] | face_kind [nf], each 16-byte aligned, and 16 bytes of slack.
+struct DevMesh {
+  size_t nv, nf, ni;
+  int32_t *vertex = nullptr, *face_offset = nullptr, *face_index = nullptr, *face_building = nullptr;
+  uint8_t* face_kind = nullptr;
+
+  DevMesh(int64_t n_vertices, int64_t n_faces, int64_t n_indices) : nv((size_t)n_vertices), nf((size_t)n_faces), ni((size_t)n_indices) {}
+  static size_t up(size_t b) { return (b + 15) & ~(size_t)15; }
+  size_t bytes() const { return up(16 * nv) + up(4 * (nf + 1)) + up(4 * ni) + up(4 * nf) + up(nf) + 16; }
+  void place(char* d)  // (nullptr where the room failed: the caller checks the staging before it uses the mesh)
+  {
+    if (!d)
+      return;
+    vertex = reinterpret_cast<int32_t*>(d);
+    face_offset = reinterpret_cast<int32_t*>(d += up(16 * nv));
+    face_index = reinterpret_cast<int32_t*>(d += up(4 * (nf + 1)));
+    face_building = reinterpret_cast<int32_t*>(d += up(4 * ni));
+    face_kind = reinterpret_cast<uint8_t*>(d += up(4 * nf));
+  }
+  // the five host arrays of a result (none NULL, an empty mesh's neither) and their download; false: out of host memory
+  template <class R>
+  bool to_host(Staging& S, R& r) const
+  {
+    if (!alloc(&r.vertex, 4 * nv) || !alloc(&r.face_offset, nf + 1) || !alloc(&r.face_index, ni) ||
+        !alloc(&r.face_building, nf) || !alloc(&r.face_kind, nf))
+      return false;
+    S.download(r.vertex, vertex, 4 * nv);
+    S.download(r.face_offset, face_offset, nf + 1);
+    S.download(r.face_index, face_index, ni);
+    S.download(r.face_building, face_building, nf);
+    S.download(r.face_kind, face_kind, nf);
+    return true;
   }
 };
 

@@ -561,25 +561,26 @@ extern "C" int bs_model_raster(bs_ctx* ctx, const int32_t* label, const int32_t*
   struct bs_model_raster res;
   memset(&res, 0, sizeof res);
   ResultGuard guard{&res};
-  hipStream_t st = ctx->stream;
   DevBuf* B = ctx->mr;
   const size_t npix = (size_t)width * (size_t)height;
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  BS_HIP(ctx, B[MR_IN_LABEL].reserve(4 * npix));
-  BS_HIP(ctx, B[MR_IN_TOP].reserve(16 * npix));
-  BS_HIP(ctx, B[MR_OUT].reserve(12 * npix));
-  BS_HIP(ctx, hipMemcpyAsync(B[MR_IN_LABEL].p, label, 4 * npix, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(B[MR_IN_TOP].p, top, 16 * npix, hipMemcpyHostToDevice, st));
-  int32_t* d_out = B[MR_OUT].as<int32_t>();
-  int32_t* const host[3] = {model, cover, mz2};
-  rc = raster(ctx, B[MR_IN_LABEL].as<int32_t>(), B[MR_IN_TOP].as<int32_t>(), width, height, model ? d_out : nullptr,
-              cover ? d_out + npix : nullptr, mz2 ? d_out + 2 * npix : nullptr, res);
+  Staging S(ctx);
+  const int32_t* d_label = S.upload(B[MR_IN_LABEL], label, npix);
+  const int32_t* d_top = S.upload(B[MR_IN_TOP], top, 4 * npix);
+  int32_t* d_out = S.room<int32_t>(B[MR_OUT], 3 * npix);  // model | cover | mz2
+  if (!S.ok())
+    return S.status();
+  int32_t* d_model = model ? d_out : nullptr;
+  int32_t* d_cover = cover ? d_out + npix : nullptr;
+  int32_t* d_mz2 = mz2 ? d_out + 2 * npix : nullptr;
+  rc = raster(ctx, d_label, d_top, width, height, d_model, d_cover, d_mz2, res);
   if (rc != BS_OK)
     return rc;
-  for (int k = 0; k < 3; k++)
-    if (host[k])
-      BS_HIP(ctx, hipMemcpyAsync(host[k], d_out + (size_t)k * npix, 4 * npix, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
+  S.download(model, d_model, npix);
+  S.download(cover, d_cover, npix);
+  S.download(mz2, d_mz2, npix);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
   guard.keep = true;
   ch.hand_over(tri, clean, simple, plain);
   *out = res;

@@ -640,19 +640,15 @@ extern "C" int bs_facet_outlines(bs_ctx* ctx, const int32_t* label, const int32_
   ctx->ol_valid = false;
   if (!label || !out || bad_image(width, height) || n_labels < 0)
     return fail(ctx, BS_ERR_INVALID, OUTLINES_INVALID);
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   const size_t npix = (size_t)width * height;
   DevBuf* B = ctx->ol;
-  BS_HIP(ctx, B[OL_IN_LABEL].reserve(4 * npix));
-  BS_HIP(ctx, hipMemcpyAsync(B[OL_IN_LABEL].p, label, 4 * npix, hipMemcpyHostToDevice, st));
-  if (top) {
-    BS_HIP(ctx, B[OL_IN_TOP].reserve(16 * npix));
-    BS_HIP(ctx, hipMemcpyAsync(B[OL_IN_TOP].p, top, 16 * npix, hipMemcpyHostToDevice, st));
-  }
+  Staging S(ctx);
+  const int32_t* d_label = S.upload(B[OL_IN_LABEL], label, npix);
+  const int32_t* d_top = S.upload(B[OL_IN_TOP], top, 4 * npix);
+  if (!S.ok())
+    return S.status();
   struct bs_outlines res;
-  int rc = bs_facet_outlines_count_dev(ctx, B[OL_IN_LABEL].as<int32_t>(), top ? B[OL_IN_TOP].as<int32_t>() : nullptr, width,
-                                       height, n_labels, &res);
+  int rc = bs_facet_outlines_count_dev(ctx, d_label, d_top, width, height, n_labels, &res);
   if (rc != BS_OK)
     return rc;
   Guard guard{&res};
@@ -660,16 +656,18 @@ extern "C" int bs_facet_outlines(bs_ctx* ctx, const int32_t* label, const int32_
   if (!alloc(&res.xy, 2 * nv) || (top && !alloc(&res.z, nv)))
     return fail(ctx, BS_ERR_NOMEM, "facet outlines: host allocation");
   if (nv > 0) {
-    BS_HIP(ctx, B[OL_OUT_XY].reserve(8 * nv));
-    if (top)
-      BS_HIP(ctx, B[OL_OUT_Z].reserve(4 * nv));
-    rc = bs_facet_outlines_emit_dev(ctx, B[OL_OUT_XY].as<int32_t>(), top ? B[OL_OUT_Z].as<int32_t>() : nullptr);
+    int32_t* d_xy = S.room<int32_t>(B[OL_OUT_XY], 2 * nv);
+    int32_t* d_z = S.room<int32_t>(B[OL_OUT_Z], nv, top != nullptr);
+    if (!S.ok())
+      return S.status();
+    rc = bs_facet_outlines_emit_dev(ctx, d_xy, d_z);
     if (rc != BS_OK)
       return rc;
-    BS_HIP(ctx, hipMemcpyAsync(res.xy, B[OL_OUT_XY].p, 8 * nv, hipMemcpyDeviceToHost, st));
-    if (top)
-      BS_HIP(ctx, hipMemcpyAsync(res.z, B[OL_OUT_Z].p, 4 * nv, hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipStreamSynchronize(st));
+    S.download(res.xy, d_xy, 2 * nv);
+    S.download(res.z, d_z, nv);
+    rc = S.finish();
+    if (rc != BS_OK)
+      return rc;
     res.ms_emit = ctx->ol_ms_emit;
   }
   *out = res;

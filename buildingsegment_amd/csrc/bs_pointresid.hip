@@ -710,27 +710,26 @@ extern "C" int bs_point_residuals(bs_ctx* ctx, const int32_t* label, const int32
   struct bs_point_residuals res;
   memset(&res, 0, sizeof res);
   ResultGuard guard{&res};
-  hipStream_t st = ctx->stream;
   DevBuf* B = ctx->pr;
   const size_t np = (size_t)n;
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  BS_HIP(ctx, B[PR_IN_XYZ].reserve(12 * np));
-  BS_HIP(ctx, B[PR_OUT].reserve(12 * np));
-  BS_HIP(ctx, hipMemcpyAsync(B[PR_IN_XYZ].p, xyz, 12 * np, hipMemcpyHostToDevice, st));
-  if (plane_idx) {
-    BS_HIP(ctx, B[PR_IN_PLANE].reserve(4 * np));
-    BS_HIP(ctx, hipMemcpyAsync(B[PR_IN_PLANE].p, plane_idx, 4 * np, hipMemcpyHostToDevice, st));
-  }
-  int32_t* d_out = B[PR_OUT].as<int32_t>();
-  int32_t* const host[3] = {label_out, r2, cover};
-  rc = residuals(ctx, B[PR_IN_XYZ].as<int32_t>(), n, bin, plane_idx ? B[PR_IN_PLANE].as<int32_t>() : nullptr, label_plane, clip2,
-                 label_out ? d_out : nullptr, r2 ? d_out + np : nullptr, cover ? d_out + 2 * np : nullptr, res);
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(B[PR_IN_XYZ], xyz, 3 * np);
+  int32_t* d_out = S.room<int32_t>(B[PR_OUT], 3 * np);  // label | r2 | cover
+  const int32_t* d_plane = S.upload(B[PR_IN_PLANE], plane_idx, np);
+  if (!S.ok())
+    return S.status();
+  int32_t* d_label_out = label_out ? d_out : nullptr;
+  int32_t* d_r2 = r2 ? d_out + np : nullptr;
+  int32_t* d_cover = cover ? d_out + 2 * np : nullptr;
+  rc = residuals(ctx, d_xyz, n, bin, d_plane, label_plane, clip2, d_label_out, d_r2, d_cover, res);
   if (rc != BS_OK)
     return rc;
-  for (int k = 0; k < 3; k++)
-    if (host[k])
-      BS_HIP(ctx, hipMemcpyAsync(host[k], d_out + (size_t)k * np, 4 * np, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
+  S.download(label_out, d_label_out, np);
+  S.download(r2, d_r2, np);
+  S.download(cover, d_cover, np);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
   guard.keep = true;
   ch.hand_over(tri, clean, simple, plain);
   *out = res;

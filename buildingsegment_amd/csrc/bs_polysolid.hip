@@ -929,40 +929,29 @@ extern "C" int bs_poly_solids(bs_ctx* ctx, const int32_t* label, const int32_t* 
   struct bs_poly_solids res;
   memset(&res, 0, sizeof res);
   ResultGuard guard{&res};
-  hipStream_t st = ctx->stream;
   DevBuf* B = ctx->ps;
-  BS_HIP(ctx, B[PS_IN_LB].reserve(4 * (size_t)std::max(n_labels, 1)));
-  if (n_labels > 0)
-    BS_HIP(ctx, hipMemcpyAsync(B[PS_IN_LB].p, label_building, 4 * (size_t)n_labels, hipMemcpyHostToDevice, st));
-  rc = poly_solids(ctx, ch.tri, ch.clean, width, B[PS_IN_LB].as<int32_t>(), n_buildings, bin, base_z, res);
+  Staging S(ctx);
+  // (without a label, label_building may be NULL: the slot then holds one entry that nobody reads, as it always has)
+  const int32_t* d_lb = n_labels > 0 ? S.upload(B[PS_IN_LB], label_building, (size_t)n_labels) : S.room<int32_t>(B[PS_IN_LB], 1);
+  if (!S.ok())
+    return S.status();
+  rc = poly_solids(ctx, ch.tri, ch.clean, width, d_lb, n_buildings, bin, base_z, res);
   if (rc != BS_OK)
     return rc;
-  const size_t nv = (size_t)res.n_vertices, nf = (size_t)res.n_faces, ni = (size_t)res.n_indices;
-  // device mesh: vertex | face_offset | face_index | face_building | face_kind, each 16-byte aligned
-  auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const size_t o_vert = 0, o_off = o_vert + up(16 * nv), o_idx = o_off + up(4 * (nf + 1)), o_bld = o_idx + up(4 * ni),
-               o_kind = o_bld + up(4 * nf), total = o_kind + up(nf);
-  BS_HIP(ctx, B[PS_OUT].reserve(total + 16));
-  char* d = B[PS_OUT].as<char>();
+  DevMesh mesh(res.n_vertices, res.n_faces, res.n_indices);
+  mesh.place(S.room<char>(B[PS_OUT], mesh.bytes()));
+  if (!S.ok())
+    return S.status();
   ctx->ps_valid = true;
-  rc = bs_poly_solids_emit_dev(ctx, reinterpret_cast<int32_t*>(d + o_vert), reinterpret_cast<int32_t*>(d + o_off),
-                               reinterpret_cast<int32_t*>(d + o_idx), reinterpret_cast<int32_t*>(d + o_bld),
-                               reinterpret_cast<uint8_t*>(d + o_kind));
+  rc = bs_poly_solids_emit_dev(ctx, mesh.vertex, mesh.face_offset, mesh.face_index, mesh.face_building, mesh.face_kind);
   ctx->ps_valid = false;
   if (rc != BS_OK)
     return rc;
-  if (!alloc(&res.vertex, 4 * nv) || !alloc(&res.face_offset, nf + 1) || !alloc(&res.face_index, ni) ||
-      !alloc(&res.face_building, nf) || !alloc(&res.face_kind, nf))
+  if (!mesh.to_host(S, res))
     return fail(ctx, BS_ERR_NOMEM, "polygon solids: host allocation");
-  if (nv)
-    BS_HIP(ctx, hipMemcpyAsync(res.vertex, d + o_vert, 16 * nv, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipMemcpyAsync(res.face_offset, d + o_off, 4 * (nf + 1), hipMemcpyDeviceToHost, st));
-  if (nf) {
-    BS_HIP(ctx, hipMemcpyAsync(res.face_index, d + o_idx, 4 * ni, hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipMemcpyAsync(res.face_building, d + o_bld, 4 * nf, hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipMemcpyAsync(res.face_kind, d + o_kind, nf, hipMemcpyDeviceToHost, st));
-  }
-  BS_HIP(ctx, hipStreamSynchronize(st));
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
   res.ms_emit_vertices = ctx->ps_ms_emit[0];
   res.ms_emit_faces = ctx->ps_ms_emit[1];
   guard.keep = true;

@@ -360,18 +360,17 @@ extern "C" int bs_grid_picture(bs_ctx* ctx, const int32_t* xyz, int64_t n, const
   int32_t width = 0, height = 0;
   if (!xyz || !image || n <= 0 || bs_grid_dims(extent, bin, &width, &height) != BS_OK)
     return fail(ctx, BS_ERR_INVALID, "null pointer, empty cloud or bad raster parameters");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t img_bytes = sizeof(double) * 3 * (size_t)width * height;
-  BS_HIP(ctx, ctx->d_xyz_h.reserve(sizeof(int32_t) * 3 * n));
-  BS_HIP(ctx, ctx->rs_img.reserve(img_bytes));
-  BS_HIP(ctx, hipMemcpyAsync(ctx->d_xyz_h.p, xyz, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
-  const int rc = bs_grid_picture_dev(ctx, ctx->d_xyz_h.as<int32_t>(), n, extent, bin, bin_height,
-                                     ctx->rs_img.as<double>(), ground_th);
+  Staging S(ctx);
+  const size_t img = 3 * (size_t)width * height;
+  const int32_t* d_xyz = S.upload(ctx->d_xyz_h, xyz, 3 * n);
+  double* d_image = S.room<double>(ctx->rs_img, img);
+  if (!S.ok())
+    return S.status();
+  const int rc = bs_grid_picture_dev(ctx, d_xyz, n, extent, bin, bin_height, d_image, ground_th);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipMemcpyAsync(image, ctx->rs_img.p, img_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return BS_OK;
+  S.download(image, d_image, img);
+  return S.finish();
 }
 
 extern "C" int bs_grid_picture_batch_dev(bs_ctx* ctx, const int32_t* d_xyz, const int64_t* tile_offset,
@@ -418,16 +417,14 @@ extern "C" int bs_grid_picture_batch(bs_ctx* ctx, const int32_t* xyz, const int6
   rc = raster_tiles(ctx, tile_offset, n_tiles, extent, bin, bin_height, tl, &npix, &nb);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t img_bytes = sizeof(double) * 3 * (size_t)npix;
-  BS_HIP(ctx, ctx->d_xyz_h.reserve(sizeof(int32_t) * 3 * n));
-  BS_HIP(ctx, ctx->rs_img.reserve(img_bytes));
-  BS_HIP(ctx, hipMemcpyAsync(ctx->d_xyz_h.p, xyz, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
-  rc = bs_grid_picture_batch_dev(ctx, ctx->d_xyz_h.as<int32_t>(), tile_offset, n_tiles, extent, bin, bin_height,
-                                 ctx->rs_img.as<double>(), ground_th);
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(ctx->d_xyz_h, xyz, 3 * n);
+  double* d_image = S.room<double>(ctx->rs_img, 3 * (size_t)npix);
+  if (!S.ok())
+    return S.status();
+  rc = bs_grid_picture_batch_dev(ctx, d_xyz, tile_offset, n_tiles, extent, bin, bin_height, d_image, ground_th);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipMemcpyAsync(image, ctx->rs_img.p, img_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return BS_OK;
+  S.download(image, d_image, 3 * (size_t)npix);
+  return S.finish();
 }

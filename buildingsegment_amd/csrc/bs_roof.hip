@@ -672,32 +672,28 @@ extern "C" int bs_roofs(bs_ctx* ctx, const int32_t* xyz, int64_t n, int32_t bin,
     return fail(ctx, BS_ERR_INVALID, ROOFS_INVALID);
   if (n >= (1ll << 29))
     return fail(ctx, BS_ERR_RANGE, "roofs: 2^29 points or more");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   const size_t npix = (size_t)width * height;
   DevBuf* B = ctx->rf;
-  BS_HIP(ctx, B[RF_IN_XYZ].reserve(12 * (size_t)n));
-  BS_HIP(ctx, B[RF_IN_MAP].reserve(4 * npix));
-  BS_HIP(ctx, B[RF_IN_PLANE].reserve(4 * (size_t)n));
-  BS_HIP(ctx, B[RF_OUT].reserve(12 * npix));
-  int32_t* d_roof = B[RF_OUT].as<int32_t>();
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(B[RF_IN_XYZ], xyz, 3 * (size_t)n);
+  const int32_t* d_map = S.upload(B[RF_IN_MAP], map, npix);
+  const int32_t* d_plane = S.upload(B[RF_IN_PLANE], plane_idx, (size_t)n);
+  int32_t* d_roof = S.room<int32_t>(B[RF_OUT], 3 * npix);  // roof | support | height
+  if (!S.ok())
+    return S.status();
   int32_t* d_support = support ? d_roof + npix : nullptr;
   int32_t* d_height = height_out ? d_roof + 2 * npix : nullptr;
-  BS_HIP(ctx, hipMemcpyAsync(B[RF_IN_XYZ].p, xyz, 12 * (size_t)n, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(B[RF_IN_MAP].p, map, 4 * npix, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(B[RF_IN_PLANE].p, plane_idx, 4 * (size_t)n, hipMemcpyHostToDevice, st));
-  const int rc = bs_roofs_dev(ctx, B[RF_IN_XYZ].as<int32_t>(), n, bin, ground_th, B[RF_IN_MAP].as<int32_t>(), width, height,
-                              B[RF_IN_PLANE].as<int32_t>(), n_planes, home, normal, center, min_votes, d_roof, d_support,
-                              d_height, out);
+  int rc = bs_roofs_dev(ctx, d_xyz, n, bin, ground_th, d_map, width, height, d_plane, n_planes, home, normal, center, min_votes,
+                        d_roof, d_support, d_height, out);
   if (rc != BS_OK)
     return rc;
-  BS_HIP(ctx, hipMemcpyAsync(roof, d_roof, 4 * npix, hipMemcpyDeviceToHost, st));
-  if (support)
-    BS_HIP(ctx, hipMemcpyAsync(support, d_support, 4 * npix, hipMemcpyDeviceToHost, st));
-  if (height_out)
-    BS_HIP(ctx, hipMemcpyAsync(height_out, d_height, 4 * npix, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
-  return BS_OK;
+  FreeUnlessKept<struct bs_roofs, bs_roofs_free> guard{out};
+  S.download(roof, d_roof, npix);
+  S.download(support, d_support, npix);
+  S.download(height_out, d_height, npix);
+  rc = S.finish();
+  guard.keep = rc == BS_OK;
+  return rc;
 }
 
 // The format is written down in include/bs_api.h.

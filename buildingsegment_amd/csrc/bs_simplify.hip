@@ -944,43 +944,22 @@ extern "C" int bs_simple_outlines(bs_ctx* ctx, const int32_t* label, const int32
   ctx->sp_valid = false;
   if (!label || !out || bad_image(width, height) || n_labels < 0 || bad_tolerance(num, den))
     return fail(ctx, BS_ERR_INVALID, SIMPLE_INVALID);
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   const size_t npix = (size_t)width * height;
   DevBuf* B = ctx->sp;
-  BS_HIP(ctx, B[SP_IN_LABEL].reserve(4 * npix));
-  BS_HIP(ctx, hipMemcpyAsync(B[SP_IN_LABEL].p, label, 4 * npix, hipMemcpyHostToDevice, st));
-  if (top) {
-    BS_HIP(ctx, B[SP_IN_TOP].reserve(16 * npix));
-    BS_HIP(ctx, hipMemcpyAsync(B[SP_IN_TOP].p, top, 16 * npix, hipMemcpyHostToDevice, st));
-  }
+  Staging S(ctx);
+  const int32_t* d_label = S.upload(B[SP_IN_LABEL], label, npix);
+  const int32_t* d_top = S.upload(B[SP_IN_TOP], top, 4 * npix);
+  if (!S.ok())
+    return S.status();
   Chain ch;  // (its simplified outlines are this call's own result)
-  struct bs_simple_outlines& res = ch.simple;
-  int rc = bs_simple_outlines_count_dev(ctx, B[SP_IN_LABEL].as<int32_t>(), top ? B[SP_IN_TOP].as<int32_t>() : nullptr, width, height,
-                                        n_labels, num, den, &res, &ch.plain);
+  int rc = bs_simple_outlines_count_dev(ctx, d_label, d_top, width, height, n_labels, num, den, &ch.simple, &ch.plain);
   if (rc != BS_OK)
     return rc;
   ch.has_plain = ch.has_simple = true;
-  const size_t nv = (size_t)res.n_svertices;
-  if (!alloc(&res.sxy, 2 * nv) || (top && !alloc(&res.sz, nv)) || !alloc(&res.s_right, nv) || !alloc(&res.s_flag, nv))
-    return fail(ctx, BS_ERR_NOMEM, "simplified outlines: host allocation");
-  if (nv > 0) {
-    BS_HIP(ctx, B[SP_OUT_XY].reserve(8 * nv));
-    BS_HIP(ctx, B[SP_OUT_Z].reserve(4 * nv));
-    BS_HIP(ctx, B[SP_OUT_RIGHT].reserve(4 * nv));
-    BS_HIP(ctx, B[SP_OUT_FLAG].reserve(nv));
-    rc = bs_simple_outlines_emit_dev(ctx, B[SP_OUT_XY].as<int32_t>(), top ? B[SP_OUT_Z].as<int32_t>() : nullptr,
-                                     B[SP_OUT_RIGHT].as<int32_t>(), B[SP_OUT_FLAG].as<uint8_t>());
-    if (rc != BS_OK)
-      return rc;
-    BS_HIP(ctx, hipMemcpyAsync(res.sxy, B[SP_OUT_XY].p, 8 * nv, hipMemcpyDeviceToHost, st));
-    if (top)
-      BS_HIP(ctx, hipMemcpyAsync(res.sz, B[SP_OUT_Z].p, 4 * nv, hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipMemcpyAsync(res.s_right, B[SP_OUT_RIGHT].p, 4 * nv, hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipMemcpyAsync(res.s_flag, B[SP_OUT_FLAG].p, nv, hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipStreamSynchronize(st));
-    res.ms_emit = ctx->sp_ms_emit;
-  }
+  rc = kept_vertices_to_host(ctx, S, ch.simple, {B[SP_OUT_XY], B[SP_OUT_Z], B[SP_OUT_RIGHT], B[SP_OUT_FLAG]},
+                             bs_simple_outlines_emit_dev, &ctx->sp_ms_emit, "simplified outlines: host allocation");
+  if (rc != BS_OK)
+    return rc;
   ch.hand_over(nullptr, nullptr, out, plain);
   return BS_OK;
 }
@@ -1003,21 +982,7 @@ extern "C" int bs_simple_outlines_write_obj(const struct bs_simple_outlines* o, 
   FILE* fo = fopen(path, "w");
   if (!fo)
     return BS_ERR_INVALID;
-  const int64_t org[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
   fprintf(fo, "# simplified outlines: %d labels, %lld rings, %lld vertices, tol2 %d/%d\n", o->n_labels, (long long)o->n_rings,
           (long long)o->n_svertices, o->tol_num, o->tol_den);
-  for (int64_t r = 0; r < o->n_rings; r++) {
-    const int32_t l = o->ring_label[r];
-    fprintf(fo, "g label_%d_ring_%lld_%s\n", l, (long long)(r - o->label_ring_offset[l]), o->ring_area2[r] > 0 ? "outer" : "hole");
-    const int64_t a = o->s_ring_offset[r], b = o->s_ring_offset[r + 1];
-    for (int64_t v = a; v < b; v++)
-      fprintf(fo, "v %lld %lld %lld\n", (long long)((int64_t)o->sxy[2 * v] * bin + org[0]),
-              (long long)((int64_t)o->sxy[2 * v + 1] * bin + org[1]), (long long)((o->sz ? (int64_t)o->sz[v] : 0) + org[2]));
-    fputs("l", fo);
-    for (int64_t v = a; v < b; v++)
-      fprintf(fo, " %lld", (long long)(v + 1));
-    fprintf(fo, " %lld\n", (long long)(a + 1));
-  }
-  const bool ok = !ferror(fo);
-  return (fclose(fo) == 0 && ok) ? BS_OK : BS_ERR_INVALID;
+  return write_kept_rings(fo, o, bin, origin);
 }

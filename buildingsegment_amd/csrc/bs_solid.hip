@@ -771,65 +771,38 @@ extern "C" int bs_solids(bs_ctx* ctx, const int32_t* map, const int32_t* roof, i
     memset(out, 0, sizeof *out);
   if (!map || !roof || !out || bad_image(width, height))
     return fail(ctx, BS_ERR_INVALID, SOLIDS_INVALID);
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   const size_t npix = (size_t)width * height;
   DevBuf* B = ctx->sd;
-  BS_HIP(ctx, B[SD_IN_MAP].reserve(4 * npix));
-  BS_HIP(ctx, B[SD_IN_ROOF].reserve(4 * npix));
-  BS_HIP(ctx, hipMemcpyAsync(B[SD_IN_MAP].p, map, 4 * npix, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(B[SD_IN_ROOF].p, roof, 4 * npix, hipMemcpyHostToDevice, st));
-  const int rc = bs_solids_count_dev(ctx, B[SD_IN_MAP].as<int32_t>(), B[SD_IN_ROOF].as<int32_t>(), width, height, n_buildings,
-                                     n_planes, normal, center, z_min, z_max, bin, base_z, flat, nullptr, out);
+  Staging S(ctx);
+  const int32_t* d_map = S.upload(B[SD_IN_MAP], map, npix);
+  const int32_t* d_roof = S.upload(B[SD_IN_ROOF], roof, npix);
+  if (!S.ok())
+    return S.status();
+  int rc = bs_solids_count_dev(ctx, d_map, d_roof, width, height, n_buildings, n_planes, normal, center, z_min, z_max, bin, base_z,
+                               flat, nullptr, out);
   if (rc != BS_OK)
     return rc;
-  const size_t nv = (size_t)out->n_vertices, nf = (size_t)out->n_faces, ni = (size_t)out->n_indices;
-  // device mesh: vertex | face_offset | face_index | face_building | face_kind, each 16-byte aligned
-  auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  const size_t o_vert = 0, o_off = o_vert + up(16 * nv), o_idx = o_off + up(4 * (nf + 1)), o_bld = o_idx + up(4 * ni),
-               o_kind = o_bld + up(4 * nf), total = o_kind + up(nf);
-  auto bail = [&](int status, const char* what, hipError_t e = hipSuccess) {
-    bs_solids_free(out);
+  FreeUnlessKept<struct bs_solids, bs_solids_free> guard{out};
+  DevMesh mesh(out->n_vertices, out->n_faces, out->n_indices);
+  mesh.place(S.room<char>(B[SD_OUT], mesh.bytes()));
+  if (S.ok()) {
+    rc = bs_solids_emit_dev(ctx, mesh.vertex, mesh.face_offset, mesh.face_index, mesh.face_building, mesh.face_kind);
+    if (rc != BS_OK)
+      return rc;
+    if (!mesh.to_host(S, *out)) {
+      ctx->sd_valid = false;
+      return fail(ctx, BS_ERR_NOMEM, "solids: host allocation");
+    }
+    S.download(top, B[SD_TOP].as<int32_t>(), 4 * npix);
+  }
+  rc = S.finish();
+  if (rc != BS_OK) {
     ctx->sd_valid = false;
-    return fail(ctx, status, what, e);
-  };
-  hipError_t e = B[SD_OUT].reserve(total + 16);
-  if (e != hipSuccess)
-    return bail(BS_ERR_HIP, "solids: device mesh", e);
-  char* d = B[SD_OUT].as<char>();
-  const int rc2 = bs_solids_emit_dev(ctx, reinterpret_cast<int32_t*>(d + o_vert), reinterpret_cast<int32_t*>(d + o_off),
-                                     reinterpret_cast<int32_t*>(d + o_idx), reinterpret_cast<int32_t*>(d + o_bld),
-                                     reinterpret_cast<uint8_t*>(d + o_kind));
-  if (rc2 != BS_OK) {
-    bs_solids_free(out);
-    return rc2;
+    return rc;
   }
-  out->vertex = (int32_t*)malloc(std::max<size_t>(16 * nv, 16));
-  out->face_offset = (int32_t*)malloc(4 * (nf + 1));
-  out->face_index = (int32_t*)malloc(std::max<size_t>(4 * ni, 4));
-  out->face_building = (int32_t*)malloc(std::max<size_t>(4 * nf, 4));
-  out->face_kind = (uint8_t*)malloc(std::max<size_t>(nf, 1));
-  if (!out->vertex || !out->face_offset || !out->face_index || !out->face_building || !out->face_kind)
-    return bail(BS_ERR_NOMEM, "solids: host allocation");
-  if (nv)
-    e = hipMemcpyAsync(out->vertex, d + o_vert, 16 * nv, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(out->face_offset, d + o_off, 4 * (nf + 1), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && nf) {
-    e = hipMemcpyAsync(out->face_index, d + o_idx, 4 * ni, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(out->face_building, d + o_bld, 4 * nf, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(out->face_kind, d + o_kind, nf, hipMemcpyDeviceToHost, st);
-  }
-  if (e == hipSuccess && top)
-    e = hipMemcpyAsync(top, B[SD_TOP].p, 16 * npix, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess)
-    e = hipStreamSynchronize(st);
-  if (e != hipSuccess)
-    return bail(BS_ERR_HIP, "solids: copy to the host", e);
   out->ms_emit_vertices = ctx->sd_ms_emit[0];
   out->ms_emit_faces = ctx->sd_ms_emit[1];
+  guard.keep = true;
   return BS_OK;
 }
 

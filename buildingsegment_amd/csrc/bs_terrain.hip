@@ -593,25 +593,23 @@ extern "C" int bs_terrain(bs_ctx* ctx, const int32_t* xyz, int64_t n, int32_t bi
   struct bs_terrain res;
   memset(&res, 0, sizeof res);
   TGuard guard{&res};
-  hipStream_t st = ctx->stream;
   DevBuf* B = ctx->tn;
   const size_t np = (size_t)width * (size_t)height;
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  BS_HIP(ctx, B[TN_IN_XYZ].reserve(12 * (size_t)n));
-  BS_HIP(ctx, B[TN_IN_MAP].reserve(4 * np));
-  BS_HIP(ctx, hipMemcpyAsync(B[TN_IN_XYZ].p, xyz, 12 * (size_t)n, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipMemcpyAsync(B[TN_IN_MAP].p, map, 4 * np, hipMemcpyHostToDevice, st));
-  rc = terrain(ctx, B[TN_IN_XYZ].as<int32_t>(), n, bin, B[TN_IN_MAP].as<int32_t>(), width, height, n_buildings, ring, q_num, q_den,
-               min_ground, fallback_z, nullptr, nullptr, nullptr, res);
+  Staging S(ctx);
+  const int32_t* d_xyz = S.upload(B[TN_IN_XYZ], xyz, 3 * (size_t)n);
+  const int32_t* d_map = S.upload(B[TN_IN_MAP], map, np);
+  if (!S.ok())
+    return S.status();
+  rc = terrain(ctx, d_xyz, n, bin, d_map, width, height, n_buildings, ring, q_num, q_den, min_ground, fallback_z, nullptr, nullptr,
+               nullptr, res);
   if (rc != BS_OK)
     return rc;
-  if (owner)
-    BS_HIP(ctx, hipMemcpyAsync(owner, B[TN_OWNER].p, 4 * np, hipMemcpyDeviceToHost, st));
-  if (dist)
-    BS_HIP(ctx, hipMemcpyAsync(dist, B[TN_DIST].p, np, hipMemcpyDeviceToHost, st));
-  if (low)
-    BS_HIP(ctx, hipMemcpyAsync(low, B[TN_LOW].p, 4 * np, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
+  S.download(owner, B[TN_OWNER].as<int32_t>(), np);
+  S.download(dist, B[TN_DIST].as<uint8_t>(), np);
+  S.download(low, B[TN_LOW].as<int32_t>(), np);
+  rc = S.finish();
+  if (rc != BS_OK)
+    return rc;
   guard.keep = true;
   *out = res;
   return BS_OK;

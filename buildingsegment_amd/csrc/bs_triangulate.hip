@@ -742,17 +742,20 @@ extern "C" int bs_outline_triangles(bs_ctx* ctx, const int32_t* label, const int
   const size_t n = 3 * (size_t)res.n_triangles;
   if (!alloc(&res.tri, n))
     return fail(ctx, BS_ERR_NOMEM, "outline triangles: host allocation");
-  if (n > 0) {
+  if (n > 0) {  // (the inputs went up in bs_clean_outlines: only the triangles are staged here)
+    Staging S(ctx);
+    int32_t* d_tri = S.room<int32_t>(ctx->tr[TR_OUT], n);
+    if (!S.ok())
+      return S.status();
     ctx->tr_valid = true;
-    BS_HIP(ctx, ctx->tr[TR_OUT].reserve(4 * n));
-    rc = bs_outline_triangles_emit_dev(ctx, ctx->tr[TR_OUT].as<int32_t>());
-    if (rc != BS_OK) {
-      ctx->tr_valid = false;
-      return rc;
-    }
+    rc = bs_outline_triangles_emit_dev(ctx, d_tri);
     ctx->tr_valid = false;
-    BS_HIP(ctx, hipMemcpyAsync(res.tri, ctx->tr[TR_OUT].p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
-    BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rc != BS_OK)
+      return rc;
+    S.download(res.tri, d_tri, n);
+    rc = S.finish();
+    if (rc != BS_OK)
+      return rc;
     res.ms_emit = ctx->tr_ms_emit;
   }
   ch.hand_over(out, clean, simple, plain);

@@ -872,43 +872,23 @@ extern "C" int bs_clean_outlines(bs_ctx* ctx, const int32_t* label, const int32_
   ctx->uc_valid = false;
   if (!label || !out || bad_image(width, height))
     return fail(ctx, BS_ERR_INVALID, "clean outlines: null pointer, width or height < 1 or width * height >= 2^29");
-  BS_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
   const size_t npix = (size_t)width * height;
   DevBuf* B = ctx->uc;
-  BS_HIP(ctx, B[UC_IN_LABEL].reserve(4 * npix));
-  BS_HIP(ctx, hipMemcpyAsync(B[UC_IN_LABEL].p, label, 4 * npix, hipMemcpyHostToDevice, st));
-  if (top) {
-    BS_HIP(ctx, B[UC_IN_TOP].reserve(16 * npix));
-    BS_HIP(ctx, hipMemcpyAsync(B[UC_IN_TOP].p, top, 16 * npix, hipMemcpyHostToDevice, st));
-  }
+  Staging S(ctx);
+  const int32_t* d_label = S.upload(B[UC_IN_LABEL], label, npix);
+  const int32_t* d_top = S.upload(B[UC_IN_TOP], top, 4 * npix);
+  if (!S.ok())
+    return S.status();
   Chain ch;  // (its clean outlines are this call's own result)
-  struct bs_clean_outlines& res = ch.clean;
-  int rc = bs_clean_outlines_count_dev(ctx, B[UC_IN_LABEL].as<int32_t>(), top ? B[UC_IN_TOP].as<int32_t>() : nullptr, width, height,
-                                       n_labels, num, den, max_rounds, cell_log2, &res, &ch.simple, &ch.plain);
+  int rc = bs_clean_outlines_count_dev(ctx, d_label, d_top, width, height, n_labels, num, den, max_rounds, cell_log2, &ch.clean,
+                                       &ch.simple, &ch.plain);
   if (rc != BS_OK)
     return rc;
   ch.has_plain = ch.has_simple = ch.has_clean = true;
-  const size_t nv = (size_t)res.n_svertices;
-  if (!alloc(&res.sxy, 2 * nv) || (top && !alloc(&res.sz, nv)) || !alloc(&res.s_right, nv) || !alloc(&res.s_flag, nv))
-    return fail(ctx, BS_ERR_NOMEM, "clean outlines: host allocation");
-  if (nv > 0) {
-    BS_HIP(ctx, B[UC_OUT_XY].reserve(8 * nv));
-    BS_HIP(ctx, B[UC_OUT_Z].reserve(4 * nv));
-    BS_HIP(ctx, B[UC_OUT_RIGHT].reserve(4 * nv));
-    BS_HIP(ctx, B[UC_OUT_FLAG].reserve(nv));
-    rc = bs_clean_outlines_emit_dev(ctx, B[UC_OUT_XY].as<int32_t>(), top ? B[UC_OUT_Z].as<int32_t>() : nullptr,
-                                    B[UC_OUT_RIGHT].as<int32_t>(), B[UC_OUT_FLAG].as<uint8_t>());
-    if (rc != BS_OK)
-      return rc;
-    BS_HIP(ctx, hipMemcpyAsync(res.sxy, B[UC_OUT_XY].p, 8 * nv, hipMemcpyDeviceToHost, st));
-    if (top)
-      BS_HIP(ctx, hipMemcpyAsync(res.sz, B[UC_OUT_Z].p, 4 * nv, hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipMemcpyAsync(res.s_right, B[UC_OUT_RIGHT].p, 4 * nv, hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipMemcpyAsync(res.s_flag, B[UC_OUT_FLAG].p, nv, hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipStreamSynchronize(st));
-    res.ms_emit = ctx->uc_ms_emit;
-  }
+  rc = kept_vertices_to_host(ctx, S, ch.clean, {B[UC_OUT_XY], B[UC_OUT_Z], B[UC_OUT_RIGHT], B[UC_OUT_FLAG]},
+                             bs_clean_outlines_emit_dev, &ctx->uc_ms_emit, "clean outlines: host allocation");
+  if (rc != BS_OK)
+    return rc;
   ch.hand_over(nullptr, out, simple, plain);
   return BS_OK;
 }
@@ -931,22 +911,8 @@ extern "C" int bs_clean_outlines_write_obj(const struct bs_clean_outlines* o, in
   FILE* fo = fopen(path, "w");
   if (!fo)
     return BS_ERR_INVALID;
-  const int64_t org[3] = {origin ? origin[0] : 0, origin ? origin[1] : 0, origin ? origin[2] : 0};
   fprintf(fo, "# clean outlines: %d labels, %lld rings, %lld vertices, tol2 %d/%d, repair_rounds %lld, n_forced %lld\n", o->n_labels,
           (long long)o->n_rings, (long long)o->n_svertices, o->tol_num, o->tol_den, (long long)o->repair_rounds,
           (long long)o->n_forced);
-  for (int64_t r = 0; r < o->n_rings; r++) {
-    const int32_t l = o->ring_label[r];
-    fprintf(fo, "g label_%d_ring_%lld_%s\n", l, (long long)(r - o->label_ring_offset[l]), o->ring_area2[r] > 0 ? "outer" : "hole");
-    const int64_t a = o->s_ring_offset[r], b = o->s_ring_offset[r + 1];
-    for (int64_t v = a; v < b; v++)
-      fprintf(fo, "v %lld %lld %lld\n", (long long)((int64_t)o->sxy[2 * v] * bin + org[0]),
-              (long long)((int64_t)o->sxy[2 * v + 1] * bin + org[1]), (long long)((o->sz ? (int64_t)o->sz[v] : 0) + org[2]));
-    fputs("l", fo);
-    for (int64_t v = a; v < b; v++)
-      fprintf(fo, " %lld", (long long)(v + 1));
-    fprintf(fo, " %lld\n", (long long)(a + 1));
-  }
-  const bool ok = !ferror(fo);
-  return (fclose(fo) == 0 && ok) ? BS_OK : BS_ERR_INVALID;
+  return write_kept_rings(fo, o, bin, origin);
 }
