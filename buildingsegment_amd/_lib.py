@@ -48,7 +48,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_terrain_dev", "bs_terrain", "bs_terrain_free", "bs_set_building_bases", "bs_get_building_bases",
            "bs_ground_dev", "bs_ground", "bs_ground_free", "bs_set_ground_model", "bs_set_ground_model_dev",
            "bs_get_ground_model", "bs_plane_quality", "bs_roof_evidence_dev", "bs_roof_evidence", "bs_set_footprint_screen",
-           "bs_set_footprint_screen_dev", "bs_get_footprint_screen"]
+           "bs_set_footprint_screen_dev", "bs_get_footprint_screen", "bs_selftest_scratch_guard",
+           "bs_selftest_scratch_check", "bs_selftest_scratch_list"]
 
 
 class Params(C.Structure):
@@ -86,6 +87,17 @@ class GrowCounters(C.Structure):
     _fields_ = [(k, C.c_int64) for k in
                 ("rounds", "rounds_capped", "rounds_big", "attempts_nomem", "waves_cut", "max_waves_end", "attempts_stolen",
                  "dropped_pend_count", "dropped_pend_store", "dropped_other", "full_refreshes", "pool_cap")]
+
+
+class ScratchSlot(C.Structure):
+    """bs_scratch_slot (include/bs_api.h): one buffer of a context allocated under the scratch guard."""
+    _fields_ = [("name", C.c_char * 24), ("address", C.c_uint64), ("requested", C.c_int64), ("guard", C.c_int64),
+                ("first_bad", C.c_int64), ("last_bad", C.c_int64), ("host", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ScratchReport(C.Structure):
+    _fields_ = [("n_guarded", C.c_int64), ("bytes_requested", C.c_int64), ("n_damaged", C.c_int64),
+                ("n_listed", C.c_int64), ("damaged", ScratchSlot * 8)]
 
 
 API_VERSION = 5  # BS_API_VERSION of include/bs_api.h this loader mirrors
@@ -444,6 +456,9 @@ def load():
     L.bs_set_audit.argtypes = [vp, C.c_int]
     L.bs_selftest_grow_limits.argtypes = [vp, C.POINTER(GrowLimits)]
     L.bs_get_grow_counters.argtypes = [vp, C.POINTER(GrowCounters)]
+    L.bs_selftest_scratch_guard.argtypes = [vp, C.c_int, C.c_int]
+    L.bs_selftest_scratch_check.argtypes = [vp, C.POINTER(ScratchReport)]
+    L.bs_selftest_scratch_list.argtypes = [vp, C.POINTER(ScratchSlot), C.c_int64, C.POINTER(C.c_int64)]
     L.bs_selftest_center_div.argtypes = [vp, ip, vp, ip, C.c_int64]
     L.bs_grid_dims.argtypes = [ip, C.c_int32, ip, ip]
     L.bs_grid_picture.argtypes = [vp, ip, C.c_int64, ip, C.c_int32, C.c_int32, dp, dp]

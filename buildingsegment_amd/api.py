@@ -262,6 +262,33 @@ class Context:
                               int(retry_big_round), 1 if full_refresh else 0, 0)
         self._check(self._L.bs_selftest_grow_limits(self._h, C.byref(lim)))
 
+    def selftest_scratch_guard(self, canary=True, poison=None):
+        """Guard every following allocation of this context's scratch (bs_selftest_scratch_guard): a canary behind the
+        requested bytes and, with poison = a byte value, that byte in front.  Only right after the context was made."""
+        flags = (1 if canary else 0) | (2 if poison is not None else 0)
+        self._check(self._L.bs_selftest_scratch_guard(self._h, flags, int(poison or 0)))
+
+    @staticmethod
+    def _scratch_slot(s) -> dict:
+        return {"name": s.name.decode(), "address": s.address, "requested": s.requested, "guard": s.guard,
+                "first_bad": s.first_bad, "last_bad": s.last_bad, "host": bool(s.host)}
+
+    def selftest_scratch_check(self) -> dict:
+        """Read every guard back (bs_selftest_scratch_check): n_guarded, bytes_requested, n_damaged and the first
+        damaged buffers by bs_ctx member name, with the damaged range relative to the end of the request."""
+        r = _lib.ScratchReport()
+        self._check(self._L.bs_selftest_scratch_check(self._h, C.byref(r)))
+        return {"n_guarded": r.n_guarded, "bytes_requested": r.bytes_requested, "n_damaged": r.n_damaged,
+                "damaged": [self._scratch_slot(r.damaged[i]) for i in range(r.n_listed)]}
+
+    def selftest_scratch_list(self) -> list:
+        """Every buffer of this context allocated under the guard (bs_selftest_scratch_list), in bs_ctx order."""
+        n = C.c_int64(0)
+        self._check(self._L.bs_selftest_scratch_list(self._h, None, 0, C.byref(n)))
+        slots = (_lib.ScratchSlot * max(n.value, 1))()
+        self._check(self._L.bs_selftest_scratch_list(self._h, slots, n.value, C.byref(n)))
+        return [self._scratch_slot(slots[i]) for i in range(n.value)]
+
     def grow_counters(self) -> dict:
         """bs_grow_counters of the last speculative region grow on this context (also after a failed one)."""
         g = _lib.GrowCounters()

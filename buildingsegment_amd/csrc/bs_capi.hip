@@ -168,6 +168,10 @@ int planes_to_host(bs_ctx* ctx, const PlaneRec* d_recs, const int32_t* d_list, i
 
 using namespace bs;
 
+namespace {
+bool scratch_members_complete(bs_ctx* c, long long born, int64_t* n_members);  // (with the scratch guard, below)
+}
+
 extern "C" {
 
 int bs_api_version(void) { return BS_API_VERSION; }
@@ -215,9 +219,14 @@ int bs_create(int device, bs_ctx** out)
     return BS_ERR_INVALID;
   if (hipSetDevice(device) != hipSuccess)
     return BS_ERR_NO_DEVICE;
+  const long long born = scratch_bufs_born;
   bs_ctx* c = new (std::nothrow) bs_ctx();
   if (!c)
     return BS_ERR_NOMEM;
+  if (!scratch_members_complete(c, scratch_bufs_born - born, nullptr)) {  // a buffer of bs_ctx the member table omits
+    delete c;
+    return BS_ERR_INTERNAL;
+  }
   c->device = device;
   if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
     delete c;
@@ -553,6 +562,171 @@ int bs_get_grow_counters(const bs_ctx* ctx, bs_grow_counters* out)
   if (!ctx || !out)
     return BS_ERR_INVALID;
   *out = ctx->gc;
+  return BS_OK;
+}
+
+// ---- scratch guard (test hook) ----------------------------------------------
+namespace {
+
+struct ScratchMember {
+  const char* name;
+  int index;  // -1: a single buffer
+  DevBuf* dev;
+  HostBuf* host;
+};
+
+// EVERY DevBuf / HostBuf member of bs_ctx, in its order.  scratch_members_complete() counts the buffers a bs_ctx
+// constructs against this table: a member added to bs_ctx and not listed here fails bs_create.
+void scratch_members(bs_ctx* c, std::vector<ScratchMember>& out)
+{
+#define BS_ONE(m) out.push_back(ScratchMember{#m, -1, &c->m, nullptr})
+#define BS_ARR(m)                                                  \
+  for (int i = 0; i < (int)(sizeof(c->m) / sizeof(c->m[0])); i++) \
+  out.push_back(ScratchMember{#m, i, &c->m[i], nullptr})
+  BS_ONE(keys_in); BS_ONE(keys_out); BS_ONE(vals_in); BS_ONE(vals_out); BS_ONE(cub_tmp); BS_ONE(uniq_keys);
+  BS_ONE(uniq_cnt); BS_ONE(misc); BS_ONE(table); BS_ONE(spts);
+  BS_ONE(fb_list); BS_ONE(d_xyz_h); BS_ONE(d_neigh_h); BS_ONE(d_normals_h); BS_ONE(d_plane_h);
+  BS_ONE(seg_neigh); BS_ONE(seg_normals);
+  BS_ONE(rg_list); BS_ONE(rg_stack); BS_ONE(rg_planes); BS_ONE(rg_stats); BS_ONE(rg_aux); BS_ONE(rg_pstore);
+  BS_ONE(rg_rec); BS_ONE(rg_radj); BS_ONE(rg_roff); BS_ONE(rg_geo); BS_ONE(rg_gs); BS_ONE(rg_disp);
+  out.push_back(ScratchMember{"rg_hout", -1, nullptr, &c->rg_hout});
+  BS_ONE(rs_keys_in); BS_ONE(rs_keys_out); BS_ONE(rs_vals_in); BS_ONE(rs_vals_out); BS_ONE(rs_cnt); BS_ONE(rs_img);
+  BS_ONE(rs_tmp);
+  BS_ONE(seg_npos);
+  BS_ARR(fp); BS_ARR(bd); BS_ARR(rf); BS_ARR(ft); BS_ARR(sd); BS_ARR(fc); BS_ARR(ol); BS_ARR(sp); BS_ARR(uc); BS_ARR(sw);
+  BS_ARR(tr); BS_ARR(ps); BS_ARR(mr); BS_ARR(pr); BS_ARR(gn);
+  BS_ONE(bases_dev);
+  BS_ARR(tn); BS_ARR(gd);
+  BS_ONE(gm_dev);
+  BS_ARR(evd);
+  BS_ONE(fs_dev);
+  BS_ARR(sh); BS_ARR(bt);
+  BS_ONE(tile_desc);
+#undef BS_ONE
+#undef BS_ARR
+}
+
+// bs_ctx constructs exactly the buffers the table lists (no device needed: a context's constructor calls no HIP)
+bool scratch_members_complete(bs_ctx* c, long long born, int64_t* n_members)
+{
+  std::vector<ScratchMember> m;
+  scratch_members(c, m);
+  if (n_members)
+    *n_members = (int64_t)m.size();
+  return born == (long long)m.size();
+}
+
+void scratch_slot(const ScratchMember& m, bs_scratch_slot* s)
+{
+  memset(s, 0, sizeof *s);
+  if (m.index < 0)
+    snprintf(s->name, sizeof s->name, "%s", m.name);
+  else
+    snprintf(s->name, sizeof s->name, "%s[%d]", m.name, m.index);
+  s->address = (uint64_t)(uintptr_t)(m.dev ? m.dev->p : m.host->p);
+  s->requested = (int64_t)(m.dev ? m.dev->cap : m.host->cap);
+  s->guard = (int64_t)(m.dev ? m.dev->guard : m.host->guard);
+  s->first_bad = s->last_bad = -1;
+  s->host = m.host ? 1 : 0;
+}
+
+}  // namespace
+
+int bs_selftest_scratch_guard(bs_ctx* ctx, int flags, int poison_byte)
+{
+  if (!ctx)
+    return BS_ERR_INVALID;
+  if ((flags & ~(BS_SCRATCH_CANARY | BS_SCRATCH_POISON)) || poison_byte < 0 || poison_byte > 255)
+    return fail(ctx, BS_ERR_INVALID, "bs_selftest_scratch_guard: flags are BS_SCRATCH_CANARY | BS_SCRATCH_POISON, the poison a byte");
+  std::vector<ScratchMember> m;
+  scratch_members(ctx, m);
+  for (const auto& b : m)
+    if (b.dev ? b.dev->p != nullptr : b.host->p != nullptr)
+      return fail(ctx, BS_ERR_INVALID, "bs_selftest_scratch_guard: the context has already allocated (set the guard right after bs_create)");
+  ctx->sg.flags = flags;
+  ctx->sg.poison = (unsigned char)poison_byte;
+  for (const auto& b : m) {
+    if (b.dev)
+      b.dev->sg = &ctx->sg;
+    else
+      b.host->sg = &ctx->sg;
+  }
+  return BS_OK;
+}
+
+int bs_selftest_scratch_list(bs_ctx* ctx, bs_scratch_slot* slots, int64_t capacity, int64_t* n_slots)
+{
+  if (!n_slots || capacity < 0 || (capacity > 0 && !slots))
+    return BS_ERR_INVALID;
+  *n_slots = 0;
+  if (!ctx) {  // the member table against what a context constructs
+    const long long before = scratch_bufs_born;
+    bs_ctx* c = new (std::nothrow) bs_ctx();
+    if (!c)
+      return BS_ERR_NOMEM;
+    const bool ok = scratch_members_complete(c, scratch_bufs_born - before, n_slots);
+    delete c;
+    return ok ? BS_OK : BS_ERR_INTERNAL;
+  }
+  std::vector<ScratchMember> m;
+  scratch_members(ctx, m);
+  for (const auto& b : m) {
+    if ((b.dev ? b.dev->guard : b.host->guard) == 0)
+      continue;
+    if (*n_slots < capacity)
+      scratch_slot(b, &slots[*n_slots]);
+    ++*n_slots;
+  }
+  return BS_OK;
+}
+
+int bs_selftest_scratch_check(bs_ctx* ctx, bs_scratch_report* rep)
+{
+  if (!ctx || !rep)
+    return BS_ERR_INVALID;
+  memset(rep, 0, sizeof *rep);
+  BS_HIP(ctx, hipSetDevice(ctx->device));
+  BS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->side)
+    BS_HIP(ctx, hipStreamSynchronize(ctx->side));
+  std::vector<ScratchMember> m;
+  scratch_members(ctx, m);
+  std::vector<unsigned char> h;
+  for (const auto& b : m) {
+    const size_t g = b.dev ? b.dev->guard : b.host->guard;
+    if (g == 0)
+      continue;
+    const size_t req = b.dev ? b.dev->cap : b.host->cap;
+    rep->n_guarded++;
+    rep->bytes_requested += (int64_t)req;
+    if (!(ctx->sg.flags & BS_SCRATCH_CANARY))  // (poison alone: the guards hold nothing to compare)
+      continue;
+    const unsigned char* v;
+    if (b.dev) {
+      h.resize(g);
+      BS_HIP(ctx, hipMemcpy(h.data(), (const char*)b.dev->p + req, g, hipMemcpyDeviceToHost));
+      v = h.data();
+    } else {
+      v = (const unsigned char*)b.host->p + req;
+    }
+    int64_t first = -1, last = -1;
+    for (size_t i = 0; i < g; i++)
+      if (v[i] != SCRATCH_CANARY) {
+        if (first < 0)
+          first = (int64_t)i;
+        last = (int64_t)i;
+      }
+    if (first < 0)
+      continue;
+    if (rep->n_damaged < BS_SCRATCH_REPORT_MAX) {
+      bs_scratch_slot* s = &rep->damaged[rep->n_damaged];
+      scratch_slot(b, s);
+      s->first_bad = first;
+      s->last_bad = last;
+      rep->n_listed++;
+    }
+    rep->n_damaged++;
+  }
   return BS_OK;
 }
 

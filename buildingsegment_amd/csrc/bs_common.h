@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <string>
 #include <vector>
@@ -13,11 +14,32 @@
 
 namespace bs {
 
+// ---- scratch guard (bs_selftest_scratch_guard): a test hook, off by default -------------------------------------
+// While a context's guard is set, every FRESH allocation of one of its buffers is `bytes + guard` long, reports
+// cap == bytes, has its guard filled with SCRATCH_CANARY (flag bit 0) and its front with the poison byte (bit 1).
+// The guard is never smaller than the slack of an unguarded allocation, so whatever stays inside its allocation
+// without the guard stays inside it with the guard.  bs_selftest_scratch_check reads the guards back.
+struct ScratchGuard {
+  int flags = 0;  // BS_SCRATCH_CANARY | BS_SCRATCH_POISON
+  unsigned char poison = 0;
+};
+enum : unsigned char { SCRATCH_CANARY = 0xC5 };
+inline size_t scratch_guard_bytes(size_t bytes)
+{
+  const size_t g = bytes / 8 + 256;
+  return g < 4096 ? (size_t)4096 : g;
+}
+// buffers constructed on this thread so far: bs_create compares the growth over `new bs_ctx` with the member table
+// of bs_capi.hip, so that a buffer added to bs_ctx and not listed there fails every bs_create
+inline thread_local long long scratch_bufs_born = 0;
+
 // ---- small device buffer that only grows, freed with its owner ------------
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
-  DevBuf() = default;
+  const ScratchGuard* sg = nullptr;  // the owner's guard switch (set by bs_selftest_scratch_guard), nullptr = none
+  size_t guard = 0;                  // guard bytes behind cap of this allocation, 0 = unguarded
+  DevBuf() { scratch_bufs_born++; }
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
   ~DevBuf() { release(); }
@@ -29,10 +51,30 @@ struct DevBuf {
       (void)hipFree(p);
     p = nullptr;
     cap = 0;
+    guard = 0;
+    if (sg && sg->flags)
+      return reserve_guarded(bytes);
     size_t want = bytes + bytes / 8 + 256;
     hipError_t e = hipMalloc(&p, want);
     if (e == hipSuccess)
       cap = want;
+    return e;
+  }
+  // the fills are synchronous: done on the device before this returns, whatever stream the caller launches on
+  hipError_t reserve_guarded(size_t bytes)
+  {
+    const size_t g = scratch_guard_bytes(bytes);
+    hipError_t e = hipMalloc(&p, bytes + g);
+    if (e != hipSuccess)
+      return e;
+    cap = bytes;
+    guard = g;
+    if (sg->flags & 1)
+      e = hipMemset((char*)p + bytes, SCRATCH_CANARY, g);
+    if (e == hipSuccess && (sg->flags & 2))
+      e = hipMemset(p, sg->poison, bytes);
+    if (e == hipSuccess)
+      e = hipDeviceSynchronize();
     return e;
   }
   void release()
@@ -41,6 +83,7 @@ struct DevBuf {
       (void)hipFree(p);
     p = nullptr;
     cap = 0;
+    guard = 0;
   }
   template <class T>
   T* as() const
@@ -54,7 +97,9 @@ struct DevBuf {
 struct HostBuf {
   void* p = nullptr;
   size_t cap = 0;
-  HostBuf() = default;
+  const ScratchGuard* sg = nullptr;  // as DevBuf (the canary only: the host writes this memory too)
+  size_t guard = 0;
+  HostBuf() { scratch_bufs_born++; }
   HostBuf(const HostBuf&) = delete;
   HostBuf& operator=(const HostBuf&) = delete;
   ~HostBuf() { release(); }
@@ -66,10 +111,18 @@ struct HostBuf {
       (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
-    size_t want = bytes + bytes / 8 + 256;
+    guard = 0;
+    const bool guarded = sg && sg->flags;
+    size_t want = bytes + (guarded ? scratch_guard_bytes(bytes) : bytes / 8 + 256);
     hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e == hipSuccess)
-      cap = want;
+    if (e != hipSuccess)
+      return e;
+    cap = guarded ? bytes : want;
+    if (guarded) {
+      guard = want - bytes;
+      if (sg->flags & 1)
+        memset((char*)p + bytes, SCRATCH_CANARY, guard);
+    }
     return e;
   }
   void release()
@@ -78,6 +131,7 @@ struct HostBuf {
       (void)hipHostFree(p);
     p = nullptr;
     cap = 0;
+    guard = 0;
   }
   template <class T>
   T* as() const
@@ -234,10 +288,11 @@ struct bs_ctx : bs_ctx_handles {
   hipStream_t stream = nullptr;
   std::string err;
   bs_timings tm{};
+  bs::ScratchGuard sg;  // bs_selftest_scratch_guard (off)
 
   // grid scratch
   bs::DevBuf keys_in, keys_out, vals_in, vals_out, cub_tmp, uniq_keys, uniq_cnt, misc;
-  bs::DevBuf table, spts, slocal;
+  bs::DevBuf table, spts;
   // kNN scratch
   bs::DevBuf fb_list, d_xyz_h, d_neigh_h, d_normals_h, d_plane_h;
   // pipeline scratch (bs_segment_dev with NULL outputs)
@@ -266,9 +321,9 @@ struct bs_ctx : bs_ctx_handles {
   // pipeline for the same cloud / k / neigh buffer: the grower takes them instead of translating indices
   bs::DevBuf seg_npos;
   // scratch of the sharded pass (bs_sharded.hip): named by use there
-  bs::DevBuf fp[24];  // scratch of bs_footprints[_dev] (bs_contour.hip)
+  bs::DevBuf fp[23];  // scratch of bs_footprints[_dev] (bs_contour.hip)
   bs::DevBuf bd[14];  // scratch of the building map, assignment and votes (bs_building.hip)
-  bs::DevBuf rf[16];  // scratch of the roof stage (bs_roof.hip)
+  bs::DevBuf rf[15];  // scratch of the roof stage (bs_roof.hip)
   bs::DevBuf ft[5];   // scratch of the plane fit (bs_fit.hip)
   // solids (bs_solid.hip): scratch, and what bs_solids_count_dev leaves for bs_solids_emit_dev (tops, clean map, offsets)
   bs::DevBuf sd[14];
@@ -288,7 +343,7 @@ struct bs_ctx : bs_ctx_handles {
   double ol_ms_emit = 0;  // the last emit
   // simplified outlines (bs_simplify.hip): scratch, and what bs_simple_outlines_count_dev leaves for
   // bs_simple_outlines_emit_dev (the finished vertex arrays)
-  bs::DevBuf sp[40];
+  bs::DevBuf sp[39];
   bool sp_valid = false, sp_has_z = false;
   int64_t sp_nsv = 0;
   double sp_ms_emit = 0;  // the last emit
@@ -306,7 +361,7 @@ struct bs_ctx : bs_ctx_handles {
     const uint8_t* flag = nullptr;
   } sp_state;
   // clean outlines (bs_uncross.hip): scratch, and what bs_clean_outlines_count_dev leaves for bs_clean_outlines_emit_dev
-  bs::DevBuf uc[32];
+  bs::DevBuf uc[29];
   bool uc_valid = false, uc_has_z = false;
   int64_t uc_nsv = 0;
   double uc_ms_emit = 0;
@@ -321,7 +376,7 @@ struct bs_ctx : bs_ctx_handles {
   const int32_t *uc_z = nullptr, *uc_right = nullptr;  // (their Z and right labels, for bs_polysolid.hip)
   // outline triangles (bs_triangulate.hip): scratch, and what bs_outline_triangles_count_dev leaves for
   // bs_outline_triangles_emit_dev (the triangles)
-  bs::DevBuf tr[16];
+  bs::DevBuf tr[13];
   bool tr_valid = false;
   int64_t tr_ntri = 0;
   double tr_ms_emit = 0;
@@ -333,20 +388,20 @@ struct bs_ctx : bs_ctx_handles {
   // polygon solids (bs_polysolid.hip): scratch, and what bs_poly_solids_count_dev leaves for bs_poly_solids_emit_dev (the
   // twins, the vertex numbers, the offsets); the emit also reads the clean vertices and the triangles, so a later clean
   // count on this context ends its validity
-  bs::DevBuf ps[36];
+  bs::DevBuf ps[29];
   bool ps_valid = false;
   int32_t ps_bin = 0, ps_base = 0, ps_nl = 0, ps_nr = 0, ps_nsv = 0;
   bool ps_bases = false;  // the count ran under bs_set_building_bases: the emit reads bases_dev
   int64_t ps_nv = 0, ps_nf = 0, ps_ni = 0, ps_ntri = 0;
   double ps_ms_emit[2] = {0, 0};  // vertex pass, face passes of the last emit
-  bs::DevBuf mr[20];  // scratch of the model raster (bs_modelraster.hip); it keeps no state between calls
-  bs::DevBuf pr[16];  // scratch of the point residuals (bs_pointresid.hip); it keeps no state between calls
+  bs::DevBuf mr[13];  // scratch of the model raster (bs_modelraster.hip); it keeps no state between calls
+  bs::DevBuf pr[15];  // scratch of the point residuals (bs_pointresid.hip); it keeps no state between calls
   bs::DevBuf gn[32];  // scratch of the roof generalisation (bs_generalise.hip); it keeps no state between calls
   // per-building bases (bs_set_building_bases): the host table, its copy on the device; empty = off
   std::vector<int32_t> bases;
   bs::DevBuf bases_dev;
-  bs::DevBuf tn[16];  // scratch of the terrain stage (bs_terrain.hip); it keeps no state between calls
-  bs::DevBuf gd[16];  // scratch of the ground stage (bs_ground.hip); it keeps no state between calls
+  bs::DevBuf tn[15];  // scratch of the terrain stage (bs_terrain.hip); it keeps no state between calls
+  bs::DevBuf gd[10];  // scratch of the ground stage (bs_ground.hip); it keeps no state between calls
   // ground model (bs_set_ground_model): the device copy of the table and its lattice; gm_on == false = off
   bs::DevBuf gm_dev;
   bool gm_on = false;

@@ -2148,7 +2148,11 @@ __global__ __launch_bounds__(64) void grow_spec2_kernel(SpecArgs a, const unsign
     o.center[1] = ccy;
     o.center[2] = ccz;
     o.list_off = list.off;
-    o.list_n = ln;
+    // An attempt that ran out of pool leaves the entries [lflushed, ln) in its LDS ring: the slab holds lflushed of them,
+    // and reset_tags_kernel walks list_n entries of the slab whatever the status (the claims that stay behind are what the
+    // full refresh after a pool exhaustion is for).  Every other status has the whole list in the slab: the flush_list(ln)
+    // that ends the attempt either succeeds (lflushed == ln) or turns the status into ST_NOMEM itself.
+    o.list_n = status == ST_NOMEM ? lflushed : ln;
     o.log_off = log.off;
     o.log_n = logn;
     o.steps = iters;

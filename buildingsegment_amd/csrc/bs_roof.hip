@@ -35,7 +35,8 @@ constexpr int FILL_GROUP = 8;  // fill rounds launched per host round trip (even
 constexpr int FILL_GRID = 512; // workgroups of a fill kernel (grid-stride over the list)
 // scratch of bs_ctx::rf
 enum { RF_KEYS, RF_KEYS2, RF_RUNS, RF_TMP, RF_BEST, RF_NEXT, RF_LIST_A, RF_LIST_B, RF_MISC, RF_TAB, RF_FIG, RF_IN_XYZ,
-       RF_IN_MAP, RF_IN_PLANE, RF_OUT };
+       RF_IN_MAP, RF_IN_PLANE, RF_OUT, RF_COUNT };
+static_assert(RF_COUNT <= (int)(sizeof(bs_ctx::rf) / sizeof(DevBuf)), "bs_ctx::rf is too short");
 
 struct Tables {  // per plane, device: entry p - 1 is plane p
   const int32_t* home;

@@ -312,6 +312,51 @@ typedef struct bs_grow_counters {
 } bs_grow_counters;
 int bs_get_grow_counters(const bs_ctx* ctx, bs_grow_counters* out);
 
+/* Self-test of the context's scratch memory (off by default; tests/test_gpu_scratch_guard.py).  Every stage cuts the
+ * buffers of its context into sub-arrays by hand, and an allocation normally carries 12.5 % + 256 B of slack that hides a
+ * write past the requested size.  While the guard is set, every FRESH allocation of one of this context's buffers
+ *   - is requested + guard bytes long, guard = max(4096, requested / 8 + 256) -- never less than the normal slack;
+ *   - counts as exactly `requested` bytes: a later request up to that size keeps the buffer and its contents, a larger
+ *     one allocates afresh, as always;
+ *   - BS_SCRATCH_CANARY: has its guard filled with the byte 0xC5, which bs_selftest_scratch_check reads back;
+ *   - BS_SCRATCH_POISON: has its requested bytes filled with poison_byte (0..255), so that a stage that reads scratch
+ *     nothing wrote reads that and not the zeros of a first allocation.  A buffer that is kept is never filled again.
+ * The page-locked host buffer the grower's kernels write gets the canary only.  Accepted only while the context has
+ * nothing allocated (right after bs_create), BS_ERR_INVALID otherwise; flags == 0 leaves the guard off.  Other contexts
+ * are not affected. */
+#define BS_SCRATCH_CANARY 1
+#define BS_SCRATCH_POISON 2
+int bs_selftest_scratch_guard(bs_ctx* ctx, int flags, int poison_byte);
+
+/* One guarded buffer: `name` is the member of bs_ctx (csrc/bs_common.h) with its array index, e.g. "rf[9]". */
+typedef struct bs_scratch_slot {
+  char name[24];
+  uint64_t address;   /* of the first requested byte (device memory; page-locked host memory where host != 0) */
+  int64_t requested;  /* bytes the stage asked for */
+  int64_t guard;      /* bytes behind them */
+  int64_t first_bad;  /* offsets of the first and the last damaged guard byte from the end of the request ... */
+  int64_t last_bad;   /* ... as of the last bs_selftest_scratch_check that listed this slot; -1 = clean / bs_..._list */
+  int32_t host;
+  int32_t reserved;
+} bs_scratch_slot;
+
+/* Synchronises the context's streams and reads every guard back. */
+#define BS_SCRATCH_REPORT_MAX 8
+typedef struct bs_scratch_report {
+  int64_t n_guarded;        /* buffers allocated under the guard */
+  int64_t bytes_requested;  /* their requested sizes, summed */
+  int64_t n_damaged;        /* buffers whose guard no longer holds the canary */
+  int64_t n_listed;         /* min(n_damaged, BS_SCRATCH_REPORT_MAX) */
+  bs_scratch_slot damaged[BS_SCRATCH_REPORT_MAX];  /* the first of them, in the order of bs_ctx */
+} bs_scratch_report;
+int bs_selftest_scratch_check(bs_ctx* ctx, bs_scratch_report* report);
+
+/* Every buffer of the context allocated under the guard, in the order of bs_ctx: up to `capacity` of them into slots
+ * (nullable with capacity 0), their number into *n_slots.  With ctx == NULL nothing is listed and *n_slots receives the
+ * number of buffer members a context has -- after checking, without a device, that the member table the names come from
+ * lists every one of them (BS_ERR_INTERNAL if not; bs_create makes the same check). */
+int bs_selftest_scratch_list(bs_ctx* ctx, bs_scratch_slot* slots, int64_t capacity, int64_t* n_slots);
+
 /* Copy the plane records of the last region-grow on this context to the host. */
 int bs_planes_fetch(bs_ctx* ctx, bs_planes* planes);
 
