@@ -33,6 +33,147 @@ def default_params(**kw) -> Params:
     return p
 
 
+# ---- what every stage of the binding shares: copies out of the library's structs, pointers into it, the input checks -------
+def _copy(ptr, shape, dtype):
+    """An owned numpy copy of the library's array at ptr, or the empty array of that shape and dtype when an extent is 0."""
+    if 0 in shape:
+        return np.zeros(shape, dtype)
+    a = np.ctypeslib.as_array(ptr, shape)
+    if a.dtype != dtype:
+        raise TypeError(f"a {a.dtype} array was to be copied as {np.dtype(dtype)}")
+    return a.copy()
+
+
+def _copy_arrays(out, table, n):
+    """{name: _copy} of the arrays of the struct `out` that share the length n: table rows are (name, dtype, columns)"""
+    return {name: _copy(getattr(out, name), (n, cols) if cols > 1 else (n,), dt) for name, dt, cols in table}
+
+
+def _rows(names, dtype):
+    """(name, dtype, 1) rows for _copy_arrays from the names of arrays of one dtype"""
+    return tuple((k, np.dtype(dtype), 1) for k in names)
+
+
+_PAD = np.zeros(4, np.int64)  # what an empty table points at: never a null pointer, never read
+
+
+def _ptr(a):
+    """the address of an optional array, None (a null pointer) for None"""
+    return None if a is None else a.ctypes.data
+
+
+def _ptr0(a):
+    """the address of a table that may be empty"""
+    return (a if a.size else _PAD).ctypes.data
+
+
+def _fill(st, src, what, table, keep):
+    """Point the array fields of the ctypes struct st at the arrays of src (a dataclass `what`, or anything with its names):
+    table rows are (name, dtype, values).  The arrays the struct then reads go to `keep`, which must outlive it."""
+    types = dict(st._fields_)
+    for name, dt, n in table:
+        a = np.ascontiguousarray(getattr(src, name), dtype=dt).reshape(-1)
+        if len(a) != n:
+            raise ValueError(f"{what}.{name} must hold {n} values")
+        keep.append(a if len(a) else np.zeros(1, dt))
+        setattr(st, name, keep[-1].ctypes.data_as(types[name]))
+    return keep
+
+
+def _columns(table, n):
+    """(name, dtype, columns) rows over n entries as the (name, dtype, values) rows of _fill"""
+    return [(name, dt, n * cols) for name, dt, cols in table]
+
+
+def _points(who, xyz):
+    xyz = np.ascontiguousarray(xyz, dtype=np.int32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{who}: xyz must be [n][3]")
+    return xyz
+
+
+def _point_labels(who, name, labels, xyz):
+    a = np.ascontiguousarray(labels, dtype=np.int32)
+    if a.shape != (len(xyz),):
+        raise ValueError(f"{who}: {name} must be [n]")
+    return a
+
+
+def _label_top(who, label, top, n_labels, need_top=False):
+    """(label, top, h, w, n_labels) of a label image [height][width] and its optional top image [height][width][4]"""
+    label = np.ascontiguousarray(label, dtype=np.int32)
+    if label.ndim != 2 or label.size == 0:
+        raise ValueError(f"{who}: label must be [height][width]")
+    if top is None and need_top:
+        raise ValueError(f"{who}: the stage needs a top image")
+    if top is not None:
+        top = np.ascontiguousarray(top, dtype=np.int32)
+        if top.shape != label.shape + (4,):
+            raise ValueError(f"{who}: top must be [height][width][4]")
+    h, w = label.shape
+    return label, top, h, w, max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+
+
+def _origin(origin):
+    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
+    if org is not None and org.shape != (3,):
+        raise ValueError("origin must be [3]")
+    return org
+
+
+def _host_image(who, image, name, dev_form):
+    if image is None:
+        raise ValueError(f"{who}: the {name} image is on the device: use {dev_form}")
+    return image
+
+
+def _has_top(who, solids):
+    if solids.top is None:
+        raise ValueError(f"{who}: the Solids carry no top image (solids(top=True))")
+
+
+def _facet_and_top(who, roof_facets, solids, dev_form):
+    """what the pipeline conveniences need of roof_facets() and solids(): both images in host memory"""
+    _host_image(who, roof_facets.facet, "facet", dev_form)
+    _has_top(who, solids)
+
+
+def _write_obj(fn, path, what, *args):
+    """One OBJ writer of the library: fn(*args, path) with arrays passed by address (None: a null pointer), a status other
+    than 0 as BsError."""
+    rc = getattr(_lib.load(), fn)(*[_ptr(a) if a is None or isinstance(a, np.ndarray) else a for a in args],
+                                  str(path).encode())
+    if rc != 0:
+        raise BsError(rc, f"cannot write {path}" + (f" (or {what})" if what else ""))
+
+
+_FREES = {getattr(_lib, cls): f"bs_{name}_free" for cls, name in (
+    ("Contours", "contours"), ("Buildings", "buildings"), ("Roofs", "roofs"), ("PlaneFits", "plane_fits"), ("Solids", "solids"),
+    ("RoofGeneralise", "roof_generalise"), ("RoofFacets", "roof_facets"), ("Outlines", "outlines"),
+    ("SimpleOutlines", "simple_outlines"), ("CleanOutlines", "clean_outlines"), ("OutlineTriangles", "outline_triangles"),
+    ("PolySolids", "poly_solids"), ("ModelRaster", "model_raster"), ("PointResiduals", "point_residuals"),
+    ("Terrain", "terrain"), ("Ground", "ground"))}
+
+
+def _free(L, out):
+    """release what the library allocated into the struct `out`"""
+    getattr(L, _FREES[type(out)])(C.byref(out))
+
+
+def _take_chain(L, *parts):
+    """The tail of a form that hands several structs back: parts are (taker, struct, *arguments) in the order of the
+    returned tuple.  Every struct is released exactly once: by its taker, or here if an earlier copy raised."""
+    got = []
+    try:
+        for take, st, *args in parts:
+            got.append(None)  # take() releases st itself, also when it raises
+            got[-1] = take(L, st, *args)
+    finally:
+        for _, st, *_ in parts[len(got):]:
+            _free(L, st)
+    return tuple(got)
+
+
 @dataclass
 class Plane:
     """struct plane (my_function.h:25-30)."""
@@ -43,18 +184,13 @@ class Plane:
 
 
 def _planes_to_list(P: Planes):
-    out = []
     n = P.n_planes
     if n == 0:
-        return out
-    off = np.ctypeslib.as_array(P.offset, (n + 1,))
-    ids = np.ctypeslib.as_array(P.id, (n,))
-    nrm = np.ctypeslib.as_array(P.normal, (3 * n,)).reshape(n, 3)
-    ctr = np.ctypeslib.as_array(P.center, (3 * n,)).reshape(n, 3)
-    pidx = np.ctypeslib.as_array(P.point_idx, (int(off[n]),)) if off[n] > 0 else np.zeros(0, np.int32)
-    for i in range(n):
-        out.append(Plane(int(ids[i]), nrm[i].copy(), ctr[i].copy(), pidx[off[i]:off[i + 1]].copy()))
-    return out
+        return []
+    off, ids = _copy(P.offset, (n + 1,), np.int64), _copy(P.id, (n,), np.int32)
+    nrm, ctr = _copy(P.normal, (n, 3), np.float64), _copy(P.center, (n, 3), np.int32)
+    pidx = _copy(P.point_idx, (int(off[n]),), np.int32)  # (copied once: every plane's pointIdx is its slice of this copy)
+    return [Plane(int(ids[i]), nrm[i].copy(), ctr[i].copy(), pidx[off[i]:off[i + 1]]) for i in range(n)]
 
 
 class Context:
@@ -101,9 +237,7 @@ class Context:
     # ---- host-buffer API ----------------------------------------------------
     def knn_normals(self, xyz, params: Params | None = None):
         p = params or default_params()
-        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
-        if xyz.ndim != 2 or xyz.shape[1] != 3:
-            raise ValueError("xyz must be [n, 3]")
+        xyz = _points("knn_normals", xyz)
         n = xyz.shape[0]
         neigh = np.empty((n, p.k), dtype=np.int32)
         normals = np.empty((n, 3), dtype=np.float64)
@@ -223,7 +357,7 @@ class Context:
         mask = np.empty((h, w), dtype=np.uint8) if return_mask else None
         out, inf = Contours(), FootprintInfo()
         self._check(self._L.bs_footprints(self._h, img.ctypes.data, w, h, threshold, kernel_size, iterations,
-                                          mask.ctypes.data if return_mask else None, C.byref(out), C.byref(inf)))
+                                          _ptr(mask), C.byref(out), C.byref(inf)))
         fp = _take_contours(self._L, out, inf)
         return (fp, mask) if return_mask else fp
 
@@ -459,8 +593,8 @@ class Context:
         mask = np.empty(int(po[-1]), dtype=np.uint8) if return_mask else None
         out, inf, co = Contours(), FootprintInfo(), np.zeros(nt + 1, dtype=np.int32)
         self._check(self._L.bs_footprints_batch(self._h, flat.ctypes.data, w.ctypes.data, h.ctypes.data, nt, threshold,
-                                                kernel_size, iterations, mask.ctypes.data if return_mask else None,
-                                                C.byref(out), co.ctypes.data, C.byref(inf)))
+                                                kernel_size, iterations, _ptr(mask), C.byref(out), co.ctypes.data,
+                                                C.byref(inf)))
         fps = _take_contours_batch(self._L, out, inf, co, w, h)
         if return_mask:
             return fps, [mask[po[t]:po[t + 1]].reshape(h[t], w[t]) for t in range(nt)]
@@ -505,9 +639,7 @@ class Context:
         (x / bin, y / bin) in bmap, -1 outside every building.  Fills the point figures of `buildings` (the object
         building_map returned for bmap): n_points, n_above, z_min, z_max, z_sum over the points with
         !(z < ground_th)."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
-        if xyz.ndim != 2 or xyz.shape[1] != 3:
-            raise ValueError("xyz must be [n, 3]")
+        xyz = _points("assign_buildings", xyz)
         bmap = np.ascontiguousarray(bmap, dtype=np.int32)
         h, w = bmap.shape
         bidx = np.empty(len(xyz), dtype=np.int32)
@@ -589,15 +721,11 @@ class Context:
         fill in synchronous rounds, per-plane figures and heights.  bmap is the building map, plane_idx the labels,
         home / normal / center the per-plane tables (entry p - 1 is plane p; home from roof_homes).  Returns Roofs with
         roof, support and height [height][width] int32 (support / height None when switched off)."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
-        if xyz.ndim != 2 or xyz.shape[1] != 3:
-            raise ValueError("xyz must be [n, 3]")
+        xyz = _points("roofs", xyz)
         bmap = np.ascontiguousarray(bmap, dtype=np.int32)
         if bmap.ndim != 2:
             raise ValueError("roofs: bmap must be [height][width]")
-        pi = np.ascontiguousarray(plane_idx, dtype=np.int32)
-        if pi.shape != (len(xyz),):
-            raise ValueError("plane_idx must be [n]")
+        pi = _point_labels("roofs", "plane_idx", plane_idx, xyz)
         h, w = bmap.shape
         tabs = _roof_tables(home, normal, center)
         roof = np.empty((h, w), dtype=np.int32)
@@ -606,8 +734,7 @@ class Context:
         out = _lib.Roofs()
         self._check(self._L.bs_roofs(self._h, xyz.ctypes.data, len(xyz), bin, float(ground_th), bmap.ctypes.data, w, h,
                                      pi.ctypes.data, len(tabs[0]), *[t.ctypes.data for t in tabs], min_votes,
-                                     roof.ctypes.data, sup.ctypes.data if support else None,
-                                     hgt.ctypes.data if height else None, C.byref(out)))
+                                     roof.ctypes.data, _ptr(sup), _ptr(hgt), C.byref(out)))
         return _take_roofs(self._L, out, roof, sup, hgt, tabs, bin)
 
     def roofs_dev(self, d_xyz, n, d_map, width, height, d_plane_idx, home, normal, center, d_roof, d_support=0,
@@ -627,16 +754,12 @@ class Context:
         """Refit the planes 1 .. n_planes from the points that carry their label.  Returns PlaneFits (arrays [n_planes],
         entry p - 1 = plane p); with residuals=True its `residual` is the [n] int32 truncated distance of every point to
         its fitted plane (INT32_MIN for the points of no fitted plane)."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
-        if xyz.ndim != 2 or xyz.shape[1] != 3:
-            raise ValueError("xyz must be [n, 3]")
-        pi = np.ascontiguousarray(plane_idx, dtype=np.int32)
-        if pi.shape != (len(xyz),):
-            raise ValueError("plane_idx must be [n]")
+        xyz = _points("plane_fit", xyz)
+        pi = _point_labels("plane_fit", "plane_idx", plane_idx, xyz)
         res = np.empty(len(xyz), dtype=np.int32) if residuals else None
         out = _lib.PlaneFits()
-        self._check(self._L.bs_plane_fit(self._h, xyz.ctypes.data, len(xyz), pi.ctypes.data, n_planes,
-                                         res.ctypes.data if residuals else None, C.byref(out)))
+        self._check(self._L.bs_plane_fit(self._h, xyz.ctypes.data, len(xyz), pi.ctypes.data, n_planes, _ptr(res),
+                                         C.byref(out)))
         return _take_fits(self._L, out, res)
 
     def plane_fit_dev(self, d_xyz, n, d_plane_idx, n_planes, d_residual=0):
@@ -683,21 +806,13 @@ class Context:
         roofs() on it (its roof image, plane tables, z_min / z_max and bin are used).  base_z defaults to
         (int) buildings.ground_th; flat [n_buildings], the top of the unroofed pixels, to z_sum / n_above truncated
         (write_buildings_obj's top) and to base_z where n_above == 0.  Returns Solids."""
-        bmap = np.ascontiguousarray(bmap, dtype=np.int32)
-        if roofs.roof is None:
-            raise ValueError("solids: the roof image is on the device: use solids_dev")
-        roof = np.ascontiguousarray(roofs.roof, dtype=np.int32)
-        if bmap.ndim != 2 or roof.shape != bmap.shape:
-            raise ValueError("solids: bmap and roofs.roof must be [height][width] of the same size")
-        base_z, flat = _solid_defaults(buildings, base_z, flat)
+        bmap, roof, base_z, flat, tabs = _solid_inputs("solids", bmap, roofs, buildings, base_z, flat)
         h, w = bmap.shape
-        tabs = _solid_tables(roofs.normal, roofs.center, roofs.z_min, roofs.z_max)
         timg = np.empty((h, w, 4), dtype=np.int32) if top else None
         out = _lib.Solids()
         self._check(self._L.bs_solids(self._h, bmap.ctypes.data, roof.ctypes.data, w, h, len(flat), len(tabs[0]),
-                                      *[t.ctypes.data for t in tabs], int(roofs.bin), base_z,
-                                      (flat if len(flat) else np.zeros(1, np.int32)).ctypes.data,
-                                      timg.ctypes.data if top else None, C.byref(out)))
+                                      *[t.ctypes.data for t in tabs], int(roofs.bin), base_z, _ptr0(flat), _ptr(timg),
+                                      C.byref(out)))
         s = _take_solids(self._L, out, timg, True)
         s.base = self.building_bases()
         return s
@@ -711,8 +826,7 @@ class Context:
         out = _lib.Solids()
         self._check(self._L.bs_solids_count_dev(self._h, d_map or None, d_roof or None, width, height, len(flat),
                                                 len(tabs[0]), *[t.ctypes.data for t in tabs], int(bin), int(base_z),
-                                                (flat if len(flat) else np.zeros(1, np.int32)).ctypes.data,
-                                                d_top or None, C.byref(out)))
+                                                _ptr0(flat), d_top or None, C.byref(out)))
         s = _take_solids(self._L, out, None, False)
         s.base = self.building_bases()
         return s
@@ -766,22 +880,14 @@ class Context:
         its highest-ranking neighbour with the longest common border, round by round until nothing moves (or max_rounds
         rounds were applied).  The arguments before min_pixels are those of solids().  Returns RoofGeneralise: the
         figures, .roof (the new roof image) and .roofs (a Roofs every later stage accepts)."""
-        bmap = np.ascontiguousarray(bmap, dtype=np.int32)
-        if roofs.roof is None:
-            raise ValueError("generalise_roofs: the roof image is on the device: use generalise_roofs_dev")
-        roof = np.ascontiguousarray(roofs.roof, dtype=np.int32)
-        if bmap.ndim != 2 or roof.shape != bmap.shape:
-            raise ValueError("generalise_roofs: bmap and roofs.roof must be [height][width] of the same size")
-        base_z, flat = _solid_defaults(buildings, base_z, flat)
+        bmap, roof, base_z, flat, tabs = _solid_inputs("generalise_roofs", bmap, roofs, buildings, base_z, flat)
         h, w = bmap.shape
-        tabs = _solid_tables(roofs.normal, roofs.center, roofs.z_min, roofs.z_max)
         par = _lib.RoofGeneraliseParams(int(min_pixels), int(merge_flat), int(step_tol), int(bend_tol), int(max_rounds))
         new = np.empty((h, w), dtype=np.int32)
         out = _lib.RoofGeneralise()
         self._check(self._L.bs_roof_generalise(self._h, bmap.ctypes.data, roof.ctypes.data, w, h, len(flat), len(tabs[0]),
-                                               *[t.ctypes.data for t in tabs], int(roofs.bin), base_z,
-                                               (flat if len(flat) else np.zeros(1, np.int32)).ctypes.data, C.byref(par),
-                                               new.ctypes.data, C.byref(out)))
+                                               *[t.ctypes.data for t in tabs], int(roofs.bin), base_z, _ptr0(flat),
+                                               C.byref(par), new.ctypes.data, C.byref(out)))
         g = _take_roof_generalise(self._L, out, new)
         g.roofs = copy.copy(roofs)  # the tables, z_min / z_max and bin stay
         g.roofs.roof, g.roofs.pixels, g.roofs.support, g.roofs.height = new, g.plane_pixels_out[1:].copy(), None, None
@@ -798,8 +904,7 @@ class Context:
         out = _lib.RoofGeneralise()
         self._check(self._L.bs_roof_generalise_dev(self._h, d_map or None, d_roof or None, width, height, len(flat),
                                                    len(tabs[0]), *[t.ctypes.data for t in tabs], int(bin), int(base_z),
-                                                   (flat if len(flat) else np.zeros(1, np.int32)).ctypes.data,
-                                                   C.byref(par), d_roof_out or None, C.byref(out)))
+                                                   _ptr0(flat), C.byref(par), d_roof_out or None, C.byref(out)))
         return _take_roof_generalise(self._L, out, None)
 
     # ---- roof facets and the edges between them (bs_roof_facets, include/bs_api.h) -------------------------------------
@@ -831,10 +936,8 @@ class Context:
 
     def roof_structure(self, bmap, roofs, solids):
         """roof_facets() from the Roofs of roofs() and the Solids of solids() on the same map."""
-        if solids.top is None:
-            raise ValueError("roof_structure: the Solids carry no top image (solids(top=True))")
-        if roofs.roof is None:
-            raise ValueError("roof_structure: the roof image is on the device: use roof_facets_dev")
+        _has_top("roof_structure", solids)
+        _host_image("roof_structure", roofs.roof, "roof", "roof_facets_dev")
         return self.roof_facets(bmap, roofs.roof, solids.top, n_buildings=solids.n_buildings, n_planes=len(roofs.z_min))
 
     # ---- facet outlines: polygon rings with holes per label (bs_facet_outlines, include/bs_api.h) ------------------------
@@ -842,18 +945,9 @@ class Context:
         """Every label of a label image ([height][width], negative = outside) as polygon rings with holes; with top
         ([height][width][4] as Solids.top) every vertex carries a Z.  n_labels defaults to label.max() + 1.  Returns
         Outlines."""
-        label = np.ascontiguousarray(label, dtype=np.int32)
-        if label.ndim != 2 or label.size == 0:
-            raise ValueError("facet_outlines: label must be [height][width]")
-        if top is not None:
-            top = np.ascontiguousarray(top, dtype=np.int32)
-            if top.shape != label.shape + (4,):
-                raise ValueError("facet_outlines: top must be [height][width][4]")
-        h, w = label.shape
-        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        label, top, h, w, nl = _label_top("facet_outlines", label, top, n_labels)
         out = _lib.Outlines()
-        self._check(self._L.bs_facet_outlines(self._h, label.ctypes.data, None if top is None else top.ctypes.data, w, h, nl,
-                                              C.byref(out)))
+        self._check(self._L.bs_facet_outlines(self._h, label.ctypes.data, _ptr(top), w, h, nl, C.byref(out)))
         return _take_outlines(self._L, out, True)
 
     def facet_outlines_dev(self, d_label, d_top, width, height, n_labels):
@@ -871,31 +965,19 @@ class Context:
 
     def roof_outlines(self, roof_facets, solids):
         """facet_outlines() of the facet image of roof_facets() / roof_structure() with the tops of solids()."""
-        if roof_facets.facet is None:
-            raise ValueError("roof_outlines: the facet image is on the device: use facet_outlines_dev")
-        if solids.top is None:
-            raise ValueError("roof_outlines: the Solids carry no top image (solids(top=True))")
+        _facet_and_top("roof_outlines", roof_facets, solids, "facet_outlines_dev")
         return self.facet_outlines(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets)
-
 
     # ---- simplified outlines: shared arcs, exact Douglas-Peucker (bs_simple_outlines, include/bs_api.h) ----------------
     def simplified_outlines(self, label, top=None, n_labels=None, num=0, den=1):
         """The outlines of facet_outlines() cut into the arcs that two labels share, every arc simplified by an exact
         Douglas-Peucker with the tolerance tol2 = num / den in lattice units squared (simplify_tolerance()).  Returns
         (SimpleOutlines, the plain Outlines without vertices)."""
-        label = np.ascontiguousarray(label, dtype=np.int32)
-        if label.ndim != 2 or label.size == 0:
-            raise ValueError("simplified_outlines: label must be [height][width]")
-        if top is not None:
-            top = np.ascontiguousarray(top, dtype=np.int32)
-            if top.shape != label.shape + (4,):
-                raise ValueError("simplified_outlines: top must be [height][width][4]")
-        h, w = label.shape
-        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        label, top, h, w, nl = _label_top("simplified_outlines", label, top, n_labels)
         out, plain = _lib.SimpleOutlines(), _lib.Outlines()
-        self._check(self._L.bs_simple_outlines(self._h, label.ctypes.data, None if top is None else top.ctypes.data, w, h, nl,
-                                               int(num), int(den), C.byref(out), C.byref(plain)))
-        return _take_simple_outlines(self._L, out, True), _take_outlines(self._L, plain, False)
+        self._check(self._L.bs_simple_outlines(self._h, label.ctypes.data, _ptr(top), w, h, nl, int(num), int(den),
+                                               C.byref(out), C.byref(plain)))
+        return _take_chain(self._L, (_take_simple_outlines, out, True), (_take_outlines, plain, False))
 
     def simplified_outlines_dev(self, d_label, d_top, width, height, n_labels, num=0, den=1):
         """Device-resident count (bs_simple_outlines_count_dev): d_label and d_top (0: no Z) are device pointers (ints).
@@ -904,7 +986,7 @@ class Context:
         out, plain = _lib.SimpleOutlines(), _lib.Outlines()
         self._check(self._L.bs_simple_outlines_count_dev(self._h, d_label or None, d_top or None, width, height,
                                                          int(n_labels), int(num), int(den), C.byref(out), C.byref(plain)))
-        return _take_simple_outlines(self._L, out, False), _take_outlines(self._L, plain, False)
+        return _take_chain(self._L, (_take_simple_outlines, out, False), (_take_outlines, plain, False))
 
     def simplified_outlines_emit_dev(self, d_sxy, d_sz, d_right, d_flag):
         """The kept vertices of the last simplified_outlines_dev on this context into device buffers (ints) of exactly
@@ -917,10 +999,7 @@ class Context:
         tolerance in millimetres (bin: the pixel edge, by default the Solids').  clean=True: clean_outlines() instead --
         polygons whose segments meet only in shared end points -- as (CleanOutlines, the plain Outlines); sweeps: the sweep
         mode of that clean count (set_outline_sweeps), None = the context's."""
-        if roof_facets.facet is None:
-            raise ValueError("roof_polygons: the facet image is on the device: use simplified_outlines_dev")
-        if solids.top is None:
-            raise ValueError("roof_polygons: the Solids carry no top image (solids(top=True))")
+        _facet_and_top("roof_polygons", roof_facets, solids, "simplified_outlines_dev")
         num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
         if clean:
             c, _, plain = self.clean_outlines(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den,
@@ -961,22 +1040,14 @@ class Context:
         > 0: a cap.  cell_log2: the broad-phase cell edge, 0 = the default.  sweeps: the sweep mode of this call
         (set_outline_sweeps), None = the context's.  Returns (CleanOutlines, the SimpleOutlines without vertices, the plain
         Outlines without vertices)."""
-        label = np.ascontiguousarray(label, dtype=np.int32)
-        if label.ndim != 2 or label.size == 0:
-            raise ValueError("clean_outlines: label must be [height][width]")
-        if top is not None:
-            top = np.ascontiguousarray(top, dtype=np.int32)
-            if top.shape != label.shape + (4,):
-                raise ValueError("clean_outlines: top must be [height][width][4]")
-        h, w = label.shape
-        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        label, top, h, w, nl = _label_top("clean_outlines", label, top, n_labels)
         out, simple, plain = _lib.CleanOutlines(), _lib.SimpleOutlines(), _lib.Outlines()
         with self._sweeps(sweeps):
-            self._check(self._L.bs_clean_outlines(self._h, label.ctypes.data, None if top is None else top.ctypes.data, w, h,
-                                                  nl, int(num), int(den), int(max_rounds), int(cell_log2), C.byref(out),
-                                                  C.byref(simple), C.byref(plain)))
-        return (_take_clean_outlines(self._L, out, True), _take_simple_outlines(self._L, simple, False),
-                _take_outlines(self._L, plain, False))
+            self._check(self._L.bs_clean_outlines(self._h, label.ctypes.data, _ptr(top), w, h, nl, int(num), int(den),
+                                                  int(max_rounds), int(cell_log2), C.byref(out), C.byref(simple),
+                                                  C.byref(plain)))
+        return _take_chain(self._L, (_take_clean_outlines, out, True), (_take_simple_outlines, simple, False),
+                           (_take_outlines, plain, False))
 
     def clean_outlines_dev(self, d_label, d_top, width, height, n_labels, num=0, den=1, max_rounds=-1, cell_log2=0,
                            sweeps=None):
@@ -987,8 +1058,8 @@ class Context:
             self._check(self._L.bs_clean_outlines_count_dev(self._h, d_label or None, d_top or None, width, height,
                                                             int(n_labels), int(num), int(den), int(max_rounds),
                                                             int(cell_log2), C.byref(out), C.byref(simple), C.byref(plain)))
-        return (_take_clean_outlines(self._L, out, False), _take_simple_outlines(self._L, simple, False),
-                _take_outlines(self._L, plain, False))
+        return _take_chain(self._L, (_take_clean_outlines, out, False), (_take_simple_outlines, simple, False),
+                           (_take_outlines, plain, False))
 
     def clean_outlines_emit_dev(self, d_sxy, d_sz, d_right, d_flag):
         """The kept vertices of the last clean_outlines_dev on this context into device buffers (ints) of exactly its
@@ -1000,21 +1071,13 @@ class Context:
         """Every label's clean rings as triangles over the clean vertices (include/bs_api.h, "outline triangles").
         Returns (OutlineTriangles, the CleanOutlines with their vertices, the SimpleOutlines without vertices, the plain
         Outlines without vertices)."""
-        label = np.ascontiguousarray(label, dtype=np.int32)
-        if label.ndim != 2 or label.size == 0:
-            raise ValueError("outline_triangles: label must be [height][width]")
-        if top is not None:
-            top = np.ascontiguousarray(top, dtype=np.int32)
-            if top.shape != label.shape + (4,):
-                raise ValueError("outline_triangles: top must be [height][width][4]")
-        h, w = label.shape
-        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        label, top, h, w, nl = _label_top("outline_triangles", label, top, n_labels)
         out, clean, simple, plain = _lib.OutlineTriangles(), _lib.CleanOutlines(), _lib.SimpleOutlines(), _lib.Outlines()
-        self._check(self._L.bs_outline_triangles(self._h, label.ctypes.data, None if top is None else top.ctypes.data, w, h, nl,
-                                                 int(num), int(den), int(cell_log2), C.byref(out), C.byref(clean),
-                                                 C.byref(simple), C.byref(plain)))
-        return (_take_outline_triangles(self._L, out, True), _take_clean_outlines(self._L, clean, True),
-                _take_simple_outlines(self._L, simple, False), _take_outlines(self._L, plain, False))
+        self._check(self._L.bs_outline_triangles(self._h, label.ctypes.data, _ptr(top), w, h, nl, int(num), int(den),
+                                                 int(cell_log2), C.byref(out), C.byref(clean), C.byref(simple),
+                                                 C.byref(plain)))
+        return _take_chain(self._L, (_take_outline_triangles, out, True), (_take_clean_outlines, clean, True),
+                           (_take_simple_outlines, simple, False), (_take_outlines, plain, False))
 
     def outline_triangles_dev(self, d_label, d_top, width, height, n_labels, num=0, den=1, cell_log2=0):
         """Device-resident count (bs_outline_triangles_count_dev): d_label and d_top (0: no Z) are device pointers (ints).
@@ -1023,8 +1086,8 @@ class Context:
         self._check(self._L.bs_outline_triangles_count_dev(self._h, d_label or None, d_top or None, width, height,
                                                            int(n_labels), int(num), int(den), int(cell_log2), C.byref(out),
                                                            C.byref(clean), C.byref(simple), C.byref(plain)))
-        return (_take_outline_triangles(self._L, out, False), _take_clean_outlines(self._L, clean, False),
-                _take_simple_outlines(self._L, simple, False), _take_outlines(self._L, plain, False))
+        return _take_chain(self._L, (_take_outline_triangles, out, False), (_take_clean_outlines, clean, False),
+                           (_take_simple_outlines, simple, False), (_take_outlines, plain, False))
 
     def outline_triangles_emit_dev(self, d_tri):
         """The triangles of the last outline_triangles_dev on this context into a device buffer (int) of
@@ -1035,10 +1098,7 @@ class Context:
         """outline_triangles() of the facet image of roof_facets() / roof_structure() with the tops of solids(), at a
         tolerance in millimetres (bin: the pixel edge, by default the Solids'), beside roof_polygons(clean=True): returns
         (OutlineTriangles, CleanOutlines, the plain Outlines).  sweeps: the sweep mode of the call (set_outline_sweeps)."""
-        if roof_facets.facet is None:
-            raise ValueError("roof_mesh: the facet image is on the device: use outline_triangles_dev")
-        if solids.top is None:
-            raise ValueError("roof_mesh: the Solids carry no top image (solids(top=True))")
+        _facet_and_top("roof_mesh", roof_facets, solids, "outline_triangles_dev")
         num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
         with self._sweeps(sweeps), self._bases(getattr(solids, "base", None)):
             t, c, _, plain = self.outline_triangles(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num,
@@ -1053,16 +1113,7 @@ class Context:
         of every label.  n_labels defaults to label.max() + 1, n_buildings to label_building.max() + 1.  Returns
         (PolySolids, OutlineTriangles, the CleanOutlines with their vertices, the SimpleOutlines without vertices, the
         plain Outlines without vertices)."""
-        label = np.ascontiguousarray(label, dtype=np.int32)
-        if label.ndim != 2 or label.size == 0:
-            raise ValueError("poly_solids: label must be [height][width]")
-        if top is None:
-            raise ValueError("poly_solids: the stage needs a top image")
-        top = np.ascontiguousarray(top, dtype=np.int32)
-        if top.shape != label.shape + (4,):
-            raise ValueError("poly_solids: top must be [height][width][4]")
-        h, w = label.shape
-        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        label, top, h, w, nl = _label_top("poly_solids", label, top, n_labels, need_top=True)
         lb = np.ascontiguousarray(label_building, dtype=np.int32).reshape(-1)
         if len(lb) != nl:
             raise ValueError("poly_solids: label_building must have one entry per label")
@@ -1072,9 +1123,9 @@ class Context:
         self._check(self._L.bs_poly_solids(self._h, label.ctypes.data, top.ctypes.data, w, h, nl, int(num), int(den),
                                            int(cell_log2), lb.ctypes.data if nl else None, nb, int(bin), int(base_z),
                                            C.byref(out), C.byref(tri), C.byref(clean), C.byref(simple), C.byref(plain)))
-        return (_take_poly_solids(self._L, out, True), _take_outline_triangles(self._L, tri, True),
-                _take_clean_outlines(self._L, clean, True), _take_simple_outlines(self._L, simple, False),
-                _take_outlines(self._L, plain, False))
+        return _take_chain(self._L, (_take_poly_solids, out, True), (_take_outline_triangles, tri, True),
+                           (_take_clean_outlines, clean, True), (_take_simple_outlines, simple, False),
+                           (_take_outlines, plain, False))
 
     def poly_solids_dev(self, d_label, d_top, width, height, n_labels, d_label_building, n_buildings, num=0, den=1, bin=1,
                         base_z=0, cell_log2=0):
@@ -1088,9 +1139,9 @@ class Context:
                                                      int(num), int(den), int(cell_log2), d_label_building or None,
                                                      int(n_buildings), int(bin), int(base_z), C.byref(out), C.byref(tri),
                                                      C.byref(clean), C.byref(simple), C.byref(plain)))
-        return (_take_poly_solids(self._L, out, False), _take_outline_triangles(self._L, tri, False),
-                _take_clean_outlines(self._L, clean, False), _take_simple_outlines(self._L, simple, False),
-                _take_outlines(self._L, plain, False))
+        return _take_chain(self._L, (_take_poly_solids, out, False), (_take_outline_triangles, tri, False),
+                           (_take_clean_outlines, clean, False), (_take_simple_outlines, simple, False),
+                           (_take_outlines, plain, False))
 
     def poly_solids_emit_dev(self, d_vertex, d_face_offset, d_face_index, d_face_building, d_face_kind):
         """The mesh of the last poly_solids_dev on this context into device buffers (ints) of exactly its sizes."""
@@ -1101,10 +1152,7 @@ class Context:
         """poly_solids() of the facet image and facet_building of roof_facets() / roof_structure() with the tops, bin and
         base_z of solids(), at a tolerance in millimetres, beside roof_mesh(): returns (PolySolids, OutlineTriangles,
         CleanOutlines, the plain Outlines).  sweeps: the sweep mode of the call (set_outline_sweeps)."""
-        if roof_facets.facet is None:
-            raise ValueError("building_model: the facet image is on the device: use poly_solids_dev")
-        if solids.top is None:
-            raise ValueError("building_model: the Solids carry no top image (solids(top=True))")
+        _facet_and_top("building_model", roof_facets, solids, "poly_solids_dev")
         b = solids.bin if bin is None else bin
         num, den = simplify_tolerance(tolerance_mm, b)
         with self._sweeps(sweeps), self._bases(getattr(solids, "base", None)):
@@ -1119,25 +1167,16 @@ class Context:
         label is [height][width], top [height][width][4] as Solids.top.  images=False leaves the three images out (None)
         and computes the figures alone.  Returns (ModelRaster, OutlineTriangles, the CleanOutlines with their vertices, the
         SimpleOutlines without vertices, the plain Outlines without vertices)."""
-        label = np.ascontiguousarray(label, dtype=np.int32)
-        if label.ndim != 2 or label.size == 0:
-            raise ValueError("model_raster: label must be [height][width]")
-        if top is None:
-            raise ValueError("model_raster: the stage needs a top image")
-        top = np.ascontiguousarray(top, dtype=np.int32)
-        if top.shape != label.shape + (4,):
-            raise ValueError("model_raster: top must be [height][width][4]")
-        h, w = label.shape
-        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
+        label, top, h, w, nl = _label_top("model_raster", label, top, n_labels, need_top=True)
         img = [np.empty((h, w), np.int32) for _ in range(3)] if images else [None] * 3
         out, tri, clean = _lib.ModelRaster(), _lib.OutlineTriangles(), _lib.CleanOutlines()
         simple, plain = _lib.SimpleOutlines(), _lib.Outlines()
         self._check(self._L.bs_model_raster(self._h, label.ctypes.data, top.ctypes.data, w, h, nl, int(num), int(den),
-                                            int(cell_log2), *[a.ctypes.data if a is not None else None for a in img],
+                                            int(cell_log2), *[_ptr(a) for a in img],
                                             C.byref(out), C.byref(tri), C.byref(clean), C.byref(simple), C.byref(plain)))
-        return (_take_model_raster(self._L, out, *img), _take_outline_triangles(self._L, tri, True),
-                _take_clean_outlines(self._L, clean, True), _take_simple_outlines(self._L, simple, False),
-                _take_outlines(self._L, plain, False))
+        return _take_chain(self._L, (_take_model_raster, out, *img), (_take_outline_triangles, tri, True),
+                           (_take_clean_outlines, clean, True), (_take_simple_outlines, simple, False),
+                           (_take_outlines, plain, False))
 
     def model_raster_dev(self, d_label, d_top, width, height, d_model=0, d_cover=0, d_mz2=0):
         """Device-resident raster (bs_model_raster_dev) of the triangles that the last outline_triangles_dev or
@@ -1154,10 +1193,7 @@ class Context:
         image of roof_facets() / roof_structure() with the tops of solids(), its per-label figures added up by
         facet_building.  sweeps: the sweep mode of the call (set_outline_sweeps).  Returns (ModelFidelity,
         ModelRaster)."""
-        if roof_facets.facet is None:
-            raise ValueError("model_fidelity: the facet image is on the device: use model_raster_dev")
-        if solids.top is None:
-            raise ValueError("model_fidelity: the Solids carry no top image (solids(top=True))")
+        _facet_and_top("model_fidelity", roof_facets, solids, "model_raster_dev")
         num, den = simplify_tolerance(tolerance_mm, solids.bin if bin is None else bin)
         with self._sweeps(sweeps), self._bases(getattr(solids, "base", None)):
             r = self.model_raster(roof_facets.facet, solids.top, n_labels=roof_facets.n_facets, num=num, den=den)[0]
@@ -1172,33 +1208,20 @@ class Context:
         doubled millimetres, None for no clipping.  outputs=False leaves the three per-point arrays out (None) and computes
         the figures alone.  Returns (PointResiduals, OutlineTriangles, the CleanOutlines with their vertices, the
         SimpleOutlines without vertices, the plain Outlines without vertices)."""
-        label = np.ascontiguousarray(label, dtype=np.int32)
-        if label.ndim != 2 or label.size == 0:
-            raise ValueError("point_residuals: label must be [height][width]")
-        if top is None:
-            raise ValueError("point_residuals: the stage needs a top image")
-        top = np.ascontiguousarray(top, dtype=np.int32)
-        if top.shape != label.shape + (4,):
-            raise ValueError("point_residuals: top must be [height][width][4]")
-        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
-        if xyz.ndim != 2 or xyz.shape[1] != 3:
-            raise ValueError("point_residuals: xyz must be [n][3]")
-        h, w = label.shape
+        label, top, h, w, nl = _label_top("point_residuals", label, top, n_labels, need_top=True)
+        xyz = _points("point_residuals", xyz)
         n = len(xyz)
-        nl = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
         pi, lp = _plane_pair("point_residuals", plane_idx, label_plane, n, nl)
         arr = [np.empty(n, np.int32) for _ in range(3)] if outputs else [None] * 3
         out, tri, clean = _lib.PointResiduals(), _lib.OutlineTriangles(), _lib.CleanOutlines()
         simple, plain = _lib.SimpleOutlines(), _lib.Outlines()
         self._check(self._L.bs_point_residuals(self._h, label.ctypes.data, top.ctypes.data, w, h, nl, int(num), int(den),
-                                               int(cell_log2), xyz.ctypes.data, n, int(bin),
-                                               pi.ctypes.data if pi is not None else None,
-                                               lp.ctypes.data if lp is not None else None, _clip2(clip2),
-                                               *[a.ctypes.data if a is not None else None for a in arr], C.byref(out),
-                                               C.byref(tri), C.byref(clean), C.byref(simple), C.byref(plain)))
-        return (_take_point_residuals(self._L, out, *arr), _take_outline_triangles(self._L, tri, True),
-                _take_clean_outlines(self._L, clean, True), _take_simple_outlines(self._L, simple, False),
-                _take_outlines(self._L, plain, False))
+                                               int(cell_log2), xyz.ctypes.data, n, int(bin), _ptr(pi), _ptr(lp),
+                                               _clip2(clip2), *[_ptr(a) for a in arr], C.byref(out), C.byref(tri),
+                                               C.byref(clean), C.byref(simple), C.byref(plain)))
+        return _take_chain(self._L, (_take_point_residuals, out, *arr), (_take_outline_triangles, tri, True),
+                           (_take_clean_outlines, clean, True), (_take_simple_outlines, simple, False),
+                           (_take_outlines, plain, False))
 
     def point_residuals_dev(self, d_xyz, n, bin=1, d_plane_idx=0, label_plane=None, clip2=None, d_label_out=0, d_r2=0,
                             d_cover=0):
@@ -1209,10 +1232,10 @@ class Context:
         lp = None if label_plane is None else np.ascontiguousarray(label_plane, dtype=np.int32).reshape(-1)
         out = _lib.PointResiduals()
         self._check(self._L.bs_point_residuals_dev(self._h, d_xyz or None, int(n), int(bin), d_plane_idx or None,
-                                                   lp.ctypes.data if lp is not None else None, _clip2(clip2),
+                                                   _ptr(lp), _clip2(clip2),
                                                    d_label_out or None, d_r2 or None, d_cover or None, C.byref(out)))
         if lp is not None and len(lp) != out.n_labels:
-            self._L.bs_point_residuals_free(C.byref(out))
+            _free(self._L, out)
             raise ValueError("point_residuals_dev: label_plane must have one entry per label of the count")
         return _take_point_residuals(self._L, out)
 
@@ -1222,10 +1245,7 @@ class Context:
         roof_structure() with the tops of solids(), its per-label figures added up by facet_building.  plane_idx: the
         planes of the points, compared with facet_plane.  clip_mm: the inlier bound in millimetres, None for no clipping.
         sweeps: the sweep mode of the call (set_outline_sweeps).  Returns (PointFidelity, PointResiduals)."""
-        if roof_facets.facet is None:
-            raise ValueError("point_fidelity: the facet image is on the device: use point_residuals_dev")
-        if solids.top is None:
-            raise ValueError("point_fidelity: the Solids carry no top image (solids(top=True))")
+        _facet_and_top("point_fidelity", roof_facets, solids, "point_residuals_dev")
         b = solids.bin if bin is None else bin
         num, den = simplify_tolerance(tolerance_mm, b)
         if clip_mm is not None and (int(clip_mm) != clip_mm or clip_mm < 0):
@@ -1277,9 +1297,7 @@ class Context:
         q = (num, den): the quantile of the ring pixels' lowest points that becomes `ground`; min_ground: the fewest ring
         pixels with a point that a quantile is taken of; fallback_z: the ground of a building with fewer.  images=False leaves
         the three images out (None).  Returns Terrain."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
-        if xyz.ndim != 2 or xyz.shape[1] != 3:
-            raise ValueError("terrain: xyz must be [n][3]")
+        xyz = _points("terrain", xyz)
         bmap = np.ascontiguousarray(bmap, dtype=np.int32)
         if bmap.ndim != 2 or bmap.size == 0:
             raise ValueError("terrain: bmap must be [height][width]")
@@ -1290,7 +1308,7 @@ class Context:
         out = _lib.Terrain()
         self._check(self._L.bs_terrain(self._h, xyz.ctypes.data, len(xyz), int(bin), bmap.ctypes.data, w, h, nb, int(ring),
                                        *_quantile(q), int(min_ground), int(fallback_z),
-                                       *[a.ctypes.data if a is not None else None for a in (owner, dist, low)], C.byref(out)))
+                                       *[_ptr(a) for a in (owner, dist, low)], C.byref(out)))
         return _take_terrain(self._L, out, owner, dist, low)
 
     def terrain_dev(self, d_xyz, n, d_map, width, height, n_buildings, bin=100, ring=10, q=(1, 2), min_ground=8, fallback_z=0,
@@ -1309,9 +1327,7 @@ class Context:
         """The ground surface of a cloud shifted to its origin, per pixel of a lattice of params["cell"] millimetres
         (include/bs_api.h, "ground").  params: a dict of ground_params(), or its keywords directly.  images=False leaves
         low, dtm and step out (None), points=False hag and cls.  Returns Ground."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
-        if xyz.ndim != 2 or xyz.shape[1] != 3:
-            raise ValueError("ground: xyz must be [n][3]")
+        xyz = _points("ground", xyz)
         p = ground_params(**kw) if params is None else dict(params, **kw)
         ext = np.ascontiguousarray(xyz.max(0) if extent is None else extent, dtype=np.int32)
         w, h = grid_dims(ext, p["cell"])
@@ -1320,7 +1336,7 @@ class Context:
         hag, cls = (np.empty(len(xyz), np.int32), np.empty(len(xyz), np.uint8)) if points else (None, None)
         out = _lib.Ground()
         self._check(self._L.bs_ground(self._h, xyz.ctypes.data, len(xyz), ext.ctypes.data, C.byref(_ground_struct(p)),
-                                      *[a.ctypes.data if a is not None else None for a in (low, dtm, step, hag, cls)],
+                                      *[_ptr(a) for a in (low, dtm, step, hag, cls)],
                                       C.byref(out)))
         return _take_ground(self._L, out, p, low, dtm, step, hag, cls)
 
@@ -1394,12 +1410,8 @@ class Context:
         evidence"): the share of them on a plane that counts (plane_ok uint8 [n_planes] of plane_quality(); None: every plane),
         over a (2r+1)^2 window.  ground_th is the raster's; a ground model of the context takes its place.  params: a dict of
         evidence_params(), or its keywords directly.  images=False leaves everything but keep out.  Returns RoofEvidence."""
-        xyz = np.ascontiguousarray(xyz, dtype=np.int32)
-        if xyz.ndim != 2 or xyz.shape[1] != 3:
-            raise ValueError("roof_evidence: xyz must be [n][3]")
-        pi = np.ascontiguousarray(plane_idx, dtype=np.int32)
-        if pi.shape != (len(xyz),):
-            raise ValueError("roof_evidence: plane_idx must be [n]")
+        xyz = _points("roof_evidence", xyz)
+        pi = _point_labels("roof_evidence", "plane_idx", plane_idx, xyz)
         p = evidence_params(**kw) if params is None else dict(params, **kw)
         ok = _plane_ok(plane_ok, n_planes)
         ext = np.ascontiguousarray(xyz.max(0) if extent is None else extent, dtype=np.int32)
@@ -1408,9 +1420,9 @@ class Context:
         imgs = [np.empty((h, w), np.int32) if images else None for _ in range(4)]
         out = _lib.RoofEvidence()
         self._check(self._L.bs_roof_evidence(self._h, xyz.ctypes.data, len(xyz), pi.ctypes.data, int(n_planes),
-                                             ok.ctypes.data if ok is not None and len(ok) else None, ext.ctypes.data, int(bin),
+                                             _ptr(ok) if int(n_planes) else None, ext.ctypes.data, int(bin),
                                              float(ground_th), p["r"], p["min_points"], p["num"], p["den"], keep.ctypes.data,
-                                             *[a.ctypes.data if a is not None else None for a in imgs], C.byref(out)))
+                                             *[_ptr(a) for a in imgs], C.byref(out)))
         return _take_evidence(out, n_planes, ok, keep, *imgs)
 
     def roof_evidence_dev(self, d_xyz, n, d_plane_idx, n_planes, extent, d_keep, plane_ok=None, bin=100, ground_th=0.0,
@@ -1423,7 +1435,7 @@ class Context:
         ext = np.ascontiguousarray(extent, dtype=np.int32)
         out = _lib.RoofEvidence()
         self._check(self._L.bs_roof_evidence_dev(self._h, d_xyz or None, int(n), d_plane_idx or None, int(n_planes),
-                                                 ok.ctypes.data if ok is not None and len(ok) else None, ext.ctypes.data,
+                                                 _ptr(ok) if int(n_planes) else None, ext.ctypes.data,
                                                  int(bin), float(ground_th), p["r"], p["min_points"], p["num"], p["den"],
                                                  d_keep or None, d_above or None, d_planar or None, d_win_above or None,
                                                  d_win_planar or None, C.byref(out)))
@@ -1646,7 +1658,7 @@ def _take_ground(L, out, p, low=None, dtm=None, step=None, hag=None, cls=None) -
         return Ground(**head, **lists, tol=int(p["tol"]), min_height=int(p["min_height"]), info=info, low=low, dtm=dtm,
                       step=step, hag=hag, cls=cls)
     finally:
-        L.bs_ground_free(C.byref(out))
+        _free(L, out)
 
 
 @dataclass
@@ -1694,17 +1706,19 @@ def _quantile(q):
     return int(num), int(den)
 
 
+_TERRAIN_ARRAYS = _rows(_lib.TERRAIN_WIDE, np.int64) + _rows(_lib.TERRAIN_NARROW, np.int32)
+
+
 def _take_terrain(L, out, owner=None, dist=None, low=None) -> Terrain:
     """Copy a bs_terrain into numpy arrays and release it."""
     n = out.n_buildings
     try:
-        arrs = {k: (np.ctypeslib.as_array(getattr(out, k), (n,)).copy() if n else np.zeros(0, dt))
-                for names, dt in ((_lib.TERRAIN_WIDE, np.int64), (_lib.TERRAIN_NARROW, np.int32)) for k in names}
+        arrs = _copy_arrays(out, _TERRAIN_ARRAYS, n)
         head = {k: getattr(out, k) for k in _lib.TERRAIN_HEAD + _lib.TERRAIN_TOTALS if k != "reserved"}
         info = {k: getattr(out, k) for k in _lib.TERRAIN_MS}
         return Terrain(**head, **arrs, info=info, owner=owner, dist=dist, low=low)
     finally:
-        L.bs_terrain_free(C.byref(out))
+        _free(L, out)
 
 
 @dataclass
@@ -1740,23 +1754,20 @@ class Buildings:
     votes: PlaneVotes | None = None
 
 
-_BUILDING_ARRAYS = (("start_xy", 2, np.int32), ("bbox", 4, np.int32), ("pixels", 1, np.int64), ("fg_pixels", 1, np.int64),
-                    ("n_points", 1, np.int64), ("n_above", 1, np.int64), ("z_min", 1, np.int32), ("z_max", 1, np.int32),
-                    ("z_sum", 1, np.int64))
+_BUILDING_ARRAYS = (("start_xy", np.int32, 2), ("bbox", np.int32, 4), ("pixels", np.int64, 1), ("fg_pixels", np.int64, 1),
+                    ("n_points", np.int64, 1), ("n_above", np.int64, 1), ("z_min", np.int32, 1), ("z_max", np.int32, 1),
+                    ("z_sum", np.int64, 1))
 
 
 def _take_buildings(L, out) -> Buildings:
     """Copy a bs_buildings into numpy arrays and release it."""
     n = out.n_buildings
     try:
-        arrs = {}
-        for name, cols, dt in _BUILDING_ARRAYS:
-            a = np.ctypeslib.as_array(getattr(out, name), (n * cols,)).copy() if n else np.zeros(0, dt)
-            arrs[name] = a.reshape(n, cols) if cols > 1 else a
+        arrs = _copy_arrays(out, _BUILDING_ARRAYS, n)
         info = {k: getattr(out, k) for k in ("ms_label_mask", "ms_label_fill", "ms_number", "ms_map", "ms_assign")}
         return Buildings(n, out.width, out.height, info=info, **arrs)
     finally:
-        L.bs_buildings_free(C.byref(out))
+        _free(L, out)
 
 
 def _buildings_struct(b: Buildings):
@@ -1764,7 +1775,7 @@ def _buildings_struct(b: Buildings):
     st = _lib.Buildings()
     st.n_buildings, st.width, st.height = b.n_buildings, b.width, b.height
     keep = []
-    for name, cols, dt in _BUILDING_ARRAYS:
+    for name, dt, cols in _BUILDING_ARRAYS:
         a = getattr(b, name)
         if a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable or a.size != b.n_buildings * cols:
             raise ValueError(f"Buildings.{name} must be a contiguous {np.dtype(dt).name} array of {b.n_buildings * cols}")
@@ -1779,29 +1790,17 @@ def write_buildings_obj(fp, buildings: Buildings, path, bin=100, origin=None, gr
     """LoD1 OBJ in millimetres through the library's writer (bs_buildings_write_obj; the format is written down in
     include/bs_api.h): the kept footprints extruded from the ground threshold to the mean height of their
     above-ground points.  origin: the shift that was subtracted from the cloud; ground_th: default buildings.ground_th."""
-    n = len(fp.contours)
-    off = np.zeros(n + 1, dtype=np.int64)
-    off[1:] = np.cumsum([len(c) for c in fp.contours]) if n else []
-    xy = np.ascontiguousarray(np.concatenate(fp.contours) if n else np.zeros((0, 2)), dtype=np.int32)
     area = np.ascontiguousarray(fp.area, dtype=np.float64)
     per = np.ascontiguousarray(fp.perimeter, dtype=np.float64)
-    if len(area) != n or len(per) != n:
+    if len(area) != len(fp.contours) or len(per) != len(fp.contours):
         raise ValueError("area and perimeter must have one entry per contour")
-    c = Contours()
-    c.n_contours, c.width, c.height = n, fp.width, fp.height
-    c.offset = off.ctypes.data_as(C.POINTER(C.c_int64))
-    c.xy = (xy if xy.size else np.zeros(2, np.int32)).ctypes.data_as(C.POINTER(C.c_int32))
-    c.area = (area if n else np.zeros(1)).ctypes.data_as(C.POINTER(C.c_double))
-    c.perimeter = (per if n else np.zeros(1)).ctypes.data_as(C.POINTER(C.c_double))
+    c, keep = _contours_struct(fp)
+    c.area = (area if area.size else _PAD).ctypes.data_as(C.POINTER(C.c_double))
+    c.perimeter = (per if per.size else _PAD).ctypes.data_as(C.POINTER(C.c_double))
     st = _buildings_struct(buildings)
-    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
-    if org is not None and org.shape != (3,):
-        raise ValueError("origin must be [3]")
     th = buildings.ground_th if ground_th is None else ground_th
-    rc = _lib.load().bs_buildings_write_obj(C.byref(c), C.byref(st), int(bin), org.ctypes.data if org is not None else None,
-                                            float(th), float(min_area), float(min_perimeter), str(path).encode())
-    if rc != 0:
-        raise BsError(rc, f"cannot write {path} (or the contours and the buildings are not of the same mask)")
+    _write_obj("bs_buildings_write_obj", path, "the contours and the buildings are not of the same mask", C.byref(c), C.byref(st),
+               int(bin), _origin(origin), float(th), float(min_area), float(min_perimeter))
 
 
 @dataclass
@@ -1833,8 +1832,8 @@ class Roofs:
     fit: "PlaneFits | None" = field(default=None, repr=False)  # roof_model(refit=True)
 
 
-_ROOF_ARRAYS = (("pixels", 1, np.int64), ("seed_pixels", 1, np.int64), ("bbox", 4, np.int32), ("n_support", 1, np.int64),
-                ("z_min", 1, np.int32), ("z_max", 1, np.int32), ("z_sum", 1, np.int64))
+_ROOF_ARRAYS = (("pixels", np.int64, 1), ("seed_pixels", np.int64, 1), ("bbox", np.int32, 4), ("n_support", np.int64, 1),
+                ("z_min", np.int32, 1), ("z_max", np.int32, 1), ("z_sum", np.int64, 1))
 
 
 def _roof_tables(home, normal, center):
@@ -1852,16 +1851,13 @@ def _take_roofs(L, out, roof, support, height, tabs, bin) -> Roofs:
     """Copy a bs_roofs into numpy arrays and release it."""
     n = out.n_planes
     try:
-        arrs = {}
-        for name, cols, dt in _ROOF_ARRAYS:
-            a = np.ctypeslib.as_array(getattr(out, name), (n * cols,)).copy() if n else np.zeros(0, dt)
-            arrs[name] = a.reshape(n, cols) if cols > 1 else a
+        arrs = _copy_arrays(out, _ROOF_ARRAYS, n)
         info = {k: getattr(out, k) for k in ("ms_vote", "ms_fill", "ms_figures", "ms_height")}
         return Roofs(n, out.width, out.height, out.fill_rounds, out.seeded_pixels, out.filled_pixels,
                      out.unroofed_pixels, info=info, roof=roof, support=support, height=height, home=tabs[0],
                      normal=tabs[1], center=tabs[2], bin=bin, **arrs)
     finally:
-        L.bs_roofs_free(C.byref(out))
+        _free(L, out)
 
 
 @dataclass
@@ -1883,23 +1879,20 @@ class PlaneFits:
     residual: np.ndarray | None = field(default=None, repr=False)
 
 
-_FIT_ARRAYS = (("status", 1, np.int32), ("n_points", 1, np.int64), ("center", 3, np.int32), ("normal", 3, np.float64),
-               ("bbox", 6, np.int32), ("dev_sum", 3, np.int64), ("moment", 6, np.int64), ("r_abs_max", 1, np.int32),
-               ("r_abs_sum", 1, np.int64), ("r_sq_sum", 1, np.int64))
+_FIT_ARRAYS = (("status", np.int32, 1), ("n_points", np.int64, 1), ("center", np.int32, 3), ("normal", np.float64, 3),
+               ("bbox", np.int32, 6), ("dev_sum", np.int64, 3), ("moment", np.int64, 6), ("r_abs_max", np.int32, 1),
+               ("r_abs_sum", np.int64, 1), ("r_sq_sum", np.int64, 1))
 
 
 def _take_fits(L, out, residual) -> PlaneFits:
     """Copy a bs_plane_fits into numpy arrays and release it."""
     n = out.n_planes
     try:
-        arrs = {}
-        for name, cols, dt in _FIT_ARRAYS:
-            a = np.ctypeslib.as_array(getattr(out, name), (n * cols,)).copy() if n else np.zeros(0, dt)
-            arrs[name] = a.reshape(n, cols) if cols > 1 else a
+        arrs = _copy_arrays(out, _FIT_ARRAYS, n)
         info = {k: getattr(out, k) for k in ("ms_sums", "ms_moments", "ms_solve", "ms_residuals")}
         return PlaneFits(n, info=info, residual=residual, **arrs)
     finally:
-        L.bs_plane_fits_free(C.byref(out))
+        _free(L, out)
 
 
 def plane_fit_apply(fits: PlaneFits, normal, center):
@@ -1969,17 +1962,9 @@ def write_roofs_obj(roofs: Roofs, bmap, path, origin=None, roof=None, normal=Non
             raise ValueError(f"Roofs.{name} must be [{n}]")
         keep.append(a if n else np.zeros(1, dt))
         setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
-    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
-    if org is not None and org.shape != (3,):
-        raise ValueError("origin must be [3]")
     h, w = roof.shape
-    rc = _lib.load().bs_roofs_write_obj(roof.ctypes.data, bmap.ctypes.data, w, h, C.byref(st),
-                                        (nrm if n else np.zeros(3)).ctypes.data,
-                                        (ctr if n else np.zeros(3, np.int32)).ctypes.data,
-                                        int(roofs.bin if bin is None else bin),
-                                        org.ctypes.data if org is not None else None, str(path).encode())
-    if rc != 0:
-        raise BsError(rc, f"cannot write {path} (or a roof value above n_planes)")
+    _write_obj("bs_roofs_write_obj", path, "a roof value above n_planes", roof, bmap, w, h, C.byref(st), _ptr0(nrm), _ptr0(ctr),
+               int(roofs.bin if bin is None else bin), _origin(origin))
 
 
 @dataclass
@@ -2019,8 +2004,8 @@ class Solids:
     base: np.ndarray | None = field(default=None, repr=False)
 
 
-_SOLID_ARRAYS = (("pixels", np.int64), ("vertices", np.int64), ("faces", np.int64), ("wall_faces", np.int64),
-                 ("crossing_walls", np.int64), ("top_min", np.int32), ("top_max", np.int32), ("volume6", np.int64))
+_SOLID_ARRAYS = (("pixels", np.int64, 1), ("vertices", np.int64, 1), ("faces", np.int64, 1), ("wall_faces", np.int64, 1),
+                 ("crossing_walls", np.int64, 1), ("top_min", np.int32, 1), ("top_max", np.int32, 1), ("volume6", np.int64, 1))
 _SOLID_TOTALS = ("bin", "base_z", "n_pixels", "n_vertices", "n_faces", "n_indices", "n_wall_faces", "n_crossing_walls",
                  "total_volume6")
 
@@ -2053,24 +2038,36 @@ def _solid_defaults(buildings, base_z, flat):
     return base_z, np.ascontiguousarray(flat, dtype=np.int32).reshape(-1)
 
 
+def _solid_inputs(who, bmap, roofs, buildings, base_z, flat):
+    """(bmap, roof image, base_z, flat, tables) of Context.solids and Context.generalise_roofs"""
+    bmap = np.ascontiguousarray(bmap, dtype=np.int32)
+    roof = np.ascontiguousarray(_host_image(who, roofs.roof, "roof", who + "_dev"), dtype=np.int32)
+    if bmap.ndim != 2 or roof.shape != bmap.shape:
+        raise ValueError(f"{who}: bmap and roofs.roof must be [height][width] of the same size")
+    base_z, flat = _solid_defaults(buildings, base_z, flat)
+    return bmap, roof, base_z, flat, _solid_tables(roofs.normal, roofs.center, roofs.z_min, roofs.z_max)
+
+
+def _take_mesh(out):
+    """the five mesh arrays of a bs_solids or a bs_poly_solids"""
+    nv, nf, ni = out.n_vertices, out.n_faces, out.n_indices
+    return dict(vertex=_copy(out.vertex, (nv, 4), np.int32), face_offset=_copy(out.face_offset, (nf + 1,), np.int32),
+                face_index=_copy(out.face_index, (ni,), np.int32), face_building=_copy(out.face_building, (nf,), np.int32),
+                face_kind=_copy(out.face_kind, (nf,), np.uint8))
+
+
 def _take_solids(L, out, top, mesh) -> Solids:
     """Copy a bs_solids into numpy arrays and release it."""
     n = out.n_buildings
     try:
-        arrs = {name: (np.ctypeslib.as_array(getattr(out, name), (n,)).copy() if n else np.zeros(0, dt))
-                for name, dt in _SOLID_ARRAYS}
+        arrs = _copy_arrays(out, _SOLID_ARRAYS, n)
         if mesh:
-            nv, nf, ni = out.n_vertices, out.n_faces, out.n_indices
-            arrs["vertex"] = np.ctypeslib.as_array(out.vertex, (nv, 4)).copy() if nv else np.zeros((0, 4), np.int32)
-            arrs["face_offset"] = np.ctypeslib.as_array(out.face_offset, (nf + 1,)).copy()
-            arrs["face_index"] = np.ctypeslib.as_array(out.face_index, (ni,)).copy() if ni else np.zeros(0, np.int32)
-            arrs["face_building"] = np.ctypeslib.as_array(out.face_building, (nf,)).copy() if nf else np.zeros(0, np.int32)
-            arrs["face_kind"] = np.ctypeslib.as_array(out.face_kind, (nf,)).copy() if nf else np.zeros(0, np.uint8)
+            arrs.update(_take_mesh(out))
         info = {k: getattr(out, k) for k in ("ms_tops", "ms_vertices", "ms_faces", "ms_figures", "ms_scans",
                                              "ms_emit_vertices", "ms_emit_faces")}
         return Solids(n, out.width, out.height, *[getattr(out, k) for k in _SOLID_TOTALS], info=info, top=top, **arrs)
     finally:
-        L.bs_solids_free(C.byref(out))
+        _free(L, out)
 
 
 def write_solids_obj(solids, path, origin=None):
@@ -2085,16 +2082,8 @@ def write_solids_obj(solids, path, origin=None):
     fb = np.ascontiguousarray(solids.face_building, dtype=np.int32).reshape(-1)
     if len(off) != len(fb) + 1 or (len(off) and int(off[-1]) != len(idx)):
         raise ValueError("write_solids_obj: face_offset must be [n_faces + 1] and end at len(face_index)")
-    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
-    if org is not None and org.shape != (3,):
-        raise ValueError("origin must be [3]")
-    pad = np.zeros(4, np.int32)
-    rc = _lib.load().bs_solids_write_obj((v if len(v) else pad).ctypes.data, len(v), off.ctypes.data,
-                                         (idx if len(idx) else pad).ctypes.data, (fb if len(fb) else pad).ctypes.data,
-                                         len(fb), int(solids.n_buildings), org.ctypes.data if org is not None else None,
-                                         str(path).encode())
-    if rc != 0:
-        raise BsError(rc, f"cannot write {path} (or the mesh arrays do not fit each other)")
+    _write_obj("bs_solids_write_obj", path, "the mesh arrays do not fit each other", _ptr0(v), len(v), off, _ptr0(idx), _ptr0(fb),
+               len(fb), int(solids.n_buildings), _origin(origin))
 
 
 @dataclass
@@ -2135,19 +2124,20 @@ class RoofGeneralise:
     roofs: "Roofs | None" = field(default=None, repr=False)
 
 
+_GEN_ARRAYS = tuple(_rows(g, np.int64) for g in (_lib.GEN_EVAL, _lib.GEN_PLANE, _lib.GEN_BUILDING))
+
+
 def _take_roof_generalise(L, out, roof) -> RoofGeneralise:
     """Copy a bs_roof_generalise into numpy arrays and release it."""
     try:
         arrs = {}
-        for group, n in ((_lib.GEN_EVAL, out.rounds + 1), (_lib.GEN_PLANE, out.n_planes + 1),
-                         (_lib.GEN_BUILDING, out.n_buildings)):
-            for name in group:
-                arrs[name] = np.ctypeslib.as_array(getattr(out, name), (n,)).copy() if n else np.zeros(0, np.int64)
+        for group, n in zip(_GEN_ARRAYS, (out.rounds + 1, out.n_planes + 1, out.n_buildings)):
+            arrs.update(_copy_arrays(out, group, n))
         info = {k: getattr(out, k) for k in _lib.GEN_MS}
         return RoofGeneralise(out.width, out.height, out.n_buildings, out.n_planes, out.rounds, out.converged,
                               *[getattr(out, k) for k in _lib.GEN_SCALARS], info=info, roof=roof, **arrs)
     finally:
-        L.bs_roof_generalise_free(C.byref(out))
+        _free(L, out)
 
 
 @dataclass
@@ -2201,16 +2191,12 @@ _EDGE_ARRAYS = (("edge_facet", np.int32, 2), ("edge_building", np.int32, 1), ("e
 def _take_roof_facets(L, out, facet) -> RoofFacets:
     """Copy a bs_roof_facets into numpy arrays and release it."""
     try:
-        arrs = {}
-        for group, n in ((_FACET_ARRAYS, out.n_facets), (_EDGE_ARRAYS, out.n_edges)):
-            for name, dt, cols in group:
-                shape = (n, cols) if cols > 1 else (n,)
-                arrs[name] = np.ctypeslib.as_array(getattr(out, name), shape).copy() if n else np.zeros(shape, dt)
+        arrs = {**_copy_arrays(out, _FACET_ARRAYS, out.n_facets), **_copy_arrays(out, _EDGE_ARRAYS, out.n_edges)}
         info = {k: getattr(out, k) for k in ("ms_label", "ms_number", "ms_figures", "ms_edges")}
         return RoofFacets(out.width, out.height, out.n_facets, out.n_edges, out.n_pixels, out.n_border, info=info,
                           facet=facet, **arrs)
     finally:
-        L.bs_roof_facets_free(C.byref(out))
+        _free(L, out)
 
 
 def _roof_facets_struct(rf):
@@ -2218,13 +2204,7 @@ def _roof_facets_struct(rf):
     st, keep = _lib.RoofFacets(), []
     st.n_facets, st.n_edges = int(rf.n_facets), int(rf.n_edges)
     st.n_pixels, st.n_border = int(rf.n_pixels), int(rf.n_border)
-    for group, n in ((_FACET_ARRAYS, st.n_facets), (_EDGE_ARRAYS, st.n_edges)):
-        for name, dt, cols in group:
-            a = np.ascontiguousarray(getattr(rf, name), dtype=dt).reshape(-1)
-            if len(a) != n * cols:
-                raise ValueError(f"RoofFacets.{name} must hold {n * cols} values")
-            keep.append(a if len(a) else np.zeros(1, dt))
-            setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
+    _fill(st, rf, "RoofFacets", _columns(_FACET_ARRAYS, st.n_facets) + _columns(_EDGE_ARRAYS, st.n_edges), keep)
     return st, keep
 
 
@@ -2255,16 +2235,9 @@ def write_roof_edges_obj(rf, bmap, top, path, bin, kinds=None, origin=None):
     kinds = roof_edge_kinds(rf) if kinds is None else np.ascontiguousarray(kinds, dtype=np.uint8).reshape(-1)
     if len(kinds) != st.n_edges:
         raise ValueError("write_roof_edges_obj: kinds must be [n_edges]")
-    kinds = kinds if len(kinds) else np.zeros(1, np.uint8)
-    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
-    if org is not None and org.shape != (3,):
-        raise ValueError("origin must be [3]")
     h, w = facet.shape
-    rc = _lib.load().bs_roof_edges_write_obj(facet.ctypes.data, bmap.ctypes.data, top.ctypes.data, w, h, int(bin), C.byref(st),
-                                             kinds.ctypes.data, org.ctypes.data if org is not None else None,
-                                             str(path).encode())
-    if rc != 0:
-        raise BsError(rc, f"cannot write {path} (or a facet pair the RoofFacets do not list)")
+    _write_obj("bs_roof_edges_write_obj", path, "a facet pair the RoofFacets do not list", facet, bmap, top, w, h, int(bin),
+               C.byref(st), _ptr0(kinds), _origin(origin))
 
 
 @dataclass
@@ -2301,22 +2274,16 @@ def _take_outlines(L, out, vertices) -> Outlines:
     """Copy a bs_outlines into numpy arrays and release it."""
     try:
         nr, nv = out.n_rings, out.n_vertices
-        arrs = {}
-        for name, dt, cols in _RING_ARRAYS:
-            shape = (nr, cols) if cols > 1 else (nr,)
-            arrs[name] = np.ctypeslib.as_array(getattr(out, name), shape).copy() if nr else np.zeros(shape, dt)
-        arrs["ring_offset"] = np.ctypeslib.as_array(out.ring_offset, (nr + 1,)).copy()
-        arrs["label_ring_offset"] = np.ctypeslib.as_array(out.label_ring_offset, (out.n_labels + 1,)).copy()
-        xy = z = None
-        if vertices:
-            xy = np.ctypeslib.as_array(out.xy, (nv, 2)).copy() if nv else np.zeros((0, 2), np.int32)
-            if out.has_z:
-                z = np.ctypeslib.as_array(out.z, (nv,)).copy() if nv else np.zeros(0, np.int32)
+        arrs = _copy_arrays(out, _RING_ARRAYS, nr)
+        arrs["ring_offset"] = _copy(out.ring_offset, (nr + 1,), np.int64)
+        arrs["label_ring_offset"] = _copy(out.label_ring_offset, (out.n_labels + 1,), np.int64)
+        xy = _copy(out.xy, (nv, 2), np.int32) if vertices else None
+        z = _copy(out.z, (nv,), np.int32) if vertices and out.has_z else None
         info = {k: getattr(out, k) for k in ("ms_halfedges", "ms_leaders", "ms_rank", "ms_rings", "ms_emit")}
         return Outlines(out.width, out.height, out.n_labels, out.n_half, nr, nv, has_z=bool(out.has_z), info=info, xy=xy, z=z,
                         **arrs)
     finally:
-        L.bs_outlines_free(C.byref(out))
+        _free(L, out)
 
 
 def _outlines_struct(o):
@@ -2324,22 +2291,10 @@ def _outlines_struct(o):
     st, keep = _lib.Outlines(), []
     st.n_labels, st.n_rings, st.n_vertices = int(o.n_labels), int(o.n_rings), int(o.n_vertices)
     st.n_half = int(o.n_half)
-
-    def put(name, dt, n):
-        a = np.ascontiguousarray(getattr(o, name), dtype=dt).reshape(-1)
-        if len(a) != n:
-            raise ValueError(f"Outlines.{name} must hold {n} values")
-        keep.append(a if len(a) else np.zeros(1, dt))
-        setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
-
-    for name, dt, cols in _RING_ARRAYS:
-        put(name, dt, st.n_rings * cols)
-    put("ring_offset", np.int64, st.n_rings + 1)
-    put("label_ring_offset", np.int64, st.n_labels + 1)
-    put("xy", np.int32, 2 * st.n_vertices)
-    if o.z is not None:
-        put("z", np.int32, st.n_vertices)
-        st.has_z = 1
+    st.has_z = int(o.z is not None)
+    _fill(st, o, "Outlines", _columns(_RING_ARRAYS, st.n_rings) + [("ring_offset", np.int64, st.n_rings + 1),
+          ("label_ring_offset", np.int64, st.n_labels + 1), ("xy", np.int32, 2 * st.n_vertices)] +
+          [("z", np.int32, st.n_vertices)] * st.has_z, keep)
     return st, keep
 
 
@@ -2350,13 +2305,7 @@ def write_outlines_obj(outlines, path, bin, origin=None):
     if outlines.xy is None:
         raise ValueError("write_outlines_obj: the vertices are on the device")
     st, keep = _outlines_struct(outlines)
-    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
-    if org is not None and org.shape != (3,):
-        raise ValueError("origin must be [3]")
-    rc = _lib.load().bs_outlines_write_obj(C.byref(st), int(bin), org.ctypes.data if org is not None else None,
-                                           str(path).encode())
-    if rc != 0:
-        raise BsError(rc, f"cannot write {path} (or the ring arrays do not fit each other)")
+    _write_obj("bs_outlines_write_obj", path, "the ring arrays do not fit each other", C.byref(st), int(bin), _origin(origin))
 
 
 @dataclass
@@ -2391,32 +2340,36 @@ class SimpleOutlines:
     s_flag: np.ndarray | None = field(default=None, repr=False)
 
 
-_SIMPLE_RING_ARRAYS = (("ring_label", np.int32), ("ring_area2", np.int64), ("s_ring_vertices", np.int64),
-                       ("s_ring_area2", np.int64), ("s_ring_arcs", np.int64))
+_SIMPLE_RING_ARRAYS = (("ring_label", np.int32, 1), ("ring_area2", np.int64, 1), ("s_ring_vertices", np.int64, 1),
+                       ("s_ring_area2", np.int64, 1), ("s_ring_arcs", np.int64, 1))
 _SIMPLE_TOTALS = ("n_rings", "n_nodes", "n_junction_nodes", "n_arcs", "n_svertices", "rounds", "max_arc_nodes")
+
+
+_SIMPLE_MS = ("ms_outlines", "ms_nodes", "ms_placing", "ms_arcs", "ms_rounds", "ms_rings", "ms_emit")
+
+
+def _take_kept_outlines(L, out, vertices, cls, ms, totals=()):
+    """Copy a bs_simple_outlines or a bs_clean_outlines into the dataclass cls (its info: the fields ms; the totals it has
+    beyond the simplified ones: totals) and release it."""
+    try:
+        nr, nv = out.n_rings, out.n_svertices
+        arrs = _copy_arrays(out, _SIMPLE_RING_ARRAYS, nr)
+        arrs["s_ring_offset"] = _copy(out.s_ring_offset, (nr + 1,), np.int64)
+        arrs["label_ring_offset"] = _copy(out.label_ring_offset, (out.n_labels + 1,), np.int64)
+        v = dict(sxy=None, sz=None, s_right=None, s_flag=None)
+        if vertices:
+            v.update(sxy=_copy(out.sxy, (nv, 2), np.int32), s_right=_copy(out.s_right, (nv,), np.int32),
+                     s_flag=_copy(out.s_flag, (nv,), np.uint8), sz=_copy(out.sz, (nv,), np.int32) if out.has_z else None)
+        return cls(out.width, out.height, out.n_labels, out.tol_num, out.tol_den, *[getattr(out, k) for k in _SIMPLE_TOTALS],
+                   has_z=bool(out.has_z), info={k: getattr(out, k) for k in ms}, **arrs, **v,
+                   **{k: getattr(out, k) for k in totals})
+    finally:
+        _free(L, out)
 
 
 def _take_simple_outlines(L, out, vertices) -> SimpleOutlines:
     """Copy a bs_simple_outlines into numpy arrays and release it."""
-    try:
-        nr, nv = out.n_rings, out.n_svertices
-        arrs = {name: np.ctypeslib.as_array(getattr(out, name), (nr,)).copy() if nr else np.zeros(0, dt)
-                for name, dt in _SIMPLE_RING_ARRAYS}
-        arrs["s_ring_offset"] = np.ctypeslib.as_array(out.s_ring_offset, (nr + 1,)).copy()
-        arrs["label_ring_offset"] = np.ctypeslib.as_array(out.label_ring_offset, (out.n_labels + 1,)).copy()
-        v = dict(sxy=None, sz=None, s_right=None, s_flag=None)
-        if vertices:
-            v["sxy"] = np.ctypeslib.as_array(out.sxy, (nv, 2)).copy() if nv else np.zeros((0, 2), np.int32)
-            v["s_right"] = np.ctypeslib.as_array(out.s_right, (nv,)).copy() if nv else np.zeros(0, np.int32)
-            v["s_flag"] = np.ctypeslib.as_array(out.s_flag, (nv,)).copy() if nv else np.zeros(0, np.uint8)
-            if out.has_z:
-                v["sz"] = np.ctypeslib.as_array(out.sz, (nv,)).copy() if nv else np.zeros(0, np.int32)
-        info = {k: getattr(out, k) for k in ("ms_outlines", "ms_nodes", "ms_placing", "ms_arcs", "ms_rounds", "ms_rings",
-                                             "ms_emit")}
-        return SimpleOutlines(out.width, out.height, out.n_labels, out.tol_num, out.tol_den,
-                              *[getattr(out, k) for k in _SIMPLE_TOTALS], has_z=bool(out.has_z), info=info, **arrs, **v)
-    finally:
-        L.bs_simple_outlines_free(C.byref(out))
+    return _take_kept_outlines(L, out, vertices, SimpleOutlines, _SIMPLE_MS)
 
 
 @dataclass
@@ -2461,58 +2414,26 @@ _CLEAN_TOTALS = ("max_rounds", "cell_log2", "n_svertices_before", "n_marked_firs
 
 def _take_clean_outlines(L, out, vertices) -> CleanOutlines:
     """Copy a bs_clean_outlines into numpy arrays and release it."""
-    try:
-        nr, nv = out.n_rings, out.n_svertices
-        arrs = {name: np.ctypeslib.as_array(getattr(out, name), (nr,)).copy() if nr else np.zeros(0, dt)
-                for name, dt in _SIMPLE_RING_ARRAYS}
-        arrs["s_ring_offset"] = np.ctypeslib.as_array(out.s_ring_offset, (nr + 1,)).copy()
-        arrs["label_ring_offset"] = np.ctypeslib.as_array(out.label_ring_offset, (out.n_labels + 1,)).copy()
-        v = dict(sxy=None, sz=None, s_right=None, s_flag=None)
-        if vertices:
-            v["sxy"] = np.ctypeslib.as_array(out.sxy, (nv, 2)).copy() if nv else np.zeros((0, 2), np.int32)
-            v["s_right"] = np.ctypeslib.as_array(out.s_right, (nv,)).copy() if nv else np.zeros(0, np.int32)
-            v["s_flag"] = np.ctypeslib.as_array(out.s_flag, (nv,)).copy() if nv else np.zeros(0, np.uint8)
-            if out.has_z:
-                v["sz"] = np.ctypeslib.as_array(out.sz, (nv,)).copy() if nv else np.zeros(0, np.int32)
-        info = {k: getattr(out, k) for k in ("ms_simplify", "ms_detect", "ms_repair", "ms_rings", "ms_emit")}
-        return CleanOutlines(out.width, out.height, out.n_labels, out.tol_num, out.tol_den,
-                             *[getattr(out, k) for k in _SIMPLE_TOTALS], has_z=bool(out.has_z), info=info, **arrs, **v,
-                             **{k: getattr(out, k) for k in _CLEAN_TOTALS})
-    finally:
-        L.bs_clean_outlines_free(C.byref(out))
+    return _take_kept_outlines(L, out, vertices, CleanOutlines, ("ms_simplify", "ms_detect", "ms_repair", "ms_rings", "ms_emit"),
+                               _CLEAN_TOTALS)
+
+
+def _kept_outlines_struct(st, o, what, scalars=()):
+    """the bs_simple_outlines or bs_clean_outlines `st` over what its writer reads of o, and the arrays to keep alive"""
+    for k in ("n_labels", "n_rings", "n_svertices", "tol_num", "tol_den") + scalars:
+        setattr(st, k, int(getattr(o, k)))
+    st.has_z = int(o.sz is not None)
+    return st, _fill(st, o, what, [("ring_label", np.int32, st.n_rings), ("ring_area2", np.int64, st.n_rings),
+                                   ("s_ring_offset", np.int64, st.n_rings + 1), ("label_ring_offset", np.int64, st.n_labels + 1),
+                                   ("sxy", np.int32, 2 * st.n_svertices)] + [("sz", np.int32, st.n_svertices)] * st.has_z, [])
 
 
 def write_clean_outlines_obj(clean, path, bin, origin=None):
     """The rings of a CleanOutlines as an OBJ through the library's writer (bs_clean_outlines_write_obj)."""
     if clean.sxy is None:
         raise ValueError("write_clean_outlines_obj: the vertices are on the device")
-    st, keep = _lib.CleanOutlines(), []
-    st.n_labels, st.n_rings, st.n_svertices = int(clean.n_labels), int(clean.n_rings), int(clean.n_svertices)
-    st.tol_num, st.tol_den = int(clean.tol_num), int(clean.tol_den)
-    st.repair_rounds, st.n_forced = int(clean.repair_rounds), int(clean.n_forced)
-
-    def put(name, dt, n):
-        a = np.ascontiguousarray(getattr(clean, name), dtype=dt).reshape(-1)
-        if len(a) != n:
-            raise ValueError(f"CleanOutlines.{name} must hold {n} values")
-        keep.append(a if len(a) else np.zeros(1, dt))
-        setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
-
-    put("ring_label", np.int32, st.n_rings)
-    put("ring_area2", np.int64, st.n_rings)
-    put("s_ring_offset", np.int64, st.n_rings + 1)
-    put("label_ring_offset", np.int64, st.n_labels + 1)
-    put("sxy", np.int32, 2 * st.n_svertices)
-    if clean.sz is not None:
-        put("sz", np.int32, st.n_svertices)
-        st.has_z = 1
-    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
-    if org is not None and org.shape != (3,):
-        raise ValueError("origin must be [3]")
-    rc = _lib.load().bs_clean_outlines_write_obj(C.byref(st), int(bin), org.ctypes.data if org is not None else None,
-                                                 str(path).encode())
-    if rc != 0:
-        raise BsError(rc, f"cannot write {path} (or the ring arrays do not fit each other)")
+    st, keep = _kept_outlines_struct(_lib.CleanOutlines(), clean, "CleanOutlines", ("repair_rounds", "n_forced"))
+    _write_obj("bs_clean_outlines_write_obj", path, "the ring arrays do not fit each other", C.byref(st), int(bin), _origin(origin))
 
 
 @dataclass
@@ -2543,24 +2464,19 @@ class OutlineTriangles:
 
 _TRI_TOTALS = ("n_labels", "n_rings", "n_svertices", "n_triangles", "n_failed_labels", "n_bridges", "n_tests",
                "max_label_occurrences", "n_labels_wave", "n_labels_lds", "n_labels_global", "wave_cap", "lds_cap")
+_TRI_LABEL_ARRAYS = (("label_status", np.int32, 1), ("label_area2", np.int64, 1), ("label_tests", np.int64, 1))
 
 
 def _take_outline_triangles(L, out, triangles) -> OutlineTriangles:
     """Copy a bs_outline_triangles into numpy arrays and release it."""
     try:
-        nl, nr, nt = out.n_labels, out.n_rings, out.n_triangles
-        arr = lambda p, n, dt: np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, dt)  # noqa: E731
-        tri = None
-        if triangles:
-            tri = np.ctypeslib.as_array(out.tri, (nt, 3)).copy() if nt else np.zeros((0, 3), np.int32)
+        nl = out.n_labels
         info = {k: getattr(out, k) for k in ("ms_clean", "ms_prologue", "ms_wave", "ms_lds", "ms_global", "ms_emit")}
-        return OutlineTriangles(*[getattr(out, k) for k in _TRI_TOTALS],
-                                tri_offset=np.ctypeslib.as_array(out.tri_offset, (nl + 1,)).copy(),
-                                label_status=arr(out.label_status, nl, np.int32), label_area2=arr(out.label_area2, nl, np.int64),
-                                label_tests=arr(out.label_tests, nl, np.int64),
-                                bridge=arr(out.bridge, 2 * nr, np.int32).reshape(-1, 2), info=info, tri=tri)
+        return OutlineTriangles(*[getattr(out, k) for k in _TRI_TOTALS], tri_offset=_copy(out.tri_offset, (nl + 1,), np.int64),
+                                **_copy_arrays(out, _TRI_LABEL_ARRAYS, nl), bridge=_copy(out.bridge, (out.n_rings, 2), np.int32),
+                                info=info, tri=_copy(out.tri, (out.n_triangles, 3), np.int32) if triangles else None)
     finally:
-        L.bs_outline_triangles_free(C.byref(out))
+        _free(L, out)
 
 
 def write_outline_triangles_obj(tri, clean, path, bin, origin=None):
@@ -2571,29 +2487,13 @@ def write_outline_triangles_obj(tri, clean, path, bin, origin=None):
     st, cl, keep = _lib.OutlineTriangles(), _lib.CleanOutlines(), []
     st.n_labels, st.n_svertices, st.n_triangles = int(tri.n_labels), int(tri.n_svertices), int(tri.n_triangles)
     st.n_failed_labels, st.n_bridges = int(tri.n_failed_labels), int(tri.n_bridges)
-    cl.n_svertices = int(clean.n_svertices)
-
-    def put(struct, src, name, dt, n):
-        a = np.ascontiguousarray(getattr(src, name), dtype=dt).reshape(-1)
-        if len(a) != n:
-            raise ValueError(f"{type(src).__name__}.{name} must hold {n} values")
-        keep.append(a if len(a) else np.zeros(1, dt))
-        setattr(struct, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
-
-    put(st, tri, "tri_offset", np.int64, st.n_labels + 1)
-    put(st, tri, "label_status", np.int32, st.n_labels)
-    put(st, tri, "tri", np.int32, 3 * st.n_triangles)
-    put(cl, clean, "sxy", np.int32, 2 * cl.n_svertices)
-    if clean.sz is not None:
-        put(cl, clean, "sz", np.int32, cl.n_svertices)
-        cl.has_z = 1
-    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
-    if org is not None and org.shape != (3,):
-        raise ValueError("origin must be [3]")
-    rc = _lib.load().bs_outline_triangles_write_obj(C.byref(st), C.byref(cl), int(bin),
-                                                    org.ctypes.data if org is not None else None, str(path).encode())
-    if rc != 0:
-        raise BsError(rc, f"cannot write {path} (or the arrays do not fit each other)")
+    cl.n_svertices, cl.has_z = int(clean.n_svertices), int(clean.sz is not None)
+    _fill(st, tri, type(tri).__name__, [("tri_offset", np.int64, st.n_labels + 1), ("label_status", np.int32, st.n_labels),
+                                        ("tri", np.int32, 3 * st.n_triangles)], keep)
+    _fill(cl, clean, type(clean).__name__, [("sxy", np.int32, 2 * cl.n_svertices)] + [("sz", np.int32, cl.n_svertices)] * cl.has_z,
+          keep)
+    _write_obj("bs_outline_triangles_write_obj", path, "the arrays do not fit each other", C.byref(st), C.byref(cl), int(bin),
+               _origin(origin))
 
 
 @dataclass
@@ -2637,24 +2537,21 @@ class PolySolids:
     face_kind: np.ndarray | None = field(default=None, repr=False)
 
 
+_POLY_ARRAYS = tuple((k, np.dtype(ct), 1) for k, ct in _lib.POLY_FIGURES)
+
+
 def _take_poly_solids(L, out, mesh) -> PolySolids:
     """Copy a bs_poly_solids into numpy arrays and release it."""
     n = out.n_buildings
     try:
-        arrs = {name: (np.ctypeslib.as_array(getattr(out, name), (n,)).copy() if n else np.zeros(0, np.dtype(ct)))
-                for name, ct in _lib.POLY_FIGURES}
+        arrs = _copy_arrays(out, _POLY_ARRAYS, n)
         if mesh:
-            nv, nf, ni = out.n_vertices, out.n_faces, out.n_indices
-            arrs["vertex"] = np.ctypeslib.as_array(out.vertex, (nv, 4)).copy() if nv else np.zeros((0, 4), np.int32)
-            arrs["face_offset"] = np.ctypeslib.as_array(out.face_offset, (nf + 1,)).copy()
-            arrs["face_index"] = np.ctypeslib.as_array(out.face_index, (ni,)).copy() if ni else np.zeros(0, np.int32)
-            arrs["face_building"] = np.ctypeslib.as_array(out.face_building, (nf,)).copy() if nf else np.zeros(0, np.int32)
-            arrs["face_kind"] = np.ctypeslib.as_array(out.face_kind, (nf,)).copy() if nf else np.zeros(0, np.uint8)
+            arrs.update(_take_mesh(out))
         info = {k: getattr(out, k) for k in _lib.POLY_MS}
         return PolySolids(n, out.n_labels, out.bin, out.base_z, out.fig_cap, *[getattr(out, k) for k in _lib.POLY_TOTALS],
                           info=info, **arrs)
     finally:
-        L.bs_poly_solids_free(C.byref(out))
+        _free(L, out)
 
 
 @dataclass
@@ -2701,17 +2598,19 @@ class ModelRaster:
     mz2: np.ndarray | None = field(default=None, repr=False)
 
 
+_MRASTER_ARRAYS = _rows(_lib.MRASTER_FIGURES, np.int64)
+
+
 def _take_model_raster(L, out, model=None, cover=None, mz2=None) -> ModelRaster:
     """Copy a bs_model_raster into numpy arrays and release it."""
     n = out.n_labels
     try:
-        arrs = {k: (np.ctypeslib.as_array(getattr(out, k), (n,)).copy() if n else np.zeros(0, np.int64))
-                for k in _lib.MRASTER_FIGURES}
+        arrs = _copy_arrays(out, _MRASTER_ARRAYS, n)
         info = {k: getattr(out, k) for k in _lib.MRASTER_MS}
         return ModelRaster(out.width, out.height, n, out.fig_cap, out.chunk, *[getattr(out, k) for k in _lib.MRASTER_TOTALS],
                            info=info, model=model, cover=cover, mz2=mz2, **arrs)
     finally:
-        L.bs_model_raster_free(C.byref(out))
+        _free(L, out)
 
 
 @dataclass
@@ -2731,20 +2630,26 @@ class ModelFidelity:
     rmse_mm: np.ndarray
 
 
-def model_fidelity_of(raster, label_building, n_buildings=None) -> ModelFidelity:
-    """The per-label figures of a ModelRaster added up by building (host only; Python integers for the sum of squares)."""
+def _by_building(who, label_building, n_labels, n_buildings):
+    """(label_building int64 [n_labels], n_buildings, add: the per-label figures v added up by building) of the fidelities"""
     lb = np.ascontiguousarray(label_building, dtype=np.int64).reshape(-1)
-    if len(lb) != raster.n_labels:
-        raise ValueError("model_fidelity_of: label_building must have one entry per label")
+    if len(lb) != n_labels:
+        raise ValueError(f"{who}: label_building must have one entry per label")
     nb = (int(lb.max()) + 1 if len(lb) else 0) if n_buildings is None else int(n_buildings)
     if len(lb) and (lb.min() < 0 or lb.max() >= nb):
-        raise ValueError("model_fidelity_of: a label_building value outside 0 .. n_buildings - 1")
+        raise ValueError(f"{who}: a label_building value outside 0 .. n_buildings - 1")
 
     def add(v):
         s = np.zeros(nb, np.int64)
         np.add.at(s, lb, v)
         return s
 
+    return lb, nb, add
+
+
+def model_fidelity_of(raster, label_building, n_buildings=None) -> ModelFidelity:
+    """The per-label figures of a ModelRaster added up by building (host only; Python integers for the sum of squares)."""
+    lb, nb, add = _by_building("model_fidelity_of", label_building, raster.n_labels, n_buildings)
     pixels, kept, errp = add(raster.pixels), add(raster.kept), add(raster.err_pixels)
     mx = np.zeros(nb, np.int64)
     np.maximum.at(mx, lb, raster.max_abs_e2)
@@ -2834,17 +2739,19 @@ class PointResiduals:
     cover: np.ndarray | None = field(default=None, repr=False)
 
 
+_PRESID_ARRAYS = _rows(_lib.PRESID_FIGURES, np.int64)
+
+
 def _take_point_residuals(L, out, label=None, r2=None, cover=None) -> PointResiduals:
     """Copy a bs_point_residuals into numpy arrays and release it."""
     n = out.n_labels
     try:
-        arrs = {k: (np.ctypeslib.as_array(getattr(out, k), (n,)).copy() if n else np.zeros(0, np.int64))
-                for k in _lib.PRESID_FIGURES}
+        arrs = _copy_arrays(out, _PRESID_ARRAYS, n)
         info = {k: getattr(out, k) for k in _lib.PRESID_MS}
         return PointResiduals(*[getattr(out, k) for k in _lib.PRESID_HEAD + _lib.PRESID_TOTALS], info=info, label=label, r2=r2,
                               cover=cover, **arrs)
     finally:
-        L.bs_point_residuals_free(C.byref(out))
+        _free(L, out)
 
 
 @dataclass
@@ -2870,18 +2777,7 @@ class PointFidelity:
 
 def point_fidelity_of(res, label_building, n_buildings=None) -> PointFidelity:
     """The per-label figures of a PointResiduals added up by building (host only; Python integers for the sum of squares)."""
-    lb = np.ascontiguousarray(label_building, dtype=np.int64).reshape(-1)
-    if len(lb) != res.n_labels:
-        raise ValueError("point_fidelity_of: label_building must have one entry per label")
-    nb = (int(lb.max()) + 1 if len(lb) else 0) if n_buildings is None else int(n_buildings)
-    if len(lb) and (lb.min() < 0 or lb.max() >= nb):
-        raise ValueError("point_fidelity_of: a label_building value outside 0 .. n_buildings - 1")
-
-    def add(v):
-        s = np.zeros(nb, np.int64)
-        np.add.at(s, lb, v)
-        return s
-
+    lb, nb, add = _by_building("point_fidelity_of", label_building, res.n_labels, n_buildings)
     points, inl, ppts = add(res.points), add(res.in_points), add(res.plane_points)
     mx = np.zeros(nb, np.int64)
     np.maximum.at(mx, lb, res.max_abs_r2)
@@ -2913,32 +2809,9 @@ def write_simple_outlines_obj(simple, path, bin, origin=None):
     (bs_simple_outlines_write_obj; the format is written down in include/bs_api.h), one group per ring."""
     if simple.sxy is None:
         raise ValueError("write_simple_outlines_obj: the vertices are on the device")
-    st, keep = _lib.SimpleOutlines(), []
-    st.n_labels, st.n_rings, st.n_svertices = int(simple.n_labels), int(simple.n_rings), int(simple.n_svertices)
-    st.tol_num, st.tol_den = int(simple.tol_num), int(simple.tol_den)
-
-    def put(name, dt, n):
-        a = np.ascontiguousarray(getattr(simple, name), dtype=dt).reshape(-1)
-        if len(a) != n:
-            raise ValueError(f"SimpleOutlines.{name} must hold {n} values")
-        keep.append(a if len(a) else np.zeros(1, dt))
-        setattr(st, name, keep[-1].ctypes.data_as(C.POINTER(C.c_int32 if dt == np.int32 else C.c_int64)))
-
-    put("ring_label", np.int32, st.n_rings)
-    put("ring_area2", np.int64, st.n_rings)
-    put("s_ring_offset", np.int64, st.n_rings + 1)
-    put("label_ring_offset", np.int64, st.n_labels + 1)
-    put("sxy", np.int32, 2 * st.n_svertices)
-    if simple.sz is not None:
-        put("sz", np.int32, st.n_svertices)
-        st.has_z = 1
-    org = None if origin is None else np.ascontiguousarray(origin, dtype=np.int32)
-    if org is not None and org.shape != (3,):
-        raise ValueError("origin must be [3]")
-    rc = _lib.load().bs_simple_outlines_write_obj(C.byref(st), int(bin), org.ctypes.data if org is not None else None,
-                                                  str(path).encode())
-    if rc != 0:
-        raise BsError(rc, f"cannot write {path} (or the ring arrays do not fit each other)")
+    st, keep = _kept_outlines_struct(_lib.SimpleOutlines(), simple, "SimpleOutlines")
+    _write_obj("bs_simple_outlines_write_obj", path, "the ring arrays do not fit each other", C.byref(st), int(bin),
+               _origin(origin))
 
 
 @dataclass
@@ -2956,17 +2829,28 @@ class Footprints:
         return [i for i in range(len(self.contours)) if self.area[i] > min_area and self.perimeter[i] > min_perimeter]
 
 
+def _contours_struct(fp):
+    """a bs_contours over the contours of a Footprints (without area and perimeter), and the arrays to keep alive"""
+    n = len(fp.contours)
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(c) for c in fp.contours]) if n else []
+    xy = np.ascontiguousarray(np.concatenate(fp.contours) if n else np.zeros((0, 2)), dtype=np.int32)
+    c = Contours()
+    c.n_contours, c.width, c.height = n, fp.width, fp.height
+    c.offset = off.ctypes.data_as(C.POINTER(C.c_int64))
+    c.xy = (xy if xy.size else _PAD).ctypes.data_as(C.POINTER(C.c_int32))
+    return c, (off, xy)
+
+
 def _contour_arrays(L, out: Contours):
     """(offset, xy, area, perimeter) copied out of a bs_contours, which is released."""
     n = out.n_contours
     try:
-        off = np.ctypeslib.as_array(out.offset, (n + 1,)).copy() if out.offset else np.zeros(1, np.int64)
-        tot = int(off[-1])
-        xy = np.ctypeslib.as_array(out.xy, (2 * tot,)).reshape(tot, 2).copy() if tot else np.zeros((0, 2), np.int32)
-        area = np.ctypeslib.as_array(out.area, (n,)).copy() if n else np.zeros(0)
-        per = np.ctypeslib.as_array(out.perimeter, (n,)).copy() if n else np.zeros(0)
+        off = _copy(out.offset, (n + 1,), np.int64) if out.offset else np.zeros(1, np.int64)
+        xy = _copy(out.xy, (int(off[-1]), 2), np.int32)
+        area, per = _copy(out.area, (n,), np.float64), _copy(out.perimeter, (n,), np.float64)
     finally:
-        L.bs_contours_free(C.byref(out))
+        _free(L, out)
     return off, xy, area, per
 
 
@@ -2989,17 +2873,8 @@ def _take_contours_batch(L, out: Contours, inf: FootprintInfo, co, widths, heigh
 def write_footprints_obj(fp: Footprints, path):
     """The reference's OBJ (my_function.cpp:64-131) through the library's writer (bs_contours_write_obj), so that
     Python and host/tmc3 --footprints= write the same bytes."""
-    n = len(fp.contours)
-    off = np.zeros(n + 1, dtype=np.int64)
-    off[1:] = np.cumsum([len(c) for c in fp.contours]) if n else []
-    xy = np.ascontiguousarray(np.concatenate(fp.contours) if n else np.zeros((0, 2)), dtype=np.int32)
-    c = Contours()
-    c.n_contours, c.width, c.height = n, fp.width, fp.height
-    c.offset = off.ctypes.data_as(C.POINTER(C.c_int64))
-    c.xy = xy.ctypes.data_as(C.POINTER(C.c_int32))
-    rc = _lib.load().bs_contours_write_obj(C.byref(c), str(path).encode())
-    if rc != 0:
-        raise BsError(rc, f"cannot write {path}")
+    c, keep = _contours_struct(fp)
+    _write_obj("bs_contours_write_obj", path, None, C.byref(c))
 
 
 def _tile_offsets(tile_offset) -> np.ndarray:
