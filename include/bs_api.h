@@ -196,6 +196,9 @@ int bs_segment_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, const bs_params
  * bs_shift_to_origin_dev: the buildingSeg constructor's bounding-box shift
  * (TMC3.cpp:55-73): min over the cloud, then xyz -= min IN PLACE; min_out [3]
  * (host, nullable) receives the subtracted minimum.  Synchronises.
+ * Contract: the extent max - min of every axis is below 2^31 (the difference is
+ * formed in int32; the reference's is undefined beyond that).  The call does not
+ * check it; api.shift_tiles_to_origin refuses such a cloud on the host.
  *
  * bs_plane_colors_dev: seg_plane::set_plane_color (my_function.cpp:260-275) for
  * the planes of the last region grow on this context: d_colors [n][3] uint16
@@ -207,7 +210,9 @@ int bs_shift_to_origin_dev(bs_ctx* ctx, int32_t* d_xyz, int64_t n, int32_t* min_
  * ply::read, ply.cpp:431-501, for the positions): d_records is the binary
  * little-endian vertex body resident on the device (n records of `stride` bytes,
  * x/y/z at byte offsets off_x/off_y/off_z, all three float32 (is_f64 = 0) or
- * float64).  d_xyz [n][3] receives (int32) trunc(value * scale) (ply.cpp:436-465;
+ * float64; d_records may have any alignment, e.g. the byte just past the header
+ * of an uploaded file: fields are assembled from bytes).  d_xyz [n][3] receives
+ * (int32) trunc(value * scale) (ply.cpp:436-465;
  * float promoted to double first).  shift_to_origin != 0 additionally applies the
  * buildingSeg constructor's bounding-box shift (TMC3.cpp:55-73) and reports the
  * subtracted minimum in min_out (host [3], nullable).  BS_ERR_RANGE if a product
@@ -381,7 +386,9 @@ int bs_segment_batch_dev(bs_ctx* ctx, const int32_t* d_xyz, const int64_t* tile_
  * plane_offset [n_tiles+1] (host, nullable). */
 int bs_batch_planes_fetch(bs_ctx* ctx, bs_planes* planes, int32_t* plane_offset);
 /* bs_shift_to_origin_dev applied to every tile separately (TMC3.cpp:55-73 per tile): min_out [n_tiles][3] (host,
- * nullable) receives each tile's subtracted minimum.  Offsets as above (every tile >= 1 point).  Synchronises. */
+ * nullable) receives each tile's subtracted minimum.  Offsets as above (every tile >= 1 point).  Synchronises.
+ * Contract as for bs_shift_to_origin_dev, per tile: the extent max - min of every axis of every tile is below 2^31 (not
+ * checked here; api.shift_tiles_to_origin refuses it on the host). */
 int bs_shift_tiles_to_origin_dev(bs_ctx* ctx, int32_t* d_xyz, const int64_t* tile_offset, int32_t n_tiles,
                                  int32_t* min_out);
 

@@ -8,7 +8,13 @@ element) this script stores in tests/golden/ply_cases.npz: the input file bytes,
 positions and colour slots the reference reads (ply.cpp:407-415,436-477) and the bytes of the file
 it writes back (binary and ascii; ply.cpp:88-186).  tests/test_host_ply_golden.py requires
 host/bs_ply.cpp to reproduce every output byte.  Fixtures are data, not source.
+
+A second file, tests/golden/ply_edge_cases.npz, holds what the same reader makes of the two files of
+tests/edge_ref/cases.py (PLY_EDGE_FILES: the sweep k / 1000, negative fractions, signed zeros, subnormals, values one
+ulp either side of a whole millimetre, the largest magnitudes that fit): input bytes and quantised positions only.
+`make_golden_ply.py` writes both files, `make_golden_ply.py edge` the second one alone.
 """
+import importlib.util
 import os
 import subprocess
 import sys
@@ -19,6 +25,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 REF = os.path.join(ROOT, "oracle", "_ref", "ref_ply")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ply_cases.npz")
+OUT_EDGE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ply_edge_cases.npz")
 
 
 def make_inputs():
@@ -64,9 +71,37 @@ def make_inputs():
     return cases
 
 
+def read_positions(td, name, data):
+    """what the reference's reader makes of the file `data`: int32 [n, 3]"""
+    fi, fo, fd = os.path.join(td, name + ".ply"), os.path.join(td, "o.ply"), os.path.join(td, "d.bin")
+    open(fi, "wb").write(data)
+    subprocess.check_call([REF, fi, "1000", fo, "0", fd])
+    raw = open(fd, "rb").read()
+    n = int(np.frombuffer(raw, np.int64, 1)[0])
+    return np.frombuffer(raw, np.int32, 3 * n, 12).reshape(n, 3).copy()
+
+
+def main_edge():
+    spec = importlib.util.spec_from_file_location("edge_cases", os.path.join(ROOT, "tests", "edge_ref", "cases.py"))
+    cases = importlib.util.module_from_spec(spec)
+    sys.modules["edge_cases"] = cases
+    spec.loader.exec_module(cases)
+    out = {}
+    with tempfile.TemporaryDirectory() as td:
+        for name, _, _ in cases.PLY_EDGE_FILES:
+            data = cases.ply_edge_file(name)
+            out[name + "/in"] = np.frombuffer(data, np.uint8)
+            out[name + "/xyz"] = read_positions(td, name, data)
+            print(name, len(out[name + "/xyz"]), "points")
+    np.savez_compressed(OUT_EDGE, **out)
+    print("wrote", OUT_EDGE, os.path.getsize(OUT_EDGE), "bytes")
+
+
 def main():
     if not os.path.exists(REF):
         sys.exit("oracle/_ref/ref_ply missing: run `make -C oracle ref` in the build container")
+    if sys.argv[1:] == ["edge"]:
+        return main_edge()
     out = {}
     with tempfile.TemporaryDirectory() as td:
         for name, data in make_inputs().items():
@@ -86,6 +121,7 @@ def main():
             print(name, n, "points, colours" if hc else "points, no colours", len(out[name + "/out_bin"]), "B written")
     np.savez_compressed(OUT, **out)
     print("wrote", OUT, os.path.getsize(OUT), "bytes")
+    main_edge()
 
 
 if __name__ == "__main__":
