@@ -49,7 +49,8 @@ EXPORTS = ["bs_api_version", "bs_sizeof_timings", "bs_strerror", "bs_params_defa
            "bs_ground_dev", "bs_ground", "bs_ground_free", "bs_set_ground_model", "bs_set_ground_model_dev",
            "bs_get_ground_model", "bs_plane_quality", "bs_roof_evidence_dev", "bs_roof_evidence", "bs_set_footprint_screen",
            "bs_set_footprint_screen_dev", "bs_get_footprint_screen", "bs_selftest_scratch_guard",
-           "bs_selftest_scratch_check", "bs_selftest_scratch_list"]
+           "bs_selftest_scratch_check", "bs_selftest_scratch_list", "bs_label_hulls_count_dev", "bs_label_hulls_emit_dev",
+           "bs_label_hulls", "bs_label_hulls_free", "bs_hull_box_corners", "bs_hull_boxes_write_obj"]
 
 
 class Params(C.Structure):
@@ -401,6 +402,27 @@ class RoofEvidence(C.Structure):
                 [(k, C.c_double) for k in EVIDENCE_MS])
 
 
+HULL_MAX_SIDE = 16383   # BS_HULL_MAX_SIDE of include/bs_api.h
+HULL_ROUND_BATCH = 4    # BS_HULL_ROUND_BATCH
+HULL_STATUS = {0: "BS_HULL_OK", 1: "BS_HULL_EMPTY", 2: "BS_HULL_TOO_LARGE"}
+HULL_TOTALS = ("n_hull_vertices", "n_ok", "n_empty", "n_too_large")
+HULL_LAYOUT = ("n_candidates", "rounds", "max_live")
+# (name, type, columns) of the per-label arrays of bs_label_hulls
+HULL_ARRAYS = (("status", C.c_int32, 1), ("box", C.c_int32, 4), ("pixels2", C.c_int64, 1), ("n_hull", C.c_int64, 1),
+               ("hull_offset", C.c_int64, 1), ("hull_area2", C.c_int64, 1), ("best_edge", C.c_int32, 1), ("dir", C.c_int32, 2),
+               ("len2", C.c_int64, 1), ("a_min", C.c_int64, 1), ("a_max", C.c_int64, 1), ("c_max", C.c_int64, 1),
+               ("area_num", C.c_int64, 1))
+HULL_MS = ("ms_outlines", "ms_candidates", "ms_rounds", "ms_order", "ms_boxes", "ms_emit")
+
+
+class LabelHulls(C.Structure):
+    """bs_label_hulls (include/bs_api.h): totals, layout figures, per-label arrays and (host-memory entry point) the hull
+    vertices, host memory owned by the library."""
+    _fields_ = ([(k, C.c_int32) for k in ("width", "height", "n_labels", "reserved")] +
+                [(k, C.c_int64) for k in HULL_TOTALS + HULL_LAYOUT] + [(k, C.POINTER(t)) for k, t, _ in HULL_ARRAYS] +
+                [("hull_xy", C.POINTER(C.c_int32))] + [(k, C.c_double) for k in HULL_MS])
+
+
 class BsError(RuntimeError):
     def __init__(self, status, detail=""):
         self.status = status
@@ -623,5 +645,13 @@ def load():
     for fn in (L.bs_set_footprint_screen, L.bs_set_footprint_screen_dev):
         fn.argtypes = [vp, vp, C.c_int32, C.c_int32]
     L.bs_get_footprint_screen.argtypes = [vp, vp, C.c_int64, i32p, i32p]
+    hlp = C.POINTER(LabelHulls)
+    L.bs_label_hulls_count_dev.argtypes = [vp, ip, C.c_int32, C.c_int32, C.c_int32, hlp]
+    L.bs_label_hulls.argtypes = [vp, ip, C.c_int32, C.c_int32, C.c_int32, hlp]
+    L.bs_label_hulls_emit_dev.argtypes = [vp, ip]
+    L.bs_label_hulls_free.argtypes = [hlp]
+    L.bs_label_hulls_free.restype = None
+    L.bs_hull_box_corners.argtypes = [hlp, C.c_int32, C.c_int32, ip, vp]
+    L.bs_hull_boxes_write_obj.argtypes = [hlp, C.c_int32, ip, C.c_char_p]
     _LIB = L
     return L

@@ -598,7 +598,7 @@ void scratch_members(bs_ctx* c, std::vector<ScratchMember>& out)
   BS_ONE(bases_dev);
   BS_ARR(tn); BS_ARR(gd);
   BS_ONE(gm_dev);
-  BS_ARR(evd);
+  BS_ARR(evd); BS_ARR(hl);
   BS_ONE(fs_dev);
   BS_ARR(sh); BS_ARR(bt);
   BS_ONE(tile_desc);

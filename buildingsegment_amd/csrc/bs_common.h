@@ -407,6 +407,13 @@ struct bs_ctx : bs_ctx_handles {
   bool gm_on = false;
   int32_t gm_w = 0, gm_h = 0, gm_cell = 0, gm_min = 0;
   bs::DevBuf evd[10];  // scratch of the roof evidence (bs_evidence.hip); it keeps no state between calls
+  // oriented boxes (bs_hull.hip): scratch, and what bs_label_hulls_count_dev leaves for bs_label_hulls_emit_dev (the strict
+  // hull vertices in their final order)
+  bs::DevBuf hl[25];
+  bool hl_valid = false;
+  int64_t hl_nv = 0;
+  const int32_t* hl_xy = nullptr;  // (inside hl)
+  double hl_ms_emit = 0;           // the last emit
   // footprint screen (bs_set_footprint_screen): the image bs_footprints ANDs into its mask; fs_ptr == nullptr = off.  The host
   // form keeps a copy in fs_dev, the _dev form the caller's pointer
   bs::DevBuf fs_dev;

@@ -2180,6 +2180,112 @@ int bs_set_footprint_screen_dev(bs_ctx* ctx, const uint8_t* d_keep, int32_t widt
  * be NULL with capacity == 0.  BS_ERR_INVALID: a null number, a negative capacity, or a null keep with capacity > 0. */
 int bs_get_footprint_screen(bs_ctx* ctx, uint8_t* keep, int64_t capacity, int32_t* width, int32_t* height);
 
+/* ---- oriented boxes: the convex hull and the minimum-area enclosing rectangle of every label ----
+ *
+ * Input: a label image as for the facet outlines: label[height][width] of int32, negative = outside, else 0 .. n_labels - 1
+ * (the building map of bs_building_map is one, the facet image of bs_roof_facets another).  C(l) is the set of lattice
+ * corners of all pixels of label l; orient(a, b, c) = (bx - ax)(cy - ay) - (by - ay)(cx - ax) in int64.
+ *
+ * Hull.  H(l) is the list of the strict vertices of the convex hull of C(l): orient(prev, v, next) > 0 at every vertex, no
+ * collinear vertex.  The order is the outlines' own (positive shoelace sum in (X, Y)); the list begins at the vertex with the
+ * lowest corner index Y * (width + 1) + X, which is always a hull vertex.  hull_area2 is the shoelace sum in int64.  Every
+ * hull vertex is the corner of a pixel that lies inside the hull, so every interior angle is at least 90 degrees and
+ * n_hull >= 4 for every label with a pixel; the lowest row of corners holds a whole pixel side, so the hull has a
+ * horizontal edge.
+ *
+ * Box.  For hull edge i let s = H[i], e = H[(i + 1) % n_hull], d = e - s, len2 = |d|^2, and over all p of H
+ *   a(p) = (p - s) . d            with minimum a_min <= 0 and maximum a_max >= len2,
+ *   c(p) = orient(s, e, p) >= 0   with maximum c_max > 0,
+ *   area_num_i = (a_max - a_min) * c_max:
+ * the rectangle with a side on edge i has the area area_num_i / len2_i.  best_edge is the edge of least area, compared
+ * exactly as area_num_i * len2_j < area_num_j * len2_i (128 bits), the lowest i on a tie.  A minimum-area enclosing rectangle
+ * always has a side on a hull edge, so this is the minimum-area rectangle.
+ *
+ * Bound.  A label whose box of lattice corners is wider or higher than BS_HULL_MAX_SIDE has the status BS_HULL_TOO_LARGE:
+ * its box and pixels2 are reported, its n_hull and every other figure are 0.  Below the bound |a|, a_max - a_min and c_max
+ * are under 2^29, area_num under 2^58 and the compared products under 2^87.  A label without a pixel has BS_HULL_EMPTY and
+ * nothing but zeros.
+ *
+ * Per label: status, box[4] = {X0, Y0, X1, Y1} (inclusive, of its corners), pixels2 (twice its pixels), n_hull,
+ * hull_offset[n_labels + 1] into hull_xy, hull_area2, best_edge, dir[2] = the d of the best edge (not reduced), len2,
+ * a_min, a_max, c_max, area_num.  Totals: n_hull_vertices, n_ok, n_empty, n_too_large.  Vertices: hull_xy
+ * [n_hull_vertices][2].  Everything above is an exact integer and independent of how the device pass is laid out.
+ *
+ * Identities.  hull_area2 >= pixels2.  2 * area_num >= hull_area2 * len2.  area_num <= (X1 - X0) * (Y1 - Y0) * len2 (the
+ * horizontal edge).  A full w x h rectangle of one label: n_hull == 4, best_edge == 0, area_num == w * h * len2.  Moving a
+ * label inside the image changes only box, hull_xy and the start corner.
+ *
+ * Layout figures (they depend on the device pass, DESIGN.md "Oriented boxes", and on nothing else): n_candidates, the
+ * convex vertices of the outer rings of the labels within the bound; rounds, the QuickHull rounds that still had a live
+ * candidate; max_live, the most live candidates at the start of a round. */
+#define BS_HULL_MAX_SIDE 16383
+#define BS_HULL_ROUND_BATCH 4   /* rounds between two reads of the live count */
+#define BS_HULL_ROUND_CAP 16384 /* more rounds than this: BS_ERR_INTERNAL (a hull within the bound cannot need them) */
+enum { BS_HULL_OK = 0, BS_HULL_EMPTY = 1, BS_HULL_TOO_LARGE = 2 };
+struct bs_label_hulls {
+  int32_t width, height;
+  int32_t n_labels;
+  int32_t reserved;
+  int64_t n_hull_vertices, n_ok, n_empty, n_too_large; /* totals */
+  int64_t n_candidates, rounds, max_live;              /* layout figures */
+  /* per label; host memory owned by the library */
+  int32_t* status;      /* [n_labels] */
+  int32_t* box;         /* [n_labels][4] */
+  int64_t* pixels2;     /* [n_labels] */
+  int64_t* n_hull;      /* [n_labels] */
+  int64_t* hull_offset; /* [n_labels + 1] */
+  int64_t* hull_area2;  /* [n_labels] */
+  int32_t* best_edge;   /* [n_labels] */
+  int32_t* dir;         /* [n_labels][2] */
+  int64_t* len2;        /* [n_labels] */
+  int64_t* a_min;       /* [n_labels] */
+  int64_t* a_max;       /* [n_labels] */
+  int64_t* c_max;       /* [n_labels] */
+  int64_t* area_num;    /* [n_labels] */
+  /* the hull vertices, host memory owned by the library: filled by the host-memory entry point only (NULL after the count) */
+  int32_t* hull_xy; /* [n_hull_vertices][2] */
+  /* device time (HIP events on the context's stream) */
+  double ms_outlines;   /* the plain outline count underneath */
+  double ms_candidates; /* boxes and status per label, the candidates, the seeds */
+  double ms_rounds;     /* the first assignment and the QuickHull rounds */
+  double ms_order;      /* the sort into walk order, the strict vertices, the offsets */
+  double ms_boxes;      /* every edge's rectangle and the best per label */
+  double ms_emit;       /* the emit (host-memory entry point only) */
+};
+
+/* Hulls, boxes and sizes.  d_label is a device pointer.  Runs bs_facet_outlines_count_dev (without top) on the image first:
+ * its context state is replaced, as by the simplified count.  The hull vertices stay in the context for the emit below; out's
+ * arrays are host memory owned by the library (bs_label_hulls_free, which accepts a zeroed struct).  An image without a
+ * labelled pixel is valid: every label BS_HULL_EMPTY.
+ * The errors are exactly those of bs_facet_outlines_count_dev (BS_ERR_INVALID, BS_ERR_RANGE).  On any error out is left
+ * untouched, and the context stays usable.  Synchronises: the three times of the outline count, once for the candidate
+ * count, once every BS_HULL_ROUND_BATCH rounds, once for the results (once in all without a labelled pixel). */
+int bs_label_hulls_count_dev(bs_ctx* ctx, const int32_t* d_label, int32_t width, int32_t height, int32_t n_labels,
+                             struct bs_label_hulls* out);
+/* The hull vertices of the last successful count on this context into a device buffer of exactly its size: d_hull_xy
+ * [n_hull_vertices][2] (may be NULL without a vertex).  May be called more than once.  BS_ERR_INVALID: no successful count
+ * (the last one on this context failed, or there was none), or d_hull_xy NULL.  Synchronises. */
+int bs_label_hulls_emit_dev(bs_ctx* ctx, int32_t* d_hull_xy);
+/* Host-memory twin: label is a host pointer; both steps, and the vertices come back in out's library-owned hull_xy. */
+int bs_label_hulls(bs_ctx* ctx, const int32_t* label, int32_t width, int32_t height, int32_t n_labels,
+                   struct bs_label_hulls* out);
+void bs_label_hulls_free(struct bs_label_hulls* h);
+
+/* The four corners of the rectangle of one label.  Host only, integers.  With s the start of the best edge (hull_xy), d = dir
+ * and n = (-dy, dx):  K0 = s + (a_min d) / len2, K1 = s + (a_max d) / len2, K2 = K1 + (c_max n) / len2, K3 = K0 + (c_max n) /
+ * len2.  Each coordinate is round(numerator * bin / len2) + origin, the numerator over len2 including s * len2; the division
+ * is done once in 128 bits and rounds half away from zero.  origin [2] (NULL: 0).
+ * BS_ERR_INVALID: null pointer (origin apart), bin < 1, no hull_xy, a label outside [0, n_labels) or not BS_HULL_OK. */
+int bs_hull_box_corners(const struct bs_label_hulls* h, int32_t label, int32_t bin, const int32_t* origin, int64_t out[4][2]);
+/* Hulls and rectangles as an OBJ of closed polylines in millimetres.  Host only, no context; origin [3] as for
+ * bs_outlines_write_obj (NULL: 0), every Z is origin[2].  The file, every number a decimal integer, every line ended by '\n':
+ *   "# oriented boxes: <n_labels> labels, <n_ok> ok, <n_empty> empty, <n_too_large> too large, <n_hull_vertices> hull vertices"
+ *   for every BS_HULL_OK label l in order: "g label_<l>_hull", its hull vertices "v X*bin+origin[0] Y*bin+origin[1] origin[2]",
+ *   one closed polyline "l i1 ... in i1"; then "g label_<l>_box", the four corners of bs_hull_box_corners as vertices and one
+ *   closed polyline.  Vertices are numbered from 1 in file order.
+ * BS_ERR_INVALID: as bs_hull_box_corners, hull_offset that does not fit n_hull, or the file cannot be written. */
+int bs_hull_boxes_write_obj(const struct bs_label_hulls* h, int32_t bin, const int32_t* origin, const char* path);
+
 #ifdef __cplusplus
 }
 #endif
