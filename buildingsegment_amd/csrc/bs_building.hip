@@ -570,11 +570,9 @@ extern "C" int bs_building_map_dev(bs_ctx* ctx, const uint8_t* d_mask, int32_t w
 
   hipcub::CountingInputIterator<int32_t> idx(0);
   hipcub::TransformInputIterator<int32_t, RootFlag, hipcub::CountingInputIterator<int32_t>> flags(idx, RootFlag{lab1, lab2});
-  size_t tmp = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, flags, scan, (int)np, st));
-  BS_HIP(ctx, B[BD_TMP].reserve(tmp));
-  size_t tb = B[BD_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[BD_TMP].p, tb, flags, scan, (int)np, st));
+  BS_HIP(ctx, cub_run(B[BD_TMP], [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, flags, scan, (int)np, st);
+  }));
   int32_t nb = 0;  // (the last padded pixel lies on the frame: never a start pixel)
   BS_HIP(ctx, hipMemcpyAsync(&nb, scan + np - 1, 4, hipMemcpyDeviceToHost, st));
   BS_HIP(ctx, hipEventRecord(ev.e[3], st));
@@ -768,14 +766,13 @@ extern "C" int bs_plane_buildings_dev(bs_ctx* ctx, const int32_t* d_plane_idx, c
     uint64_t* run_key = B[BD_RUNS].as<uint64_t>();
     int32_t* run_len = reinterpret_cast<int32_t*>(run_key + n);
     vote_keys_kernel<<<nblk(n, 256), 256, 0, st>>>(d_plane_idx, d_building_idx, n, npl, nb, none, keys, d_bad);
-    size_t t1 = 0, t2 = 0;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, t1, keys, sorted, (int)n, 0, bits, st));
-    BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, sorted, run_key, run_len, d_nruns, (int)n, st));
-    BS_HIP(ctx, B[BD_TMP].reserve(std::max(t1, t2)));
-    size_t tb = B[BD_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(B[BD_TMP].p, tb, keys, sorted, (int)n, 0, bits, st));
-    tb = B[BD_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(B[BD_TMP].p, tb, sorted, run_key, run_len, d_nruns, (int)n, st));
+    auto sort = [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, keys, sorted, (int)n, 0, bits, st); };
+    auto runs = [&](void* tmp, size_t& bytes) {
+      return hipcub::DeviceRunLengthEncode::Encode(tmp, bytes, sorted, run_key, run_len, d_nruns, (int)n, st);
+    };
+    BS_HIP(ctx, cub_room(B[BD_TMP], sort, runs));
+    BS_HIP(ctx, cub_run(B[BD_TMP], sort));
+    BS_HIP(ctx, cub_run(B[BD_TMP], runs));
     vote_runs_kernel<<<nblk(n, 256), 256, 0, st>>>(run_key, run_len, d_nruns, none, nb, v);
   }
   std::vector<unsigned long long> hv(3 * (size_t)npl);

@@ -684,13 +684,11 @@ int footprints_tiles_dev(bs_ctx* ctx, const double* d_image, const int32_t* widt
   cc_union_tiled_kernel<<<nblk(np, 256), 256, 0, st>>>(m, d_tl, d_pb, nt, np, parent);
   cc_flatten_kernel<<<nblk(np, 256), 256, 0, st>>>(parent, np);
   flags_tiled_kernel<<<nblk(np, 256), 256, 0, st>>>(m, parent, d_tl, d_pb, nt, np, bflag, rflag, d_fg);
-  size_t tmp = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, bflag, bscan, (int)np, st));
-  BS_HIP(ctx, B[8].reserve(tmp));
-  size_t tb = B[8].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[8].p, tb, bflag, bscan, (int)np, st));
-  tb = B[8].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[8].p, tb, rflag, rscan, (int)np, st));
+  auto scan = [&](auto* count, auto* sum, int64_t n) {
+    return [=](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, count, sum, (int)n, st); };
+  };
+  BS_HIP(ctx, cub_run(B[8], scan(bflag, bscan, np)));
+  BS_HIP(ctx, cub_run(B[8], scan(rflag, rscan, np)));
   rbase_kernel<<<nblk(nt + 1, 256), 256, 0, st>>>(rflag, rscan, d_pb, nt, np, d_rb);
   std::vector<int32_t> h_rb(nt + 1);
   int32_t h_tail[2] = {0, 0};
@@ -749,11 +747,7 @@ int footprints_tiles_dev(bs_ctx* ctx, const double* d_image, const int32_t* widt
     BS_HIP(ctx, hipMemsetAsync(cnt, 0, 8 * (2 * n1 + 5 * (int64_t)nc), st));
     contour_count_tiled_kernel<<<nblk(nc, 256), 256, 0, st>>>(m, d_tl, d_pb, nt, d_rb, rpix, nc, bscan, succ, kind,
                                                                nxt[cur], val[cur], last[cur], cnt, cstart, d_err);
-    tmp = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, cnt, off, (int)n1, st));
-    BS_HIP(ctx, B[8].reserve(tmp));
-    tb = B[8].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[8].p, tb, cnt, off, (int)n1, st));
+    BS_HIP(ctx, cub_run(B[8], scan(cnt, off, n1)));
     int h_err = 0;
     BS_HIP(ctx, hipMemcpyAsync(&total, off + nc, 8, hipMemcpyDeviceToHost, st));
     BS_HIP(ctx, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));

@@ -120,7 +120,6 @@ extern "C" int bs_roof_facets_dev(bs_ctx* ctx, const int32_t* d_map, const int32
     BS_HIP(ctx, hipEventCreate(&e));
 
   hipcub::CountingInputIterator<int32_t> idx(0);
-  size_t t1 = 0, t2 = 0;
   BS_HIP(ctx, B[FC_PARENT].reserve(4 * (size_t)npix));
   BS_HIP(ctx, B[FC_SCAN].reserve(4 * (size_t)npix));
   BS_HIP(ctx, B[FC_FLAGS].reserve((size_t)npix));
@@ -130,9 +129,11 @@ extern "C" int bs_roof_facets_dev(bs_ctx* ctx, const int32_t* d_map, const int32
   uint8_t* flags = B[FC_FLAGS].as<uint8_t>();
   int* d_bad = B[FC_MISC].as<int>();
   hipcub::TransformInputIterator<int32_t, RootFlag, hipcub::CountingInputIterator<int32_t>> roots(idx, RootFlag{parent});
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t1, roots, scan, (int)npix, st));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, FlagIt(flags, FlagCount()), scan, (int)npix, st));
-  BS_HIP(ctx, B[FC_TMP].reserve(std::max<size_t>(std::max(t1, t2), 256)));
+  auto number = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, roots, scan, (int)npix, st); };
+  auto offsets = [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, FlagIt(flags, FlagCount()), scan, (int)npix, st);
+  };
+  BS_HIP(ctx, cub_room(B[FC_TMP], number, offsets));
 
   // ---- label (into the context: nothing of the caller's is written before the checks have passed) ----
   BS_HIP(ctx, hipMemsetAsync(d_bad, 0, 4, st));
@@ -146,8 +147,7 @@ extern "C" int bs_roof_facets_dev(bs_ctx* ctx, const int32_t* d_map, const int32
   facet_flatten_kernel<<<nblk(npix, 256), 256, 0, st>>>(parent, npix);
   BS_HIP(ctx, hipEventRecord(ev.e[1], st));
   // ---- number ----
-  size_t tb = B[FC_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[FC_TMP].p, tb, roots, scan, (int)npix, st));
+  BS_HIP(ctx, cub_run(B[FC_TMP], number));
   BS_HIP(ctx, hipEventRecord(ev.e[2], st));
   int h_bad = 0;
   int32_t last_rank = 0, last_parent = -1;
@@ -177,8 +177,7 @@ extern "C" int bs_roof_facets_dev(bs_ctx* ctx, const int32_t* d_map, const int32
   facet_figures_kernel<<<grid_of(npix), 256, 0, st>>>(d_map, d_roof, top, parent, d_facet, w, h, flags, F);
   BS_HIP(ctx, hipEventRecord(ev.e[5], st));
   // ---- edges: at most 2 * width * height < 2^31 border edges (the check on the image), so every sum below fits 32 bits ----
-  tb = B[FC_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[FC_TMP].p, tb, FlagIt(flags, FlagCount()), scan, (int)npix, st));
+  BS_HIP(ctx, cub_run(B[FC_TMP], offsets));
   BS_HIP(ctx, hipEventRecord(ev.e[6], st));
   int32_t last_off = 0;
   uint8_t last_flag = 0;
@@ -216,16 +215,15 @@ extern "C" int bs_roof_facets_dev(bs_ctx* ctx, const int32_t* d_map, const int32
     int32_t* svals = B[FC_VALS2].as<int32_t>();
     int32_t* eid = B[FC_EID].as<int32_t>();
     hipcub::TransformInputIterator<int32_t, HeadFlag, hipcub::CountingInputIterator<int32_t>> heads(idx, HeadFlag{sorted});
-    size_t t3 = 0, t4 = 0;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t3, keys, sorted, vals, svals, nbi, 0, end_bit, st));
-    BS_HIP(ctx, hipcub::DeviceScan::InclusiveSum(nullptr, t4, heads, eid, nbi, st));
-    BS_HIP(ctx, B[FC_TMP].reserve(std::max(t3, t4)));
+    auto sort = [&](void* tmp, size_t& bytes) {
+      return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, sorted, vals, svals, nbi, 0, end_bit, st);
+    };
+    auto ids = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::InclusiveSum(tmp, bytes, heads, eid, nbi, st); };
+    BS_HIP(ctx, cub_room(B[FC_TMP], sort, ids));
     BS_HIP(ctx, hipEventRecord(ev.e[7], st));
     edge_emit_kernel<<<grid_of(npix), 256, 0, st>>>(flags, scan, d_facet, w, npix, keys, vals);
-    tb = B[FC_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(B[FC_TMP].p, tb, keys, sorted, vals, svals, nbi, 0, end_bit, st));
-    tb = B[FC_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::InclusiveSum(B[FC_TMP].p, tb, heads, eid, nbi, st));
+    BS_HIP(ctx, cub_run(B[FC_TMP], sort));
+    BS_HIP(ctx, cub_run(B[FC_TMP], ids));
     BS_HIP(ctx, hipEventRecord(ev.e[8], st));
     int32_t h_ne = 0;
     BS_HIP(ctx, hipMemcpyAsync(&h_ne, eid + nbord - 1, 4, hipMemcpyDeviceToHost, st));

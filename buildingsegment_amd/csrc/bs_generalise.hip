@@ -314,6 +314,21 @@ struct Job {  // one call
   double ms_tops = 0, ms_facets = 0, ms_decide = 0;
 };
 
+// the two scans over the pixels that every evaluation runs; generalise_dev sizes their slot ahead, before the arrays exist
+// (the rounds are launch-bound: every run here takes the slot as it was sized, cub_run_sized -- DESIGN.md)
+auto number_scan(const int32_t* parent, int32_t* scan, int64_t npix, hipStream_t st)
+{
+  hipcub::TransformInputIterator<int32_t, RootFlag, hipcub::CountingInputIterator<int32_t>> roots(
+      hipcub::CountingInputIterator<int32_t>(0), RootFlag{parent});
+  return [=](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, roots, scan, (int)npix, st); };
+}
+auto border_scan(const uint8_t* flags, int32_t* scan, int64_t npix, hipStream_t st)
+{
+  return [=](void* tmp, size_t& bytes) {
+    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, FlagIt(flags, FlagCount()), scan, (int)npix, st);
+  };
+}
+
 // One evaluation of the image in GN_ROOF: tops into `top`, facets and edges, the decision.  It leaves the facet image in
 // GN_FACET and the new plane of every facet in GN_NEWP for the apply.
 int evaluate(Job& J, int4* top, Eval* out)
@@ -334,7 +349,6 @@ int evaluate(Job& J, int4* top, Eval* out)
   int* d_bad = reinterpret_cast<int*>(counters + CN_BAD);
   Events<8>& ev = J.ev;
   hipcub::CountingInputIterator<int32_t> idx(0);
-  hipcub::TransformInputIterator<int32_t, RootFlag, hipcub::CountingInputIterator<int32_t>> roots(idx, RootFlag{parent});
 
   BS_HIP(ctx, hipMemsetAsync(counters, 0, 8 * CN_ROOFED, st));  // (CN_ROOFED belongs to the figures pass)
   if (J.nb > 0)
@@ -353,8 +367,7 @@ int evaluate(Job& J, int4* top, Eval* out)
       facet_seam_kernel<<<nblk(total, 256), 256, 0, st>>>(cls, w, h, n_h, total, parent);
   }
   facet_flatten_kernel<<<nblk(npix, 256), 256, 0, st>>>(parent, npix);
-  size_t tb = B[GN_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[GN_TMP].p, tb, roots, scan, (int)npix, st));
+  BS_HIP(ctx, cub_run_sized(B[GN_TMP], number_scan(parent, scan, npix, st)));
   int h_bad = 0;
   int32_t last_rank = 0, last_parent = -1;
   BS_HIP(ctx, hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, st));
@@ -383,8 +396,7 @@ int evaluate(Job& J, int4* top, Eval* out)
   facet_fig_init_kernel<<<nblk(nf, 256), 256, 0, st>>>(F, nf);
   facet_write_kernel<<<nblk(npix, 256), 256, 0, st>>>(parent, scan, npix, facet);
   facet_figures_kernel<<<grid_of(npix), 256, 0, st>>>(cmap, roof, top, parent, facet, w, h, flags, F);
-  tb = B[GN_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[GN_TMP].p, tb, FlagIt(flags, FlagCount()), scan, (int)npix, st));
+  BS_HIP(ctx, cub_run_sized(B[GN_TMP], border_scan(flags, scan, npix, st)));
   int32_t last_off = 0;
   uint8_t last_flag = 0;
   BS_HIP(ctx, hipMemcpyAsync(&last_off, scan + npix - 1, 4, hipMemcpyDeviceToHost, st));
@@ -409,15 +421,14 @@ int evaluate(Job& J, int4* top, Eval* out)
     int32_t* svals = B[GN_VALS2].as<int32_t>();
     int32_t* eid = B[GN_EID].as<int32_t>();
     hipcub::TransformInputIterator<int32_t, HeadFlag, hipcub::CountingInputIterator<int32_t>> heads(idx, HeadFlag{sorted});
-    size_t t3 = 0, t4 = 0;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t3, keys, sorted, vals, svals, nbi, 0, end_bit, st));
-    BS_HIP(ctx, hipcub::DeviceScan::InclusiveSum(nullptr, t4, heads, eid, nbi, st));
-    BS_HIP(ctx, B[GN_TMP].reserve(std::max(t3, t4)));
+    auto sort = [&](void* tmp, size_t& bytes) {
+      return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, sorted, vals, svals, nbi, 0, end_bit, st);
+    };
+    auto ids = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::InclusiveSum(tmp, bytes, heads, eid, nbi, st); };
+    BS_HIP(ctx, cub_room(B[GN_TMP], sort, ids));
     edge_emit_kernel<<<grid_of(npix), 256, 0, st>>>(flags, scan, facet, w, npix, keys, vals);
-    tb = B[GN_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(B[GN_TMP].p, tb, keys, sorted, vals, svals, nbi, 0, end_bit, st));
-    tb = B[GN_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::InclusiveSum(B[GN_TMP].p, tb, heads, eid, nbi, st));
+    BS_HIP(ctx, cub_run_sized(B[GN_TMP], sort));
+    BS_HIP(ctx, cub_run_sized(B[GN_TMP], ids));
     int32_t h_ne = 0;
     BS_HIP(ctx, hipMemcpyAsync(&h_ne, eid + nbord - 1, 4, hipMemcpyDeviceToHost, st));
     BS_HIP(ctx, hipStreamSynchronize(st));
@@ -448,12 +459,10 @@ int evaluate(Job& J, int4* top, Eval* out)
   int32_t* next2 = B[GN_NEXT2].as<int32_t>();
   int32_t* dist = B[GN_DIST].as<int32_t>();
   int32_t* dist2 = B[GN_DIST2].as<int32_t>();
-  size_t t5 = 0;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, t5, rkey, rsorted, (int)nf, 0, 63, st));
-  BS_HIP(ctx, B[GN_TMP].reserve(t5));
+  auto rank = [&](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, rkey, rsorted, (int)nf, 0, 63, st); };
+  BS_HIP(ctx, cub_room(B[GN_TMP], rank));
   rank_key_kernel<<<nblk(nf, 256), 256, 0, st>>>(F.pixels, nf, rkey);
-  tb = B[GN_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(B[GN_TMP].p, tb, rkey, rsorted, (int)nf, 0, 63, st));
+  BS_HIP(ctx, cub_run_sized(B[GN_TMP], rank));
   order_kernel<<<nblk(nf, 256), 256, 0, st>>>(rsorted, nf, order, best);
   if (ne > 0)
     candidates_kernel<<<grid_of(ne), 256, 0, st>>>(E, ne, F.pixels, F.plane, order, J.rule, best, counters);
@@ -563,8 +572,6 @@ extern "C" int bs_roof_generalise_dev(bs_ctx* ctx, const int32_t* d_map, const i
   for (auto& e : J.ev.e)
     BS_HIP(ctx, hipEventCreate(&e));
 
-  hipcub::CountingInputIterator<int32_t> idx(0);
-  size_t t1 = 0, t2 = 0;
   BS_HIP(ctx, B[GN_ROOF].reserve(4 * (size_t)npix));
   BS_HIP(ctx, B[GN_CMAP].reserve(4 * (size_t)npix));
   BS_HIP(ctx, B[GN_TOP0].reserve(16 * (size_t)npix));
@@ -577,12 +584,7 @@ extern "C" int bs_roof_generalise_dev(bs_ctx* ctx, const int32_t* d_map, const i
   BS_HIP(ctx, B[GN_TAB].reserve(44 * mp + 4 * mb));
   BS_HIP(ctx, B[GN_BFAC].reserve(8 * mb));
   BS_HIP(ctx, B[GN_FIG].reserve(24 * mb + 16 * (mp + 1)));
-  {
-    hipcub::TransformInputIterator<int32_t, RootFlag, hipcub::CountingInputIterator<int32_t>> roots(idx, RootFlag{nullptr});
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t1, roots, (int32_t*)nullptr, (int)npix, st));
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, FlagIt(nullptr, FlagCount()), (int32_t*)nullptr, (int)npix, st));
-  }
-  BS_HIP(ctx, B[GN_TMP].reserve(std::max<size_t>(std::max(t1, t2), 256)));
+  BS_HIP(ctx, cub_room(B[GN_TMP], number_scan(nullptr, nullptr, npix, st), border_scan(nullptr, nullptr, npix, st)));
   double* tab_normal = B[GN_TAB].as<double>();
   int32_t* tab_center = reinterpret_cast<int32_t*>(tab_normal + 3 * mp);
   int32_t* tab_zmin = tab_center + 3 * mp;

@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "bs_common.h"
+#include "bs_host.h"
 
 namespace bs {
 
@@ -164,9 +165,6 @@ inline int grid_blocks(int64_t n, int bs) { return (int)((n + bs - 1) / bs); }
 
 }  // namespace
 
-// Occupied-cell count at a trial cell size (keys only, or pairs: see sort_count_keys).  (Counting by insertion into an open-addressing table instead
-// of sorting was measured: the points arrive in the caller's order, 50 M random probes into a 1 GB table take 4.5 ms
-// against 2.7 ms for the radix sort -- grid stage 19.7 instead of 11.0 ms.)
 // Bits a Morton cell key occupies when the longest axis has ext / cell + 1 cells: the radix sorts run over these only
 // (33 instead of 63 bits at 50 M points: 5 instead of 8 passes).
 static int morton_key_bits(int64_t ext, int cell)
@@ -177,43 +175,54 @@ static int morton_key_bits(int64_t ext, int cell)
   return std::min(63, 3 * bits);
 }
 
-// sort the keys in keys_in over [0, end_bit) and count the distinct ones (synchronises).  pairs: vals_in goes along
-// into vals_out, which is then what step 3 of build_grid would produce at this cell size (the same keys, the same
-// stable sort) -- an accepted trial is the grid's sort.
-static int sort_count_keys(bs_ctx* ctx, int64_t n, int end_bit, int64_t* ncell, bool pairs)
+// room for the keys and values of n points, before and behind the sort, and for the few words every pass reads back
+static int order_room(bs_ctx* ctx, int64_t n)
+{
+  BS_HIP(ctx, ctx->misc.reserve(256));
+  BS_HIP(ctx, ctx->keys_in.reserve(sizeof(uint64_t) * n));
+  BS_HIP(ctx, ctx->keys_out.reserve(sizeof(uint64_t) * n));
+  BS_HIP(ctx, ctx->vals_in.reserve(sizeof(int32_t) * n));
+  BS_HIP(ctx, ctx->vals_out.reserve(sizeof(int32_t) * n));
+  return BS_OK;
+}
+
+// stable radix sort of keys_in over [0, end_bit) into keys_out; pairs: vals_in goes along into vals_out
+static int sort_cells(bs_ctx* ctx, int64_t n, int end_bit, bool pairs)
 {
   hipStream_t st = ctx->stream;
   uint64_t* kin = ctx->keys_in.as<uint64_t>();
   uint64_t* kout = ctx->keys_out.as<uint64_t>();
   int32_t* vin = ctx->vals_in.as<int32_t>();
   int32_t* vout = ctx->vals_out.as<int32_t>();
-  size_t tb = 0;
-  if (pairs) {
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
-    BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
-  } else {
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, kin, kout, (int)n, 0, end_bit, st));
-    BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(ctx->cub_tmp.p, tb, kin, kout, (int)n, 0, end_bit, st));
-  }
+  if (pairs)
+    BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+      return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, kin, kout, vin, vout, (int)n, 0, end_bit, st);
+    }));
+  else
+    BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+      return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, kin, kout, (int)n, 0, end_bit, st);
+    }));
+  return BS_OK;
+}
+
+// Occupied-cell count at a trial cell size: sort the keys in keys_in over [0, end_bit) and count the distinct ones
+// (synchronises).  pairs: vals_out is then what step 3 of a builder would produce at this cell size (the same keys, the
+// same stable sort) -- an accepted trial is the grid's sort.  (Counting by insertion into an open-addressing table
+// instead of sorting was measured: the points arrive in the caller's order, 50 M random probes into a 1 GB table take
+// 4.5 ms against 2.7 ms for the radix sort -- grid stage 19.7 instead of 11.0 ms.)
+static int sort_count_keys(bs_ctx* ctx, int64_t n, int end_bit, int64_t* ncell, bool pairs)
+{
+  hipStream_t st = ctx->stream;
+  if (int rc = sort_cells(ctx, n, end_bit, pairs))
+    return rc;
   unsigned long long* cnt = ctx->misc.as<unsigned long long>() + 8;
   BS_HIP(ctx, hipMemsetAsync(cnt, 0, sizeof(unsigned long long), st));
-  count_heads_kernel<<<std::min(grid_blocks(n, 256), 1024), 256, 0, st>>>(kout, n, cnt);
+  count_heads_kernel<<<std::min(grid_blocks(n, 256), 1024), 256, 0, st>>>(ctx->keys_out.as<uint64_t>(), n, cnt);
   unsigned long long h = 0;
   BS_HIP(ctx, hipMemcpyAsync(&h, cnt, sizeof h, hipMemcpyDeviceToHost, st));
   BS_HIP(ctx, hipStreamSynchronize(st));
   *ncell = (int64_t)h;
   return BS_OK;
-}
-
-static int count_cells(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, const int mn[3], int cell, int64_t ext,
-                       int64_t* ncell, bool pairs)
-{
-  cellkey_kernel<<<grid_blocks(n, 256), 256, 0, ctx->stream>>>(d_xyz, n, mn[0], mn[1], mn[2], cell, 1,
-                                                               ctx->keys_in.as<uint64_t>(),
-                                                               pairs ? ctx->vals_in.as<int32_t>() : nullptr);
-  return sort_count_keys(ctx, n, morton_key_bits(ext, cell), ncell, pairs);
 }
 
 // BS_GRID_REUSE=0 (read in every call): no trial sorts pairs, step 3 always sorts again
@@ -223,58 +232,29 @@ static bool grid_reuse_on()
   return !e || atoi(e) != 0;
 }
 
-int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t n, double radius,
-               int k, int cell_hint, GridDev* out)
+// Step 2 of a builder, the cell size: >= radius so one ring certifies the hybrid search, and a density-driven size
+// giving ~max(4, k/2) points per occupied cell (a hint is taken as it is).  write_keys(cell, values) launches the key
+// kernel of the builder at a trial size, with the values where asked, and returns the bits its keys occupy; a trial
+// runs only where fits(cell).  The first trial is usually rejected and sorts keys only.  With reuse every later trial
+// writes the values and sorts pairs: if its cell size is the one the rule ends on, its output IS step 3's (Morton keys,
+// the same stable sort) and step 3 is skipped.  sorted_cell: the cell size whose sorted pairs are in keys_out /
+// vals_out, 0 = none.
+template <class WriteKeys, class Fits>
+static int trial_cell(bs_ctx* ctx, int64_t n, int64_t ext, double radius, int k, int cell_hint, bool reuse, WriteKeys&& write_keys,
+                      Fits&& fits, int* cell_out, int* sorted_cell)
 {
-  hipStream_t st = ctx->stream;
-  if (n <= 0 || n >= (int64_t)INT_MAX - 64)
-    return fail(ctx, BS_ERR_INVALID, "point count out of range");
-  BS_HIP(ctx, ctx->misc.reserve(256));
-  BS_HIP(ctx, ctx->keys_in.reserve(sizeof(uint64_t) * n));
-  BS_HIP(ctx, ctx->keys_out.reserve(sizeof(uint64_t) * n));
-  BS_HIP(ctx, ctx->vals_in.reserve(sizeof(int32_t) * n));
-  BS_HIP(ctx, ctx->vals_out.reserve(sizeof(int32_t) * n));
-
-  // 1. bounding box
-  int32_t init[6] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN};
-  int32_t* d_mnmx = ctx->misc.as<int32_t>();
-  BS_HIP(ctx, hipMemcpyAsync(d_mnmx, init, sizeof init, hipMemcpyHostToDevice, st));
-  bbox_kernel<<<std::min(grid_blocks(n, 256), 512), 256, 0, st>>>(d_xyz, n, d_mnmx);
-  int32_t bb[6];
-  BS_HIP(ctx, hipMemcpyAsync(bb, d_mnmx, sizeof bb, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
-  // exact-arithmetic domain: moment sums stay below 2^53, d^2 keys below 2^64
-  const int32_t LIM = 1 << 23;
-  for (int a = 0; a < 3; a++)
-    if (bb[a] <= -LIM || bb[3 + a] >= LIM)
-      return fail(ctx, BS_ERR_RANGE, "coordinates must satisfy |c| < 2^23 mm (8.4 km): shift the cloud to its bounding-box origin first "
-                                     "(bs_shift_to_origin_dev, or the buildingSeg constructor as TMC3.cpp:210 does)");
-
-  // 2. cell size: >= radius so one ring certifies the hybrid search, and a
-  // density-driven size giving ~max(4, k/2) points per occupied cell
-  int64_t ext = 1;
-  for (int a = 0; a < 3; a++)
-    ext = std::max<int64_t>(ext, (int64_t)bb[3 + a] - bb[a] + 1);
-  static const int morton = []() {
-    const char* e = getenv("BS_GRID_ORDER");  // developer A/B switch: "raster" restores the x-fastest cell order
-    return (e && e[0] == 'r') ? 0 : 1;
-  }();
-  // The first trial is usually rejected and sorts keys only.  Every later trial writes the values and sorts pairs: if
-  // its cell size is the one the rule ends on, its output IS step 3's (Morton keys, the same stable sort) and step 3
-  // is skipped.  sorted_cell: the cell size whose sorted pairs are in keys_out / vals_out, 0 = none.
-  const bool reuse = morton && grid_reuse_on();
-  int sorted_cell = 0;
   int cell = cell_hint > 0 ? cell_hint : (int)std::max(1.0, std::ceil(radius));
+  *sorted_cell = 0;
   if (cell_hint <= 0) {
     const double target = std::max(4.0, 0.5 * k);
     const int cmin = cell;
-    for (int it = 0; it < 4; it++) {
+    for (int it = 0; it < 4 && fits(cell); it++) {
       int64_t nc = 0;
       const bool pairs = reuse && it >= 1;
-      int rc = count_cells(ctx, d_xyz, n, bb, cell, ext, &nc, pairs);
-      if (rc != BS_OK)
+      const int end_bit = write_keys(cell, pairs);
+      if (int rc = sort_count_keys(ctx, n, end_bit, &nc, pairs))
         return rc;
-      sorted_cell = pairs ? cell : 0;
+      *sorted_cell = pairs ? cell : 0;
       double occ = (double)n / (double)std::max<int64_t>(nc, 1);
       if (occ >= 0.7 * target && occ <= 1.6 * target)
         break;
@@ -287,22 +267,23 @@ int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t
       cell = ncell;
     }
   }
-  while (ext / cell + 1 >= (1 << 21))
-    cell *= 2;
+  *cell_out = cell;
+  return BS_OK;
+}
 
-  // 3. keys + sort (unless the last trial did both at this cell size)
-  uint64_t* kin = ctx->keys_in.as<uint64_t>();
+// Steps 3 to 6 of a builder over the keys and values in keys_in / vals_in, and the fields of the result that do not
+// depend on the boxes.  sorted: the last trial has sorted them at this cell size already.  morton: how the table stores
+// a key (table_insert_kernel).  d_gidx: the global index of every point, or null for its position.
+static int finish_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t n, int end_bit, bool sorted, int morton,
+                       int cell, GridDev* out)
+{
+  hipStream_t st = ctx->stream;
   uint64_t* kout = ctx->keys_out.as<uint64_t>();
-  int32_t* vin = ctx->vals_in.as<int32_t>();
   int32_t* vout = ctx->vals_out.as<int32_t>();
-  size_t tb = 0;
-  if (sorted_cell != cell) {
-    cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, bb[0], bb[1], bb[2], cell, morton, kin, vin);
-    const int end_bit = morton ? morton_key_bits(ext, cell) : 63;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
-    BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
-  }
+  // 3. sort (unless the last trial did at this cell size)
+  if (!sorted)
+    if (int rc = sort_cells(ctx, n, end_bit, true))
+      return rc;
 
   // 4. unique cells (run-length encode), starts (exclusive scan)
   BS_HIP(ctx, ctx->uniq_keys.reserve(sizeof(uint64_t) * n));
@@ -311,19 +292,17 @@ int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t
   int32_t* ucnt = ctx->uniq_cnt.as<int32_t>();
   int32_t* ustart = ucnt + n;
   int32_t* d_nruns = ctx->misc.as<int32_t>() + 32;
-  tb = 0;
-  BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(nullptr, tb, kout, ukeys, ucnt, d_nruns, (int)n, st));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(ctx->cub_tmp.p, tb, kout, ukeys, ucnt, d_nruns, (int)n, st));
+  BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceRunLengthEncode::Encode(tmp, bytes, kout, ukeys, ucnt, d_nruns, (int)n, st);
+  }));
   int32_t nruns = 0;
   BS_HIP(ctx, hipMemcpyAsync(&nruns, d_nruns, sizeof nruns, hipMemcpyDeviceToHost, st));
   BS_HIP(ctx, hipStreamSynchronize(st));
   if (nruns <= 0)
     return fail(ctx, BS_ERR_INTERNAL, "grid: no occupied cells");
-  tb = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ucnt, ustart, nruns, st));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(ctx->cub_tmp.p, tb, ucnt, ustart, nruns, st));
+  BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, ucnt, ustart, nruns, st);
+  }));
 
   // 5. hash table
   uint32_t hs = 64;
@@ -339,18 +318,13 @@ int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t
   gather_sorted_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, d_gidx, vout, n, ctx->spts.as<int4>());
   BS_HIP(ctx, hipGetLastError());
 
-  out->mn[0] = bb[0];
-  out->mn[1] = bb[1];
-  out->mn[2] = bb[2];
-  for (int a = 0; a < 3; a++)
-    out->dim[a] = (int32_t)(((int64_t)bb[3 + a] - bb[a]) / cell + 1);
   out->cell = cell;
   out->hmask = hs - 1;
   out->table = table;
   out->spts = ctx->spts.as<int4>();
   out->slocal = vout;
   out->n = n;
-  ctx->order_n = n;  // vals_out holds the cell-sorted order of this cloud
+  ctx->order_n = n;  // vals_out holds the cell-sorted order of this cloud (of the concatenation, for a batch)
   ctx->order_xyz = d_xyz;
   return BS_OK;
 }
@@ -370,6 +344,57 @@ int bbox_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bb[6])
   return BS_OK;
 }
 
+int build_grid(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_gidx, int64_t n, double radius,
+               int k, int cell_hint, GridDev* out)
+{
+  if (n <= 0 || n >= (int64_t)INT_MAX - 64)
+    return fail(ctx, BS_ERR_INVALID, "point count out of range");
+  if (int rc = order_room(ctx, n))
+    return rc;
+
+  // 1. bounding box
+  int32_t bb[6];
+  if (int rc = bbox_dev(ctx, d_xyz, n, bb))
+    return rc;
+  // exact-arithmetic domain: moment sums stay below 2^53, d^2 keys below 2^64
+  const int32_t LIM = 1 << 23;
+  for (int a = 0; a < 3; a++)
+    if (bb[a] <= -LIM || bb[3 + a] >= LIM)
+      return fail(ctx, BS_ERR_RANGE, "coordinates must satisfy |c| < 2^23 mm (8.4 km): shift the cloud to its bounding-box origin first "
+                                     "(bs_shift_to_origin_dev, or the buildingSeg constructor as TMC3.cpp:210 does)");
+
+  // 2. cell size (every trial counts Morton cells; a single cloud's key bits are clamped, so every trial fits)
+  int64_t ext = 1;
+  for (int a = 0; a < 3; a++)
+    ext = std::max<int64_t>(ext, (int64_t)bb[3 + a] - bb[a] + 1);
+  static const int morton = []() {
+    const char* e = getenv("BS_GRID_ORDER");  // developer A/B switch: "raster" restores the x-fastest cell order
+    return (e && e[0] == 'r') ? 0 : 1;
+  }();
+  auto write_keys = [&](int c, int order, bool values) {
+    cellkey_kernel<<<grid_blocks(n, 256), 256, 0, ctx->stream>>>(d_xyz, n, bb[0], bb[1], bb[2], c, order, ctx->keys_in.as<uint64_t>(),
+                                                                 values ? ctx->vals_in.as<int32_t>() : nullptr);
+    return order ? morton_key_bits(ext, c) : 63;
+  };
+  int cell = 0, sorted_cell = 0;
+  if (int rc = trial_cell(ctx, n, ext, radius, k, cell_hint, morton && grid_reuse_on(),
+                          [&](int c, bool values) { return write_keys(c, 1, values); }, [](int) { return true; }, &cell, &sorted_cell))
+    return rc;
+  while (ext / cell + 1 >= (1 << 21))
+    cell *= 2;
+
+  // 3 to 6. keys (unless the last trial wrote and sorted them at this cell size), sort, cells, table, sorted copy
+  const bool sorted = sorted_cell == cell;
+  const int end_bit = sorted ? 0 : write_keys(cell, morton, true);
+  if (int rc = finish_grid(ctx, d_xyz, d_gidx, n, end_bit, sorted, morton, cell, out))
+    return rc;
+  for (int a = 0; a < 3; a++) {
+    out->mn[a] = bb[a];
+    out->dim[a] = (int32_t)(((int64_t)bb[3 + a] - bb[a]) / cell + 1);
+  }
+  return BS_OK;
+}
+
 // Spatial (Morton) order of a cloud WITHOUT a search grid: what the region grower needs when it is handed
 // foreign buffers (bs_region_grow[_dev], the component-sharded stage 3) -- its records, masks, reverse lists and
 // owner passes address points by their position in a spatially coherent order (bs_grow_spec.hip, "Index
@@ -378,21 +403,13 @@ int bbox_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bb[6])
 // domain here: only an order is produced).  Result: ctx->vals_out = original index of every position.
 int build_spatial_order(bs_ctx* ctx, const int32_t* d_xyz, int64_t n)
 {
-  hipStream_t st = ctx->stream;
   if (n <= 0 || n >= (int64_t)INT_MAX - 64)
     return fail(ctx, BS_ERR_INVALID, "point count out of range");
-  BS_HIP(ctx, ctx->misc.reserve(256));
-  BS_HIP(ctx, ctx->keys_in.reserve(sizeof(uint64_t) * n));
-  BS_HIP(ctx, ctx->keys_out.reserve(sizeof(uint64_t) * n));
-  BS_HIP(ctx, ctx->vals_in.reserve(sizeof(int32_t) * n));
-  BS_HIP(ctx, ctx->vals_out.reserve(sizeof(int32_t) * n));
-  int32_t init[6] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN};
-  int32_t* d_mnmx = ctx->misc.as<int32_t>();
-  BS_HIP(ctx, hipMemcpyAsync(d_mnmx, init, sizeof init, hipMemcpyHostToDevice, st));
-  bbox_kernel<<<std::min(grid_blocks(n, 256), 512), 256, 0, st>>>(d_xyz, n, d_mnmx);
+  if (int rc = order_room(ctx, n))
+    return rc;
   int32_t bb[6];
-  BS_HIP(ctx, hipMemcpyAsync(bb, d_mnmx, sizeof bb, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
+  if (int rc = bbox_dev(ctx, d_xyz, n, bb))
+    return rc;
   int64_t ext = 1;
   for (int a = 0; a < 3; a++)
     ext = std::max<int64_t>(ext, (int64_t)bb[3 + a] - bb[a] + 1);
@@ -400,19 +417,10 @@ int build_spatial_order(bs_ctx* ctx, const int32_t* d_xyz, int64_t n)
   int64_t cell = 128;
   while (ext / cell + 1 >= (1 << 21))
     cell *= 2;
-  int bits = 1;
-  while (((int64_t)1 << bits) < ext / cell + 1)
-    bits++;
-  uint64_t* kin = ctx->keys_in.as<uint64_t>();
-  uint64_t* kout = ctx->keys_out.as<uint64_t>();
-  int32_t* vin = ctx->vals_in.as<int32_t>();
-  int32_t* vout = ctx->vals_out.as<int32_t>();
-  cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, bb[0], bb[1], bb[2], (int)cell, 1, kin, vin);
-  const int end_bit = std::min(63, 3 * bits);
-  size_t tb = 0;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
+  cellkey_kernel<<<grid_blocks(n, 256), 256, 0, ctx->stream>>>(d_xyz, n, bb[0], bb[1], bb[2], (int)cell, 1, ctx->keys_in.as<uint64_t>(),
+                                                               ctx->vals_in.as<int32_t>());
+  if (int rc = sort_cells(ctx, n, morton_key_bits(ext, (int)cell), true))
+    return rc;
   BS_HIP(ctx, hipGetLastError());
   ctx->order_n = n;
   ctx->order_xyz = d_xyz;
@@ -552,11 +560,8 @@ int build_grid_tiled(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_off, co
   const int64_t n = off[nt];
   if (nt < 1 || n <= 0 || n >= (int64_t)INT_MAX - 64)
     return fail(ctx, BS_ERR_INVALID, "point count out of range");
-  BS_HIP(ctx, ctx->misc.reserve(256));
-  BS_HIP(ctx, ctx->keys_in.reserve(sizeof(uint64_t) * n));
-  BS_HIP(ctx, ctx->keys_out.reserve(sizeof(uint64_t) * n));
-  BS_HIP(ctx, ctx->vals_in.reserve(sizeof(int32_t) * n));
-  BS_HIP(ctx, ctx->vals_out.reserve(sizeof(int32_t) * n));
+  if (int rc = order_room(ctx, n))
+    return rc;
   BS_HIP(ctx, ctx->bt[BT_MNMX].reserve(sizeof(int32_t) * 6 * nt));
   BS_HIP(ctx, ctx->bt[BT_DESC].reserve(sizeof(TileDesc) * nt));
 
@@ -594,105 +599,36 @@ int build_grid_tiled(bs_ctx* ctx, const int32_t* d_xyz, const int32_t* d_off, co
   const TileDesc* d_desc = ctx->bt[BT_DESC].as<TileDesc>();
 
   // 2. cell size (build_grid's rule, counted with the tiled keys; the keys are always Morton keys here)
-  const bool reuse = grid_reuse_on();
-  int sorted_cell = 0;
-  int cell = cell_hint > 0 ? cell_hint : (int)std::max(1.0, std::ceil(radius));
-  if (cell_hint <= 0) {
-    const double target = std::max(4.0, 0.5 * k);
-    const int cmin = cell;
-    for (int it = 0; it < 4 && fits(cell); it++) {
-      const int mb = morton_key_bits(ext, cell);
-      const bool pairs = reuse && it >= 1;  // (as in build_grid)
-      tiled_cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, d_off, nt, d_desc, cell, mb,
-                                                                ctx->keys_in.as<uint64_t>(),
-                                                                pairs ? ctx->vals_in.as<int32_t>() : nullptr);
-      int64_t nc = 0;
-      rc = sort_count_keys(ctx, n, tbits + mb, &nc, pairs);
-      if (rc != BS_OK)
-        return rc;
-      sorted_cell = pairs ? cell : 0;
-      double occ = (double)n / (double)std::max<int64_t>(nc, 1);
-      if (occ >= 0.7 * target && occ <= 1.6 * target)
-        break;
-      double f = std::sqrt(target / occ);
-      f = std::min(4.0, std::max(0.25, f));
-      int ncell = (int)std::floor(cell * f + 0.5);
-      ncell = std::max(ncell, cmin);
-      if (ncell == cell || (int64_t)ncell > ext)
-        break;
-      cell = ncell;
-    }
-  }
+  auto write_keys = [&](int c, bool values) {
+    const int mb = morton_key_bits(ext, c);
+    tiled_cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, d_off, nt, d_desc, c, mb, ctx->keys_in.as<uint64_t>(),
+                                                              values ? ctx->vals_in.as<int32_t>() : nullptr);
+    return tbits + mb;
+  };
+  int cell = 0, sorted_cell = 0;
+  rc = trial_cell(ctx, n, ext, radius, k, cell_hint, grid_reuse_on(), write_keys, fits, &cell, &sorted_cell);
+  if (rc != BS_OK)
+    return rc;
   while (!fits(cell))
     cell *= 2;
   const int mbits = morton_key_bits(ext, cell);
   BS_HIP(ctx, upload_desc(cell));
 
-  // 3. keys + sort: (tile, Morton cell), unless the last trial did both at this cell size
-  uint64_t* kin = ctx->keys_in.as<uint64_t>();
-  uint64_t* kout = ctx->keys_out.as<uint64_t>();
-  int32_t* vin = ctx->vals_in.as<int32_t>();
-  int32_t* vout = ctx->vals_out.as<int32_t>();
-  size_t tb = 0;
-  if (sorted_cell != cell) {
-    tiled_cellkey_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, n, d_off, nt, d_desc, cell, mbits, kin, vin);
-    const int end_bit = tbits + mbits;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
-    BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, st));
-  }
-
-  // 4. unique cells, starts
-  BS_HIP(ctx, ctx->uniq_keys.reserve(sizeof(uint64_t) * n));
-  BS_HIP(ctx, ctx->uniq_cnt.reserve(sizeof(int32_t) * 2 * n));
-  uint64_t* ukeys = ctx->uniq_keys.as<uint64_t>();
-  int32_t* ucnt = ctx->uniq_cnt.as<int32_t>();
-  int32_t* ustart = ucnt + n;
-  int32_t* d_nruns = ctx->misc.as<int32_t>() + 32;
-  tb = 0;
-  BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(nullptr, tb, kout, ukeys, ucnt, d_nruns, (int)n, st));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(ctx->cub_tmp.p, tb, kout, ukeys, ucnt, d_nruns, (int)n, st));
-  int32_t nruns = 0;
-  BS_HIP(ctx, hipMemcpyAsync(&nruns, d_nruns, sizeof nruns, hipMemcpyDeviceToHost, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
-  if (nruns <= 0)
-    return fail(ctx, BS_ERR_INTERNAL, "grid: no occupied cells");
-  tb = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ucnt, ustart, nruns, st));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(ctx->cub_tmp.p, tb, ucnt, ustart, nruns, st));
-
-  // 5. hash table keyed by the sort key itself (morton = 0: stored as it is)
-  uint32_t hs = 64;
-  while (hs < (uint32_t)nruns * 2u)
-    hs <<= 1;
-  BS_HIP(ctx, ctx->table.reserve(sizeof(CellEntry) * (size_t)hs));
-  CellEntry* table = ctx->table.as<CellEntry>();
-  table_clear_kernel<<<(hs + 255) / 256, 256, 0, st>>>(table, hs);
-  table_insert_kernel<<<(nruns + 255) / 256, 256, 0, st>>>(ukeys, ucnt, ustart, nruns, 0, table, hs - 1);
-
-  // 6. cell-sorted point copy (w = concatenation index)
-  BS_HIP(ctx, ctx->spts.reserve(sizeof(int4) * n));
-  gather_sorted_kernel<<<grid_blocks(n, 256), 256, 0, st>>>(d_xyz, nullptr, vout, n, ctx->spts.as<int4>());
-  BS_HIP(ctx, hipGetLastError());
-
+  // 3 to 6. keys (tile, Morton cell) unless the last trial wrote and sorted them at this cell size; the table is keyed
+  // by the sort key itself (morton = 0: stored as it is); the w of a sorted point is its concatenation index
+  const bool sorted = sorted_cell == cell;
+  const int end_bit = sorted ? 0 : write_keys(cell, true);
+  rc = finish_grid(ctx, d_xyz, nullptr, n, end_bit, sorted, 0, cell, out);
+  if (rc != BS_OK)
+    return rc;
   for (int a = 0; a < 3; a++) {
     out->mn[a] = desc[0].mn[a];
     out->dim[a] = desc[0].dim[a];
   }
-  out->cell = cell;
-  out->hmask = hs - 1;
-  out->table = table;
-  out->spts = ctx->spts.as<int4>();
-  out->slocal = vout;
-  out->n = n;
   out->tiles = d_desc;
   out->tile_off = d_off;
   out->n_tiles = nt;
   out->mbits = mbits;
-  ctx->order_n = n;  // vals_out holds the cell-sorted order of the concatenation
-  ctx->order_xyz = d_xyz;
   return BS_OK;
 }
 

@@ -2828,10 +2828,9 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   static_mask_kernel<<<xcd_grid(nblk(n, 256)), 256, 0, st>>>(a, rows, row_stride, gs, hmask, rpos, lmask);
   {
     hipcub::TransformInputIterator<int64_t, ToI64, const int32_t*> in(rpos, ToI64());
-    size_t tb = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveScan(nullptr, tb, in, roff, hipcub::Sum(), (int64_t)0, (int)(n + 1), st));
-    BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveScan(ctx->cub_tmp.p, tb, in, roff, hipcub::Sum(), (int64_t)0, (int)(n + 1), st));
+    BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+      return hipcub::DeviceScan::ExclusiveScan(tmp, bytes, in, roff, hipcub::Sum(), (int64_t)0, (int)(n + 1), st);
+    }));
   }
   unsigned long long* rcur = cand_raw;
   BS_HIP(ctx, hipMemcpyAsync(rcur, roff, sizeof(int64_t) * n, hipMemcpyDeviceToDevice, st));
@@ -3097,10 +3096,9 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
     if (ncand_all == 0 && npend == 0)
       break;  // no plane attempt left: omega is the final owner array
     if (ncand_all > 0) {
-      size_t tb = 0;
-      BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, cand_raw, d_cand, ncand_all, 0, 64, st));
-      BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-      BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(ctx->cub_tmp.p, tb, cand_raw, d_cand, ncand_all, 0, 64, st));
+      BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+        return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, cand_raw, d_cand, ncand_all, 0, 64, st);
+      }));
     }
     const int ncand = std::min<int>(ncand_all, max_waves);
     gc.rounds_capped += ncand_all > max_waves ? 1 : 0;
@@ -3136,10 +3134,9 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
         BS_HIP(ctx, hipMemsetAsync(tmin1, 0xff, sizeof(unsigned long long) * (nt1 + nt2), st));
         tile_min_kernel<<<nblk(ncand, 256), 256, 0, st>>>(d_cand, ncand, tmin1, tmin2);
         dispatch_key_kernel<<<nblk(ncand, 256), 256, 0, st>>>(d_cand, ncand, tmin1, tmin2, dkeys_in);
-        size_t tb = 0;
-        BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, dkeys_in, dkeys_out, ncand, 0, 20, st));
-        BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-        BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(ctx->cub_tmp.p, tb, dkeys_in, dkeys_out, ncand, 0, 20, st));
+        BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+          return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, dkeys_in, dkeys_out, ncand, 0, 20, st);
+        }));
         d_order = dkeys_out;
       }
       (void)hipEventRecord(ctx->ev[6], st);
@@ -3199,10 +3196,9 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
     int nh = ncand;
     PlaneOut* d_outh = d_out;
     if (compact) {
-      size_t tb = 0;
-      BS_HIP(ctx, hipcub::DeviceSelect::If(nullptr, tb, d_out, d_outc, d_misc + 20, ncand, KeepForHost(), st));
-      BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-      BS_HIP(ctx, hipcub::DeviceSelect::If(ctx->cub_tmp.p, tb, d_out, d_outc, d_misc + 20, ncand, KeepForHost(), st));
+      BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+        return hipcub::DeviceSelect::If(tmp, bytes, d_out, d_outc, d_misc + 20, ncand, KeepForHost(), st);
+      }));
       BS_HIP(ctx, hipMemcpyAsync(h_flags + 14, d_misc + 20, sizeof(int32_t), hipMemcpyDeviceToHost, st));
       BS_HIP(ctx, hipStreamSynchronize(st));
       nh = h_flags[14];

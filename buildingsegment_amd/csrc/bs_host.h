@@ -1,6 +1,7 @@
 // bs_host.h -- the small host helpers that every stage file used to define for itself: launch sizes, the events of a call's
-// timings, the zeroed host arrays of a result, the staging of a host entry point through the context's buffers (Staging) and
-// the device mesh of the two solid stages (DevMesh).  Everything is internal to a translation unit.
+// timings, the zeroed host arrays of a result, the temporary storage of a hipCUB call (cub_room, cub_run), the staging of a
+// host entry point through the context's buffers (Staging) and the device mesh of the two solid stages (DevMesh).  Everything
+// is internal to a translation unit.
 #pragma once
 
 #include <algorithm>
@@ -45,6 +46,40 @@ inline int bits_of(int64_t n)  // bits that hold 0 .. n - 1 (at least 1)
   while (b < 32 && (1ll << b) < n)
     b++;
   return b;
+}
+
+// The temporary storage of a hipCUB call.  An operation is written once, as a callable hipError_t op(void* tmp, size_t& bytes)
+// that hands its two parameters to the hipcub::Device... call as the first two arguments.  cub_room sizes a slot ahead for
+// every operation it will hold (where the stage makes room for its other buffers); cub_run asks the operation again, with the
+// arguments it is about to run with, grows a slot that is short (DevBuf::reserve returns at once where it is not) and runs.
+template <class... Ops>
+hipError_t cub_room(DevBuf& tmp, Ops&&... ops)
+{
+  size_t need = 256;
+  hipError_t e = hipSuccess;
+  auto ask = [&](auto&& op) {
+    size_t bytes = 0;
+    hipError_t r = op(nullptr, bytes);
+    need = std::max(need, bytes);
+    if (e == hipSuccess)
+      e = r;
+  };
+  (ask(ops), ...);
+  return e != hipSuccess ? e : tmp.reserve(need);
+}
+
+template <class Op>
+hipError_t cub_run_sized(DevBuf& tmp, Op&& op)  // the slot as cub_room sized it for this very callable: no second question
+{
+  size_t bytes = tmp.cap;
+  return op(tmp.p, bytes);
+}
+
+template <class Op>
+hipError_t cub_run(DevBuf& tmp, Op&& op)
+{
+  hipError_t e = cub_room(tmp, op);
+  return e != hipSuccess ? e : cub_run_sized(tmp, op);
 }
 
 // frees a half-built result through its own bs_..._free unless it is kept

@@ -668,17 +668,17 @@ extern "C" int bs_label_hulls_count_dev(bs_ctx* ctx, const int32_t* d_label, int
   int32_t* cpos = B[HL_CPOS].as<int32_t>();
   const LabelDev L = label_dev_at(B[HL_LABEL].p, nl);
   const FigDev F = fig_dev_at(B[HL_FIG].p, nl);
-  size_t t1 = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t1, CandIt(hlab, IsCandidate()), cpos, n, st));
-  BS_HIP(ctx, B[HL_TMP].reserve(std::max<size_t>(t1, 256)));
+  auto scan_cand = [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, CandIt(hlab, IsCandidate()), cpos, n, st);
+  };
+  BS_HIP(ctx, cub_room(B[HL_TMP], scan_cand));
   BS_HIP(ctx, hipMemsetAsync(d_err, 0, 8, st));
   BS_HIP(ctx, hipMemsetAsync(d_live, 0, 4 * (size_t)LIVE_SLOTS, st));
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
   hull_label_init_kernel<<<nblk(n_labels, 256), 256, 0, st>>>(L, n_labels);
   hull_ring_kernel<<<nblk(nr, 256), 256, 0, st>>>(RO, nr, n_labels, L, d_err);
   hull_flag_kernel<<<nblk(n, 256), 256, 0, st>>>(hnum, flags, leader, slot, RO, L, n, nr, n_labels, npix, hlab, d_err);
-  size_t tb = B[HL_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[HL_TMP].p, tb, CandIt(hlab, IsCandidate()), cpos, n, st));
+  BS_HIP(ctx, cub_run_sized(B[HL_TMP], scan_cand));
   int h_err = 0;
   int32_t last_pos = 0, last_lab = -1;
   BS_HIP(ctx, hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
@@ -761,21 +761,21 @@ extern "C" int bs_label_hulls_count_dev(bs_ctx* ctx, const int32_t* d_label, int
     const int nhb = nblk(nh, 256);
     hipcub::CountingInputIterator<int32_t> idx(0);
     hipcub::TransformInputIterator<int32_t, KeepCount, hipcub::CountingInputIterator<int32_t>> kept(idx, KeepCount{keep, nh});
-    size_t t2 = 0, t3 = 0, t4 = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, HullIt(edge, IsHull()), hpos, nc, st));
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t3, keys, skeys, vals, svals, nh, 0, end_bit, st));
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t4, kept, spos, nh + 1, st));
-    BS_HIP(ctx, B[HL_TMP].reserve(std::max(t2, std::max(t3, t4))));
+    auto scan_hull = [&](void* tmp, size_t& bytes) {
+      return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, HullIt(edge, IsHull()), hpos, nc, st);
+    };
+    auto sort = [&](void* tmp, size_t& bytes) {
+      return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, skeys, vals, svals, nh, 0, end_bit, st);
+    };
+    auto scan_kept = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, kept, spos, nh + 1, st); };
+    BS_HIP(ctx, cub_room(B[HL_TMP], scan_hull, sort, scan_kept));
     BS_HIP(ctx, hipEventRecord(ev.e[3], st));
-    tb = B[HL_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[HL_TMP].p, tb, HullIt(edge, IsHull()), hpos, nc, st));
+    BS_HIP(ctx, cub_run_sized(B[HL_TMP], scan_hull));
     hull_keys_kernel<<<ncb, 256, 0, st>>>(edge, hpos, cxy, clab, chain, nc, nh, keys, vals, d_err);
-    tb = B[HL_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(B[HL_TMP].p, tb, keys, skeys, vals, svals, nh, 0, end_bit, st));
+    BS_HIP(ctx, cub_run_sized(B[HL_TMP], sort));
     hull_label_lo_kernel<<<nblk((int64_t)n_labels + 1, 256), 256, 0, st>>>(skeys, nh, n_labels, bits_of(nh) + 1, lo_of);
     hull_strict_kernel<<<nhb, 256, 0, st>>>(skeys, svals, cxy, lo_of, nh, n_labels, nc, keep, d_err);
-    tb = B[HL_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[HL_TMP].p, tb, kept, spos, nh + 1, st));
+    BS_HIP(ctx, cub_run_sized(B[HL_TMP], scan_kept));
     hull_offset_kernel<<<nblk((int64_t)n_labels + 1, 256), 256, 0, st>>>(lo_of, spos, nh, n_labels, F.hoff, d_err);
     hull_place_kernel<<<nhb, 256, 0, st>>>(keep, spos, svals, cxy, clab, L, nh, nc, n_labels, hxy, d_err);
     BS_HIP(ctx, hipEventRecord(ev.e[4], st));

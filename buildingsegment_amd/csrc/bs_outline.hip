@@ -424,14 +424,14 @@ extern "C" int bs_facet_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   int32_t* base = B[OL_BASE].as<int32_t>();
   int* d_bad = B[OL_MISC].as<int>();
   int* d_err = d_bad + 1;
-  size_t t1 = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t1, SideIt(flags, SideCount()), base, (int)npix, st));
-  BS_HIP(ctx, B[OL_TMP].reserve(std::max<size_t>(t1, 256)));
+  auto sides = [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, SideIt(flags, SideCount()), base, (int)npix, st);
+  };
+  BS_HIP(ctx, cub_room(B[OL_TMP], sides));
   BS_HIP(ctx, hipMemsetAsync(d_bad, 0, 8, st));
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
   outline_flags_kernel<<<grid_of(npix), 256, 0, st>>>(d_label, w, h, n_labels, flags, d_bad);
-  size_t tb = B[OL_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[OL_TMP].p, tb, SideIt(flags, SideCount()), base, (int)npix, st));
+  BS_HIP(ctx, cub_run_sized(B[OL_TMP], sides));
   BS_HIP(ctx, hipEventRecord(ev.e[1], st));
   int h_bad = 0;
   int32_t last_base = 0;
@@ -492,11 +492,7 @@ extern "C" int bs_facet_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   BS_HIP(ctx, hipEventRecord(ev.e[5], st));
   // ---- rings: a slot per leader ----
   hipcub::TransformInputIterator<int32_t, LeadFlag, hipcub::CountingInputIterator<int32_t>> leads(idx, LeadFlag{leader});
-  size_t t2 = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, leads, slot, n, st));
-  BS_HIP(ctx, B[OL_TMP].reserve(t2));
-  tb = B[OL_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[OL_TMP].p, tb, leads, slot, n, st));
+  BS_HIP(ctx, cub_run(B[OL_TMP], [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, leads, slot, n, st); }));
   BS_HIP(ctx, hipEventRecord(ev.e[6], st));
   int h_err = 0;
   int32_t last_slot = 0, last_leader = -1;
@@ -532,18 +528,17 @@ extern "C" int bs_facet_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   const int end_bit = 32 + bits_of(n_labels);
   hipcub::TransformInputIterator<int32_t, VertexCount, hipcub::CountingInputIterator<int32_t>> counts(idx,
                                                                                                       VertexCount{RO.vertices, nr});
-  size_t t3 = 0, t4 = 0;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t3, keys, skeys, vals, svals, nr, 0, end_bit, st));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t4, counts, RO.offset, nr + 1, st));
-  BS_HIP(ctx, B[OL_TMP].reserve(std::max(t3, t4)));
+  auto sort = [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, skeys, vals, svals, nr, 0, end_bit, st);
+  };
+  auto offsets = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, counts, RO.offset, nr + 1, st); };
+  BS_HIP(ctx, cub_room(B[OL_TMP], sort, offsets));
   BS_HIP(ctx, hipEventRecord(ev.e[7], st));
   outline_slot_init_kernel<<<nblk(nr, 256), 256, 0, st>>>(F, nr);
   outline_figures_kernel<<<grid_of(n), 256, 0, st>>>(hnum, leader, slot, suffix, d_label, w, n, nr, keys, vals, F, d_err);
-  tb = B[OL_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(B[OL_TMP].p, tb, keys, skeys, vals, svals, nr, 0, end_bit, st));
+  BS_HIP(ctx, cub_run_sized(B[OL_TMP], sort));
   outline_gather_kernel<<<nblk(nr, 256), 256, 0, st>>>(skeys, svals, nr, F, RO, d_err);
-  tb = B[OL_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[OL_TMP].p, tb, counts, RO.offset, nr + 1, st));
+  BS_HIP(ctx, cub_run_sized(B[OL_TMP], offsets));
   outline_label_offset_kernel<<<nblk((int64_t)n_labels + 1, 256), 256, 0, st>>>(RO.label, nr, n_labels, bits_of(nr) + 1, lro);
   outline_place_kernel<<<nb, 256, 0, st>>>(vert, leader, slot, suffix, nx[cw], n, nr, RO, dest, d_err);
   BS_HIP(ctx, hipEventRecord(ev.e[8], st));

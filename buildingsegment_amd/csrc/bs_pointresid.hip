@@ -581,13 +581,9 @@ int residuals(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const i
   const int chunk_grid = (int)std::max<long long>(1, std::min<long long>(n_chunks, CHUNK_GRID));
   if (n_items > 0)
     pr_lists_kernel<false><<<chunk_grid, CHUNK, 0, st>>>(A, spanscan, rows, n_rows, n_items, cnt, off, list, d_words + W_ERR, d_counters);
-  {
-    size_t t3 = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t3, PixCountIt(Idx64(0), PixCount{nullptr, 0}), (unsigned*)nullptr, (int)(npix + 1), st));
-    BS_HIP(ctx, B[PR_TMP].reserve(std::max<size_t>(t3, 256)));
-    size_t tbytes = B[PR_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[PR_TMP].p, tbytes, PixCountIt(Idx64(0), PixCount{cnt, npix}), off, (int)(npix + 1), st));
-  }
+  BS_HIP(ctx, cub_run(B[PR_TMP], [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, PixCountIt(Idx64(0), PixCount{cnt, npix}), off, (int)(npix + 1), st);
+  }));
   if (n_items > 0) {
     BS_HIP(ctx, hipMemsetAsync(cnt, 0, 4 * (size_t)npix, st));
     pr_lists_kernel<true><<<chunk_grid, CHUNK, 0, st>>>(A, spanscan, rows, n_rows, n_items, cnt, off, list, d_words + W_ERR, d_counters);

@@ -648,18 +648,7 @@ int poly_solids(bs_ctx* ctx, const struct bs_outline_triangles& t, const struct 
   Events<4> ev;
   for (int i = 0; i < 4; i++)
     BS_HIP(ctx, hipEventCreate(&ev.e[i]));
-  size_t t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, t6 = 0;
   const int col_bits = std::min(64, 33 + bits_of(nb));  // (one bit above the building: ~0 sorts behind every column)
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t1, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                                 (int32_t*)nullptr, (int32_t*)nullptr, nsv, 0, 64, st));
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t2, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                 (uint32_t*)nullptr, m, 0, 32, st));
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t3, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                                 (uint32_t*)nullptr, (uint32_t*)nullptr, m, 0, col_bits, st));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t4, (uint32_t*)nullptr, (uint32_t*)nullptr, m + 1, st));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t5, WallFlagIt(Idx(0), WallFlag{nullptr, 0}), (int32_t*)nullptr, nsv + 1, st));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t6, WallCountIt(Idx(0), WallCount{nullptr, 0}), (long long*)nullptr, nsv + 1, st));
-  BS_HIP(ctx, B[PS_TMP].reserve(std::max({t1, t2, t3, t4, t5, t6, (size_t)256})));
   BS_HIP(ctx, B[PS_MISC].reserve(256));
   for (int b : {PS_LC, PS_LV0})
     BS_HIP(ctx, B[b].reserve(4 * (size_t)nl));
@@ -703,7 +692,19 @@ int poly_solids(bs_ctx* ctx, const struct bs_outline_triangles& t, const struct 
   int32_t *vnum = B[PS_VNUM].as<int32_t>(), *vsrc = B[PS_VSRC].as<int32_t>(), *wcnt = B[PS_WCNT].as<int32_t>();
   int32_t* wscan = B[PS_WSCAN].as<int32_t>();
   long long* iscan = B[PS_ISCAN].as<long long>();
-  size_t tbytes = B[PS_TMP].cap;
+  auto sort = [st](auto* k0, auto* k1, auto* v0, auto* v1, auto n, int bits) {  // (n: int32 over the ring vertices, int64 over the entries, as ever)
+    return [=](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, k0, k1, v0, v1, n, 0, bits, st); };
+  };
+  auto scan = [st](auto counts, auto* sums, auto n) {
+    return [=](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, counts, sums, n, st); };
+  };
+  auto sort_twins = sort(tk0, tk1, tv0, tv1, nsv, 64);
+  auto sort_z = sort(zk0, zk1, ev0, ev1, m, 32);
+  auto sort_col = sort(ck1, ck0, ev1, ev2, m, col_bits);
+  auto scan_heads = scan(head, hscan, m + 1);
+  auto scan_walls = scan(WallFlagIt(Idx(0), WallFlag{wcnt, nsv}), wscan, nsv + 1);
+  auto scan_index = scan(WallCountIt(Idx(0), WallCount{wcnt, nsv}), iscan, nsv + 1);
+  BS_HIP(ctx, cub_room(B[PS_TMP], sort_twins, sort_z, sort_col, scan_heads, scan_walls, scan_index));
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
   BS_HIP(ctx, hipMemsetAsync(d_words, 0, 4 * W_COUNT, st));
   BS_HIP(ctx, hipMemcpyAsync(B[PS_LC].p, lc.data(), 4 * (size_t)nl, hipMemcpyHostToDevice, st));
@@ -714,28 +715,23 @@ int poly_solids(bs_ctx* ctx, const struct bs_outline_triangles& t, const struct 
   ps_fig_init_kernel<<<sweep(nb), 256, 0, st>>>(f, nb);
   // 1. twins (the keys of the vertex entries come out of the same pass)
   ps_keys_kernel<<<sweep(nsv), 256, 0, st>>>(A, tk0, tv0, twin, zk0, ev0, ck0, d_words);
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(B[PS_TMP].p, tbytes, tk0, tk1, tv0, tv1, nsv, 0, 64, st));
+  BS_HIP(ctx, cub_run(B[PS_TMP], sort_twins));
   ps_twins_kernel<<<sweep(nsv), 256, 0, st>>>(A, tk1, tv1, twin, d_err);
   BS_HIP(ctx, hipEventRecord(ev.e[1], st));
   // 2. vertices: two stable passes, Z first
-  tbytes = B[PS_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(B[PS_TMP].p, tbytes, zk0, zk1, ev0, ev1, m, 0, 32, st));
+  BS_HIP(ctx, cub_run(B[PS_TMP], sort_z));
   ps_gather_kernel<<<sweep(m), 256, 0, st>>>(ev1, ck0, m, ck1, d_err);
-  tbytes = B[PS_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(B[PS_TMP].p, tbytes, ck1, ck0, ev1, ev2, m, 0, col_bits, st));
+  BS_HIP(ctx, cub_run(B[PS_TMP], sort_col));
   ps_heads_kernel<<<sweep(m + 1), 256, 0, st>>>(ck0, ev2, zk0, m, head, d_err);
-  tbytes = B[PS_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[PS_TMP].p, tbytes, head, hscan, m + 1, st));
+  BS_HIP(ctx, cub_run(B[PS_TMP], scan_heads));
   ps_numbers_kernel<<<sweep(m), 256, 0, st>>>(ck0, ev2, head, hscan, m, nb, vnum, vsrc, f, d_err);
   BS_HIP(ctx, hipEventRecord(ev.e[2], st));
   // 3. count
   ps_wall_kernel<<<sweep(nsv), 256, 0, st>>>(A, twin, vnum, nb, wcnt, f, d_err);
   if (ntri > 0)
     ps_tri_kernel<<<sweep(ntri), 256, 0, st>>>(A, nb, f, d_err);
-  tbytes = B[PS_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[PS_TMP].p, tbytes, WallFlagIt(Idx(0), WallFlag{wcnt, nsv}), wscan, nsv + 1, st));
-  tbytes = B[PS_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[PS_TMP].p, tbytes, WallCountIt(Idx(0), WallCount{wcnt, nsv}), iscan, nsv + 1, st));
+  BS_HIP(ctx, cub_run(B[PS_TMP], scan_walls));
+  BS_HIP(ctx, cub_run(B[PS_TMP], scan_index));
   BS_HIP(ctx, hipEventRecord(ev.e[3], st));
   int h_words[W_COUNT] = {};
   uint32_t h_nv = 0;

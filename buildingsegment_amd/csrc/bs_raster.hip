@@ -305,16 +305,13 @@ int grid_picture_tiles_dev(bs_ctx* ctx, const int32_t* d_xyz, const int64_t* til
   int end_bit = 1;
   while (end_bit < 32 && (1ull << end_bit) <= (unsigned long long)npix)
     end_bit++;
-  size_t tmp_sort = 0, tmp_scan = 0;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, keys_in, keys_out, vals_in, vals_out, (int)m, 0,
-                                                 end_bit, st));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, cnt, off, (int)npix, st));
-  BS_HIP(ctx, ctx->rs_tmp.reserve(std::max(tmp_sort, tmp_scan)));
-  size_t tb = ctx->rs_tmp.cap;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->rs_tmp.p, tb, keys_in, keys_out, vals_in, vals_out, (int)m, 0,
-                                                 end_bit, st));
-  tb = ctx->rs_tmp.cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(ctx->rs_tmp.p, tb, cnt, off, (int)npix, st));
+  auto sort = [&](void* tmp, size_t& bytes) {
+    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (int)m, 0, end_bit, st);
+  };
+  auto scan = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, off, (int)npix, st); };
+  BS_HIP(ctx, cub_room(ctx->rs_tmp, sort, scan));
+  BS_HIP(ctx, cub_run(ctx->rs_tmp, sort));
+  BS_HIP(ctx, cub_run(ctx->rs_tmp, scan));
   accumulate_kernel<<<nblk(npix, 64), 64, 0, st>>>(d_xyz, bin, npix, off, cnt, vals_out, d_image);
   int h_bad = 0;
   std::vector<double> h_th(n_tiles);

@@ -522,16 +522,9 @@ extern "C" int bs_roofs_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_
   int bits = 1;
   while (bits < 64 && (1ull << bits) <= none)
     bits++;
-  size_t t1 = 0, t2 = 0;
-  if (npl > 0) {
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, t1, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)n, 0, bits, st));
-    BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(nullptr, t2, (uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                      (int32_t*)nullptr, (int32_t*)nullptr, (int)n, st));
-  }
   BS_HIP(ctx, B[RF_KEYS].reserve(8 * (size_t)n));
   BS_HIP(ctx, B[RF_KEYS2].reserve(8 * (size_t)n));
   BS_HIP(ctx, B[RF_RUNS].reserve(12 * (size_t)n));
-  BS_HIP(ctx, B[RF_TMP].reserve(std::max<size_t>(std::max(t1, t2), 256)));
   BS_HIP(ctx, B[RF_BEST].reserve(8 * (size_t)npix));
   BS_HIP(ctx, B[RF_NEXT].reserve(4 * (size_t)npix));
   BS_HIP(ctx, B[RF_LIST_A].reserve(4 * (size_t)npix + 256));
@@ -552,6 +545,16 @@ extern "C" int bs_roofs_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_
   int32_t* d_rounds = d_bad + 2;
   int32_t* d_nkeys = d_bad + 3;
   int32_t* d_cnt = d_bad + 4;          // [FILL_GROUP + 1]: round k of a group reads d_cnt[k] and fills d_cnt[k + 1]
+  // the sort and the runs of the votes: sized for every point here, run over the nk points that count
+  auto sort = [=](int count) {
+    return [=](void* tmp, size_t& bytes) { return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, keys, sorted, count, 0, bits, st); };
+  };
+  auto runs = [=](int count) {
+    return [=](void* tmp, size_t& bytes) {
+      return hipcub::DeviceRunLengthEncode::Encode(tmp, bytes, sorted, run_key, run_len, d_nruns, count, st);
+    };
+  };
+  BS_HIP(ctx, npl > 0 ? cub_room(B[RF_TMP], sort((int)n), runs((int)n)) : cub_room(B[RF_TMP]));  // (no plane: neither runs)
   double* tab_normal = B[RF_TAB].as<double>();
   int32_t* tab_center = reinterpret_cast<int32_t*>(tab_normal + 3 * m);
   int32_t* tab_home = tab_center + 3 * m;
@@ -585,10 +588,8 @@ extern "C" int bs_roofs_dev(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_
     return fail(ctx, BS_ERR_RANGE, "roofs: a point's pixel lies outside the image (cloud not shifted, or another bin?)");
   const int nk = h_flags[3];
   if (npl > 0 && nk > 0) {
-    size_t tb = B[RF_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(B[RF_TMP].p, tb, keys, sorted, nk, 0, bits, st));
-    tb = B[RF_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(B[RF_TMP].p, tb, sorted, run_key, run_len, d_nruns, nk, st));
+    BS_HIP(ctx, cub_run(B[RF_TMP], sort(nk)));
+    BS_HIP(ctx, cub_run(B[RF_TMP], runs(nk)));
     runs_kernel<<<nblk(nk, 256), 256, 0, st>>>(run_key, run_len, d_nruns, none, npl, best);
   }
   seed_kernel<<<nblk(npix, 256), 256, 0, st>>>(d_map, best, w, h, min_votes, d_roof, d_support, next, lists[0], d_cnt);

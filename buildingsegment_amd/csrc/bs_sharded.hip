@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "bs_common.h"
+#include "bs_host.h"
 
 namespace bs {
 
@@ -666,40 +667,17 @@ void assign_components(const std::vector<int64_t>& roots, const std::vector<int6
       return fail(ctx, BS_ERR_NOMEM, "bs_segment_sharded: device allocation failed"); \
   } while (0)
 
-int sort_pairs_u64(bs_ctx* ctx, const uint64_t* kin, uint64_t* kout, const int32_t* vin, int32_t* vout, int64_t n, int end_bit)
+// radix sort of n keys, and of their values where there are any, through the context's slot
+template <class K, class V = void>
+int radix_sort(bs_ctx* ctx, const K* kin, K* kout, int64_t n, int end_bit = (int)sizeof(K) * 8, const V* vin = nullptr,
+               V* vout = nullptr)
 {
-  size_t tb = 0;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, ctx->stream));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, ctx->stream));
-  return BS_OK;
-}
-
-int sort_pairs_u32(bs_ctx* ctx, const uint32_t* kin, uint32_t* kout, const int32_t* vin, int32_t* vout, int64_t n, int end_bit)
-{
-  size_t tb = 0;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, end_bit, ctx->stream));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, end_bit, ctx->stream));
-  return BS_OK;
-}
-
-int sort_pairs_i32(bs_ctx* ctx, const int32_t* kin, int32_t* kout, const int32_t* vin, int32_t* vout, int64_t n)
-{
-  size_t tb = 0;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, 32, ctx->stream));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->cub_tmp.p, tb, kin, kout, vin, vout, (int)n, 0, 32, ctx->stream));
-  return BS_OK;
-}
-
-template <class K>
-int sort_keys(bs_ctx* ctx, const K* kin, K* kout, int64_t n)
-{
-  size_t tb = 0;
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, tb, kin, kout, (int)n, 0, (int)sizeof(K) * 8, ctx->stream));
-  BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-  BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(ctx->cub_tmp.p, tb, kin, kout, (int)n, 0, (int)sizeof(K) * 8, ctx->stream));
+  BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+    if constexpr (std::is_void_v<V>)
+      return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, kin, kout, (int)n, 0, end_bit, ctx->stream);
+    else
+      return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, kin, kout, vin, vout, (int)n, 0, end_bit, ctx->stream);
+  }));
   return BS_OK;
 }
 
@@ -767,7 +745,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
     SH_CHECK(ka && kb && va && vb && srt);
     if (m > 0) {
       morton_key_kernel<<<nblk_clamped(m, 256), 256, 0, st>>>(rows, m, origin, shift, ka, va);
-      rc = sort_pairs_u64(ctx, ka, kb, va, vb, m, 63);
+      rc = radix_sort(ctx, ka, kb, m, 63, va, vb);
       if (rc != BS_OK)
         return rc;
       gather_int4_kernel<<<nblk_clamped(m, 256), 256, 0, st>>>(rows, vb, m, srt);
@@ -826,15 +804,14 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
       int32_t* d_cnt = (int32_t*)P.buf<int64_t>(SMALL, 64);
       if (n_own > 0) {
         voxel_key_kernel<<<nblk_clamped(n_own, 256), 256, 0, st>>>(own, n_own, origin, v, vk);
-        rc = sort_keys<uint64_t>(ctx, vk, vs, n_own);
+        rc = radix_sort(ctx, vk, vs, n_own);
         if (rc != BS_OK)
           return rc;
         uint64_t* occ_tmp = (uint64_t*)P.buf<int32_t>(VALS_A, 2 * (size_t)n_own + 16);
         SH_CHECK(occ_tmp);
-        size_t tb = 0;
-        BS_HIP(ctx, hipcub::DeviceSelect::Unique(nullptr, tb, vs, occ_tmp, d_cnt, (int)n_own, st));
-        BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-        BS_HIP(ctx, hipcub::DeviceSelect::Unique(ctx->cub_tmp.p, tb, vs, occ_tmp, d_cnt, (int)n_own, st));
+        BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+          return hipcub::DeviceSelect::Unique(tmp, bytes, vs, occ_tmp, d_cnt, (int)n_own, st);
+        }));
         int32_t c32 = 0;
         BS_HIP(ctx, hipMemcpyAsync(&c32, d_cnt, sizeof c32, hipMemcpyDeviceToHost, st));
         BS_HIP(ctx, hipStreamSynchronize(st));
@@ -864,10 +841,9 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
         if (r == rank || n_own == 0 || cnts[r] == 0)
           continue;
         halo_mark_kernel<<<nblk_clamped(n_own, 256), 256, 0, st>>>(vk, n_own, occ_all + (size_t)r * cap, cnts[r], flags);
-        size_t tb = 0;
-        BS_HIP(ctx, hipcub::DeviceSelect::Flagged(nullptr, tb, own, flags, send + soff, d_cnt, (int)n_own, st));
-        BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-        BS_HIP(ctx, hipcub::DeviceSelect::Flagged(ctx->cub_tmp.p, tb, own, flags, send + soff, d_cnt, (int)n_own, st));
+        BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+          return hipcub::DeviceSelect::Flagged(tmp, bytes, own, flags, send + soff, d_cnt, (int)n_own, st);
+        }));
         int32_t c32 = 0;
         BS_HIP(ctx, hipMemcpyAsync(&c32, d_cnt, sizeof c32, hipMemcpyDeviceToHost, st));
         BS_HIP(ctx, hipStreamSynchronize(st));
@@ -964,13 +940,12 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
     int64_t nruns = 0;
     int32_t* d_cnt = (int32_t*)P.buf<int64_t>(SMALL, 64);
     if (n_own > 0) {
-      rc = sort_keys<int32_t>(ctx, root, rs, n_own);
+      rc = radix_sort(ctx, root, rs, n_own);
       if (rc != BS_OK)
         return rc;
-      size_t tb = 0;
-      BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(nullptr, tb, rs, ur, uc, d_cnt, (int)n_own, st));
-      BS_HIP(ctx, ctx->cub_tmp.reserve(tb));
-      BS_HIP(ctx, hipcub::DeviceRunLengthEncode::Encode(ctx->cub_tmp.p, tb, rs, ur, uc, d_cnt, (int)n_own, st));
+      BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+        return hipcub::DeviceRunLengthEncode::Encode(tmp, bytes, rs, ur, uc, d_cnt, (int)n_own, st);
+      }));
       int32_t c32 = 0;
       BS_HIP(ctx, hipMemcpyAsync(&c32, d_cnt, sizeof c32, hipMemcpyDeviceToHost, st));
       BS_HIP(ctx, hipStreamSynchronize(st));
@@ -1025,7 +1000,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
       int bits = 1;
       while ((1 << bits) < world)
         bits++;
-      rc = sort_pairs_u32(ctx, dk, dks, dv, dvs, n_own, bits);  // (radix sort is stable: the slab order survives inside a destination)
+      rc = radix_sort(ctx, dk, dks, n_own, bits, dv, dvs);  // (radix sort is stable: the slab order survives inside a destination)
       if (rc != BS_OK)
         return rc;
       int64_t* d_pos = P.buf<int64_t>(SMALL, 64 + world) + 64;
@@ -1086,7 +1061,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
   int32_t np_local = 0;
   if (n_loc > 0) {
     row_gidx_kernel<<<nblk_clamped(n_loc, 256), 256, 0, st>>>(g_own, n_loc, gl, io);
-    lrc = sort_pairs_i32(ctx, gl, sg, io, perm, n_loc);
+    lrc = radix_sort(ctx, gl, sg, n_loc, 32, io, perm);
     if (lrc == BS_OK) {
       dup_check_kernel<<<nblk_clamped(n_loc, 256), 256, 0, st>>>(sg, n_loc, d_bad);
       int4* srt = (int4*)P.buf<char>(SEND, (size_t)n_loc * sizeof(int4) + 64);
@@ -1170,7 +1145,7 @@ int sharded_impl(bs_ctx* ctx, const bs_comm_ops* comm, const int32_t* d_xyz, con
     }
   }
   if (np_tot > 0) {
-    rc = sort_keys<int32_t>(ctx, seeds_cat, seeds_sorted, np_tot);
+    rc = radix_sort(ctx, seeds_cat, seeds_sorted, np_tot);
     if (rc != BS_OK)
       return rc;
   }

@@ -744,9 +744,8 @@ extern "C" int bs_simple_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label,
   int32_t* val[2] = {B[SP_VAL0].as<int32_t>(), B[SP_VAL1].as<int32_t>()};
   const RingFig F = ring_fig_at(B[SP_RING].p, (size_t)nr);
   hipcub::TransformInputIterator<int32_t, NodeCount, hipcub::CountingInputIterator<int32_t>> counts(idx, NodeCount{F.nodes, nr});
-  size_t t1 = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t1, counts, F.noff, nr + 1, st));
-  BS_HIP(ctx, B[SP_TMP].reserve(std::max<size_t>(t1, 256)));
+  auto scan_nodes = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, counts, F.noff, nr + 1, st); };
+  BS_HIP(ctx, cub_room(B[SP_TMP], scan_nodes));
   BS_HIP(ctx, hipMemsetAsync(d_words, 0, 4 * W_COUNT, st));
   BS_HIP(ctx, hipEventRecord(ev.e[0], st));
   simplify_nodes_kernel<<<nb, 256, 0, st>>>(d_label, d_top, hnum, vert, w, h, n, hflag, isnode, hright, hcidx, hz, d_err);
@@ -759,8 +758,7 @@ extern "C" int bs_simple_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label,
   const int32_t* suffix = val[cw];
   simplify_ring_init_kernel<<<nblk(nr, 256), 256, 0, st>>>(F, nr);
   simplify_ring_nodes_kernel<<<nb, 256, 0, st>>>(leader, slot, of_slot, suffix, nx[cw], n, nr, F.nodes, d_err);
-  size_t tb = B[SP_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[SP_TMP].p, tb, counts, F.noff, nr + 1, st));
+  BS_HIP(ctx, cub_run(B[SP_TMP], scan_nodes));
   BS_HIP(ctx, hipEventRecord(ev.e[2], st));
   int h_err = 0;
   int32_t n_nodes = 0;
@@ -796,20 +794,18 @@ extern "C" int bs_simple_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label,
   uint8_t* forced = B[SP_FORCED].as<uint8_t>();
   int32_t* kscan = B[SP_KSCAN].as<int32_t>();
   hipcub::TransformInputIterator<int32_t, ArcStart, hipcub::CountingInputIterator<int32_t>> starts(idx, ArcStart{A.flag});
-  size_t t2 = 0, t3 = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::InclusiveSum(nullptr, t2, starts, arc, N, st));
-  {
-    hipcub::TransformInputIterator<int32_t, KeptFlag, hipcub::CountingInputIterator<int32_t>> kf(idx, KeptFlag{seg[0], N});
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t3, kf, kscan, N + 1, st));
-  }
-  BS_HIP(ctx, B[SP_TMP].reserve(std::max(t2, t3)));
+  auto scan_arcs = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::InclusiveSum(tmp, bytes, starts, arc, N, st); };
+  auto scan_kept = [&](const int2* segs) {  // (the buffer that holds the kept flags is known after the rounds)
+    hipcub::TransformInputIterator<int32_t, KeptFlag, hipcub::CountingInputIterator<int32_t>> kf(idx, KeptFlag{segs, N});
+    return [=](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, kf, kscan, N + 1, st); };
+  };
+  BS_HIP(ctx, cub_room(B[SP_TMP], scan_arcs, scan_kept(seg[0])));
   const int NB = nblk(N, 256), g = node_grid(N);
   simplify_ring_figures_kernel<<<node_grid(n), 256, 0, st>>>(hflag, hcidx, leader, slot, of_slot, suffix, F.nodes, n, nr, F.junctions,
                                                            F.first_junction, F.lowest, d_err);
   simplify_rot_kernel<<<nblk(nr, 256), 256, 0, st>>>(F, nr, d_err);
   simplify_scatter_kernel<<<nb, 256, 0, st>>>(hflag, hcidx, hright, hz, leader, slot, of_slot, suffix, F, w, n, nr, N, has_z, A, d_err);
-  tb = B[SP_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::InclusiveSum(B[SP_TMP].p, tb, starts, arc, N, st));
+  BS_HIP(ctx, cub_run(B[SP_TMP], scan_arcs));
   simplify_arc_start_kernel<<<NB, 256, 0, st>>>(A.flag, arc, N, astart, d_err);
   simplify_seg_init_kernel<<<g, 256, 0, st>>>(A.flag, arc, astart, A.ring, F.noff, N, nr, seg[0], best[0], tie[0], forced,
                                               d_words + W_MAXARC, d_err);
@@ -844,9 +840,7 @@ extern "C" int bs_simple_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label,
   }
   BS_HIP(ctx, hipEventRecord(ev.e[4], st));
   // ---- rings: the kept flags scanned, the place of every kept vertex, area2 ----
-  hipcub::TransformInputIterator<int32_t, KeptFlag, hipcub::CountingInputIterator<int32_t>> kf(idx, KeptFlag{seg[cur], N});
-  tb = B[SP_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[SP_TMP].p, tb, kf, kscan, N + 1, st));
+  BS_HIP(ctx, cub_run(B[SP_TMP], scan_kept(seg[cur])));
   simplify_ring_offsets_kernel<<<nblk((int64_t)nr + 1, 256), 256, 0, st>>>(kscan, F, nr, N, d_err);
   simplify_final_kernel<<<NB, 256, 0, st>>>(seg[cur], kscan, A, F, N, nr, has_z, O, d_err);
   simplify_area_kernel<<<g, 256, 0, st>>>(O.xy, O.ring, F.soff, kscan, N, nr, F.area2, d_err);

@@ -561,10 +561,6 @@ extern "C" int bs_solids_count_dev(bs_ctx* ctx, const int32_t* d_map, const int3
   for (auto& e : ev.e)
     BS_HIP(ctx, hipEventCreate(&e));
 
-  size_t t1 = 0, t2 = 0, t3 = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t1, CornerIt(nullptr, ByteCount()), (int32_t*)nullptr, (int)nc, st));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, FaceIt(nullptr, FaceCount()), (int32_t*)nullptr, (int)npix, st));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t3, IndexIt(nullptr, IndexCount()), (int32_t*)nullptr, (int)npix, st));
   BS_HIP(ctx, B[SD_TOP].reserve(16 * (size_t)npix));
   BS_HIP(ctx, B[SD_MAP].reserve(4 * (size_t)npix));
   BS_HIP(ctx, B[SD_CCNT].reserve((size_t)nc));
@@ -572,7 +568,6 @@ extern "C" int bs_solids_count_dev(bs_ctx* ctx, const int32_t* d_map, const int3
   BS_HIP(ctx, B[SD_PCNT].reserve(2 * (size_t)npix));
   BS_HIP(ctx, B[SD_FOFF].reserve(4 * (size_t)npix));
   BS_HIP(ctx, B[SD_IOFF].reserve(4 * (size_t)npix));
-  BS_HIP(ctx, B[SD_TMP].reserve(std::max<size_t>(std::max(t1, std::max(t2, t3)), 256)));
   BS_HIP(ctx, B[SD_TAB].reserve(44 * mp + 4 * mb));
   BS_HIP(ctx, B[SD_FIG].reserve(56 * mb + 64));
   BS_HIP(ctx, B[SD_MISC].reserve(256));
@@ -585,6 +580,14 @@ extern "C" int bs_solids_count_dev(bs_ctx* ctx, const int32_t* d_map, const int3
   int32_t* foff = B[SD_FOFF].as<int32_t>();
   int32_t* ioff = B[SD_IOFF].as<int32_t>();
   int* d_bad = B[SD_MISC].as<int>();
+  // the scans of the mesh offsets, run once the counts are checked
+  auto scan = [st](auto counts, int32_t* sums, int64_t n) {
+    return [=](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, counts, sums, (int)n, st); };
+  };
+  auto scan_v = scan(CornerIt(ccnt, ByteCount()), voff, nc);
+  auto scan_f = scan(FaceIt(pcnt, FaceCount()), foff, npix);
+  auto scan_i = scan(IndexIt(pcnt, IndexCount()), ioff, npix);
+  BS_HIP(ctx, cub_room(B[SD_TMP], scan_v, scan_f, scan_i));
   double* tab_normal = B[SD_TAB].as<double>();
   int32_t* tab_center = reinterpret_cast<int32_t*>(tab_normal + 3 * mp);
   int32_t* tab_zmin = tab_center + 3 * mp;
@@ -671,16 +674,13 @@ extern "C" int bs_solids_count_dev(bs_ctx* ctx, const int32_t* d_map, const int3
   }
 
   // ---- scans (the sums fit 32 bits: checked above) ----
-  size_t tb = B[SD_TMP].cap;
   hipError_t e = hipEventRecord(ev.e[5], st);
   if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(B[SD_TMP].p, tb, CornerIt(ccnt, ByteCount()), voff, (int)nc, st);
-  tb = B[SD_TMP].cap;
+    e = cub_run(B[SD_TMP], scan_v);
   if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(B[SD_TMP].p, tb, FaceIt(pcnt, FaceCount()), foff, (int)npix, st);
-  tb = B[SD_TMP].cap;
+    e = cub_run(B[SD_TMP], scan_f);
   if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(B[SD_TMP].p, tb, IndexIt(pcnt, IndexCount()), ioff, (int)npix, st);
+    e = cub_run(B[SD_TMP], scan_i);
   if (e == hipSuccess)
     e = hipEventRecord(ev.e[6], st);
   if (e == hipSuccess && d_top)

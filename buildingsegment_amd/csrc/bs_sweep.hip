@@ -415,16 +415,14 @@ int sweep_begin(bs_ctx* ctx, const SweepRun& R, long long* h_items)
   long long* ioff = B[SW_IOFF].as<long long>();
   hipcub::CountingInputIterator<int32_t> idx(0);
   hipcub::TransformInputIterator<long long, ItemCount, hipcub::CountingInputIterator<int32_t>> ic(idx, ItemCount{icnt, R.N});
-  size_t t = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t, ic, ioff, R.N + 1, R.st));
-  BS_HIP(ctx, B[SW_TMP].reserve(std::max<size_t>(t, 256)));
+  auto scan = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, ic, ioff, R.N + 1, R.st); };
+  BS_HIP(ctx, cub_room(B[SW_TMP], scan));
   const SweepDev D = dev_of(R);
   BS_HIP(ctx, hipMemsetAsync(R.d_words + W_S_LENS, 0, 4 * (W_COUNT - W_S_LENS), R.st));
   BS_HIP(ctx, hipMemsetAsync(B[SW_BITS].p, 0, 4 * words, R.st));
   sweep_bitmap_kernel<<<sweep(R.N), 256, 0, R.st>>>(D, B[SW_BITS].as<uint32_t>(), R.d_words + W_ERR);
   sweep_runs_kernel<<<sweep(R.N), 256, 0, R.st>>>(D, icnt, R.d_words);
-  t = B[SW_TMP].cap;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[SW_TMP].p, t, ic, ioff, R.N + 1, R.st));
+  BS_HIP(ctx, cub_run(B[SW_TMP], scan));
   BS_HIP(ctx, hipMemcpyAsync(h_items, ioff + R.N, 8, hipMemcpyDeviceToHost, R.st));
   return BS_OK;
 }
@@ -444,14 +442,12 @@ int sweep_detect(bs_ctx* ctx, const SweepRun& R, int32_t nseg, long long n_items
     long long* coff = B[SW_COFF].as<long long>();
     hipcub::CountingInputIterator<int32_t> idx(0);
     hipcub::TransformInputIterator<long long, CornerCount, hipcub::CountingInputIterator<int32_t>> cc(idx, CornerCount{ccnt, n});
-    size_t t = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t, cc, coff, n + 1, R.st));
-    BS_HIP(ctx, B[SW_TMP].reserve(t));
+    auto scan = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cc, coff, n + 1, R.st); };
+    BS_HIP(ctx, cub_room(B[SW_TMP], scan));
     const SweepDev D = dev_of(R);
     sweep_items_kernel<<<sweep(n), 256, 0, R.st>>>(D, B[SW_ICNT].as<int32_t>(), B[SW_IOFF].as<long long>(), n, item, ccnt,
                                                    R.d_words + W_ERR);
-    t = B[SW_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[SW_TMP].p, t, cc, coff, n + 1, R.st));
+    BS_HIP(ctx, cub_run(B[SW_TMP], scan));
     sweep_test_kernel<<<SWEEP_CAP, 256, 0, R.st>>>(D, coff, item, n, B[SW_BITS].as<uint32_t>(), smark, R.d_words);
   }
   sweep_marks_kernel<<<sweep(nseg), 256, 0, R.st>>>(smark, mark, nseg, R.mode, R.d_words);

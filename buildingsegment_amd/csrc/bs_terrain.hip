@@ -486,19 +486,15 @@ int terrain(bs_ctx* ctx, const int32_t* d_xyz, int64_t n, int32_t bin, const int
   if (nb > 0) {
     if (nk > 0) {
       const int end_bit = 32 + std::max(bits_of((uint32_t)nb - 1u), 1);
-      size_t t1 = 0;
-      BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(nullptr, t1, keys, keys, (int)nk, 0, end_bit, st));
-      BS_HIP(ctx, B[TN_TMP].reserve(std::max<size_t>(t1, 256)));
       BS_HIP(ctx, B[TN_SORTED].reserve(8 * (size_t)nk));
-      size_t tb = B[TN_TMP].cap;
-      BS_HIP(ctx, hipcub::DeviceRadixSort::SortKeys(B[TN_TMP].p, tb, keys, B[TN_SORTED].as<unsigned long long>(), (int)nk, 0, end_bit, st));
+      BS_HIP(ctx, cub_run(B[TN_TMP], [&](void* tmp, size_t& bytes) {
+        return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, keys, B[TN_SORTED].as<unsigned long long>(), (int)nk, 0, end_bit, st);
+      }));
       sorted = B[TN_SORTED].as<unsigned long long>();
     }
-    size_t t2 = 0;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, f.wide, off, nb, st));
-    BS_HIP(ctx, B[TN_TMP].reserve(std::max<size_t>(t2, 256)));
-    size_t tb = B[TN_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[TN_TMP].p, tb, f.wide + F_GROUND_PIXELS * (long long)nb1, off, nb, st));
+    BS_HIP(ctx, cub_run(B[TN_TMP], [&](void* tmp, size_t& bytes) {
+      return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, f.wide + F_GROUND_PIXELS * (long long)nb1, off, nb, st);
+    }));
     tn_pick_kernel<<<nblk(nb, 256), 256, 0, st>>>(sorted, nk, off, nb, q_num, q_den, min_ground, fallback_z, f, d_words);
   }
   std::vector<unsigned char> h_fig(fig_bytes);

@@ -12,6 +12,7 @@
 #include <cstdio>
 
 #include "bs_common.h"
+#include "bs_host.h"
 
 namespace bs {
 namespace {
@@ -119,13 +120,9 @@ template <class Count>
 hipError_t scan_counts(DevBuf& tmp, const Count& count, long long n, long long* scan, long long* total, hipStream_t st)
 {
   using It = hipcub::TransformInputIterator<long long, Count, Idx64>;  // (the type the two files have always scanned over)
-  size_t bytes = 0;
-  hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, It(Idx64(0), Count{nullptr, 0}), (long long*)nullptr, (int)(n + 1), st);
-  if (e == hipSuccess)
-    e = tmp.reserve(std::max<size_t>(bytes, 256));
-  bytes = tmp.cap;
-  if (e == hipSuccess)
-    e = hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, It(Idx64(0), count), scan, (int)(n + 1), st);
+  hipError_t e = cub_run(tmp, [&](void* t, size_t& bytes) {
+    return hipcub::DeviceScan::ExclusiveSum(t, bytes, It(Idx64(0), count), scan, (int)(n + 1), st);
+  });
   if (e == hipSuccess)
     e = hipMemcpyAsync(total, scan + n, 8, hipMemcpyDeviceToHost, st);
   return e;

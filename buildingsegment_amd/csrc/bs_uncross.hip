@@ -678,10 +678,9 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   hipcub::CountingInputIterator<int32_t> idx(0);
   hipcub::TransformInputIterator<int32_t, KeptFlag, hipcub::CountingInputIterator<int32_t>> kf(idx, KeptFlag{segK, N});
   hipcub::TransformInputIterator<long long, CellCount, hipcub::CountingInputIterator<int32_t>> cc(idx, CellCount{cnt, kscan + N});
-  size_t t1 = 0, t2 = 0;
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t1, kf, kscan, N + 1, st));
-  BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(nullptr, t2, cc, eoff, N + 1, st));
-  BS_HIP(ctx, B[UC_TMP].reserve(std::max<size_t>(std::max(t1, t2), 256)));
+  auto scan_kept = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, kf, kscan, N + 1, st); };
+  auto scan_cells = [&](void* tmp, size_t& bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cc, eoff, N + 1, st); };
+  BS_HIP(ctx, cub_room(B[UC_TMP], scan_kept, scan_cells));
   const uint32_t ncx = ((uint32_t)width >> k) + 1, ncy = ((uint32_t)height >> k) + 1;
   const int key_bits = bits_of((int64_t)ncx * ncy);
   const int g = sweep(N);
@@ -696,13 +695,11 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
   for (;;) {
     // ---- detect ----
     BS_HIP(ctx, hipEventRecord(ev.e[0], st));
-    size_t tb = B[UC_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[UC_TMP].p, tb, kf, kscan, N + 1, st));
+    BS_HIP(ctx, cub_run(B[UC_TMP], scan_kept));
     uncross_list_kernel<<<g, 256, 0, st>>>(segK, kscan, N, klist, d_err);
     uncross_segments_kernel<<<g, 256, 0, st>>>(kscan, klist, S.xy, S.right, S.ring, S.noff, rlabel, N, nr, k, segxy, seglab, mark, cnt,
                                                d_err);
-    tb = B[UC_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceScan::ExclusiveSum(B[UC_TMP].p, tb, cc, eoff, N + 1, st));
+    BS_HIP(ctx, cub_run(B[UC_TMP], scan_cells));
     long long E64 = 0, I64 = 0;
     if (mode) {  // the sweep pass's items: counted here, so that their count travels in the first read
       BS_HIP(ctx, hipEventRecord(ev.e[6], st));
@@ -738,12 +735,12 @@ extern "C" int bs_clean_outlines_count_dev(bs_ctx* ctx, const int32_t* d_label, 
     int32_t* val0 = B[UC_VAL0].as<int32_t>();
     int32_t* val1 = B[UC_VAL1].as<int32_t>();
     int2* run = B[UC_RUN].as<int2>();
-    size_t t3 = 0;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, t3, key0, key1, val0, val1, E, 0, key_bits, st));
-    BS_HIP(ctx, B[UC_TMP].reserve(t3));
+    auto sort = [&](void* tmp, size_t& bytes) {
+      return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key0, key1, val0, val1, E, 0, key_bits, st);
+    };
+    BS_HIP(ctx, cub_room(B[UC_TMP], sort));
     uncross_fill_kernel<<<sweep(nseg), 256, 0, st>>>(segxy, cnt, eoff, nseg, E, k, ncx, key0, val0, d_err);
-    tb = B[UC_TMP].cap;
-    BS_HIP(ctx, hipcub::DeviceRadixSort::SortPairs(B[UC_TMP].p, tb, key0, key1, val0, val1, E, 0, key_bits, st));
+    BS_HIP(ctx, cub_run(B[UC_TMP], sort));
     uncross_runs_kernel<<<sweep(E), 256, 0, st>>>(key1, val1, E, nseg, run, d_words + W_MAXCELL, d_err);
     uncross_pairs_light_kernel<<<sweep(E), 256, 0, st>>>(run, val1, segxy, seglab, E, nseg, mark, d_err);
     uncross_pairs_heavy_kernel<<<sweep(E), 256, 0, st>>>(run, val1, segxy, seglab, E, nseg, mark, d_err);
