@@ -71,31 +71,48 @@ def best_box(ring):
     return best
 
 
+def edge_products(ring):
+    """[(area_num_i, len2_i)] of every hull edge: what the comparison area_num_i * len2_j < area_num_j * len2_i sees"""
+    return [(b[4], b[0]) for b in (edge_box(ring, i) for i in range(len(ring)))]
+
+
+def ring_of(r, l):
+    """the hull of label l as a list of (X, Y) in Python integers"""
+    return [(int(p[0]), int(p[1])) for p in r.hull_xy[int(r.hull_offset[l]):int(r.hull_offset[l + 1])]]
+
+
 def label_hulls(label, n_labels=None):
-    label = np.asarray(label, np.int64)
+    """from the image: its labelled pixels (np.nonzero), then pixel_hulls"""
+    label = np.asarray(label)
     n_labels = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
-    r = SimpleNamespace(width=label.shape[1], image_height=label.shape[0], n_labels=n_labels)
+    ys, xs = np.nonzero(label >= 0)
+    return pixel_hulls(xs, ys, label[ys, xs], label.shape[1], label.shape[0], n_labels)
+
+
+def pixel_hulls(xs, ys, labs, width, height, n_labels):
+    """the definition from the list of labelled pixels (x, y, label) of a width x height image, in any order"""
+    xs, ys, labs = (np.asarray(v, np.int64).ravel() for v in (xs, ys, labs))
+    r = SimpleNamespace(width=int(width), image_height=int(height), n_labels=n_labels)
     for k in PER_LABEL:
         cols = {"box": 4, "dir": 2}.get(k)
         n = n_labels + (k == "hull_offset")
         r.__dict__[k] = np.zeros((n, cols) if cols else n, np.int32 if k in ("status", "box", "best_edge", "dir") else np.int64)
     xy = []
-    flat = label.ravel()
-    order = np.argsort(flat, kind="stable")  # the pixels of every label, grouped once
-    lo = np.searchsorted(flat[order], np.arange(n_labels + 1))
+    order = np.argsort(labs, kind="stable")  # the pixels of every label, grouped once
+    lo = np.searchsorted(labs[order], np.arange(n_labels + 1))
     for l in range(n_labels):
         r.hull_offset[l] = len(xy)
         pix = order[lo[l]:lo[l + 1]]
         pts = set()
         for dx, dy in ((0, 0), (1, 0), (0, 1), (1, 1)):
-            pts.update(zip((pix % label.shape[1] + dx).tolist(), (pix // label.shape[1] + dy).tolist()))
+            pts.update(zip((xs[pix] + dx).tolist(), (ys[pix] + dy).tolist()))
         if not pts:
             r.status[l] = EMPTY
             continue
-        xs, ys = [p[0] for p in pts], [p[1] for p in pts]
-        r.box[l] = (min(xs), min(ys), max(xs), max(ys))
+        cx, cy = [p[0] for p in pts], [p[1] for p in pts]
+        r.box[l] = (min(cx), min(cy), max(cx), max(cy))
         r.pixels2[l] = 2 * len(pix)
-        if max(xs) - min(xs) > MAX_SIDE or max(ys) - min(ys) > MAX_SIDE:
+        if max(cx) - min(cx) > MAX_SIDE or max(cy) - min(cy) > MAX_SIDE:
             r.status[l] = TOO_LARGE
             continue
         ring = hull(pts)

@@ -1,7 +1,9 @@
 """The device pass of the oriented boxes (buildingsegment_amd/csrc/bs_hull.hip) restated in numpy, array operation for
 kernel: the candidates in ascending half-edge order, the two seeds per label, the QuickHull rounds with their 64-bit bids
 (distance << 32 | candidate, the highest wins), the sort into walk order, the strictness pass and the boxes.  Its result must
-equal brute.py's; its layout figures (n_candidates, rounds, max_live) are what the device must report."""
+equal brute.py's; its layout figures (n_candidates, rounds, max_live) are what the device must report.  It starts from the
+labelled pixels (pixel_hulls) and lays them out in an image without the empty rows and columns between them (squeeze), so a
+few pixels in a large image cost what the pixels cost."""
 from __future__ import annotations
 
 import importlib.util
@@ -26,15 +28,27 @@ def _load(name, path):
 brute = _load("hull_brute", os.path.join(HERE, "brute.py"))
 orf = _load("outline_ref", os.path.join(HERE, "..", "outline_ref", "outline_ref.py"))
 ROUND_BATCH = 4
+CORNER_SHIFT = 14  # corner index = (y << 14) | x, box-relative, both <= 16383
 
 
 def _orient(ax, ay, bx, by, cx, cy):
     return (bx - ax) * (cy - ay) - (by - ay) * (cx - ax)
 
 
-def candidates(label, n_labels):
+def squeeze(xs, ys, labs, width, height):
+    """(small, cols, rows): the image of the listed pixels without its empty rows and columns, except one after every
+    occupied one (so what did not touch still does not touch); cols[x], rows[y] are the places of the small image's columns
+    and rows in the large one.  The occupied pixels keep their order and their neighbours, hence the half-edges theirs."""
+    cols = np.union1d(xs, xs[xs + 1 < width] + 1) if len(xs) else np.zeros(1, np.int64)
+    rows = np.union1d(ys, ys[ys + 1 < height] + 1) if len(ys) else np.zeros(1, np.int64)
+    small = np.full((len(rows), len(cols)), -1, np.int64)
+    small[np.searchsorted(rows, ys), np.searchsorted(cols, xs)] = labs
+    return small, cols, rows
+
+
+def candidates(xs, ys, labs, width, height, n_labels):
     """(label, X, Y) of every candidate in ascending half-edge order, and box / pixels2 / status per label"""
-    label = np.asarray(label, np.int64)
+    label, cols, rows = squeeze(xs, ys, labs, width, height)
     h, w = label.shape
     box = np.zeros((n_labels, 4), np.int64)
     pixels2 = np.zeros(n_labels, np.int64)
@@ -49,7 +63,7 @@ def candidates(label, n_labels):
     for l in range(n_labels):
         rb = o.ring_bbox[(o.ring_label == l) & (o.ring_area2 > 0)].astype(np.int64)
         if len(rb):
-            box[l] = (rb[:, 0].min(), rb[:, 1].min(), rb[:, 2].max(), rb[:, 3].max())
+            box[l] = (cols[rb[:, 0].min()], rows[rb[:, 1].min()], cols[rb[:, 2].max() - 1] + 1, rows[rb[:, 3].max() - 1] + 1)
             big = box[l, 2] - box[l, 0] > brute.MAX_SIDE or box[l, 3] - box[l, 1] > brute.MAX_SIDE
             status[l] = brute.TOO_LARGE if big else brute.OK
     leader = tr["leader"]
@@ -59,23 +73,31 @@ def candidates(label, n_labels):
     np.add.at(ring_area, leader, sx * (y + orf.SY[k1]) - (x + orf.SX[k1]) * sy)
     lab = label[y, x]
     cand = ((flags[y * w + x] >> ((k + 3) % 4)) & 1 == 1) & (ring_area[leader] > 0) & (status[lab] == brute.OK)
-    return lab[cand], sx[cand], sy[cand], box, pixels2, status
+    return lab[cand], (cols[x] + orf.SX[k])[cand], (rows[y] + orf.SY[k])[cand], box, pixels2, status
 
 
 def label_hulls(label, n_labels=None):
-    label = np.asarray(label, np.int64)
+    """from the image: its labelled pixels (np.nonzero), then pixel_hulls"""
+    label = np.asarray(label)
     n_labels = max(int(label.max()) + 1, 0) if n_labels is None else int(n_labels)
-    clab, X, Y, box, pixels2, status = candidates(label, n_labels)
+    ys, xs = np.nonzero(label >= 0)
+    return pixel_hulls(xs, ys, label[ys, xs], label.shape[1], label.shape[0], n_labels)
+
+
+def pixel_hulls(xs, ys, labs, width, height, n_labels):
+    """the restatement from the list of labelled pixels (x, y, label) of a width x height image, in any order"""
+    xs, ys, labs = (np.asarray(v, np.int64).ravel() for v in (xs, ys, labs))
+    clab, X, Y, box, pixels2, status = candidates(xs, ys, labs, width, height, n_labels)
     nc = len(clab)
     r = brute.label_hulls(np.full((1, 1), -1), n_labels)  # (the zeroed result)
-    r.width, r.image_height = label.shape[1], label.shape[0]
+    r.width, r.image_height = int(width), int(height)
     r.box[:], r.pixels2[:], r.status[:] = box, pixels2, status
     r.n_ok, r.n_empty, r.n_too_large = (int((status == s).sum()) for s in (brute.OK, brute.EMPTY, brute.TOO_LARGE))
     r.info = dict(n_candidates=nc, rounds=0, max_live=0)
     if nc == 0:
         return r
     rx, ry = X - box[clab, 0], Y - box[clab, 1]
-    ck = (ry << 14) | rx
+    ck = (ry << CORNER_SHIFT) | rx
     ids = np.arange(nc)
     key = (ck << 32) | ids
     smin, smax = np.full(n_labels, np.iinfo(np.int64).max), np.zeros(n_labels, np.int64)

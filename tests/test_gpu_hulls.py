@@ -1,6 +1,8 @@
 """Oriented boxes on the device (bs_label_hulls, bs_label_hulls_count_dev / _emit_dev; include/bs_api.h) against the
 definition in Python integers (tests/hull_ref/brute.py); the layout figures against the numpy restatement of the device pass
-(tests/hull_ref/hull_ref.py).  Everything is an exact integer: every comparison is ==.
+(tests/hull_ref/hull_ref.py).  Everything is an exact integer: every comparison is ==.  The sparse cases (compared products
+around and above 2^64, coordinates at the bound, round counts around the batch) are built for what tests/test_hulls_cpu.py
+asserts of them; DESIGN.md "Oriented boxes under test" has the list and what a changed line of the kernels fails.
 
 The guarded-scratch test runs under test_gpu_scratch_guard's own `guarded` contexts, so that the slots of bs_ctx::hl count in
 that module's coverage assertion (which runs after this file in a run of the whole suite)."""
@@ -11,23 +13,30 @@ import pytest
 
 from buildingsegment_amd import _lib, api, hulls
 
-from test_hulls_cpu import FUZZ, NAMED, brute, cases  # noqa: E402
+from test_hulls_cpu import FUZZ, MAGNITUDE, NAMED, ROUNDS, SPARSE, SPARSE_FUZZ, brute, cases, sparse_pair  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 LAYOUT = ("n_candidates", "rounds", "max_live")
 PATTERN = -0x5A5A5A5B  # no lattice coordinate of the cases
 
 
-def check(ctx, c, want=None, ref=None):
+def check(ctx, c, want=None, ref=None, layout=True):
     """the host-memory entry point against the definition, its layout figures against the restatement"""
     want = cases.run_brute(c) if want is None else want
-    ref = cases.run_ref(c) if ref is None else ref
+    ref = cases.run_ref(c) if ref is None and layout else ref
     got = hulls.label_hulls(ctx, c[0], n_labels=c[1])
     assert brute.same(got, want) is None, brute.same(got, want)
     assert (got.n_labels, got.width, got.image_height) == (c[1],) + c[0].shape[::-1]
-    assert {k: got.info[k] for k in LAYOUT} == ref.info
+    if layout:
+        assert {k: got.info[k] for k in LAYOUT} == ref.info
     brute.identities(got)
     return got
+
+
+def check_sparse(ctx, name):
+    """a sparse case: the image for the device, the two references from its pixel list (tests/test_hulls_cpu.py asserts what
+    the case was built for)"""
+    return check(ctx, cases.dense(SPARSE[name]), *sparse_pair(name))
 
 
 @pytest.mark.parametrize("name", sorted(NAMED))
@@ -38,6 +47,31 @@ def test_named_case(gpu_ctx, name):
 @pytest.mark.parametrize("name", sorted(FUZZ))
 def test_fuzz(gpu_ctx, name):
     check(gpu_ctx, FUZZ[name])
+
+
+@pytest.mark.parametrize("name", sorted(MAGNITUDE))
+def test_magnitude_case(gpu_ctx, name):
+    """the compared products on both sides of 2^64 (high words zero, different, equal, the tie), the coordinates at the bound
+    of either axis, a small label beside a huge one"""
+    check_sparse(gpu_ctx, name)
+
+
+@pytest.mark.parametrize("name", sorted(ROUNDS))
+def test_round_case(gpu_ctx, name):
+    """5, 8, 9 and 13 rounds against the batch of 4 between two reads of the live count; labels of 1, 5 and 9 together"""
+    got = check_sparse(gpu_ctx, name)
+    assert got.info["rounds"] == (9 if name == "rounds_1_5_9" else int(name.split("_")[1]))
+
+
+@pytest.mark.parametrize("name", sorted(SPARSE_FUZZ))
+def test_sparse_fuzz(gpu_ctx, name):
+    check_sparse(gpu_ctx, name)
+
+
+def test_full_bound(gpu_ctx):
+    """a box of 16383 x 16383 in an image of 16384 x 16384: both coordinates at the bound, compared products up to 2^84.8.
+    Against the definition from the pixel list alone."""
+    check(gpu_ctx, cases.dense(cases.full_bound()), sparse_pair("full_bound")[0], layout=False)
 
 
 def test_figures_of_the_shapes(gpu_ctx):
@@ -115,6 +149,19 @@ def test_emit_twice_and_before_any_count(gpu_ctx):
         assert np.array_equal(xy[:-1], want.hull_xy) and (xy[-1] == PATTERN).all()
     got.hull_xy = want.hull_xy
     assert brute.same(got, want) is None
+    # the same round with products above 2^64 and a 4096 x 4096 image
+    lab, nl = cases.dense(SPARSE["ladder_4096"])
+    want = sparse_pair("ladder_4096")[0]
+    d_label = torch.from_numpy(lab).cuda()
+    got = hulls.label_hulls_dev(gpu_ctx, d_label.data_ptr(), lab.shape[1], lab.shape[0], nl)
+    assert got.hull_xy is None and got.n_hull_vertices == want.n_hull_vertices == 8
+    d_xy = torch.full((got.n_hull_vertices + 1, 2), PATTERN, dtype=torch.int32, device="cuda")
+    hulls.label_hulls_emit_dev(gpu_ctx, d_xy.data_ptr())
+    torch.cuda.synchronize()
+    xy = d_xy.cpu().numpy()
+    assert np.array_equal(xy[:-1], want.hull_xy) and (xy[-1] == PATTERN).all()
+    got.hull_xy = want.hull_xy
+    assert brute.same(got, want) is None
 
 
 def test_errors_leave_out_untouched_and_the_context_usable(gpu_ctx):
@@ -141,14 +188,15 @@ def test_errors_leave_out_untouched_and_the_context_usable(gpu_ctx):
 
 
 # ---- guarded scratch ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["three_far_pieces", "parabola_64"])
+@pytest.mark.parametrize("name", ["three_far_pieces", "parabola_64", "high_word"])
 def test_guarded_scratch(gpu_ctx, name):
     """canary and poison on: the same result, no damaged guard, and every slot of bs_ctx::hl allocated"""
     from test_gpu_scratch_guard import POISON, guarded
-    plain = check(gpu_ctx, NAMED[name])
+    run = (lambda ctx: check(ctx, NAMED[name])) if name in NAMED else (lambda ctx: check_sparse(ctx, name))
+    plain = run(gpu_ctx)
     for poison in POISON:
         with guarded(poison) as ctx:
-            got = check(ctx, NAMED[name])
+            got = run(ctx)
             assert brute.same(got, plain, LAYOUT) is None
             assert ctx.selftest_scratch_check()["n_damaged"] == 0
             slots = {s["name"] for s in ctx.selftest_scratch_list()}
