@@ -15,7 +15,7 @@ OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libbuildingsegment_hip.so")
 SOURCES = ["bs_capi.hip", "bs_grid.hip", "bs_knn.hip", "bs_grow.hip", "bs_grow_spec.hip", "bs_prepost.hip", "bs_raster.hip",
            "bs_contour.hip", "bs_building.hip", "bs_roof.hip", "bs_solid.hip", "bs_facet.hip", "bs_outline.hip", "bs_simplify.hip", "bs_uncross.hip", "bs_sweep.hip", "bs_triangulate.hip", "bs_polysolid.hip", "bs_modelraster.hip", "bs_pointresid.hip", "bs_generalise.hip", "bs_terrain.hip", "bs_ground.hip", "bs_evidence.hip", "bs_hull.hip", "bs_fit.hip", "bs_shard.hip", "bs_sharded.hip", "bs_batch.hip"]
-HEADERS = ["bs_common.h", "bs_uf.h", "bs_segscan.h", "bs_outline.h", "bs_sweep.h", "bs_normal.h", "bs_centerdiv.h", "bs_comm.h", "bs_roofheight.h", "bs_tops.h", "bs_groundrule.h", "bs_facet_dev.h", "bs_host.h", "bs_chain.h", "bs_trispan.h", "../../include/bs_api.h", "../../include/bs_detmath.h"]
+HEADERS = ["bs_common.h", "bs_uf.h", "bs_segscan.h", "bs_outline.h", "bs_sweep.h", "bs_normal.h", "bs_centerdiv.h", "bs_comm.h", "bs_roofheight.h", "bs_tops.h", "bs_groundrule.h", "bs_facet_dev.h", "bs_host.h", "bs_grow_layout.h", "bs_chain.h", "bs_trispan.h", "../../include/bs_api.h", "../../include/bs_detmath.h"]
 # -ffp-contract=off: no FMA fusion anywhere -- host and device must round identically.
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-result"]

@@ -58,6 +58,7 @@
 
 #include "bs_centerdiv.h"
 #include "bs_common.h"
+#include "bs_grow_layout.h"
 #include "bs_host.h"
 
 namespace bs {
@@ -67,8 +68,6 @@ namespace {
 constexpr int32_t INF = 0x7fffffff;
 constexpr int32_t LOWER_BIT = (int32_t)0x80000000;  // in a reverse-list entry: the source's original index is below the target's
 constexpr int32_t POS_MASK = 0x7fffffff;
-constexpr int MAX_WAVES = 1 << 18;  // upper bound of plane attempts grown per round (the 50 M cloud has 158 k candidates in round 1)
-constexpr int MAX_PENDING = 32768;  // finished planes waiting for earlier attempts
 
 enum : int32_t { ST_NONE = 0, ST_DONE = 1, ST_FAILED0 = 2, ST_NOMEM = 3, ST_WATCHDOG = 4, ST_STOLEN = 5 };
 
@@ -2603,7 +2602,7 @@ __global__ void label_kernel(const int32_t* __restrict__ owner, int64_t n, const
 // lowest candidate inside it, so the lowest candidate of a tile of positions (Morton order: a compact piece of
 // space) is probably a real seed: those go first -- tiles of 2^16 positions, then of 2^12 -- and the rest
 // follows in seed order.  Only the dispatch order changes; the attempts keep their numbers (w = rank by seed).
-constexpr int TILE1 = 12, TILE2 = 16;
+// (TILE1 = 12, TILE2 = 16: bs_grow_layout.h, which sizes the tile arrays)
 __global__ void tile_min_kernel(const unsigned long long* __restrict__ cand, int ncand, unsigned long long* __restrict__ tmin1,
                                 unsigned long long* __restrict__ tmin2)
 {
@@ -2646,269 +2645,286 @@ struct ToI64 {
   __host__ __device__ int64_t operator()(int32_t v) const { return (int64_t)v; }
 };
 
-}  // namespace
+static_assert(sizeof(PlaneOut) == 136 && sizeof(CopyDesc) == 32, "tests/cpp/grow_layout_check.cpp stands in for them with these sizes");
 
-int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_normals, const int32_t* d_neigh,
-                            int64_t n, const bs_params& p, int32_t* d_plane_idx)
+// ---- the host side: configuration, scratch, and the phases of the header comment ---------------------------------
+#define BS_TRY(call)       \
+  do {                     \
+    const int _rc = (call); \
+    if (_rc != BS_OK)      \
+      return _rc;          \
+  } while (0)
+
+// Every switch of a run.  Read once at the top of each call (the tests set them between calls of one process); the
+// limits hook (bs_selftest_grow_limits, ctx->lim) wins over the environment.  DESIGN.md, "Grower: the host side", has the table.
+struct GrowConfig {
+  bs_grow_limits lim;
+  int retry_max_list = RETRY_MAX_LIST, retry_big_round = 1024;
+  bool retry_env = false;         // retry_max_list was set, by either: it then holds in rounds of every size
+  int64_t max_waves = MAX_WAVES;  // as asked for; GrowSizes clamps it to wave_cap
+  bool dispatch_order, foreign_identity, do_validate3;  // developer A/B switches
+  // Scheduling of the owner passes.  BS_OWNER_WORKLIST=0: the dirty groups are found by their flags,
+  // `pull_sub` per workgroup (pull_pass_kernel; the re-evaluation of a point is the same code).  BS_OWNER_GRID: fewer
+  // workgroups per pass than the default; BS_OWNER_GROUP: fewer passes per host round trip.  Results do not depend on them.
+  bool use_wl, own_grid_set = false;
+  int own_grid = 0, own_group = PULL_GROUP;
+  bool dbg, dbg_planes, verify, force_full_refresh, grow_v2, audit;
+};
+
+GrowConfig read_grow_config(const bs_ctx* ctx)
 {
-  hipStream_t st = ctx->stream;
-  ctx->rg_valid = false;
-  ctx->bt_valid = false;
-  ctx->rg_omega = nullptr;
-  ctx->rg_prio = nullptr;
-  ctx->rg_seeds = nullptr;
-  ctx->rg_nplanes = 0;
-  const int K = p.k;
-  const int64_t list_cap = 2 * n + 64;
-  const int64_t planes_cap = n / std::max(1, p.th_point_count) + 64;
-  // round pool: lists + stacks + logs of every concurrent attempt
-  // concurrent plane attempts per round: more waves let late-index planes start in earlier rounds
-  // (lim: bs_selftest_grow_limits, the in-process form of the BS_* switches below; read once, here and further down)
-  const bs_grow_limits lim = ctx->lim;
-  bs_grow_counters& gc = ctx->gc;
-  gc = bs_grow_counters{};
-  int retry_max_list = RETRY_MAX_LIST;
-  bool retry_env = false;
-  if (const char* e = getenv("BS_RETRY_MAX_LIST")) {
-    retry_max_list = atoi(e);
-    retry_env = true;
-  }
-  if (lim.retry_max_list >= 0) {
-    retry_max_list = lim.retry_max_list;
-    retry_env = true;
-  }
-  int retry_big_round = 1024;
-  if (const char* e = getenv("BS_RETRY_BIG_ROUND"))
-    retry_big_round = atoi(e);
-  if (lim.retry_big_round >= 0)
-    retry_big_round = lim.retry_big_round;
-  // Plane attempts per round: ALL candidates.  A round is a barrier bounded by its longest plane, and the big
-  // planes of a large scene are independent of each other -- but their seeds are spread over the whole index
-  // range: with the lowest 32 768 candidates per round (round 1) the 50 M cloud grew its 136 k-, 131 k- and
-  // 122 k-entry planes one round AFTER the 80 k-entry one although nothing connected them (39 k + 68 k + 35 k
-  // sequential steps; a cap of 65 536 was worse still: 68 k + 66 k + 35 k).  The ~90 % of the attempts that fail
-  // at depth 0 cost one step and 1.5 KB of pool each.  (Bounded at 2^18: with 655 k attempts on the 200 M scene the
-  // round pool outgrew 16 GB and the FIRST call on a fresh context took 3 s longer; 2^18 keeps the pool at 12 GB.)
-  int max_waves = MAX_WAVES;
-  if (const char* e = getenv("BS_MAX_WAVES"))
-    max_waves = atoi(e);
-  if (lim.max_waves > 0)
-    max_waves = (int)std::min<int64_t>(lim.max_waves, MAX_WAVES);
-  const int wave_cap = (int)std::max<int64_t>(1, std::min<int64_t>(MAX_WAVES, n / 8 + 64));  // sizes the per-attempt arrays
-  max_waves = (int)std::max<int64_t>(1, std::min<int64_t>(max_waves, wave_cap));
-  // (sized for wave_cap attempts, not for max_waves: the audit replays wave_cap attempts per batch whatever BS_MAX_WAVES
-  // or bs_selftest_grow_limits say -- on a pool sized for the lowered number its replays ended ST_NOMEM and the audit
-  // failed with "no progress" on a correct result; without a lowered max_waves the two are the same number)
-  const unsigned long long pool_cap = (unsigned long long)std::max<int64_t>(
-      std::min<int64_t>(64 * n, (int64_t)3 << 30), 8 * n + (int64_t)(2 * 256 + 32 * 32) * 2 * wave_cap);
-  // (a lowered pool: the buffer keeps its size, the attempts are told a smaller one)
-  const unsigned long long pool_cap_eff = lim.pool_cap > 0 ? std::min<unsigned long long>(pool_cap, (unsigned long long)lim.pool_cap) : pool_cap;
-  gc.pool_cap = (int64_t)pool_cap_eff;
-  gc.max_waves_end = max_waves;
-  BS_HIP(ctx, ctx->rg_list.reserve(sizeof(int32_t) * list_cap));
-  BS_HIP(ctx, ctx->rg_planes.reserve(sizeof(PlaneRec) * planes_cap));
+  GrowConfig c;
+  c.lim = ctx->lim;
+  const auto set = [](const char* name) { return getenv(name) != nullptr; };
+  const auto is_zero = [](const char* name) { return getenv(name) && atoi(getenv(name)) == 0; };
+  const auto env_int = [](const char* name, auto& v) {  // true: the variable is set, and v is its value
+    const char* e = getenv(name);
+    v = e ? atoi(e) : v;
+    return e != nullptr;
+  };
+  c.retry_env = env_int("BS_RETRY_MAX_LIST", c.retry_max_list) || c.lim.retry_max_list >= 0;
+  if (c.lim.retry_max_list >= 0)
+    c.retry_max_list = c.lim.retry_max_list;
+  env_int("BS_RETRY_BIG_ROUND", c.retry_big_round);
+  if (c.lim.retry_big_round >= 0)
+    c.retry_big_round = c.lim.retry_big_round;
+  env_int("BS_MAX_WAVES", c.max_waves);
+  if (c.lim.max_waves > 0)
+    c.max_waves = std::min<int64_t>(c.lim.max_waves, MAX_WAVES);
+  c.dispatch_order = !set("BS_NO_DISPATCH_ORDER");
+  c.foreign_identity = set("BS_FOREIGN_ORDER_IDENTITY");
+  c.do_validate3 = !set("BS_NO_VALIDATE3");
+  c.use_wl = !is_zero("BS_OWNER_WORKLIST");
+  c.own_grid_set = env_int("BS_OWNER_GRID", c.own_grid);
+  if (env_int("BS_OWNER_GROUP", c.own_group))
+    c.own_group = std::max(2, std::min(PULL_GROUP, c.own_group));
+  c.dbg = set("BS_DEBUG");  // (not once per attempt: 158 k of them in a first round)
+  c.dbg_planes = set("BS_DEBUG_PLANES");
+  c.verify = set("BS_VERIFY");
+  c.force_full_refresh = c.lim.full_refresh != 0 || set("BS_FULL_REFRESH");  // debugging aid: the pre-incremental behaviour
+  c.grow_v2 = !is_zero("BS_GROW_V2");
+  c.audit = ctx->audit || set("BS_AUDIT");
+  return c;
+}
+
+using Layout = GrowLayout<PlaneOut, CopyDesc>;
+
+// every buffer of a call, the side stream and its events
+int reserve_scratch(bs_ctx* ctx, const GrowSizes& sz, int K)
+{
+  const int64_t n = sz.n;
+  const Layout bytes(sz);
+  BS_HIP(ctx, ctx->rg_list.reserve(sizeof(int32_t) * sz.list_cap));
+  BS_HIP(ctx, ctx->rg_planes.reserve(sizeof(PlaneRec) * sz.planes_cap));
   BS_HIP(ctx, ctx->rg_stats.reserve(sizeof(GrowStats)));
-  // aux layout (int32 units): misc[1024] | hmask | omega | base | dead | prio | rpos(n+64) | vmark | seeds |
-  //                            (u8) flags | ps | occ | dirty0 | dirty1 | bdirty0 | bdirty1 | bcand |
-  //                            (i32) worklist0[nb256] | worklist1[nb256] | (u32) gflag0[nb256] | gflag1[nb256] |
-  //                            PlaneOut[MAX_WAVES + MAX_PENDING] | CopyDesc[]
-  const size_t n_i32 = (size_t)(7 * n + planes_cap + 1024 + 128);
-  const size_t nb256 = (size_t)((n + 255) / 256);
-  const size_t aux_bytes = sizeof(int32_t) * n_i32 + (size_t)5 * n + 3 * nb256 + 16 * nb256 + 8192 +
-                           sizeof(PlaneOut) * ((size_t)wave_cap + MAX_PENDING) +
-                           sizeof(CopyDesc) * ((size_t)wave_cap + MAX_PENDING);
-  BS_HIP(ctx, ctx->rg_aux.reserve(aux_bytes));
-  BS_HIP(ctx, ctx->rg_stack.reserve(sizeof(int32_t) * pool_cap));
+  BS_HIP(ctx, ctx->rg_aux.reserve(bytes.aux_bytes));
+  BS_HIP(ctx, ctx->rg_stack.reserve(sizeof(int32_t) * sz.pool_cap));
   // reverse lists: <= n (k - 1) entries with 64-bit offsets (200 M points at k = 16 are 3.0e9 entries)
   BS_HIP(ctx, ctx->rg_radj.reserve(sizeof(int32_t) * (size_t)(n * (K - 1) + 16)));
   BS_HIP(ctx, ctx->rg_roff.reserve(sizeof(int64_t) * (size_t)(n + 2)));
-  int64_t* roff = ctx->rg_roff.as<int64_t>();
-  int32_t* aux = ctx->rg_aux.as<int32_t>();
-  int32_t* d_misc = aux;  // [0]=any [1]=ncand [2]=min_idx ; [16..17] pool top (u64)
-  uint32_t* hmask = (uint32_t*)(aux + 1024);
-  int32_t* omega = aux + 1024 + n;
-  int32_t* base = aux + 1024 + 2 * n;
-  int32_t* dead = aux + 1024 + 3 * n;
-  int32_t* prio = aux + 1024 + 4 * n;    // original index of every position (n entries)
-  int32_t* rpos = aux + 1024 + 5 * n;    // n + 1 (+ pad): reverse-list counts / fill cursors, later the candidate scratch
-  int32_t* vmark = aux + 1024 + 6 * n + 64;    // duplicate detection of validate1 (n entries)
-  int32_t* d_seeds = aux + 1024 + 7 * n + 64;  // committed seeds (planes_cap)
-  uint8_t* flags = (uint8_t*)(aux + n_i32);
-  uint8_t* ps = flags + n;
-  uint32_t* occ = (uint32_t*)(((uintptr_t)(ps + n) + 15) & ~(uintptr_t)15);  // bitmap, 16-byte aligned: (n + 31) / 32 words
-  uint8_t* dirty0 = (uint8_t*)occ + ((n + 31) / 32) * 4 + 16;
-  uint8_t* dirty1 = dirty0 + n;
-  uint8_t* bdirty0 = dirty1 + n;  // one flag per 256 points
-  uint8_t* bdirty1 = bdirty0 + nb256;
-  uint8_t* bcand = bdirty1 + nb256;  // one flag per 256 positions: can the group still hold a plane seed?
-  // worklists of the owner passes (see wl_flush): two lists of groups and, for the dirty groups, two flag arrays
-  int32_t* wl_list[2];
-  uint32_t* wl_flag[2];
-  wl_list[0] = (int32_t*)(((uintptr_t)(bcand + nb256) + 15) & ~(uintptr_t)15);
-  wl_list[1] = wl_list[0] + nb256;
-  wl_flag[0] = (uint32_t*)(wl_list[1] + nb256);
-  wl_flag[1] = wl_flag[0] + nb256;
-  PlaneOut* d_out = (PlaneOut*)(((uintptr_t)(wl_flag[1] + nb256) + 255) & ~(uintptr_t)255);
-  PlaneOut* d_pend = d_out + wave_cap;
-  CopyDesc* d_copy = (CopyDesc*)(d_pend + MAX_PENDING);
-  int32_t* radj = ctx->rg_radj.as<int32_t>();
-  unsigned long long* d_pool_top = (unsigned long long*)(d_misc + 16);
-  Pool pool = {ctx->rg_stack.as<int32_t>(), d_pool_top, pool_cap_eff};
-
-  SpecArgs a;
-  a.xyz = d_xyz;
-  a.normals = d_normals;
-  a.neigh = d_neigh;
-  a.n = n;
-  a.K = K;
-  a.th = (double)p.th_thickness;
-  a.cos_th = p.cos_th;
-  a.th_count = p.th_point_count;
-  a.F = 0;
-  a.pad = 0;
-
-  const int KC = K <= 16 ? 16 : 32;
-  const int quads = 4 + KC / 4;
-  BS_HIP(ctx, ctx->rg_rec.reserve(sizeof(int4) * (size_t)quads * n));
-  int4* rec = ctx->rg_rec.as<int4>();
-  // scratch: the 64-bit fill cursors of the reverse lists during setup, then the candidate lists
-  // (unsorted | sorted, one (original index << 32 | position) key each)
-  BS_HIP(ctx, ctx->rg_geo.reserve(sizeof(unsigned long long) * 2 * (size_t)(n + 64)));
-  unsigned long long* cand_raw = ctx->rg_geo.as<unsigned long long>();
+  BS_HIP(ctx, ctx->rg_rec.reserve(sizeof(int4) * (size_t)sz.quads * n));
+  BS_HIP(ctx, ctx->rg_geo.reserve(bytes.geo_bytes));
   BS_HIP(ctx, ctx->rg_gs.reserve(sizeof(int4) * 3 * (size_t)(n + 1)));  // compact geometry by position (setup only)
-  int4* gs = ctx->rg_gs.as<int4>();
-  unsigned long long* d_cand = cand_raw + n + 64;
-  // dispatch order of big rounds: tile minima + sort keys
-  const size_t nt1 = (size_t)(n >> TILE1) + 2, nt2 = (size_t)(n >> TILE2) + 2;
-  BS_HIP(ctx, ctx->rg_disp.reserve(sizeof(unsigned long long) * (nt1 + nt2) + sizeof(uint32_t) * 2 * (size_t)wave_cap + 64 +
-                                    sizeof(PlaneOut) * (size_t)wave_cap));
-  unsigned long long* tmin1 = ctx->rg_disp.as<unsigned long long>();
-  unsigned long long* tmin2 = tmin1 + nt1;
-  uint32_t* dkeys_in = reinterpret_cast<uint32_t*>(tmin2 + nt2);
-  uint32_t* dkeys_out = dkeys_in + wave_cap;
-  PlaneOut* d_outc = reinterpret_cast<PlaneOut*>(((uintptr_t)(dkeys_out + wave_cap) + 15) & ~(uintptr_t)15);  // finished attempts of a big round, compacted
-  const bool dispatch_order = getenv("BS_NO_DISPATCH_ORDER") == nullptr;  // developer A/B switch
-  // positions = the search grid's cell-sorted (Morton) order of THIS cloud when it is cached on the context
-  const int32_t* order = (ctx->order_n == n && ctx->order_xyz == d_xyz) ? ctx->vals_out.as<int32_t>() : nullptr;
-  int32_t* pos = nullptr;
-  const int32_t* npos = (order && ctx->npos_neigh == d_neigh && ctx->npos_k == K) ? ctx->seg_npos.as<int32_t>() : nullptr;
-  (void)hipEventRecord(ctx->ev[8], st);
-  if (!npos) {
-    // Foreign input (bs_region_grow[_dev], the component-sharded stage 3): no search grid of THIS cloud's current
-    // contents is at hand (a cached order is keyed by pointer only).  The grower builds the Morton order itself --
-    // bounding box, keys, one radix sort -- instead of falling back to the identity, where every neighbour of every
-    // pass is a random HBM access (setup 134 ms instead of 31 at 50 M, HBM-latency steps).
-    static const bool identity = getenv("BS_FOREIGN_ORDER_IDENTITY") != nullptr;  // developer A/B switch
-    order = nullptr;
-    if (!identity) {
-      const int orc = build_spatial_order(ctx, d_xyz, n);
-      if (orc != BS_OK)
-        return orc;
-      order = ctx->vals_out.as<int32_t>();
-    }
+  BS_HIP(ctx, ctx->rg_disp.reserve(bytes.disp_bytes));
+  // page-locked: 158 k attempts in the first round of the 50 M cloud are 18 MB each way
+  BS_HIP(ctx, ctx->rg_hout.reserve(bytes.hout_bytes));
+  BS_HIP(ctx, ctx->rg_pstore.reserve(sizeof(int32_t) * sz.pstore_cap));
+  if (!ctx->side) {
+    BS_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+    BS_HIP(ctx, hipEventCreateWithFlags(&ctx->sev[0], hipEventDisableTiming));
+    BS_HIP(ctx, hipEventCreateWithFlags(&ctx->sev[1], hipEventDisableTiming));
   }
-  // (npos only exists for a cloud the fused pipeline just searched WITHOUT global-index indirection: spts[s].w is
-  // the original index then, and the position-ordered normals belong to exactly this normals buffer)
-  const int4* spts_in = npos ? ctx->spts.as<int4>() : nullptr;
-  const double* pnorm_in = (npos && ctx->npos_normals == d_normals) ? pnorm_of(ctx->seg_npos.as<int32_t>(), n, K) : nullptr;
-  if (order && !npos) {
-    pos = vmark;  // (free until the validation marks are cleared below)
-    invert_order_kernel<<<nblk(n, 256), 256, 0, st>>>(order, n, pos);
-  }
-  if (KC == 16)
-    build_records_kernel<16><<<nblk(n, 256), 256, 0, st>>>(a, order, pos, npos, rec, prio, gs, spts_in, pnorm_in);
-  else
-    build_records_kernel<32><<<nblk(n, 256), 256, 0, st>>>(a, order, pos, npos, rec, prio, gs, spts_in, pnorm_in);
-  // static masks + reverse-list counts in one pass, offsets by a 64-bit exclusive scan over n + 1
-  // entries (roff[n] = total), then the fill
-  BS_HIP(ctx, hipMemsetAsync(rpos, 0, sizeof(int32_t) * (n + 1), st));
-  uint32_t* lmask = reinterpret_cast<uint32_t*>(vmark);  // (free until the validation marks are cleared after the fill)
-  const int32_t* rows = npos ? npos : reinterpret_cast<const int32_t*>(rec) + 16;
-  const int row_stride = npos ? K : quads * 4;
-  static_mask_kernel<<<xcd_grid(nblk(n, 256)), 256, 0, st>>>(a, rows, row_stride, gs, hmask, rpos, lmask);
-  {
-    hipcub::TransformInputIterator<int64_t, ToI64, const int32_t*> in(rpos, ToI64());
-    BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
-      return hipcub::DeviceScan::ExclusiveScan(tmp, bytes, in, roff, hipcub::Sum(), (int64_t)0, (int)(n + 1), st);
-    }));
-  }
-  unsigned long long* rcur = cand_raw;
-  BS_HIP(ctx, hipMemcpyAsync(rcur, roff, sizeof(int64_t) * n, hipMemcpyDeviceToDevice, st));
-  rev_fill_kernel<<<xcd_grid(nblk(n, 256)), 256, 0, st>>>(hmask, rows, row_stride, n, rcur, radj, lmask);
-  // initial state: no plane; the first owner fixed point is computed by decided states (see
-  // decide_pass_kernel), after which nothing is dirty
-  fill_i32_kernel<<<nblk(n, 256), 256, 0, st>>>(base, n, INF);
-  seed_flags_kernel<<<nblk(n, 256), 256, 0, st>>>(hmask, n, K, ps);
-  BS_HIP(ctx, hipMemsetAsync(vmark, 0, sizeof(int32_t) * n, st));
-  BS_HIP(ctx, hipMemsetAsync(occ, 0, sizeof(uint32_t) * (size_t)((n + 31) / 32 + 2), st));
-  int64_t passes = 0;
+  return BS_OK;
+}
+
+// One call of launch_region_grow_spec, made once reserve_scratch has run: context, switches, sizes, the pointers into the
+// scratch (the layout is its base) and the state of the rounds.  The member functions are the phases, in the order of the call.
+struct SpecRun : Layout {
+  bs_ctx* const ctx;
+  const hipStream_t st;
+  const GrowConfig cfg;
+  const GrowSizes sz;
+  const int64_t n;
+  const int K;
+  int32_t* const d_plane_idx;
+  bs_grow_counters& gc;
+  SpecArgs a;
+  int32_t* const radj = ctx->rg_radj.as<int32_t>();  // the buffers used whole
+  int32_t* const pstore = ctx->rg_pstore.as<int32_t>();
+  int64_t* const roff = ctx->rg_roff.as<int64_t>();
+  int4 *const rec = ctx->rg_rec.as<int4>(), *const gs = ctx->rg_gs.as<int4>();
+  Pool pool = {ctx->rg_stack.as<int32_t>(), &misc->pool_top, sz.pool_cap_eff};
   // 256-point groups per workgroup of a pass: enough workgroups to fill the chip in the heavy first
   // passes, few enough that an (almost) idle pass costs microseconds
-  const int pull_sub = (int)std::max<int64_t>(1, std::min<int64_t>(64, (int64_t)nb256 / 4096));
+  const int pull_sub;
   // the candidate scan does real work in most groups until the last rounds: fewer groups per workgroup keep it parallel
-  const int cand_sub = std::max(1, pull_sub / 8);
-  // Scheduling of the owner passes, read per call.  BS_OWNER_WORKLIST=0: the dirty groups are found
-  // by their flags, `pull_sub` per workgroup (pull_pass_kernel; the re-evaluation of a point is the same code).
-  // BS_OWNER_GRID: fewer workgroups per pass than the default; BS_OWNER_GROUP: fewer passes per host round trip.
-  // Results do not depend on any of them.
-  const bool use_wl = !(getenv("BS_OWNER_WORKLIST") && atoi(getenv("BS_OWNER_WORKLIST")) == 0);
-  // a few thousand workgroups share the list: enough to fill the chip twice over in a heavy pass, and a pass
-  // with a handful of groups costs the launch of the rest (they leave after one scalar load)
-  int own_grid = (int)std::min<size_t>(nb256, 4096);
-  if (const char* e = getenv("BS_OWNER_GRID"))
-    own_grid = std::max(1, std::min(own_grid, atoi(e)));
-  constexpr int PULL_GROUP = 16;
-  int own_group = PULL_GROUP;
-  if (const char* e = getenv("BS_OWNER_GROUP"))
-    own_group = std::max(2, std::min(PULL_GROUP, atoi(e)));
-  int* const wl_cnt = d_misc + 64;  // three list lengths, see wl_flush
-  int64_t wl_pass = 0;              // owner passes launched so far: which list and which counter the next one reads
-  bool wl_marked = false;           // plane_apply_kernel has marked groups since the last settle
-  const bool dbg = getenv("BS_DEBUG") != nullptr;  // (not once per attempt: 158 k of them in a first round)
-  // per-round results read by the host: page-locked (158 k attempts in the first round of the 50 M cloud are
-  // 18 MB each way)
-  BS_HIP(ctx, ctx->rg_hout.reserve(sizeof(PlaneOut) * ((size_t)wave_cap + MAX_PENDING) + 256));
-  PlaneOut* const h_out = ctx->rg_hout.as<PlaneOut>();
-  PlaneOut* const h_pend = h_out + wave_cap;
-  int32_t* const h_flags = reinterpret_cast<int32_t*>(h_pend + MAX_PENDING);  // small scalars copied back per pass / round
-  int32_t* const h_cnt = h_flags + 48;
+  const int cand_sub;
+  int own_grid;
+  // Step engine.  grow_spec2_kernel<16> (hot loop + complete step, assumption log in an LDS ring) takes every round at
+  // k <= 16, the crowded first one included: round 1 of the 50 M cloud in 82-86 ms against the first engine's 94-97 ms,
+  // the facade's growth launches in 120.6 against 123.1 ms.  At k > 16 it would need 255 VGPRs (one wave per SIMD),
+  // and the first engine, grow_spec_kernel, wins there (urban 10 M k=32: 112 against 128 ms).
+  // BS_GROW_V2=0 puts k <= 16 on the first engine as well (the fallback; same results).
+  const bool use_spec2;
+  const int32_t* npos = nullptr;  // neighbour rows by position, when the fused pipeline left them
+  // owner passes
+  uint8_t *dcur = dirty0, *dnext = dirty1, *bcur = bdirty0, *bnext = bdirty1;
+  int64_t wl_pass = 0;     // owner passes launched so far: which list and which counter the next one reads
+  bool wl_marked = false;  // plane_apply_kernel has marked groups since the last settle
+  int64_t passes = 0;
+  // the rounds
+  int max_waves;
+  int32_t F = 0;
+  std::vector<PlaneOut> pending;
+  int64_t pstore_top = 0;
+  std::vector<PlaneRec> recs;
+  std::vector<int32_t> seeds;
+  std::vector<CopyDesc> copies;
+  int64_t list_used = 0, largest = 0, attempts = 0, rounds = 0, grow_launches = 0, incons[3] = {0, 0, 0};
+  double grow_ms = 0.0;
+  bool timed_round = false, full_refresh, dead_dirty = false, cand_listed = false, v3_pending = false;
+  int32_t ncand_all = 0, rejects_seen = 0;
+  int refused_rounds = 0, forge_mode = 0;
+  // this round
+  int npend = 0, ncand = 0, nh = 0, finals = 0, dropped = 0;
+  PlaneOut* d_outh = nullptr;  // the device array h_out mirrors
+  int32_t next_ncand_all = 0, new_min = 0, rejects_now = 0, first_bad = 0;
+  bool nomem_lowest = false;
+  std::vector<PlaneOut> next_pending;
+
+  SpecRun(bs_ctx* c, const GrowConfig& cf, const GrowSizes& s, const int32_t* d_xyz, const double* d_normals, const int32_t* d_neigh,
+          const bs_params& p, int32_t* out)
+      : Layout(s, c->rg_aux.p, c->rg_disp.p, c->rg_hout.p, c->rg_geo.p), ctx(c), st(c->stream), cfg(cf), sz(s), n(s.n), K(p.k),
+        d_plane_idx(out), gc(c->gc), a{d_xyz, d_normals, d_neigh, s.n, p.k, (double)p.th_thickness, p.cos_th, p.th_point_count, 0, 0},
+        pull_sub((int)std::max<int64_t>(1, std::min<int64_t>(64, (int64_t)sz.nb256 / 4096))), cand_sub(std::max(1, pull_sub / 8)),
+        use_spec2(sz.KC == 16 && cfg.grow_v2), max_waves(sz.max_waves), full_refresh(cfg.force_full_refresh)
   {
-    // decided states in groups of own_group passes with one copy-back per group, as propagate() below does it: a pass
+    // a few thousand workgroups share the list: enough to fill the chip twice over in a heavy pass, and a pass
+    // with a handful of groups costs the launch of the rest (they leave after one scalar load)
+    own_grid = (int)std::min<size_t>(sz.nb256, 4096);
+    if (cfg.own_grid_set)
+      own_grid = std::max(1, std::min(own_grid, cfg.own_grid));
+  }
+  // validate3 runs on the side stream beside the owner passes: whatever way the call is left (a failed HIP call,
+  // the watchdog, a refused plane), nothing of it may still be in flight on the buffers the next call reuses
+  ~SpecRun()
+  {
+    if (v3_pending && ctx->side)
+      (void)hipStreamSynchronize(ctx->side);
+  }
+
+  // positions = the search grid's cell-sorted (Morton) order of THIS cloud when it is cached on the context
+  int order_and_records()
+  {
+    const int32_t* order = (ctx->order_n == n && ctx->order_xyz == a.xyz) ? ctx->vals_out.as<int32_t>() : nullptr;
+    npos = (order && ctx->npos_neigh == a.neigh && ctx->npos_k == K) ? ctx->seg_npos.as<int32_t>() : nullptr;
+    (void)hipEventRecord(ctx->ev[8], st);
+    if (!npos) {
+      // Foreign input (bs_region_grow[_dev], the component-sharded stage 3): no search grid of THIS cloud's current
+      // contents is at hand (a cached order is keyed by pointer only).  The grower builds the Morton order itself --
+      // bounding box, keys, one radix sort -- instead of falling back to the identity, where every neighbour of every
+      // pass is a random HBM access (setup 134 ms instead of 31 at 50 M, HBM-latency steps).
+      order = nullptr;
+      if (!cfg.foreign_identity) {
+        BS_TRY(build_spatial_order(ctx, a.xyz, n));
+        order = ctx->vals_out.as<int32_t>();
+      }
+    }
+    // (npos only exists for a cloud the fused pipeline just searched WITHOUT global-index indirection: spts[s].w is
+    // the original index then, and the position-ordered normals belong to exactly this normals buffer)
+    const int4* spts_in = npos ? ctx->spts.as<int4>() : nullptr;
+    const double* pnorm_in = (npos && ctx->npos_normals == a.normals) ? pnorm_of(ctx->seg_npos.as<int32_t>(), n, K) : nullptr;
+    int32_t* pos = nullptr;
+    if (order && !npos) {
+      pos = pos_in_vmark();
+      invert_order_kernel<<<nblk(n, 256), 256, 0, st>>>(order, n, pos);
+    }
+    if (sz.KC == 16)
+      build_records_kernel<16><<<nblk(n, 256), 256, 0, st>>>(a, order, pos, npos, rec, prio, gs, spts_in, pnorm_in);
+    else
+      build_records_kernel<32><<<nblk(n, 256), 256, 0, st>>>(a, order, pos, npos, rec, prio, gs, spts_in, pnorm_in);
+    return BS_OK;
+  }
+
+  // static masks + reverse-list counts in one pass, offsets by a 64-bit exclusive scan over n + 1
+  // entries (roff[n] = total), then the fill
+  int masks_and_reverse_lists()
+  {
+    BS_HIP(ctx, hipMemsetAsync(rpos, 0, sizeof(int32_t) * (n + 1), st));
+    uint32_t* lmask = lmask_in_vmark();
+    const int32_t* rows = npos ? npos : reinterpret_cast<const int32_t*>(rec) + 16;
+    const int row_stride = npos ? K : sz.quads * 4;
+    static_mask_kernel<<<xcd_grid(nblk(n, 256)), 256, 0, st>>>(a, rows, row_stride, gs, hmask, rpos, lmask);
+    {
+      hipcub::TransformInputIterator<int64_t, ToI64, const int32_t*> in(rpos, ToI64());
+      BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+        return hipcub::DeviceScan::ExclusiveScan(tmp, bytes, in, roff, hipcub::Sum(), (int64_t)0, (int)(n + 1), st);
+      }));
+    }
+    unsigned long long* rcur = rcur_in_cand_raw();
+    BS_HIP(ctx, hipMemcpyAsync(rcur, roff, sizeof(int64_t) * n, hipMemcpyDeviceToDevice, st));
+    rev_fill_kernel<<<xcd_grid(nblk(n, 256)), 256, 0, st>>>(hmask, rows, row_stride, n, rcur, radj, lmask);
+    return BS_OK;
+  }
+
+  // initial state: no plane; the first owner fixed point is computed by decided states (see
+  // decide_pass_kernel), after which nothing is dirty
+  int first_fixed_point()
+  {
+    fill_i32_kernel<<<nblk(n, 256), 256, 0, st>>>(base, n, INF);
+    seed_flags_kernel<<<nblk(n, 256), 256, 0, st>>>(hmask, n, K, ps);
+    BS_HIP(ctx, hipMemsetAsync(vmark, 0, sizeof(int32_t) * n, st));
+    BS_HIP(ctx, hipMemsetAsync(occ, 0, sizeof(uint32_t) * (size_t)((n + 31) / 32 + 2), st));
+    // decided states in groups of own_group passes with one copy-back per group, as settle() below does it: a pass
     // behind the deciding one leaves after one scalar load (13 passes and 13 round trips at 50 M before).  Whatever
     // BS_OWNER_WORKLIST says: the grouping is BS_OWNER_GROUP's.  (`passes`, and with it GrowStats.steps, counts
     // launches: 16 here at 50 M where it counted 13.)
-    uint8_t* state = dirty1;  // scratch until the dirty flags are cleared below
-    uint8_t* bund = bdirty1;
-    int32_t* const d_any = d_misc + 32;  // (d_flip below)
+    uint8_t* state = state_in_dirty1();
+    uint8_t* bund = bund_in_bdirty1();
+    int32_t* const d_any = misc->flip;
     decide_init_kernel<<<nblk(n, 256), 256, 0, st>>>(hmask, n, state, bund);
     for (int it = 0;; it++) {
       BS_HIP(ctx, hipMemsetAsync(d_any, 0, sizeof(int32_t) * PULL_GROUP, st));
-      for (int g = 0; g < own_group; g++, passes++)
-        decide_pass_kernel<<<(int)((nb256 + pull_sub - 1) / pull_sub), 256, 0, st>>>(n, pull_sub, prio, roff, radj, state, bund,
-                                                                                    d_any + g, g ? d_any + g - 1 : nullptr);
-      BS_HIP(ctx, hipMemcpyAsync(h_cnt, d_any + own_group - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      for (int g = 0; g < cfg.own_group; g++, passes++)
+        decide_pass_kernel<<<(int)((sz.nb256 + pull_sub - 1) / pull_sub), 256, 0, st>>>(n, pull_sub, prio, roff, radj, state, bund,
+                                                                                       d_any + g, g ? d_any + g - 1 : nullptr);
+      BS_HIP(ctx, hipMemcpyAsync(&hf->decided_any, d_any + cfg.own_group - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
       BS_HIP(ctx, hipStreamSynchronize(st));
-      if (h_cnt[0] == 0)
+      if (hf->decided_any == 0)
         break;
       if (it > 4 * 1000 * 1000)
         return fail(ctx, BS_ERR_INTERNAL, "orphan fixed point (decided states) did not converge");
     }
-    decide_finish_kernel<<<nblk(n, 256), 256, 0, st>>>(n, prio, roff, radj, state, omega, occ, rec, quads, rpos);
-    BS_HIP(ctx, hipMemsetAsync(wl_cnt, 0, 3 * sizeof(int), st));
-    BS_HIP(ctx, hipMemsetAsync(wl_flag[0], 0, sizeof(uint32_t) * 2 * nb256, st));
+    decide_finish_kernel<<<nblk(n, 256), 256, 0, st>>>(n, prio, roff, radj, state, omega, occ, rec, sz.quads, minr_in_rpos());
+    BS_HIP(ctx, hipMemsetAsync(misc->wl_cnt, 0, 3 * sizeof(int), st));
+    BS_HIP(ctx, hipMemsetAsync(wl_flag[0], 0, sizeof(uint32_t) * 2 * sz.nb256, st));
+    BS_HIP(ctx, hipMemsetAsync(dirty0, 0, n, st));
+    BS_HIP(ctx, hipMemsetAsync(dirty1, 0, n, st));
+    BS_HIP(ctx, hipMemsetAsync(bdirty0, 0, sz.nb256, st));
+    BS_HIP(ctx, hipMemsetAsync(bdirty1, 0, sz.nb256, st));
+    BS_HIP(ctx, hipMemsetAsync(bcand, 1, sz.nb256, st));
+    BS_HIP(ctx, hipMemsetAsync(dead, 0, sizeof(int32_t) * n, st));
+    BS_TRY(settle());
+    (void)hipEventRecord(ctx->ev[9], st);
+    forge_mode = ctx->forge_mode;  // self-test, once per call
+    ctx->forge_mode = 0;
+    BS_HIP(ctx, hipMemsetAsync(&misc->rej, 0, sizeof(RefusalStats), st));
+    return BS_OK;
   }
-  BS_HIP(ctx, hipMemsetAsync(dirty0, 0, n, st));
-  BS_HIP(ctx, hipMemsetAsync(dirty1, 0, n, st));
-  BS_HIP(ctx, hipMemsetAsync(bdirty0, 0, nb256, st));
-  BS_HIP(ctx, hipMemsetAsync(bdirty1, 0, nb256, st));
-  BS_HIP(ctx, hipMemsetAsync(bcand, 1, nb256, st));
-  BS_HIP(ctx, hipMemsetAsync(dead, 0, sizeof(int32_t) * n, st));
-  uint8_t* dcur = dirty0;
-  uint8_t* dnext = dirty1;
-  uint8_t* bcur = bdirty0;
-  uint8_t* bnext = bdirty1;
-  // The passes are launched in groups of PULL_GROUP with ONE host round trip per group: a pass that finds
-  // nothing dirty costs microseconds, a round trip ~50 us, and a plane insertion settles in 8-25 passes.
+
+  // BS_VERIFY: `launch` gets the word its checking kernel counts into; one round trip
+  template <class L>
+  int verify_count(int& nb, L launch)
+  {
+    BS_HIP(ctx, hipMemsetAsync(&misc->verify_bad, 0, sizeof(int), st));
+    launch(&misc->verify_bad);
+    BS_HIP(ctx, hipMemcpyAsync(&nb, &misc->verify_bad, sizeof nb, hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipStreamSynchronize(st));
+    return BS_OK;
+  }
+
+  // Lets the owners settle.  The passes are launched in groups of PULL_GROUP with ONE host round trip per group: a pass
+  // that finds nothing dirty costs microseconds, a round trip ~50 us, and a plane insertion settles in 8-25 passes.
   // Every pass reports its flips in its own word; the structure is a fixed point when the LAST pass of a
   // group flipped nothing (the passes after the settling one find no dirty point and do nothing).
   // (16 per group: a settling takes 8-26 passes, so ONE round trip usually decides it; the passes launched after
@@ -2916,11 +2932,13 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
   // (BS_OWNER_GROUP lowers the passes per group.  The worklist of the dirty groups, its counters and wl_pass carry
   // over from one group to the next and from one settle to the next: the first pass of a group reads what the last
   // pass of the group before it, or plane_apply_kernel, appended.)
-  int32_t* const d_flip = d_misc + 32;
-  int32_t* const h_flip = h_flags + 32;
-  int32_t* const d_pstat = d_misc + 128;  // BS_DEBUG: four statistics per pass of a group, see pull_stats
-  auto propagate = [&]() -> int {
-    if (use_wl && wl_marked)
+  int settle()
+  {
+    const size_t nb256 = sz.nb256;
+    const int quads = sz.quads, own_group = cfg.own_group;
+    const bool dbg = cfg.dbg;
+    int32_t *const d_flip = misc->flip, *const d_pstat = misc->pstat, *const wl_cnt = misc->wl_cnt, *const minr = minr_in_rpos();
+    if (cfg.use_wl && wl_marked)
       wl_compact_kernel<<<(int)((nb256 + WL_CAP - 1) / WL_CAP), 256, 0, st>>>(bcur, (int)nb256, wl_flag[wl_pass & 1], wl_list[wl_pass & 1],
                                                                       wl_cnt + wl_pass % 3);
     wl_marked = false;
@@ -2929,25 +2947,24 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       if (dbg)
         BS_HIP(ctx, hipMemsetAsync(d_pstat, 0, sizeof(int32_t) * 4 * PULL_GROUP, st));
       for (int g = 0; g < own_group; g++) {
-        if (use_wl) {
+        if (cfg.use_wl) {
           const int cur = (int)(wl_pass & 1);
           pull_list_kernel<<<own_grid, 256, 0, st>>>(n, K, hmask, prio, ps, base, roff, radj, omega, occ, dcur, dnext, wl_list[cur],
                                                     wl_list[cur ^ 1], wl_flag[cur], wl_flag[cur ^ 1], wl_cnt, (int)(wl_pass % 3),
                                                     (int)((wl_pass + 1) % 3), (int)((wl_pass + 2) % 3), rec, quads, d_flip + g,
-                                                    rpos /* = minr after the setup */, dbg ? d_pstat + 4 * g : nullptr);
+                                                    minr, dbg ? d_pstat + 4 * g : nullptr);
           wl_pass++;
         } else {
           pull_pass_kernel<<<(int)((nb256 + pull_sub - 1) / pull_sub), 256, 0, st>>>(n, K, pull_sub, hmask, prio, ps, base, roff, radj,
                                                                                     omega, occ, dcur, dnext, bcur, bnext, rec, quads,
-                                                                                    d_flip + g, rpos /* = minr after the setup */,
-                                                                                    g ? d_flip + g - 1 : nullptr,
+                                                                                    d_flip + g, minr, g ? d_flip + g - 1 : nullptr,
                                                                                     dbg ? d_pstat + 4 * g : nullptr);
         }
         passes++;
         std::swap(dcur, dnext);  // dcur now holds the newly dirtied points (the old dcur was cleared by the pass)
         std::swap(bcur, bnext);
       }
-      BS_HIP(ctx, hipMemcpyAsync(h_flip, d_flip, sizeof(int32_t) * PULL_GROUP, hipMemcpyDeviceToHost, st));
+      BS_HIP(ctx, hipMemcpyAsync(hf->flip, d_flip, sizeof(int32_t) * PULL_GROUP, hipMemcpyDeviceToHost, st));
       if (dbg) {
         int32_t hs[4 * PULL_GROUP];
         BS_HIP(ctx, hipMemcpyAsync(hs, d_pstat, sizeof hs, hipMemcpyDeviceToHost, st));
@@ -2958,13 +2975,12 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
                     (long)(passes - own_group + g), hs[4 * g], hs[4 * g + 1], hs[4 * g + 2], hs[4 * g + 3]);
       }
       BS_HIP(ctx, hipStreamSynchronize(st));
-      if (!h_flip[own_group - 1]) {
-        if (getenv("BS_VERIFY")) {
-          BS_HIP(ctx, hipMemsetAsync(d_misc + 3, 0, sizeof(int), st));
-          verify_fixpoint_kernel<<<nblk(n, 256), 256, 0, st>>>(n, hmask, prio, ps, base, roff, radj, omega, occ, d_misc + 3);
+      if (!hf->flip[own_group - 1]) {
+        if (cfg.verify) {
           int nb = 0;
-          BS_HIP(ctx, hipMemcpyAsync(&nb, d_misc + 3, sizeof nb, hipMemcpyDeviceToHost, st));
-          BS_HIP(ctx, hipStreamSynchronize(st));
+          BS_TRY(verify_count(nb, [&](int* bad) {
+            verify_fixpoint_kernel<<<nblk(n, 256), 256, 0, st>>>(n, hmask, prio, ps, base, roff, radj, omega, occ, bad);
+          }));
           if (nb)
             fprintf(stderr, "[bs] VERIFY: owner structure is not a fixed point at %d points (pass %ld)\n", nb, (long)passes);
         }
@@ -2972,236 +2988,166 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       }
     }
     return fail(ctx, BS_ERR_INTERNAL, "orphan fixed point did not converge");
-  };
-  int rc = propagate();
-  if (rc != BS_OK)
-    return rc;
-  (void)hipEventRecord(ctx->ev[9], st);
-
-  // persistent store for planes that finished consistently but cannot be
-  // finalised yet (an earlier attempt is still open): kept across rounds and
-  // re-validated instead of being re-grown
-  const int64_t pstore_cap = 6 * n + 65536;
-  BS_HIP(ctx, ctx->rg_pstore.reserve(sizeof(int32_t) * pstore_cap));
-  const int64_t pstore_lim = lim.pstore_cap > 0 ? std::min<int64_t>(pstore_cap, lim.pstore_cap) : pstore_cap;
-  const int pend_lim = lim.max_pending > 0 ? (int)std::min<int64_t>(MAX_PENDING, lim.max_pending) : MAX_PENDING;
-  int32_t* pstore = ctx->rg_pstore.as<int32_t>();
-  int64_t pstore_top = 0;
-  std::vector<PlaneOut> pending;
-
-  std::vector<PlaneRec> recs;
-  std::vector<int32_t> seeds;
-  std::vector<CopyDesc> copies;
-  int64_t list_used = 0, largest = 0, attempts = 0, rounds = 0, grow_launches = 0;
-  double grow_ms = 0.0;
-  bool timed_round = false;
-  const bool force_full_refresh = lim.full_refresh != 0 || getenv("BS_FULL_REFRESH") != nullptr;  // debugging aid: the pre-incremental behaviour
-  bool full_refresh = force_full_refresh;
-  int32_t F = 0;
-  auto commit_plane = [&](const PlaneOut& o, const int32_t* src_pool) -> int {
-    attempts++;
-    if (!o.keep)
-      return BS_OK;  // rolled back: no trace
-    if (list_used + o.list_n > list_cap || (int64_t)recs.size() >= planes_cap)
-      return fail(ctx, BS_ERR_INTERNAL, "region grow (speculative): list pool overflow");
-    copies.push_back({src_pool + o.list_off, ctx->rg_list.as<int32_t>() + list_used, o.list_n, prio});
-    PlaneRec r;
-    for (int c = 0; c < 3; c++) {
-      r.normal[c] = o.normal[c];
-      r.center[c] = o.center[c];
-    }
-    r.list_off = list_used;
-    r.list_n = o.list_n;
-    r.id = (int32_t)recs.size() + 1;
-    r.seed = o.seed;
-    r.pad = 0;
-    recs.push_back(r);
-    seeds.push_back(o.seed);
-    list_used += o.list_n;
-    largest = std::max<int64_t>(largest, o.list_n);
-    return BS_OK;
-  };
-  auto flush_copies = [&]() -> int {
-    for (size_t off = 0; off < copies.size(); off += (size_t)wave_cap + MAX_PENDING) {
-      const int nd = (int)std::min<size_t>(copies.size() - off, (size_t)wave_cap + MAX_PENDING);
-      BS_HIP(ctx, hipMemcpyAsync(d_copy, copies.data() + off, sizeof(CopyDesc) * nd, hipMemcpyHostToDevice, st));
-      copy_lists_kernel<<<dim3(nd, 8), 256, 0, st>>>(d_copy, nd);
-      BS_HIP(ctx, hipStreamSynchronize(st));  // descriptors are reused
-    }
-    copies.clear();
-    return BS_OK;
-  };
-  bool cand_listed = false;
-  int32_t ncand_all = 0;
-  bool v3_pending = false;
-  // validate3 runs on the side stream beside the owner passes: whatever way this function is left (a failed HIP call,
-  // the watchdog, a refused plane), nothing of it may still be in flight on the buffers the next call reuses
-  struct SideGuard {
-    bs_ctx* c;
-    bool* pending;
-    ~SideGuard()
-    {
-      if (*pending && c->side)
-        (void)hipStreamSynchronize(c->side);
-    }
-  } side_guard{ctx, &v3_pending};
-  bool dead_dirty = false;
-  if (!ctx->side) {
-    BS_HIP(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-    BS_HIP(ctx, hipEventCreateWithFlags(&ctx->sev[0], hipEventDisableTiming));
-    BS_HIP(ctx, hipEventCreateWithFlags(&ctx->sev[1], hipEventDisableTiming));
   }
-  int32_t rejects_seen = 0;
-  int refused_rounds = 0;
-  int64_t incons[3] = {0, 0, 0};
-  int forge_mode = ctx->forge_mode;
-  ctx->forge_mode = 0;
-  const bool do_validate3 = getenv("BS_NO_VALIDATE3") == nullptr;  // developer A/B switch
-  // Step engine.  grow_spec2_kernel<16> (hot loop + complete step, assumption log in an LDS ring) takes every round at
-  // k <= 16, the crowded first one included: round 1 of the 50 M cloud in 82-86 ms against the first engine's 94-97 ms,
-  // the facade's growth launches in 120.6 against 123.1 ms.  At k > 16 it would need 255 VGPRs (one wave per SIMD),
-  // and the first engine, grow_spec_kernel, wins there (urban 10 M k=32: 112 against 128 ms).
-  // BS_GROW_V2=0 puts k <= 16 on the first engine as well (the fallback; same results).
-  const bool use_spec2 = KC == 16 && !(getenv("BS_GROW_V2") && atoi(getenv("BS_GROW_V2")) == 0);
-  auto launch_grow = [&](int cnt, const unsigned long long* cd, PlaneOut* o, int rml, const uint32_t* ord) {
+
+  // ---- the launches that are made from more than one place ----
+  // candidates from F_ up under the current owners (all_seeds: every attempt that exists), appended unordered to cand_raw
+  void launch_cand_flag(int32_t F_, int all_seeds, int32_t* min_idx)
+  {
+    cand_flag_kernel<<<(int)((sz.nb256 + cand_sub - 1) / cand_sub), 256, 0, st>>>(rec, sz.quads, K, n, F_, prio, ps, all_seeds, omega, min_idx,
+                                                                                 cand_raw, &misc->cand.listed, bcand, cand_sub);
+  }
+  // a listing on its own, with its round trip
+  int list_and_count(int32_t F_, int all_seeds, int32_t& count)
+  {
+    BS_HIP(ctx, hipMemsetAsync(&misc->cand.listed, 0, sizeof(int32_t), st));
+    launch_cand_flag(F_, all_seeds, nullptr);
+    BS_HIP(ctx, hipMemcpyAsync(&hf->ncand, &misc->cand.listed, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipStreamSynchronize(st));
+    count = hf->ncand;
+    return BS_OK;
+  }
+  void launch_grow(int cnt, const unsigned long long* cd, PlaneOut* o, int rml, const uint32_t* ord)
+  {
     const int64_t cap = 512 * n + 4096;
     if (use_spec2)
       grow_spec2_kernel<16><<<cnt, 64, 0, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
-    else if (KC == 16)
+    else if (sz.KC == 16)
       grow_spec_kernel<16><<<cnt, 64, 0, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
     else
       grow_spec_kernel<32><<<cnt, 64, 0, st>>>(a, cd, cnt, rec, dead, pool, o, cap, rml, ord);
-  };
-  BS_HIP(ctx, hipMemsetAsync(d_misc + 4, 0, 12 * sizeof(int), st));  // [4] refused planes, [5] forged seed + 1, [6] forged one refused, [12..15] refusals by check
-  for (;;) {
+  }
+  // frees the claims of the attempts in d_out
+  void reset_tags(int cnt) { reset_tags_kernel<<<cnt, VT, 0, st>>>(d_out, cnt, pool.base, rec, sz.quads, K); }
+  // dead[] is only ever written for seeds of the attempts in d_cand: clear exactly those (not 4 n bytes per round)
+  void reset_dead(int cnt) { reset_dead_kernel<<<nblk(cnt, 256), 256, 0, st>>>(d_cand, cnt, dead); }
+  void apply_planes(PlaneOut* o, int cnt, const int32_t* lists)
+  {
+    plane_apply_kernel<<<cnt, VT, 0, st>>>(o, cnt, lists, base, ps, dcur, bcur, omega, occ, rec, sz.quads);
+    wl_marked = true;
+  }
+
+  // Lowest new plane-attempt candidates under the current owners (pending planes are in the structure, their seeds are
+  // not candidates).  One pass: the sparse candidates are appended unordered and the few entries are sorted; a flag
+  // array + stream compaction over all n points cost 0.7 ms per round at 50 M.  The list is usually left over from the
+  // end of the previous round: the pass that looks for the lowest NEW candidate sees exactly the owners this round
+  // starts from unless planes were dropped.  Leaves ncand_all == 0 && npend == 0 when no plane attempt is left.
+  int list_candidates()
+  {
     rounds++;
     gc.rounds = rounds;
     a.F = F;
-    const int npend = (int)pending.size();
-    // lowest new plane-attempt candidates under the current owners (pending
-    // planes are in the structure, their seeds are not candidates)
-    // (one pass: the sparse candidates are appended unordered into rpos -- free after the reverse
-    // lists were built -- and the few entries are sorted; a flag array + stream compaction over
-    // all n points cost 0.7 ms per round at 50 M)
-    // (the list is usually left over from the end of the previous round: the pass that looks for the
-    // lowest NEW candidate sees exactly the owners this round starts from unless planes were dropped)
-    if (!cand_listed) {
-      BS_HIP(ctx, hipMemsetAsync(d_misc + 1, 0, sizeof(int32_t), st));
-      cand_flag_kernel<<<(int)((nb256 + cand_sub - 1) / cand_sub), 256, 0, st>>>(rec, quads, K, n, F, prio, ps, 0, omega, nullptr, cand_raw, d_misc + 1, bcand, cand_sub);
-      BS_HIP(ctx, hipMemcpyAsync(h_flags + 11, d_misc + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      BS_HIP(ctx, hipStreamSynchronize(st));
-      ncand_all = h_flags[11];
-    }
+    npend = (int)pending.size();
+    if (!cand_listed)
+      BS_TRY(list_and_count(F, 0, ncand_all));
     cand_listed = false;
     if (ncand_all == 0 && npend == 0)
-      break;  // no plane attempt left: omega is the final owner array
+      return BS_OK;
     if (ncand_all > 0) {
       BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
         return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, cand_raw, d_cand, ncand_all, 0, 64, st);
       }));
     }
-    const int ncand = std::min<int>(ncand_all, max_waves);
+    ncand = std::min<int>(ncand_all, max_waves);
     gc.rounds_capped += ncand_all > max_waves ? 1 : 0;
     gc.rounds_big += ncand >= 4096 ? 1 : 0;
     if (npend)
       BS_HIP(ctx, hipMemcpyAsync(d_pend, pending.data(), sizeof(PlaneOut) * npend, hipMemcpyHostToDevice, st));
-    if (ncand > 0) {
-      // grow them concurrently against the current owners
-      // Records are maintained incrementally: pull_pass_kernel writes every owner change
-      // into the record and reset_tags_kernel frees the claims of the previous round.  A
-      // full pass is only needed after a pool exhaustion (claims of a plane that ran out
-      // of memory between claiming and listing are not recorded anywhere).
-      if (full_refresh) {
-        refresh_records_kernel<<<nblk(n, 256), 256, 0, st>>>(omega, rec, quads, n);
-        gc.full_refreshes++;
-        full_refresh = force_full_refresh;
-      } else if (getenv("BS_VERIFY")) {
-        BS_HIP(ctx, hipMemsetAsync(d_misc + 3, 0, sizeof(int), st));
-        verify_records_kernel<<<nblk(n, 256), 256, 0, st>>>(omega, rec, quads, n, d_misc + 3);
-        int nb = 0;
-        BS_HIP(ctx, hipMemcpyAsync(&nb, d_misc + 3, sizeof nb, hipMemcpyDeviceToHost, st));
-        BS_HIP(ctx, hipStreamSynchronize(st));
-        if (nb)
-          fprintf(stderr, "[bs] VERIFY: %d records differ from a full refresh (round %ld)\n", nb, (long)rounds);
-      }
-      if (dead_dirty) {  // after a pool exhaustion stale tags can point at seeds outside the round's candidate list
-        BS_HIP(ctx, hipMemsetAsync(dead, 0, sizeof(int32_t) * n, st));
-        dead_dirty = false;
-      }
-      BS_HIP(ctx, hipMemsetAsync(d_pool_top, 0, sizeof(unsigned long long), st));
-      const uint32_t* d_order = nullptr;
-      if (dispatch_order && ncand >= 4096) {  // see dispatch_key_kernel
-        BS_HIP(ctx, hipMemsetAsync(tmin1, 0xff, sizeof(unsigned long long) * (nt1 + nt2), st));
-        tile_min_kernel<<<nblk(ncand, 256), 256, 0, st>>>(d_cand, ncand, tmin1, tmin2);
-        dispatch_key_kernel<<<nblk(ncand, 256), 256, 0, st>>>(d_cand, ncand, tmin1, tmin2, dkeys_in);
-        BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
-          return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, dkeys_in, dkeys_out, ncand, 0, 20, st);
-        }));
-        d_order = dkeys_out;
-      }
-      (void)hipEventRecord(ctx->ev[6], st);
-      // In-launch re-growth of a plane that lost a point: always for short lists.  For long lists only in rounds
-      // with many attempts: such a round lasts as long as its longest independent plane, so a long plane that
-      // is grown again has the time to finish inside the same launch (urban 10 M: +20 %); in a round of a few
-      // chained planes (the facade) the re-growth only repeats work the next round does anyway (-23 %).
-      const int rml = (ncand >= retry_big_round && !retry_env) ? 0x7fffffff : retry_max_list;
-      launch_grow(ncand, d_cand, d_out, rml, d_order);
-      (void)hipEventRecord(ctx->ev[7], st);
-      grow_launches++;
-      timed_round = true;
-      if (forge_mode) {  // self-test: corrupt one finished plane (see forge_kernel); once per call
-        forge_kernel<<<1, 64, 0, st>>>(d_out, ncand, pool.base, forge_mode, d_misc + 5);
-        forge_mode = 0;
-      }
-      validate1_kernel<<<ncand, VT, 0, st>>>(d_out, ncand, pool.base, rec, quads, dead, n, vmark,
-                                             (int32_t)((rounds & 0x3ff) << 20), d_misc + 4);
-      if (do_validate3) {
-        // beside the owner passes: it only reads the finished lists and the records' geometry, and is one
-        // wave of sequential f64 adds per plane -- the main stream's kernels are memory bound
-        BS_HIP(ctx, hipEventRecord(ctx->sev[0], st));
-        BS_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->sev[0], 0));
-        validate3_kernel<<<ncand, V3T, 0, ctx->side>>>(d_out, ncand, pool.base, rec, quads, d_misc + 4);
-        BS_HIP(ctx, hipEventRecord(ctx->sev[1], ctx->side));
-        v3_pending = true;
-      }
-      reset_tags_kernel<<<ncand, VT, 0, st>>>(d_out, ncand, pool.base, rec, quads, K);
-      // dead[] is only ever written for seeds of this round's attempts: clear exactly those (not 4 n bytes per round)
-      reset_dead_kernel<<<nblk(ncand, 256), 256, 0, st>>>(d_cand, ncand, dead);
-      // insert the finished planes and let the owners settle
-      plane_apply_kernel<<<ncand, VT, 0, st>>>(d_out, ncand, pool.base, base, ps, dcur, bcur, omega, occ, rec, quads);
-      wl_marked = true;
-      rc = propagate();
-      if (rc != BS_OK)
-        return rc;
-      validate2_kernel<<<ncand, VT, 0, st>>>(d_out, ncand, pool.base, omega, rec, quads, K);
+    return BS_OK;
+  }
+
+  // grows the round's attempts concurrently against the current owners, inserts the finished planes and lets the owners settle
+  int grow_and_insert()
+  {
+    // Records are maintained incrementally: pull_pass_kernel writes every owner change
+    // into the record and reset_tags_kernel frees the claims of the previous round.  A
+    // full pass is only needed after a pool exhaustion (claims of a plane that ran out
+    // of memory between claiming and listing are not recorded anywhere).
+    if (full_refresh) {
+      refresh_records_kernel<<<nblk(n, 256), 256, 0, st>>>(omega, rec, sz.quads, n);
+      gc.full_refreshes++;
+      full_refresh = cfg.force_full_refresh;
+    } else if (cfg.verify) {
+      int nb = 0;
+      BS_TRY(verify_count(nb, [&](int* bad) { verify_records_kernel<<<nblk(n, 256), 256, 0, st>>>(omega, rec, sz.quads, n, bad); }));
+      if (nb)
+        fprintf(stderr, "[bs] VERIFY: %d records differ from a full refresh (round %ld)\n", nb, (long)rounds);
     }
+    if (dead_dirty) {  // after a pool exhaustion stale tags can point at seeds outside the round's candidate list
+      BS_HIP(ctx, hipMemsetAsync(dead, 0, sizeof(int32_t) * n, st));
+      dead_dirty = false;
+    }
+    BS_HIP(ctx, hipMemsetAsync(pool.top, 0, sizeof(unsigned long long), st));
+    const uint32_t* d_order = nullptr;
+    if (cfg.dispatch_order && ncand >= 4096) {  // see dispatch_key_kernel
+      BS_HIP(ctx, hipMemsetAsync(tmin1, 0xff, sizeof(unsigned long long) * (sz.nt1 + sz.nt2), st));
+      tile_min_kernel<<<nblk(ncand, 256), 256, 0, st>>>(d_cand, ncand, tmin1, tmin2);
+      dispatch_key_kernel<<<nblk(ncand, 256), 256, 0, st>>>(d_cand, ncand, tmin1, tmin2, dkeys_in);
+      BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
+        return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, dkeys_in, dkeys_out, ncand, 0, 20, st);
+      }));
+      d_order = dkeys_out;
+    }
+    (void)hipEventRecord(ctx->ev[6], st);
+    // In-launch re-growth of a plane that lost a point: always for short lists.  For long lists only in rounds
+    // with many attempts: such a round lasts as long as its longest independent plane, so a long plane that
+    // is grown again has the time to finish inside the same launch (urban 10 M: +20 %); in a round of a few
+    // chained planes (the facade) the re-growth only repeats work the next round does anyway (-23 %).
+    const int rml = (ncand >= cfg.retry_big_round && !cfg.retry_env) ? 0x7fffffff : cfg.retry_max_list;
+    launch_grow(ncand, d_cand, d_out, rml, d_order);
+    (void)hipEventRecord(ctx->ev[7], st);
+    grow_launches++;
+    timed_round = true;
+    if (forge_mode) {  // self-test: corrupt one finished plane (see forge_kernel); once per call
+      forge_kernel<<<1, 64, 0, st>>>(d_out, ncand, pool.base, forge_mode, &misc->rej.forged_seed1);
+      forge_mode = 0;
+    }
+    validate1_kernel<<<ncand, VT, 0, st>>>(d_out, ncand, pool.base, rec, sz.quads, dead, n, vmark, (int32_t)((rounds & 0x3ff) << 20),
+                                           &misc->rej.refused);
+    if (cfg.do_validate3) {
+      // beside the owner passes: it only reads the finished lists and the records' geometry, and is one
+      // wave of sequential f64 adds per plane -- the main stream's kernels are memory bound
+      BS_HIP(ctx, hipEventRecord(ctx->sev[0], st));
+      BS_HIP(ctx, hipStreamWaitEvent(ctx->side, ctx->sev[0], 0));
+      validate3_kernel<<<ncand, V3T, 0, ctx->side>>>(d_out, ncand, pool.base, rec, sz.quads, &misc->rej.refused);
+      BS_HIP(ctx, hipEventRecord(ctx->sev[1], ctx->side));
+      v3_pending = true;
+    }
+    reset_tags(ncand);
+    reset_dead(ncand);
+    apply_planes(d_out, ncand, pool.base);
+    BS_TRY(settle());
+    validate2_kernel<<<ncand, VT, 0, st>>>(d_out, ncand, pool.base, omega, rec, sz.quads, K);
+    return BS_OK;
+  }
+
+  // Lowest candidate under the new owners (= first attempt that is not established yet) and, in the same pass, the
+  // candidate list of the next round; then everything the host judges by, with the round's one blocking wait.
+  int read_back()
+  {
     if (npend)
-      validate2_kernel<<<npend, VT, 0, st>>>(d_pend, npend, pstore, omega, rec, quads, K);
-    // lowest candidate under the new owners (= first attempt that is not established yet) and, in the
-    // same pass, the candidate list of the next round
+      validate2_kernel<<<npend, VT, 0, st>>>(d_pend, npend, pstore, omega, rec, sz.quads, K);
     const int32_t init2[2] = {0, INF};
-    BS_HIP(ctx, hipMemcpyAsync(d_misc + 1, init2, sizeof init2, hipMemcpyHostToDevice, st));
-    cand_flag_kernel<<<(int)((nb256 + cand_sub - 1) / cand_sub), 256, 0, st>>>(rec, quads, K, n, F, prio, ps, 0, omega, d_misc + 2, cand_raw, d_misc + 1, bcand, cand_sub);
-    // (d_misc[1] = number of candidates listed, d_misc[2] = the lowest one: one copy into the page-locked flags)
-    BS_HIP(ctx, hipMemcpyAsync(h_flags + 8, d_misc + 1, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(&misc->cand, init2, sizeof init2, hipMemcpyHostToDevice, st));
+    launch_cand_flag(F, 0, &misc->cand.lowest);
+    BS_HIP(ctx, hipMemcpyAsync(&hf->next_cand, &misc->cand, sizeof(CandCount), hipMemcpyDeviceToHost, st));
     if (v3_pending) {  // validate3's verdicts (PlaneOut.v3ok, the refusal counter) are read below
       BS_HIP(ctx, hipStreamWaitEvent(st, ctx->sev[1], 0));
       v3_pending = false;
     }
-    BS_HIP(ctx, hipMemcpyAsync(h_flags + 10, d_misc + 4, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    BS_HIP(ctx, hipMemcpyAsync(&hf->refused, &misc->rej.refused, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     // A big round's attempts mostly failed at depth 0 (152 k of 158 k in the first round of the 50 M cloud) and the
     // host never looks at those: only the others travel, in seed order (20 MB each way and a 2 ms walk over
     // page-locked memory otherwise).  nh = entries on the host, d_outh = the device array they mirror.
-    const bool compact = ncand >= 4096 && !dbg;
-    int nh = ncand;
-    PlaneOut* d_outh = d_out;
-    if (compact) {
+    nh = ncand;
+    d_outh = d_out;
+    if (ncand >= 4096 && !cfg.dbg) {
       BS_HIP(ctx, cub_run(ctx->cub_tmp, [&](void* tmp, size_t& bytes) {
-        return hipcub::DeviceSelect::If(tmp, bytes, d_out, d_outc, d_misc + 20, ncand, KeepForHost(), st);
+        return hipcub::DeviceSelect::If(tmp, bytes, d_out, d_outc, &misc->n_for_host, ncand, KeepForHost(), st);
       }));
-      BS_HIP(ctx, hipMemcpyAsync(h_flags + 14, d_misc + 20, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      BS_HIP(ctx, hipMemcpyAsync(&hf->n_for_host, &misc->n_for_host, sizeof(int32_t), hipMemcpyDeviceToHost, st));
       BS_HIP(ctx, hipStreamSynchronize(st));
-      nh = h_flags[14];
+      nh = hf->n_for_host;
       d_outh = d_outc;
     }
     if (nh)
@@ -3209,19 +3155,27 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
     if (npend)
       BS_HIP(ctx, hipMemcpyAsync(h_pend, d_pend, sizeof(PlaneOut) * npend, hipMemcpyDeviceToHost, st));
     BS_HIP(ctx, hipStreamSynchronize(st));
-    const int32_t next_ncand_all = h_flags[8], new_min = h_flags[9], rejects_now = h_flags[10];
+    next_ncand_all = hf->next_cand.listed;
+    new_min = hf->next_cand.lowest;
+    rejects_now = hf->refused;
     if (timed_round) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]) == hipSuccess)
         grow_ms += ms;
       timed_round = false;
     }
-    // first attempt (by seed index) whose result is not established
-    int32_t first_bad = new_min;
-    bool nomem_lowest = false;
+    return BS_OK;
+  }
+
+  // first_bad: the first attempt (by seed index) whose result is not established; nomem_lowest: the round pool was
+  // too small for the lowest attempt, so fewer attempts share it from now on
+  int judge()
+  {
+    first_bad = new_min;
+    nomem_lowest = false;
     for (int w = 0; w < nh; w++) {
       const PlaneOut& o = h_out[w];
-      if (dbg && o.list_n > n + 1)
+      if (cfg.dbg && o.list_n > n + 1)
         fprintf(stderr, "[bs] IMPOSSIBLE list: round %ld w=%d seed=%d status=%d consistent=%d list_n=%ld steps=%ld log=%ld thief=%d\n",
                 (long)rounds, w, o.seed, o.status, o.consistent, (long)o.list_n, (long)o.steps, (long)o.log_n, o.thief);
       if (o.status == ST_WATCHDOG)
@@ -3252,175 +3206,217 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
       gc.waves_cut++;
       gc.max_waves_end = max_waves;
     }
+    return BS_OK;
+  }
+
+  // BS_DEBUG: what the round's attempts ended as, and when the longest of them ran
+  void report_round() const
+  {
 #ifdef BS_PROBE
-    if (dbg) {
-      unsigned long long hp[32];
-      (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_prof2), sizeof(hp));
-      const double nstep = (double)hp[10] + 1.0;
-      fprintf(stderr, "[prof2] steps=%llu expansions=%llu | pop+issue=%.0f state=%.0f wait=%.0f test+classify=%.0f claims+walk=%.0f log+counters=%.0f "
-                      "flushchk=%.0f list+defer=%.0f push=%.0f top=%.0f (cycles per step, cumulative over rounds)\n",
-              hp[10], hp[11], hp[0] / nstep, hp[1] / nstep, hp[2] / nstep, hp[3] / nstep, hp[4] / nstep, hp[5] / nstep, hp[6] / nstep,
-              hp[7] / nstep, hp[8] / nstep, hp[9] / nstep);
-      // exits of the hot loop in this round (every plane; the counters are reset after each print; engine 3 is
-      // grow_spec2_kernel, 1 grow_spec_kernel, as in profiles/r04_grow_exits_urban_50m.txt)
-      unsigned long long he[16];
-      (void)hipMemcpyFromSymbol(he, HIP_SYMBOL(g_exit2), sizeof(he));
-      fprintf(stderr, "[exits] round %ld attempts %d engine %d | hot steps %llu complete steps %llu | lifo-empty %llu watchdog %llu "
-                      "refill %llu stolen %llu earlier-claim %llu list-ring %llu lifo-window %llu log-ring %llu\n",
-              (long)rounds, ncand, use_spec2 ? 3 : 1, he[9], he[10], he[0], he[1], he[2], he[3], he[4], he[6], he[7], he[8]);
-      memset(he, 0, sizeof(he));
-      (void)hipMemcpyToSymbol(HIP_SYMBOL(g_exit2), he, sizeof(he));
-    }
+    unsigned long long hp[32];
+    (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_prof2), sizeof(hp));
+    const double nstep = (double)hp[10] + 1.0;
+    fprintf(stderr, "[prof2] steps=%llu expansions=%llu | pop+issue=%.0f state=%.0f wait=%.0f test+classify=%.0f claims+walk=%.0f log+counters=%.0f "
+                    "flushchk=%.0f list+defer=%.0f push=%.0f top=%.0f (cycles per step, cumulative over rounds)\n",
+            hp[10], hp[11], hp[0] / nstep, hp[1] / nstep, hp[2] / nstep, hp[3] / nstep, hp[4] / nstep, hp[5] / nstep, hp[6] / nstep,
+            hp[7] / nstep, hp[8] / nstep, hp[9] / nstep);
+    // exits of the hot loop in this round (every plane; the counters are reset after each print; engine 3 is
+    // grow_spec2_kernel, 1 grow_spec_kernel, as in profiles/r04_grow_exits_urban_50m.txt)
+    unsigned long long he[16];
+    (void)hipMemcpyFromSymbol(he, HIP_SYMBOL(g_exit2), sizeof(he));
+    fprintf(stderr, "[exits] round %ld attempts %d engine %d | hot steps %llu complete steps %llu | lifo-empty %llu watchdog %llu "
+                    "refill %llu stolen %llu earlier-claim %llu list-ring %llu lifo-window %llu log-ring %llu\n",
+            (long)rounds, ncand, use_spec2 ? 3 : 1, he[9], he[10], he[0], he[1], he[2], he[3], he[4], he[6], he[7], he[8]);
+    memset(he, 0, sizeof(he));
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_exit2), he, sizeof(he));
 #endif
-    if (dbg) {
-      int cnt[6] = {0, 0, 0, 0, 0, 0}, cons = 0, pcons = 0;
-      int64_t maxsteps = 0, sumsteps = 0, maxlist = 0;
-      for (int w = 0; w < ncand; w++) {
-        cnt[h_out[w].status]++;
-        cons += h_out[w].status == ST_DONE && h_out[w].consistent;
-        maxsteps = std::max(maxsteps, h_out[w].steps);
-        sumsteps += h_out[w].steps;
-        maxlist = std::max(maxlist, h_out[w].list_n);
-      }
-      for (int w = 0; w < npend; w++)
-        pcons += h_pend[w].consistent;
-      {  // when did the longest attempts start and end, relative to the first wave of the launch?
-        int64_t t0 = INT64_MAX, t1 = 0;
-        std::vector<int> idx;
-        for (int w = 0; w < ncand; w++) {
-          t0 = std::min(t0, h_out[w].t_start);
-          t1 = std::max(t1, h_out[w].t_end);
-          if (h_out[w].steps > 2000)
-            idx.push_back(w);
-        }
-        std::sort(idx.begin(), idx.end(), [&](int x, int y) { return h_out[x].steps > h_out[y].steps; });
-        fprintf(stderr, "[bs]   launch span %.2f ms; longest attempts (w, steps, status, start ms, end ms, us/step):", (t1 - t0) / 1e5);
-        for (size_t q = 0; q < std::min<size_t>(idx.size(), 12); q++) {
-          const PlaneOut& o = h_out[idx[q]];
-          fprintf(stderr, " [%d %ld %d %.2f %.2f %.3f xcc%d se%d cu%d simd%d]", idx[q], (long)o.steps, o.status, (o.t_start - t0) / 1e5,
-                  (o.t_end - t0) / 1e5, (o.t_end - o.t_start) / 100.0 / (double)o.steps, (o.pad5 >> 16) & 0xf, (o.pad5 >> 13) & 7,
-                  (o.pad5 >> 8) & 0xf, (o.pad5 >> 4) & 3);
-        }
-        fprintf(stderr, "\n");
-        if (ncand > 20000) {
-          fprintf(stderr, "[bs]   start ms by w:");
-          for (int w = 0; w < ncand; w += 8192)
-            fprintf(stderr, " %d:%.2f", w, (h_out[w].t_start - t0) / 1e5);
-          double life0 = 0, lifep = 0;
-          int64_t n0 = 0, npl = 0;
-          for (int w = 0; w < ncand; w++) {
-            if (h_out[w].status == ST_FAILED0) {
-              life0 += (h_out[w].t_end - h_out[w].t_start) / 100.0;
-              n0++;
-            } else {
-              lifep += (h_out[w].t_end - h_out[w].t_start) / 100.0;
-              npl++;
-            }
-          }
-          fprintf(stderr, "\n[bs]   mean lifetime: failed0 %.1f us (%ld), others %.1f us (%ld); wave-time total %.1f ms\n", life0 / std::max<int64_t>(n0, 1),
-                  (long)n0, lifep / std::max<int64_t>(npl, 1), (long)npl, (life0 + lifep) / 1e3);
-        }
-      }
-      int why[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int w = 0; w < ncand; w++)
-        if (h_out[w].status == ST_DONE && !h_out[w].consistent)
-          why[h_out[w].pad4 & 7]++;
-      fprintf(stderr, "[bs]   inconsistent new planes by failed test (1 seed row, 2 list, 4 log; sums): 1:%d 2:%d 3:%d 4:%d 5:%d 6:%d 7:%d\n",
-              why[1], why[2], why[3], why[4], why[5], why[6], why[7]);
-      fprintf(stderr,
-              "[bs] round %ld F=%d ncand_all=%d grown=%d done=%d (consistent %d) failed0=%d nomem=%d stolen=%d "
-              "pending=%d (consistent %d) first_bad=%d new_min=%d maxsteps=%ld sumsteps=%ld maxlist=%ld passes=%ld\n",
-              (long)rounds, F, ncand_all, ncand, cnt[ST_DONE], cons, cnt[ST_FAILED0], cnt[ST_NOMEM], cnt[ST_STOLEN],
-              npend, pcons, first_bad, new_min, (long)maxsteps, (long)sumsteps, (long)maxlist, (long)passes);
-      if (getenv("BS_DEBUG_PLANES"))
-        for (int w = 0; w < ncand; w++)
-          fprintf(stderr, "[bs]   plane seed=%d status=%d consistent=%d steps=%ld list=%ld log=%ld thief=%d\n",
-                  h_out[w].seed, h_out[w].status, h_out[w].consistent, (long)h_out[w].steps, (long)h_out[w].list_n,
-                  (long)h_out[w].log_n, h_out[w].thief);
+    int cnt[6] = {0, 0, 0, 0, 0, 0}, cons = 0, pcons = 0;
+    int64_t maxsteps = 0, sumsteps = 0, maxlist = 0;
+    for (int w = 0; w < ncand; w++) {
+      cnt[h_out[w].status]++;
+      cons += h_out[w].status == ST_DONE && h_out[w].consistent;
+      maxsteps = std::max(maxsteps, h_out[w].steps);
+      sumsteps += h_out[w].steps;
+      maxlist = std::max(maxlist, h_out[w].list_n);
     }
-    // merge pending and new planes in seed order: below first_bad -> final,
-    // consistent ones above it stay pending, the rest is dropped from the structure
-    std::vector<PlaneOut> next_pending;
-    int finals = 0, dropped = 0;
-    int pend_room = pend_lim;  // old pending planes that stay have priority over new ones
+    for (int w = 0; w < npend; w++)
+      pcons += h_pend[w].consistent;
+    {  // when did the longest attempts start and end, relative to the first wave of the launch?
+      int64_t t0 = INT64_MAX, t1 = 0;
+      std::vector<int> idx;
+      for (int w = 0; w < ncand; w++) {
+        t0 = std::min(t0, h_out[w].t_start);
+        t1 = std::max(t1, h_out[w].t_end);
+        if (h_out[w].steps > 2000)
+          idx.push_back(w);
+      }
+      std::sort(idx.begin(), idx.end(), [&](int x, int y) { return h_out[x].steps > h_out[y].steps; });
+      fprintf(stderr, "[bs]   launch span %.2f ms; longest attempts (w, steps, status, start ms, end ms, us/step):", (t1 - t0) / 1e5);
+      for (size_t q = 0; q < std::min<size_t>(idx.size(), 12); q++) {
+        const PlaneOut& o = h_out[idx[q]];
+        fprintf(stderr, " [%d %ld %d %.2f %.2f %.3f xcc%d se%d cu%d simd%d]", idx[q], (long)o.steps, o.status, (o.t_start - t0) / 1e5,
+                (o.t_end - t0) / 1e5, (o.t_end - o.t_start) / 100.0 / (double)o.steps, (o.pad5 >> 16) & 0xf, (o.pad5 >> 13) & 7,
+                (o.pad5 >> 8) & 0xf, (o.pad5 >> 4) & 3);
+      }
+      fprintf(stderr, "\n");
+      if (ncand > 20000) {
+        fprintf(stderr, "[bs]   start ms by w:");
+        for (int w = 0; w < ncand; w += 8192)
+          fprintf(stderr, " %d:%.2f", w, (h_out[w].t_start - t0) / 1e5);
+        double life0 = 0, lifep = 0;
+        int64_t n0 = 0, npl = 0;
+        for (int w = 0; w < ncand; w++) {
+          if (h_out[w].status == ST_FAILED0) {
+            life0 += (h_out[w].t_end - h_out[w].t_start) / 100.0;
+            n0++;
+          } else {
+            lifep += (h_out[w].t_end - h_out[w].t_start) / 100.0;
+            npl++;
+          }
+        }
+        fprintf(stderr, "\n[bs]   mean lifetime: failed0 %.1f us (%ld), others %.1f us (%ld); wave-time total %.1f ms\n", life0 / std::max<int64_t>(n0, 1),
+                (long)n0, lifep / std::max<int64_t>(npl, 1), (long)npl, (life0 + lifep) / 1e3);
+      }
+    }
+    int why[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int w = 0; w < ncand; w++)
+      if (h_out[w].status == ST_DONE && !h_out[w].consistent)
+        why[h_out[w].pad4 & 7]++;
+    fprintf(stderr, "[bs]   inconsistent new planes by failed test (1 seed row, 2 list, 4 log; sums): 1:%d 2:%d 3:%d 4:%d 5:%d 6:%d 7:%d\n",
+            why[1], why[2], why[3], why[4], why[5], why[6], why[7]);
+    fprintf(stderr,
+            "[bs] round %ld F=%d ncand_all=%d grown=%d done=%d (consistent %d) failed0=%d nomem=%d stolen=%d "
+            "pending=%d (consistent %d) first_bad=%d new_min=%d maxsteps=%ld sumsteps=%ld maxlist=%ld passes=%ld\n",
+            (long)rounds, F, ncand_all, ncand, cnt[ST_DONE], cons, cnt[ST_FAILED0], cnt[ST_NOMEM], cnt[ST_STOLEN],
+            npend, pcons, first_bad, new_min, (long)maxsteps, (long)sumsteps, (long)maxlist, (long)passes);
+    if (cfg.dbg_planes)
+      for (int w = 0; w < ncand; w++)
+        fprintf(stderr, "[bs]   plane seed=%d status=%d consistent=%d steps=%ld list=%ld log=%ld thief=%d\n",
+                h_out[w].seed, h_out[w].status, h_out[w].consistent, (long)h_out[w].steps, (long)h_out[w].list_n,
+                (long)h_out[w].log_n, h_out[w].thief);
+  }
+
+  // a final plane: its record, its seed, and the copy of its list (positions -> original indices) into rg_list
+  int commit_plane(const PlaneOut& o, const int32_t* src_pool)
+  {
+    attempts++;
+    if (!o.keep)
+      return BS_OK;  // rolled back: no trace
+    if (list_used + o.list_n > sz.list_cap || (int64_t)recs.size() >= sz.planes_cap)
+      return fail(ctx, BS_ERR_INTERNAL, "region grow (speculative): list pool overflow");
+    copies.push_back({src_pool + o.list_off, ctx->rg_list.as<int32_t>() + list_used, o.list_n, prio});
+    PlaneRec r;
+    for (int c = 0; c < 3; c++) {
+      r.normal[c] = o.normal[c];
+      r.center[c] = o.center[c];
+    }
+    r.list_off = list_used;
+    r.list_n = o.list_n;
+    r.id = (int32_t)recs.size() + 1;
+    r.seed = o.seed;
+    r.pad = 0;
+    recs.push_back(r);
+    seeds.push_back(o.seed);
+    list_used += o.list_n;
+    largest = std::max<int64_t>(largest, o.list_n);
+    return BS_OK;
+  }
+
+  // merge pending and new planes in seed order: below first_bad -> final,
+  // consistent ones above it stay pending, the rest is dropped from the structure
+  int merge()
+  {
+    next_pending.clear();
+    finals = dropped = 0;
+    int pend_room = sz.pend_lim;  // old pending planes that stay have priority over new ones
     for (int w = 0; w < npend; w++)
       pend_room -= (h_pend[w].consistent && h_pend[w].seed >= first_bad) ? 1 : 0;
-    {
-      int ip = 0, iw = 0;
-      while (ip < npend || iw < nh) {
-        const bool take_p = (iw >= nh) || (ip < npend && h_pend[ip].seed < h_out[iw].seed);
-        PlaneOut& o = take_p ? h_pend[ip] : h_out[iw];
-        const int32_t* src = take_p ? pstore : pool.base;
-        if (take_p)
-          ip++;
+    int ip = 0, iw = 0;
+    while (ip < npend || iw < nh) {
+      const bool take_p = (iw >= nh) || (ip < npend && h_pend[ip].seed < h_out[iw].seed);
+      PlaneOut& o = take_p ? h_pend[ip] : h_out[iw];
+      const int32_t* src = take_p ? pstore : pool.base;
+      if (take_p)
+        ip++;
+      else
+        iw++;
+      o.pad = 0;  // command for plane_apply_kernel: 2 = drop
+      if (o.status != ST_DONE)
+        continue;  // never entered the structure
+      if (!o.consistent || !o.v3ok) {
+        o.pad = 2;
+        dropped++;
+        gc.dropped_other++;
+        continue;  // re-enters as a candidate (or orphan maker) next round
+      }
+      if (o.seed < first_bad) {
+        finals++;
+        if (cfg.dbg && o.keep)
+          fprintf(stderr, "[bs]   commit seed=%d n=%ld log=%ld steps=%ld from=%s round=%ld first_bad=%d\n", o.seed,
+                  (long)o.list_n, (long)o.log_n, (long)o.steps, take_p ? "pending" : "new", (long)rounds, first_bad);
+        BS_TRY(commit_plane(o, src));
+      } else if (take_p) {
+        next_pending.push_back(o);
+      } else if (pend_room > 0 && pstore_top + o.list_n + o.log_n + 8 <= sz.pstore_lim) {
+        pend_room--;
+        PlaneOut q = o;
+        q.list_off = pstore_top;
+        copies.push_back({pool.base + o.list_off, pstore + q.list_off, o.list_n, nullptr});
+        pstore_top += (o.list_n + 3) & ~(int64_t)3;
+        q.log_off = pstore_top;
+        if (o.log_n)
+          copies.push_back({pool.base + o.log_off, pstore + q.log_off, o.log_n, nullptr});
+        pstore_top += (o.log_n + 3) & ~(int64_t)3;
+        next_pending.push_back(q);
+      } else {
+        o.pad = 2;  // no room to keep it: drop, it will be grown again
+        dropped++;
+        if (pend_room > 0)
+          gc.dropped_pend_store++;
         else
-          iw++;
-        o.pad = 0;  // command for plane_apply_kernel: 2 = drop
-        if (o.status != ST_DONE)
-          continue;  // never entered the structure
-        if (!o.consistent || !o.v3ok) {
-          o.pad = 2;
-          dropped++;
-          gc.dropped_other++;
-          continue;  // re-enters as a candidate (or orphan maker) next round
-        }
-        if (o.seed < first_bad) {
-          finals++;
-          if (dbg && o.keep)
-            fprintf(stderr, "[bs]   commit seed=%d n=%ld log=%ld steps=%ld from=%s round=%ld first_bad=%d\n", o.seed,
-                    (long)o.list_n, (long)o.log_n, (long)o.steps, take_p ? "pending" : "new", (long)rounds, first_bad);
-          rc = commit_plane(o, src);
-          if (rc != BS_OK)
-            return rc;
-        } else if (take_p) {
-          next_pending.push_back(o);
-        } else if (pend_room > 0 && pstore_top + o.list_n + o.log_n + 8 <= pstore_lim) {
-          pend_room--;
-          PlaneOut q = o;
-          q.list_off = pstore_top;
-          copies.push_back({pool.base + o.list_off, pstore + q.list_off, o.list_n, nullptr});
-          pstore_top += (o.list_n + 3) & ~(int64_t)3;
-          q.log_off = pstore_top;
-          if (o.log_n)
-            copies.push_back({pool.base + o.log_off, pstore + q.log_off, o.log_n, nullptr});
-          pstore_top += (o.log_n + 3) & ~(int64_t)3;
-          next_pending.push_back(q);
-        } else {
-          o.pad = 2;  // no room to keep it: drop, it will be grown again
-          dropped++;
-          if (pend_room > 0)
-            gc.dropped_pend_store++;
-          else
-            gc.dropped_pend_count++;
-        }
+          gc.dropped_pend_count++;
       }
     }
-    rc = flush_copies();
-    if (rc != BS_OK)
-      return rc;
+    for (size_t off = 0; off < copies.size(); off += (size_t)sz.wave_cap + MAX_PENDING) {
+      const int nd = (int)std::min<size_t>(copies.size() - off, (size_t)sz.wave_cap + MAX_PENDING);
+      BS_HIP(ctx, hipMemcpyAsync(d_copy, copies.data() + off, sizeof(CopyDesc) * nd, hipMemcpyHostToDevice, st));
+      copy_lists_kernel<<<dim3(nd, 8), 256, 0, st>>>(d_copy, nd);
+      BS_HIP(ctx, hipStreamSynchronize(st));  // descriptors are reused
+    }
+    copies.clear();
+    return BS_OK;
+  }
+
+  // takes the dropped planes out of the structure and lets the owners settle; without a drop the owners are unchanged
+  // since the candidate pass of read_back, and its list is the next round's
+  int apply_drops()
+  {
     if (dropped) {
       if (nh) {
         BS_HIP(ctx, hipMemcpyAsync(d_outh, h_out, sizeof(PlaneOut) * nh, hipMemcpyHostToDevice, st));
-        plane_apply_kernel<<<nh, VT, 0, st>>>(d_outh, nh, pool.base, base, ps, dcur, bcur, omega, occ, rec, quads);
-        wl_marked = true;
+        apply_planes(d_outh, nh, pool.base);
       }
       if (npend) {
         BS_HIP(ctx, hipMemcpyAsync(d_pend, h_pend, sizeof(PlaneOut) * npend, hipMemcpyHostToDevice, st));
-        plane_apply_kernel<<<npend, VT, 0, st>>>(d_pend, npend, pstore, base, ps, dcur, bcur, omega, occ, rec, quads);
-        wl_marked = true;
+        apply_planes(d_pend, npend, pstore);
       }
-      rc = propagate();
-      if (rc != BS_OK)
-        return rc;
+      BS_TRY(settle());
     } else {
-      cand_listed = true;  // owners unchanged since the candidate pass above: its list is the next round's
+      cand_listed = true;
       ncand_all = next_ncand_all;
     }
     pending.swap(next_pending);
     if (pending.empty())
       pstore_top = 0;
-    if (first_bad == INF)
-      break;  // every plane attempt is final; omega holds the remaining orphan makers' fixed point
+    return BS_OK;
+  }
+
+  // moves F up; done: every plane attempt is final and omega holds the remaining orphan makers' fixed point
+  int advance(bool& done)
+  {
+    done = first_bad == INF;
+    if (done)
+      return BS_OK;
     // a plane the validation refused is simply grown again; only a refusal that repeats is fatal
     const bool refused = rejects_now > rejects_seen;
     rejects_seen = rejects_now;
@@ -3431,69 +3427,71 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
     F = first_bad;
     if (rounds > 4 * n + 16)
       return fail(ctx, BS_ERR_INTERNAL, "region grow (speculative): round limit");
+    return BS_OK;
   }
-  int32_t* owner_final = omega;
-  // labels and plane records
-  const int np = (int)recs.size();
-  if (np > 0) {
-    BS_HIP(ctx, hipMemcpyAsync(d_seeds, seeds.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
-    BS_HIP(ctx, hipMemcpyAsync(ctx->rg_planes.p, recs.data(), sizeof(PlaneRec) * np, hipMemcpyHostToDevice, st));
-  }
-  label_kernel<<<nblk(n, 256), 256, 0, st>>>(owner_final, n, d_seeds, np, prio, d_plane_idx);
-  int32_t vstat[12] = {0};
-  BS_HIP(ctx, hipMemcpyAsync(vstat, d_misc + 4, sizeof vstat, hipMemcpyDeviceToHost, st));
-  GrowStats hs;
-  hs.n_planes = np;
-  hs.error = 0;
-  hs.list_used = list_used;
-  hs.seed_attempts = attempts;
-  hs.largest = largest;
-  hs.steps = passes;
-  BS_HIP(ctx, hipMemcpyAsync(ctx->rg_stats.p, &hs, sizeof hs, hipMemcpyHostToDevice, st));
-  BS_HIP(ctx, hipStreamSynchronize(st));
-  BS_HIP(ctx, hipGetLastError());
-  ctx->rg_n = n;
-  ctx->rg_valid = true;
-  ctx->rg_omega = owner_final;
-  ctx->rg_prio = prio;
-  ctx->rg_seeds = d_seeds;
-  ctx->rg_nplanes = np;
-  ctx->tm.largest_plane = largest;
-  ctx->tm.n_seed_attempts = attempts;
-  ctx->tm.rg_rounds = rounds;
-  ctx->tm.grow_kernel_ms = grow_ms;
-  ctx->tm.grow_kernel_launches = grow_launches;
-  ctx->tm.validation_rejects = vstat[0];
-  ctx->tm.forged_seed = vstat[1] - 1;
-  ctx->tm.forged_refused = vstat[2];
-  ctx->tm.rej_v1_robbed = vstat[8];
-  ctx->tm.rej_v1_tag = vstat[9];
-  ctx->tm.rej_v1_dup = vstat[10];
-  ctx->tm.rej_v3_state = vstat[11];
-  ctx->tm.incons_seed = incons[0];
-  ctx->tm.incons_list = incons[1];
-  ctx->tm.incons_log = incons[2];
+
+  // labels, plane records, statistics: omega is the final owner array
+  int finish()
   {
+    const int np = (int)recs.size();
+    if (np > 0) {
+      BS_HIP(ctx, hipMemcpyAsync(d_seeds, seeds.data(), sizeof(int32_t) * np, hipMemcpyHostToDevice, st));
+      BS_HIP(ctx, hipMemcpyAsync(ctx->rg_planes.p, recs.data(), sizeof(PlaneRec) * np, hipMemcpyHostToDevice, st));
+    }
+    label_kernel<<<nblk(n, 256), 256, 0, st>>>(omega, n, d_seeds, np, prio, d_plane_idx);
+    RefusalStats rej{};
+    BS_HIP(ctx, hipMemcpyAsync(&rej, &misc->rej, sizeof rej, hipMemcpyDeviceToHost, st));
+    GrowStats hs;
+    hs.n_planes = np;
+    hs.error = 0;
+    hs.list_used = list_used;
+    hs.seed_attempts = attempts;
+    hs.largest = largest;
+    hs.steps = passes;
+    BS_HIP(ctx, hipMemcpyAsync(ctx->rg_stats.p, &hs, sizeof hs, hipMemcpyHostToDevice, st));
+    BS_HIP(ctx, hipStreamSynchronize(st));
+    BS_HIP(ctx, hipGetLastError());
+    ctx->rg_n = n;
+    ctx->rg_valid = true;
+    ctx->rg_omega = omega;
+    ctx->rg_prio = prio;
+    ctx->rg_seeds = d_seeds;
+    ctx->rg_nplanes = np;
+    ctx->tm.largest_plane = largest;
+    ctx->tm.n_seed_attempts = attempts;
+    ctx->tm.rg_rounds = rounds;
+    ctx->tm.grow_kernel_ms = grow_ms;
+    ctx->tm.grow_kernel_launches = grow_launches;
+    ctx->tm.validation_rejects = rej.refused;
+    ctx->tm.forged_seed = rej.forged_seed1 - 1;
+    ctx->tm.forged_refused = rej.forged_refused;
+    ctx->tm.rej_v1_robbed = rej.v1_robbed;
+    ctx->tm.rej_v1_tag = rej.v1_tag;
+    ctx->tm.rej_v1_dup = rej.v1_dup;
+    ctx->tm.rej_v3_state = rej.v3_state;
+    ctx->tm.incons_seed = incons[0];
+    ctx->tm.incons_list = incons[1];
+    ctx->tm.incons_log = incons[2];
     float ms = 0.f;
     ctx->tm.grow_setup_ms = hipEventElapsedTime(&ms, ctx->ev[8], ctx->ev[9]) == hipSuccess ? (double)ms : 0.0;
+    ctx->tm.audit_attempts = -1;
+    ctx->tm.audit_mismatches = 0;
+    ctx->tm.audit_ms = 0.0;
+    return BS_OK;
   }
-  ctx->tm.audit_attempts = -1;
-  ctx->tm.audit_mismatches = 0;
-  ctx->tm.audit_ms = 0.0;
-  if (ctx->audit || getenv("BS_AUDIT")) {
-    // Every plane attempt that exists under the final owners, grown again without speculation (a.F = INF:
-    // an owner below the seed is final and taken, everything else is free at the seed's time) and compared
-    // with what was committed -- see bs_set_audit in include/bs_api.h.
+
+  // Every plane attempt that exists under the final owners, grown again without speculation (a.F = INF:
+  // an owner below the seed is final and taken, everything else is free at the seed's time) and compared
+  // with what was committed -- see bs_set_audit in include/bs_api.h.
+  int audit()
+  {
     const auto t0 = std::chrono::steady_clock::now();
-    pool.cap = pool_cap;  // (the replay is the judge: it never runs on a pool bs_selftest_grow_limits lowered)
-    BS_HIP(ctx, hipMemsetAsync(bcand, 1, nb256, st));
-    BS_HIP(ctx, hipMemsetAsync(d_misc + 1, 0, sizeof(int32_t), st));
-    BS_HIP(ctx, hipMemsetAsync(d_misc + 8, 0, 2 * sizeof(int32_t), st));
-    cand_flag_kernel<<<(int)((nb256 + cand_sub - 1) / cand_sub), 256, 0, st>>>(rec, quads, K, n, 0, prio, ps, 1, omega, nullptr,
-                                                                              cand_raw, d_misc + 1, bcand, cand_sub);
-    BS_HIP(ctx, hipMemcpyAsync(h_flags + 11, d_misc + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    BS_HIP(ctx, hipStreamSynchronize(st));
-    const int na = h_flags[11];
+    const int np = (int)recs.size(), wave_cap = sz.wave_cap;
+    pool.cap = sz.pool_cap;  // (the replay is the judge: it never runs on a pool bs_selftest_grow_limits lowered)
+    BS_HIP(ctx, hipMemsetAsync(bcand, 1, sz.nb256, st));
+    BS_HIP(ctx, hipMemsetAsync(&misc->audit, 0, sizeof(AuditStats), st));
+    int32_t na = 0;
+    BS_TRY(list_and_count(0, 1, na));
     // Committed planes only ever claim their own points, so all of them replay concurrently.  An attempt the
     // reference rolled back gave its points free again: its replay may claim points that belong to later
     // planes (or to another rolled-back attempt), so these are replayed one at a time on clean tags.
@@ -3517,76 +3515,116 @@ int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_n
     if (na > 0)
       BS_HIP(ctx, hipMemcpyAsync(d_cand, hc_sorted.data(), sizeof(unsigned long long) * na, hipMemcpyHostToDevice, st));
     a.F = INF;
-    auto grow_n = [&](int off, int cnt, PlaneOut* o) { launch_grow(cnt, d_cand + off, o, 0, nullptr); };
     auto compare_n = [&](int cnt, int32_t* retry) {
       audit_compare_kernel<<<cnt, VT, 0, st>>>(d_out, cnt, pool.base, prio, d_seeds, ctx->rg_planes.as<PlaneRec>(), np,
-                                               ctx->rg_list.as<int32_t>(), a.th_count, d_misc + 8, dead, retry);
+                                               ctx->rg_list.as<int32_t>(), a.th_count, &misc->audit.mismatches, dead, retry);
     };
     for (int off = 0; off < n_committed; off += wave_cap) {
       const int cnt = std::min(n_committed - off, wave_cap);
-      BS_HIP(ctx, hipMemsetAsync(d_pool_top, 0, sizeof(unsigned long long), st));
-      grow_n(off, cnt, d_out);
+      BS_HIP(ctx, hipMemsetAsync(pool.top, 0, sizeof(unsigned long long), st));
+      launch_grow(cnt, d_cand + off, d_out, 0, nullptr);
       compare_n(cnt, nullptr);
-      reset_tags_kernel<<<cnt, VT, 0, st>>>(d_out, cnt, pool.base, rec, quads, K);
+      reset_tags(cnt);
     }
     // Attempts the reference rolled back (:203-208): a few hundred points each.  They gave their points free again, so
     // two of them (or one and a later plane) may want the same point: all of them are replayed CONCURRENTLY, and those
     // that met another attempt of the batch -- robbed, or one logged "held by an earlier in-flight attempt" -- are
     // replayed again in the next batch, on clean tags.  The lowest seed of a batch always comes through, so the
     // batches shrink; in practice one or two suffice (one launch per attempt before: 0.6 s at 50 M, 3 s at 200 M).
-    {
-      std::vector<unsigned long long> pend(hc_sorted.begin() + n_committed, hc_sorted.end()), next;
-      int32_t* d_retry = reinterpret_cast<int32_t*>(dkeys_in);  // (free outside the rounds: wave_cap words)
-      std::vector<int32_t> h_retry;
-      int batches = 0;
-      while (!pend.empty()) {
-        next.clear();
-        for (size_t off = 0; off < pend.size(); off += (size_t)wave_cap) {
-          const int cnt = (int)std::min<size_t>(pend.size() - off, (size_t)wave_cap);
-          BS_HIP(ctx, hipMemcpyAsync(d_cand, pend.data() + off, sizeof(unsigned long long) * cnt, hipMemcpyHostToDevice, st));
-          BS_HIP(ctx, hipMemsetAsync(d_pool_top, 0, sizeof(unsigned long long), st));
-          reset_dead_kernel<<<nblk(cnt, 256), 256, 0, st>>>(d_cand, cnt, dead);
-          grow_n(0, cnt, d_out);
-          compare_n(cnt, d_retry);
-          reset_tags_kernel<<<cnt, VT, 0, st>>>(d_out, cnt, pool.base, rec, quads, K);
-          reset_dead_kernel<<<nblk(cnt, 256), 256, 0, st>>>(d_cand, cnt, dead);
-          h_retry.resize((size_t)cnt);
-          BS_HIP(ctx, hipMemcpyAsync(h_retry.data(), d_retry, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st));
-          BS_HIP(ctx, hipStreamSynchronize(st));
-          for (int i = 0; i < cnt; i++)
-            if (h_retry[i])
-              next.push_back(pend[off + i]);
-        }
-        if (next.size() == pend.size()) {
-          // (what the lowest attempts of the stuck batch ended as: the last sub-batch is still in d_out)
-          const size_t last_off = (pend.size() - 1) / (size_t)wave_cap * (size_t)wave_cap;
-          const int nshow = (int)std::min<size_t>(pend.size() - last_off, 3);
-          std::vector<PlaneOut> ho((size_t)nshow);
-          BS_HIP(ctx, hipMemcpy(ho.data(), d_out, sizeof(PlaneOut) * nshow, hipMemcpyDeviceToHost));
-          std::string msg = "audit: a batch of rolled-back attempts made no progress (" + std::to_string(pend.size()) + " left;";
-          for (const PlaneOut& o : ho)
-            msg += " seed " + std::to_string(o.seed) + " status " + std::to_string(o.status) + " list " + std::to_string(o.list_n) +
-                   " log " + std::to_string(o.log_n) + " thief " + std::to_string(o.thief) + ";";
-          msg += ")";
-          return fail(ctx, BS_ERR_INTERNAL, msg.c_str());
-        }
-        pend.swap(next);
-        batches++;
+    std::vector<unsigned long long> pend(hc_sorted.begin() + n_committed, hc_sorted.end()), next;
+    int32_t* d_retry = retry_in_dkeys_in();
+    std::vector<int32_t> h_retry;
+    int batches = 0;
+    while (!pend.empty()) {
+      next.clear();
+      for (size_t off = 0; off < pend.size(); off += (size_t)wave_cap) {
+        const int cnt = (int)std::min<size_t>(pend.size() - off, (size_t)wave_cap);
+        BS_HIP(ctx, hipMemcpyAsync(d_cand, pend.data() + off, sizeof(unsigned long long) * cnt, hipMemcpyHostToDevice, st));
+        BS_HIP(ctx, hipMemsetAsync(pool.top, 0, sizeof(unsigned long long), st));
+        reset_dead(cnt);
+        launch_grow(cnt, d_cand, d_out, 0, nullptr);
+        compare_n(cnt, d_retry);
+        reset_tags(cnt);
+        reset_dead(cnt);
+        h_retry.resize((size_t)cnt);
+        BS_HIP(ctx, hipMemcpyAsync(h_retry.data(), d_retry, sizeof(int32_t) * cnt, hipMemcpyDeviceToHost, st));
+        BS_HIP(ctx, hipStreamSynchronize(st));
+        for (int i = 0; i < cnt; i++)
+          if (h_retry[i])
+            next.push_back(pend[off + i]);
       }
-      if (dbg)
-        fprintf(stderr, "[bs] audit: %d rolled-back attempts replayed in %d batches\n", na - n_committed, batches);
+      if (next.size() == pend.size()) {
+        // (what the lowest attempts of the stuck batch ended as: the last sub-batch is still in d_out)
+        const size_t last_off = (pend.size() - 1) / (size_t)wave_cap * (size_t)wave_cap;
+        const int nshow = (int)std::min<size_t>(pend.size() - last_off, 3);
+        std::vector<PlaneOut> ho((size_t)nshow);
+        BS_HIP(ctx, hipMemcpy(ho.data(), d_out, sizeof(PlaneOut) * nshow, hipMemcpyDeviceToHost));
+        std::string msg = "audit: a batch of rolled-back attempts made no progress (" + std::to_string(pend.size()) + " left;";
+        for (const PlaneOut& o : ho)
+          msg += " seed " + std::to_string(o.seed) + " status " + std::to_string(o.status) + " list " + std::to_string(o.list_n) +
+                 " log " + std::to_string(o.log_n) + " thief " + std::to_string(o.thief) + ";";
+        msg += ")";
+        return fail(ctx, BS_ERR_INTERNAL, msg.c_str());
+      }
+      pend.swap(next);
+      batches++;
     }
-    BS_HIP(ctx, hipMemcpyAsync(h_flags + 12, d_misc + 8, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (cfg.dbg)
+      fprintf(stderr, "[bs] audit: %d rolled-back attempts replayed in %d batches\n", na - n_committed, batches);
+    BS_HIP(ctx, hipMemcpyAsync(&hf->audit, &misc->audit, sizeof(AuditStats), hipMemcpyDeviceToHost, st));
     BS_HIP(ctx, hipStreamSynchronize(st));
     BS_HIP(ctx, hipGetLastError());
     ctx->tm.audit_attempts = na;
-    ctx->tm.audit_mismatches = (int64_t)h_flags[12] + (h_flags[13] != np ? 1 : 0);
+    ctx->tm.audit_mismatches = (int64_t)hf->audit.mismatches + (hf->audit.committed_met != np ? 1 : 0);
     ctx->tm.audit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (dbg || ctx->tm.audit_mismatches)
-      fprintf(stderr, "[bs] audit: %d attempts replayed, %d of %d committed planes met, %d mismatches, %.1f ms\n", na, h_flags[13], np,
-              h_flags[12], ctx->tm.audit_ms);
+    if (cfg.dbg || ctx->tm.audit_mismatches)
+      fprintf(stderr, "[bs] audit: %d attempts replayed, %d of %d committed planes met, %d mismatches, %.1f ms\n", na, hf->audit.committed_met, np,
+              hf->audit.mismatches, ctx->tm.audit_ms);
+    return BS_OK;
   }
+};
+
+}  // namespace
+
+int launch_region_grow_spec(bs_ctx* ctx, const int32_t* d_xyz, const double* d_normals, const int32_t* d_neigh,
+                            int64_t n, const bs_params& p, int32_t* d_plane_idx)
+{
+  ctx->rg_valid = false;
+  ctx->bt_valid = false;
+  ctx->rg_omega = nullptr;
+  ctx->rg_prio = nullptr;
+  ctx->rg_seeds = nullptr;
+  ctx->rg_nplanes = 0;
+  const GrowConfig cfg = read_grow_config(ctx);
+  const GrowSizes sz(n, p.k, p.th_point_count, cfg.max_waves, cfg.lim);
+  ctx->gc = bs_grow_counters{};
+  ctx->gc.pool_cap = (int64_t)sz.pool_cap_eff;
+  ctx->gc.max_waves_end = sz.max_waves;
+  BS_TRY(reserve_scratch(ctx, sz, p.k));
+  SpecRun r(ctx, cfg, sz, d_xyz, d_normals, d_neigh, p, d_plane_idx);
+  BS_TRY(r.order_and_records());
+  BS_TRY(r.masks_and_reverse_lists());
+  BS_TRY(r.first_fixed_point());
+  for (bool done = false; !done;) {
+    BS_TRY(r.list_candidates());
+    if (r.ncand_all == 0 && r.npend == 0)
+      break;  // no plane attempt left: omega is the final owner array
+    if (r.ncand > 0)
+      BS_TRY(r.grow_and_insert());
+    BS_TRY(r.read_back());
+    BS_TRY(r.judge());
+    if (r.cfg.dbg)
+      r.report_round();
+    BS_TRY(r.merge());
+    BS_TRY(r.apply_drops());
+    BS_TRY(r.advance(done));
+  }
+  BS_TRY(r.finish());
+  if (r.cfg.audit)
+    BS_TRY(r.audit());
   return BS_OK;
 }
+
+#undef BS_TRY
 
 }  // namespace bs
